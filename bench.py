@@ -9,15 +9,24 @@ generate_stream_segment loop body (tts_model.rs:1006-1070) for all 32 rows: Flow
 flow head + Mimi decode -> 32 x 1920 PCM samples (32 x 80 ms of audio), copied to pinned host
 memory inside the step (the graphs end in async D2H copies; fetch() reads host memory).
 
-The utterance length is fixed at 125 frames whatever --steps says: a timed job is the admission of
-all B utterances (voice-KV copy + 40-token text prefill per row) followed by the 125 batched steps
-that deliver their 10 s of audio. --steps K times max(MIN_JOBS, ceil(K / 125)) such jobs back to
-back (MIN_JOBS = 16, >= 1 s of GPU work, so one scheduling hiccup cannot move the line by
-percent); `steps` in the output is the number of steps actually timed (`steps_requested` = K).
+A timed job is the admission of all B utterances (voice-KV copy + 40-token text prefill per row)
+followed by the batched steps that deliver their audio: 125 steps for a 10-s utterance. --steps N
+times exactly N steps: N // 125 whole jobs back to back, then one shorter job of the N % 125 steps
+left over (its utterances are cut at that many frames). The default, 2000 steps, is 16 whole jobs
+(>= 1 s of GPU work, so one scheduling hiccup cannot move the line by percent); `steps` in the
+output is the number of steps timed, and `ms_per_step` the wall time of all timed jobs over it.
 value = audio seconds produced by all ranks / max-over-ranks wall time of all timed jobs;
 `per_job` gives the median, min and max of the per-job values (each job's time max over ranks).
 The voice state is precomputed (as in configs[1]); warmup = one short job of W steps on the same
 rows.
+
+A plain run does only that: set up, warm up, time the N steps, print the line. --full adds every
+other leg (p50 first-chunk latency, the int8 / fp8 / bf16 / distinct-voices variants, the per-op
+times and rooflines, the voice-state and text-driven benchmarks, the CPU baselines), each of
+which a --no-* option can switch off again. --dump-outputs DIR writes what the last timed step
+delivered (the fetch of the last job's last frame: PCM, latents, EOS logits, valid / last flags of
+every row) as DIR/<name>.npy in float32; the inputs depend on the arguments only (seeded weights,
+prompts, texts and noise streams), so two builds can be compared output for output.
 
 Any PTTS_* environment variable, or a library whose build id differs from the checked-out
 sources (a stale binary or a -DPTTS_PROBES measurement build), marks the line "NOT A PRODUCT RUN"
@@ -52,7 +61,12 @@ METRIC = "audio-sec/wall-sec (RTF) per GPU at batch=32 + p50 first-chunk latency
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: fp32 matrix/vector peak
 BATCH, PROMPT_FRAMES, TEXT_TOKENS, UTT_FRAMES = 32, 125, 40, 125  # 125 frames = 10 s per utterance
-MIN_JOBS = 16  # timed jobs per run whatever --steps says (~1.3 s of GPU work at B = 32)
+DEFAULT_STEPS = 16 * UTT_FRAMES  # 16 whole jobs (~1.3 s of GPU work at B = 32)
+
+
+def job_schedule(steps, frames=UTT_FRAMES):
+    """Frames per timed job for `steps` timed steps: whole `frames`-frame jobs, then the rest."""
+    return [frames] * (steps // frames) + ([steps % frames] if steps % frames else [])
 
 
 def measured_traffic(op):
@@ -309,12 +323,13 @@ def cpu_baseline_leg(procs):
 
 
 def _refwav():
-    """The reference's assets/ref.wav as held by tests/golden/ref_voice.safetensors (int16, 48 kHz,
-    the whole file; gen_golden.py refdata)."""
-    from safetensors.numpy import load_file
+    """The reference's assets/ref.wav as held by tests/golden/ref.wav (mono int16, 48 kHz, the whole
+    file; gen_golden.py refdata)."""
+    import wave
 
-    g = load_file(str(ROOT / "tests" / "golden" / "ref_voice.safetensors"))
-    return g["refwav_i16"].astype(np.float32) / np.float32(32768.0), 48000
+    with wave.open(str(ROOT / "tests" / "golden" / "ref.wav"), "rb") as w:
+        raw = np.frombuffer(w.readframes(w.getnframes()), np.int16)
+        return raw.astype(np.float32) / np.float32(32768.0), w.getframerate()
 
 
 def voice_state_bench(pt, dev, reps=5):
@@ -408,14 +423,22 @@ def cpu_voice_leg(procs):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=UTT_FRAMES,
-                    help="steps to time: ceil(steps / 125) whole jobs of 125-frame utterances")
+    ap.add_argument("--steps", type=int, default=DEFAULT_STEPS,
+                    help="steps to time: steps // 125 whole jobs of 125-frame utterances, then one job of the "
+                         "steps left over")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (first-chunk latency, precision and "
+                         "distinct-voices variants, per-op times and rooflines, voice-state and text benchmarks, "
+                         "CPU baselines); the --no-* options below switch single legs off again")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step delivered (PCM, latents, EOS logits, valid / last flags "
+                         "of every row) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=16, help="CPU baseline worker processes (<= CPU share)")
     ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--ops-out", default="", help="write per-op timings of the step plan (JSON)")
+    ap.add_argument("--ops-out", default="", help="with --full: write per-op timings of the step plan (JSON)")
     ap.add_argument("--no-op-times", action="store_true", help="skip the per-op HIP-event pass (PMC runs)")
     ap.add_argument("--no-quant-variant", action="store_true",
                     help="skip the extra jobs on the int8-weight (weight_quant = QUANT_FLOW_LM), fp8_gemm and "
@@ -447,6 +470,13 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU-only check of the N-rank launch path (gloo, stand-in engine; measures nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.ops_out and not args.full:
+        ap.error("--ops-out belongs to the per-op pass: add --full")
+    if not args.full:  # a plain run: the timed steps and the line, nothing else
+        args.no_cpu_baseline = args.no_latency = args.no_op_times = args.no_quant_variant = True
+        args.no_distinct_voices = args.no_voice_bench = args.no_text_bench = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_replicas(args.gpus))
@@ -478,7 +508,8 @@ def main():
 
     B, W = args.batch, args.warmup
     K = args.profile_frames if args.profile_frames > 0 else UTT_FRAMES
-    jobs = max(MIN_JOBS, -(-args.steps // K)) if args.profile_frames <= 0 else 1
+    sched = job_schedule(args.steps) if args.profile_frames <= 0 else [K]  # frames of each timed job
+    jobs, steps = len(sched), sum(sched)
     pipeline = not args.no_pipeline
     back_frames = args.back_frames if pipeline else 1
     back_mfma = {"f32": 0, "f32x6": 2}[args.back_mfma]
@@ -518,8 +549,8 @@ def main():
     def timed_job(eng, distinct_voices=False):
         """Warmup job, then the timed ones: per job, admission of all B utterances (voice KV prefix +
         text prefill) and the 125 batched steps of their 10 s of audio, i.e. first prefill to last
-        PCM frame (in pinned host memory) of B utterances. Returns (elapsed, admission) seconds,
-        max over ranks. The voice state is precomputed: ONE voice shared by all rows (they read its
+        PCM frame (in pinned host memory) of B utterances. Returns (elapsed, admission, per-job)
+        seconds, max over ranks, and the last job's fetch (this rank's). The voice state is precomputed: ONE voice shared by all rows (they read its
         KV prefix, KvStore::pre), or with distinct_voices a voice of its own per row (B distinct
         125-frame prompts: every row reads its own 6-MB prefix)."""
         if distinct_voices:
@@ -549,23 +580,23 @@ def main():
         eng.sync()
         job_s = []
         t0 = time.perf_counter()
-        admit(1, K)
+        admit(1, sched[0])
         eng.sync()
         admit_s = time.perf_counter() - t0  # one admission, alone (the later ones overlap, below)
         tj = t0
         for j in range(jobs):
-            run_calls(K)  # the K frames, then the calls that drain the last one
+            run_calls(sched[j])  # the job's frames, then the calls that drain the last one
             if j + 1 < jobs and not args.no_overlap_admission:
                 # the next job's admission is issued now: its voice-KV copy and text prefill queue
                 # behind this job's last front part and run beside its last back passes (the
                 # engine resets the back part's slot state only after those, ptts_slots_open)
-                admit(2 + j, K)
+                admit(2 + j, sched[j + 1])
             r = eng.fetch(B)  # the last frame of every row (waits for this job's last back pass)
             assert r.valid.all() and r.last.all(), "bench produced invalid frames"
             assert np.isfinite(r.pcm).all(), "bench produced non-finite PCM"
             if j + 1 < jobs and args.no_overlap_admission:
                 eng.sync()
-                admit(2 + j, K)
+                admit(2 + j, sched[j + 1])
             t = time.perf_counter()
             job_s.append(t - tj)
             tj = t
@@ -574,7 +605,7 @@ def main():
         elapsed = t1 - t0
         if dist is not None:
             elapsed, admit_s, *job_s = max_over_ranks(dist, [elapsed, admit_s, *job_s], dev)
-        return elapsed, admit_s, job_s
+        return elapsed, admit_s, job_s, r
 
     def pcm_sample(e, n_frames=24):
         """Every row's PCM, latents and EOS logits of n_frames frames at temp 0 (no EOS) from the
@@ -623,12 +654,11 @@ def main():
                 "stop_frame_within_1": round(float(np.mean(diffs <= 1)), 3),
                 "sample": f"{B} rows x {rpcm.shape[1]} frames, temp 0, bench voice and texts, against the f32 engine"}
 
-    elapsed, admit_s, job_s = timed_job(eng)
-    steps = jobs * K
+    elapsed, admit_s, job_s, last_fetch = timed_job(eng)
 
-    audio_sec = world * jobs * B * K * 1920 / 24000.0
+    audio_sec = world * B * steps * 1920 / 24000.0
     value = audio_sec / elapsed
-    job_vals = sorted(world * B * K * 1920 / 24000.0 / t for t in job_s)
+    job_vals = sorted(world * B * n * 1920 / 24000.0 / t for n, t in zip(sched, job_s))
     per_job = {"jobs": jobs, "median": round(float(np.median(job_vals)), 2), "min": round(job_vals[0], 2),
                "max": round(job_vals[-1], 2)}
 
@@ -636,6 +666,14 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+
+    # ---- what the last timed step delivered (this rank's rows), for build-to-build comparison
+    if args.dump_outputs:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        for name in ("pcm", "latents", "eos_logits", "valid", "last"):
+            if hasattr(last_fetch, name):  # (the selftest stand-in has no latents or EOS logits)
+                np.save(out_dir / f"{name}.npy", np.asarray(getattr(last_fetch, name), np.float32))
 
     # ---- p50 first-chunk latency (config 2): text prefill + 1 step, voice precomputed
     p50 = None
@@ -663,8 +701,8 @@ def main():
     # instead of the bench's one shared voice; the headline's shared-prefix benefit, made visible
     distinct = None
     if not args.no_distinct_voices and world == 1:
-        d_el, d_ad, _ = timed_job(eng, distinct_voices=True)
-        distinct = {"value": round(jobs * B * K * 1920 / 24000.0 / d_el, 2), "unit": "audio-sec/wall-sec",
+        d_el, d_ad, _, _ = timed_job(eng, distinct_voices=True)
+        distinct = {"value": round(B * steps * 1920 / 24000.0 / d_el, 2), "unit": "audio-sec/wall-sec",
                     "ms_per_step": round(1000.0 * d_el / steps, 4),
                     "steady_ms_per_step": round(1000.0 * (d_el - d_ad) / steps, 4),
                     "voices": f"{B} distinct {PROMPT_FRAMES}-frame prompts (one per row)",
@@ -757,9 +795,9 @@ def main():
     if not args.no_quant_variant and world == 1:
         eq = pt.Engine(device=local_rank, max_slots=B, max_ctx=max_ctx, lsd_decode_steps=1, seed=0x5EED,
                        pipeline=pipeline, back_frames=back_frames, weight_quant=pt.QUANT_FLOW_LM)
-        q_el, q_ad, _ = timed_job(eq)
+        q_el, q_ad, _, _ = timed_job(eq)
         q_acc = accuracy_vs_f32(pcm_sample(eq), ref_sample)
-        quant = {"value": round(jobs * B * K * 1920 / 24000.0 / q_el, 2), "unit": "audio-sec/wall-sec",
+        quant = {"value": round(B * steps * 1920 / 24000.0 / q_el, 2), "unit": "audio-sec/wall-sec",
                  "ms_per_step": round(1000.0 * q_el / steps, 4),
                  "steady_ms_per_step": round(1000.0 * (q_el - q_ad) / steps, 4),
                  "weight_quant": "flow_lm int8 (quantize.rs QuantizeConfig::default, per-tensor symmetric; equals "
@@ -768,9 +806,9 @@ def main():
         eq.close()
         ef = pt.Engine(device=local_rank, max_slots=B, max_ctx=max_ctx, lsd_decode_steps=1, seed=0x5EED,
                        pipeline=pipeline, back_frames=back_frames, fp8_gemm=True)
-        f_el, f_ad, _ = timed_job(ef)
+        f_el, f_ad, _, _ = timed_job(ef)
         f_acc = accuracy_vs_f32(pcm_sample(ef), ref_sample)
-        fp8 = {"value": round(jobs * B * K * 1920 / 24000.0 / f_el, 2), "unit": "audio-sec/wall-sec",
+        fp8 = {"value": round(B * steps * 1920 / 24000.0 / f_el, 2), "unit": "audio-sec/wall-sec",
                "ms_per_step": round(1000.0 * f_el / steps, 4),
                "steady_ms_per_step": round(1000.0 * (f_el - f_ad) / steps, 4),
                "gemm": "fp8 e4m3 W8A8 on v_mfma_f32_32x32x16_fp8_fp8 (row-scaled weights, per-slice "
@@ -783,13 +821,13 @@ def main():
         # engine's (= the f32 oracle within 1e-7, tests/test_gpu_bench_shape.py) on a 24-frame sample
         eb = pt.Engine(device=local_rank, max_slots=B, max_ctx=max_ctx, lsd_decode_steps=1, seed=0x5EED,
                        pipeline=pipeline, back_frames=back_frames, back_bf16=True)
-        b_el, b_ad, _ = timed_job(eb)
+        b_el, b_ad, _, _ = timed_job(eb)
         bp = pcm_sample(eb)[0]
         eb.close()
         ref_pcm = ref_sample[0]
         err = ((bp - ref_pcm) ** 2).sum(-1)
         snr = 10 * np.log10((ref_pcm ** 2).sum(-1) / np.maximum(err, 1e-30))
-        bf16 = {"value": round(jobs * B * K * 1920 / 24000.0 / b_el, 2), "unit": "audio-sec/wall-sec",
+        bf16 = {"value": round(B * steps * 1920 / 24000.0 / b_el, 2), "unit": "audio-sec/wall-sec",
                 "ms_per_step": round(1000.0 * b_el / steps, 4),
                 "steady_ms_per_step": round(1000.0 * (b_el - b_ad) / steps, 4),
                 "mfma": "Mimi decoder transformer GEMMs + SEANet decoder convs on v_mfma_f32_32x32x16_bf16 "

@@ -219,12 +219,13 @@ def voice(threads):
     from _oracle import resample
 
     o = _oracle("libptts_cpu_fast.so")
-    from safetensors.numpy import load_file
+    import wave
 
-    g = load_file(str(ROOT / "tests" / "golden" / "ref_voice.safetensors"))
+    with wave.open(str(ROOT / "tests" / "golden" / "ref.wav"), "rb") as w:
+        refwav_i16 = np.frombuffer(w.readframes(w.getnframes()), np.int16)
     cases = [(f"{s}s_randn", np.random.default_rng(s).standard_normal(24000 * s).astype(np.float32), 24000)
              for s in (3, 15, 60)]
-    cases.append(("ref_wav", g["refwav_i16"].astype(np.float32) / np.float32(32768.0), 48000))
+    cases.append(("ref_wav", refwav_i16.astype(np.float32) / np.float32(32768.0), 48000))
 
     def run(x, sr):
         t0 = time.monotonic()

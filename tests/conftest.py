@@ -16,9 +16,23 @@ def pytest_configure(config):
 
 
 def load_golden(name: str) -> dict:
+    """A golden fixture; one whose tensors do not fit a 1-MiB file continues in <stem>.part2.safetensors."""
     from safetensors.numpy import load_file
 
-    return load_file(str(GOLDEN / name))
+    d = load_file(str(GOLDEN / name))
+    part2 = GOLDEN / (Path(name).stem + ".part2.safetensors")
+    if part2.exists():
+        d.update(load_file(str(part2)))
+    return d
+
+
+def load_ref_wav() -> np.ndarray:
+    """The samples of the reference's assets/ref.wav (tests/golden/ref.wav: mono int16, 48 kHz)."""
+    import wave
+
+    with wave.open(str(GOLDEN / "ref.wav"), "rb") as w:
+        assert (w.getnchannels(), w.getsampwidth(), w.getframerate()) == (1, 2, 48000)
+        return np.frombuffer(w.readframes(w.getnframes()), np.int16)
 
 
 @pytest.fixture(autouse=True, scope="session")

@@ -243,6 +243,16 @@ def run_resample(torch, tag):
     return out
 
 
+def save_split(fx, name, part2):
+    """name.safetensors, with the tensors named in `part2` in name.part2.safetensors (committed files
+    stay under 1 MiB; conftest.load_golden puts the two together)."""
+    from safetensors.numpy import save_file
+
+    save_file({k: np.ascontiguousarray(v) for k, v in fx.items() if k not in part2}, str(HERE / f"{name}.safetensors"))
+    if part2:
+        save_file({k: np.ascontiguousarray(fx[k]) for k in part2}, str(HERE / f"{name}.part2.safetensors"))
+
+
 def main():
     torch = _import_reference()
     torch.set_num_threads(8)
@@ -259,8 +269,9 @@ def main():
             assert (w.getnchannels(), w.getsampwidth(), w.getframerate()) == (1, 2, 48000)
             raw = np.frombuffer(w.readframes(w.getnframes()), np.int16)
         mi = load_file(str(REF.parent / "assets" / "ref_mimi_input.safetensors"))["mimi_input"].reshape(-1)
-        save_file({"refwav_i16": np.ascontiguousarray(raw), "ref_mimi_input": np.ascontiguousarray(mi, np.float32)},
-                  str(HERE / "ref_voice.safetensors"))
+        assert raw.size == 331708
+        shutil.copyfile(REF.parent / "assets" / "ref.wav", HERE / "ref.wav")  # the samples, as the file itself
+        save_file({"ref_mimi_input": np.ascontiguousarray(mi, np.float32)}, str(HERE / "ref_voice.safetensors"))
         # real-weight intermediates of the reference's test_decoder_parity / voice conditioning
         # (meaningful only with the gated checkpoint; the weights-gated GPU tests use them)
         for f in ("ref_decoder_intermediates.safetensors", "ref_voice_conditioning.safetensors"):
@@ -283,7 +294,7 @@ def main():
         # slides over 1600 positions (attention.rs:167-264, sdpa.rs:128-171)
         fx = run_e2e(torch, flm, mimi, F=125, S=40, N=100, lsd_steps=1, tag="e2e_long")
         del fx["tout"]
-        save_file({k: np.ascontiguousarray(v) for k, v in fx.items()}, str(HERE / "e2e_long.safetensors"))
+        save_split(fx, "e2e_long", ("pcm",))
         print("long fixture written to", HERE)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "hello":  # BASELINE configs[0] on synthetic weights
@@ -303,7 +314,7 @@ def main():
             fx = run_e2e(torch, flm, mimi, F=125, S=len(ids), N=(2 + 2) * 13, lsd_steps=1, tag="hello",
                          ids=ids, eos_threshold=thr, frames_after_eos=5)
             del fx["tout"]
-            save_file({k: np.ascontiguousarray(v) for k, v in fx.items()}, str(HERE / f"{name}.safetensors"))
+            save_split(fx, name, ("prompt",) if name == "hello_world_maxlen" else ())
             print(name, "stop", fx["stop"], "eos logits", fx["eos_logit"].min(), fx["eos_logit"].max())
         return
     if len(sys.argv) > 1 and sys.argv[1] == "voice":  # only the voice-cloning front-end fixtures

@@ -79,13 +79,14 @@ def test_bench_gpus_flag_launches_replica_ranks(gpus):
     """`bench.py --gpus 2` outside a torch.distributed environment re-launches itself as 2 ranks
     under torch.distributed.run (a child process, never exec), each rank runs its replica, rank 0
     reports the whole job: n_gpus 2, "replicas x2", global batch 2 x 32, 125-frame utterances and
-    at least MIN_JOBS (16) timed jobs whatever --steps asks, with the per-job median / min / max. CPU only: --launcher-selftest swaps in a stand-in engine and gloo."""
+    exactly the --steps timed steps (270 = two whole jobs and one of 20 frames), with the per-job
+    median / min / max. CPU only: --launcher-selftest swaps in a stand-in engine and gloo."""
     import json
     import subprocess
     import sys
 
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--launcher-selftest", "--steps",
-                        "20", "--warmup", "1"], capture_output=True, text=True, timeout=400,
+                        "270", "--warmup", "1"], capture_output=True, text=True, timeout=400,
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -93,6 +94,7 @@ def test_bench_gpus_flag_launches_replica_ranks(gpus):
     out = json.loads(lines[0])
     assert out["n_gpus"] == gpus and out["config"]["parallelism"] == f"replicas x{gpus}"
     assert out["config"]["global_batch"] == 32 * gpus and out["config"]["utterance_frames"] == 125
-    assert out["steps"] == 16 * 125 and out["steps_requested"] == 20 and out["scaling"] == "weak"
+    assert out["steps"] == 270 and out["steps_requested"] == 270 and out["scaling"] == "weak"
+    assert out["ms_per_step"] > 0
     pj = out["per_job"]
-    assert pj["jobs"] == 16 and pj["min"] <= pj["median"] <= pj["max"]
+    assert pj["jobs"] == 3 and pj["min"] <= pj["median"] <= pj["max"]

@@ -2,7 +2,7 @@
 the int8-quantised FlowLM and the fp8 MFMA path) and the kernel-level decode seam.
 
 Pinning:
-  * assets/ref.wav -> assets/ref_mimi_input (tests/golden/ref_voice.safetensors, both whole
+  * assets/ref.wav -> assets/ref_mimi_input (tests/golden/ref.wav and ref_voice.safetensors, both whole
     files): the reference's own resampler pair (test_input_parity, parity_tests.rs:378-433);
   * the voice conditioning and the generation from it against the C oracle (pinned to the
     reference's Python modules by tests/test_oracle.py), with the same weights: synthetic, the
@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 import pytest
-from conftest import LAT_TOL, PCM_TOL, load_golden, pcm_err
+from conftest import LAT_TOL, PCM_TOL, load_golden, load_ref_wav, pcm_err
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -32,7 +32,7 @@ def _params(**kw):
 
 def _refwav():
     g = load_golden("ref_voice.safetensors")
-    return g["refwav_i16"].astype(np.float32) / np.float32(32768.0), g["ref_mimi_input"]
+    return load_ref_wav().astype(np.float32) / np.float32(32768.0), g["ref_mimi_input"]
 
 
 def test_decode_latents_matches_reference_golden(gpu_engine):

@@ -4,18 +4,17 @@ pause markers, and text-driven generation through the engine.
 Pinning: token ids are bit-exact against tests/golden/text_ids.json, produced by the `tokenizers`
 library (the binding of the crate the reference links) configured as the reference's native
 loader (text.rs:58-79) and as Tokenizer::from_file on the reference's tokenizer.json
-(gen_text_golden.py). The string rules restate tts_model.rs / pause.rs and carry the reference's
+(gen_text_golden.py; the file itself is tests/golden/reference_tokenizer.json). The string rules restate tts_model.rs / pause.rs and carry the reference's
 own unit tests (tts_model.rs:1239-1290, pause.rs:187-249, text.rs:316-390)."""
 
 import json
 import struct
-from pathlib import Path
 
 import numpy as np
 import pytest
 from conftest import GOLDEN
 
-REF_JSON = Path("/root/reference/crates/pocket-tts/assets/tokenizer.json")
+REF_JSON = GOLDEN / "reference_tokenizer.json"  # the reference's crates/pocket-tts/assets/tokenizer.json
 
 
 def golden():
@@ -71,8 +70,6 @@ def test_sentencepiece_model_loader_matches():
 
 
 def test_reference_tokenizer_json_native_and_wasm_configs():
-    if not REF_JSON.exists():
-        pytest.skip("reference tokenizer.json not present")
     from pocket_tts_amd.text import load_tokenizer
 
     g = golden()

@@ -4,8 +4,8 @@ encoder and the whole WAV -> voice path.
 Pinning:
   * resampler: the reference's own real-data pair, assets/ref.wav -> assets/ref_mimi_input
     (test_input_parity, parity_tests.rs:379-433; the head is committed in
-    tests/golden/resample.safetensors, and the full pair is checked when /root/reference is
-    present), plus synthetic signals through the Python reference's convert_audio at 5 rates;
+    tests/golden/resample.safetensors, the whole pair in tests/golden/ref.wav and
+    tests/golden/ref_voice.safetensors), plus synthetic signals through the Python reference's convert_audio at 5 rates;
   * chunked encode: the reference's Python streaming modules driven the way the Rust driver
     chunks (gen_golden.py:run_encoder_chunked).
 Tolerances: resampler 1e-6 abs (f64 accumulation here vs scipy's f32 upfirdn); encoder
@@ -18,13 +18,12 @@ is UNPINNED. The oracle's restatement is checked against properties of the publi
 limited tone at the walk's positions), and the GPU kernel against the oracle bit for bit."""
 
 import struct
-from pathlib import Path
 
 import numpy as np
 import pytest
-from conftest import LAT_TOL, PCM_TOL, load_golden, pcm_err
+from conftest import GOLDEN, LAT_TOL, PCM_TOL, load_golden, load_ref_wav, pcm_err
 
-REF_ASSETS = Path("/root/reference/assets")
+REF_WAV = GOLDEN / "ref.wav"  # the reference's assets/ref.wav
 RATES = (48000, 44100, 16000, 22050, 8000)
 
 
@@ -108,11 +107,9 @@ def test_read_wav_float_and_truncated():
 
 def test_read_reference_wav():
     """The reference's own assets/ref.wav: 48 kHz mono s16, 331,708 samples."""
-    if not (REF_ASSETS / "ref.wav").exists():
-        pytest.skip("reference assets not present")
     from pocket_tts_amd.audio import read_wav
 
-    x, sr = read_wav(REF_ASSETS / "ref.wav")
+    x, sr = read_wav(REF_WAV)
     g = load_golden("resample.safetensors")
     assert sr == 48000 and x.shape == (1, int(g["ref_lengths"][0]))
     np.testing.assert_array_equal(x[0, :24064], g["refwav_head_i16"].astype(np.float32) / 32768.0)
@@ -137,17 +134,12 @@ def test_oracle_resample_matches_reference_ref_wav_pair():
     x = g["refwav_head_i16"].astype(np.float32) / 32768.0
     y = resample(x, 48000)[:12000]
     assert np.abs(y - g["ref_mimi_input_head"]).max() <= 1e-6
-    if (REF_ASSETS / "ref_mimi_input.safetensors").exists():  # the whole file, when present
-        import wave
-
-        from safetensors.numpy import load_file
-
-        with wave.open(str(REF_ASSETS / "ref.wav"), "rb") as w:
-            xs = np.frombuffer(w.readframes(w.getnframes()), np.int16).astype(np.float32) / 32768.0
-        m = load_file(str(REF_ASSETS / "ref_mimi_input.safetensors"))["mimi_input"].reshape(-1)
-        y = resample(xs, 48000)
-        assert np.abs(y - m[:y.size]).max() <= 1e-6 and not m[y.size:].any()
-        assert m.size == (y.size + 1919) // 1920 * 1920
+    # the whole file: ref.wav as shipped against the reference's whole ref_mimi_input
+    xs = load_ref_wav().astype(np.float32) / 32768.0
+    m = load_golden("ref_voice.safetensors")["ref_mimi_input"].reshape(-1)
+    y = resample(xs, 48000)
+    assert np.abs(y - m[:y.size]).max() <= 1e-6 and not m[y.size:].any()
+    assert m.size == (y.size + 1919) // 1920 * 1920
 
 
 def _septic_positions(n, sr_from, sr_to=24000):
@@ -393,13 +385,13 @@ def test_gpu_voice_errors(gpu_engine):
 
 
 def test_oracle_resample_matches_whole_reference_pair():
-    """The whole assets/ref.wav -> assets/ref_mimi_input pair (tests/golden/ref_voice.safetensors):
+    """The whole assets/ref.wav -> assets/ref_mimi_input pair (tests/golden/ref.wav, ref_voice.safetensors):
     the oracle's resample_poly restatement equals the reference's convert_audio output, which the
     reference zero-pads to whole frames (87 x 1920)."""
     from _oracle import resample
 
     g = load_golden("ref_voice.safetensors")
-    x = g["refwav_i16"].astype(np.float32) / np.float32(32768.0)
+    x = load_ref_wav().astype(np.float32) / np.float32(32768.0)
     y = resample(x, 48000)
     mi = g["ref_mimi_input"]
     assert x.size == 331708 and y.size == 165854 and mi.size == 87 * 1920

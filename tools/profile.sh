@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 FR=${FRAMES:-30}
 NOVAR="--no-cpu-baseline --no-quant-variant --no-latency --no-distinct-voices --no-voice-bench --no-text-bench"
-timeout -k 10 300 python bench.py $NOVAR --ops-out "$OUT/bench_ops.json" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 300 python bench.py --full $NOVAR --ops-out "$OUT/bench_ops.json" > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { echo "bench failed"; tail -5 "$OUT/bench.err"; exit 1; }
 tail -n 1 "$OUT/bench.json" | cut -c1-300
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
