@@ -58,7 +58,9 @@ typedef struct ptts_engine_config {
   int device;           /* HIP device ordinal (one engine per GPU) */
   int max_slots;        /* concurrent utterances (batch rows) */
   int max_ctx;          /* FlowLM KV capacity per slot, positions (voice + text + frames) */
-  int lsd_decode_steps; /* TTSModel.lsd_decode_steps (tts_model.rs:22-49), engine-wide */
+  int lsd_decode_steps; /* TTSModel.lsd_decode_steps (tts_model.rs:22-49): the cap on every
+                           utterance's own Euler step count, and the count of an utterance
+                           admitted without one (ptts_slot_open_ex) */
   uint64_t synth_seed;  /* synthetic weights (tests/golden/synth.py rule) if weights_path == NULL */
   const char* weights_path; /* local safetensors with TTSModel state-dict names, or NULL */
   void* weight_blob;        /* optional caller-owned device buffer of ptts_weight_blob_bytes() */
@@ -235,6 +237,22 @@ int ptts_slot_open(ptts_engine* e, int slot, const ptts_voice* v, const int32_t*
  * burst of requests, or a batch job starting). */
 int ptts_slots_open(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                     const int* n_ids, const ptts_gen_params* params);
+/* The same admissions with the utterance's own LSD Euler step count (the reference's
+ * TTSModel.lsd_decode_steps, a field a caller may change between calls, and the server's per-request
+ * lsd_steps): lsd_steps in [1, cfg.lsd_decode_steps], or 0 (for ptts_slots_open_ex also a NULL
+ * array) for the engine's default, cfg.lsd_decode_steps; anything else is PTTS_ERR_INVALID and
+ * admits nothing. Rows with different counts share one batched step, and each computes what an
+ * engine created with lsd_decode_steps = its count would. ptts_slot_open, ptts_slots_open and
+ * ptts_generate are these calls with the default. */
+int ptts_slot_open_ex(ptts_engine* e, int slot, const ptts_voice* v, const int32_t* ids, int n_ids,
+                      const ptts_gen_params* p, int lsd_steps);
+int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
+                       const int* n_ids, const ptts_gen_params* params, const int* lsd_steps);
+/* *cap: cfg.lsd_decode_steps. *last_run: the Euler steps the most recent step call ran (0 before
+ * the first): the largest count among that call's rows still open (admitted, not closed, last
+ * frame not yet fetched), so a call whose open rows all use one step pays for one. Either pointer
+ * may be NULL. */
+int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run);
 int ptts_slot_close(ptts_engine* e, int slot);
 
 /* THE batched hot path: one iteration of the loop body of generate_stream_segment

@@ -232,15 +232,33 @@ void ptts_voice_destroy(ptts_voice* v) { ptts::voice_destroy(v); }
 
 int ptts_slot_open(ptts_engine* e, int slot, const ptts_voice* v, const int32_t* ids, int n_ids,
                    const ptts_gen_params* p) {
-  return guard([&] {
-    if (!p) throw ptts::Error(PTTS_ERR_INVALID, "null params");
-    eng(e).slot_open(slot, v, ids, n_ids, *p);
-  });
+  return ptts_slot_open_ex(e, slot, v, ids, n_ids, p, 0);
 }
 
 int ptts_slots_open(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                     const int* n_ids, const ptts_gen_params* params) {
-  return guard([&] { eng(e).slots_open(n, slots, voices, ids, n_ids, params); });
+  return ptts_slots_open_ex(e, n, slots, voices, ids, n_ids, params, nullptr);
+}
+
+int ptts_slot_open_ex(ptts_engine* e, int slot, const ptts_voice* v, const int32_t* ids, int n_ids,
+                      const ptts_gen_params* p, int lsd_steps) {
+  return guard([&] {
+    if (!p) throw ptts::Error(PTTS_ERR_INVALID, "null params");
+    eng(e).slot_open(slot, v, ids, n_ids, *p, lsd_steps);
+  });
+}
+
+int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
+                       const int* n_ids, const ptts_gen_params* params, const int* lsd_steps) {
+  return guard([&] { eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd_steps); });
+}
+
+int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run) {
+  return guard([&] {
+    if (!e || !e->impl) throw ptts::Error(PTTS_ERR_INVALID, "null engine");
+    if (cap) *cap = e->impl->lsd_cap();
+    if (last_run) *last_run = e->impl->lsd_last_run();
+  });
 }
 
 int ptts_probe_overlap(ptts_engine* e, int n_rows, int reps, double* us8) {

@@ -81,7 +81,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
   check_model_config(cfg.cfg_yaml);  // before any device work
   PTTS_REQUIRE(cfg.max_slots >= 1 && cfg.max_slots <= 256, "max_slots must be in [1, 256]");
   PTTS_REQUIRE(cfg.max_ctx >= 16 && cfg.max_ctx <= 8192, "max_ctx must be in [16, 8192]");
-  PTTS_REQUIRE(cfg.lsd_decode_steps >= 1 && cfg.lsd_decode_steps <= 64, "lsd_decode_steps must be in [1, 64]");
+  PTTS_REQUIRE(cfg.lsd_decode_steps >= 1 && cfg.lsd_decode_steps <= LSD_MAX, "lsd_decode_steps must be in [1, 64]");
   dev_ = cfg.device;
   max_slots_ = cfg.max_slots;
   max_ctx_ = cfg.max_ctx;
@@ -190,6 +190,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
   slot_voice_.assign(B, nullptr);
   drained_.assign(B, 1);
   admit_call_.assign(B, -1);
+  slot_lsd_.assign(B, 0);
   share_voice_ = probe_env("PTTS_NO_SHARED_VOICE") == nullptr;
 #ifdef PTTS_PROBES
   if (probe_env("PTTS_STAMPS")) {
@@ -240,7 +241,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
     ca_[i] = dalloc(BF * T * ch);
     trb_[i] = dalloc((size_t)RATIOS[i] * ch);
   }
-  temb_ = dalloc((size_t)lsd_ * FD);
+  temb_ = dalloc((size_t)temb_row0(lsd_ + 1) * FD);  // every count 1 .. lsd_, triangular (finalize)
   rope_ = dalloc((size_t)max_ctx_ * 64);
   temb_tmp_ = dalloc((size_t)2 * lsd_ * FD);
 
@@ -586,7 +587,9 @@ void Engine::finalize() {
     tw.l2b[i] = W(L_.te_l2b[i]);
     tw.alpha[i] = W(L_.te_alpha[i]);
   }
-  time_embeddings(tw, lsd_, temb_tmp_, temb_, stream_);
+  // the time embeddings of every per-row step count n = 1 .. cap (s = i / n, t = (i + 1) / n,
+  // mlp.rs:296-319), triangular: the n rows of count n start at row n (n - 1) / 2
+  for (int n = 1; n <= lsd_; ++n) time_embeddings(tw, n, temb_tmp_, temb_ + (size_t)temb_row0(n) * FD, stream_);
   rope_table(rope_, max_ctx_, stream_);
   for (int i = 0, ch = MD / 2; i < 3; ++i, ch /= 2)  // bias of the phase-merged transposed convs
     for (int p = 0; p < RATIOS[i]; ++p)
@@ -1034,7 +1037,9 @@ bool Engine::head_uniform_stride() const {
 }
 
 // FRONT part of a step (FlowLM + flow head) for rows [0, B), handing its frame to buffer `hb`.
-void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
+// It runs lsd_run Euler steps (lsd_run_for: >= the count of every row of [0, B) that may be active).
+void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
+  PTTS_REQUIRE(lsd_run >= 1 && lsd_run <= lsd_, "lsd_run outside [1, cap]");
   int S = 1;
   // ---- FlowLM step (flow_lm.rs:98-164): input_linear -> transformer -> out_norm. The input
   // projection + norm1 of layer 0 (x_, h_) were computed by the previous step's front_commit, or
@@ -1047,20 +1052,20 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
     const float* P = partial_;
     const float* bias = W(L_.cond_eos_b);
     const float* temb = temb_;
-    const int lsd = lsd_;
+    const int lsd = lsd_run, cap = lsd_;
     SlotState* st = st_;
     float *ys = ysilu_, *cur = cur_, *eos = eos_;
-    ops.push_back({"head.flow_cond", [=](hipStream_t s) { flow_cond(P, S, B, bias, temb, lsd, st, ys, cur, eos, s); },
+    ops.push_back({"head.flow_cond", [=](hipStream_t s) { flow_cond(P, S, B, bias, temb, lsd, cap, st, ys, cur, eos, s); },
                    (double)B * NCOND * (S + 1) + 4.0 * lsd * B * FD,
                    4.0 * ((double)S * B * NCOND + NCOND + lsd * FD + lsd * (double)B * FD + B * (LDIM + 1.0))});
   }
   // all adaLN modulations of all lsd steps in one GEMM (mlp.rs:322-368)
-  linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_ * B, W(L_.ada_w), NADA, FD, &S);
+  linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_run * B, W(L_.ada_w), NADA, FD, &S);
   {
     RowReduceArgs a{};
     a.P = partial_;
     a.S = S;
-    a.M = lsd_ * B;
+    a.M = lsd_run * B;
     a.N = NADA;
     a.bias = W(L_.ada_b);
     a.Y = mods_;
@@ -1068,7 +1073,7 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
     if (use_head_chain(B)) {  // side jobs: x0 into hand-off region 0, empty the other regions
       const size_t r0 = (size_t)((B + 15) / 16 * 16) * FD;  // floats per hand-off region
       a.fill = hx_ + r0;
-      a.fill_n4 = (long)((hx_floats(B) - r0) / 4);
+      a.fill_n4 = (long)((hx_floats(B, lsd_run) - r0) / 4);  // the regions of this run, not of the cap
       a.x0_cur = cur_;
       a.x0_w = fh_inw_t_;
       a.x0_b = W(L_.inproj_b);
@@ -1084,8 +1089,8 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
   if (use_head_chain(B)) {
     FlowHeadArgs f{};
     f.B = B;
-    f.lsd = lsd_;
-    f.euler_scale = 1.0f / (float)lsd_;
+    f.lsd = lsd_run;
+    f.st = st_;
     f.cur = cur_;
     f.mods = mods_;
     f.ldm = NADA;
@@ -1107,12 +1112,12 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
     f.ctr = hctr_;
     f.err = herr_;
     f.dbg = probe_env("PTTS_HEAD_DBG") ? (unsigned long long*)strtoull(probe_env("PTTS_HEAD_DBG"), nullptr, 0) : nullptr;
-    const double fl = 2.0 * lsd_ * B * ((double)FD * LDIM + 2.0 * FDEPTH * FD * FD + (double)LDIM * FD);
+    const double fl = 2.0 * lsd_run * B * ((double)FD * LDIM + 2.0 * FDEPTH * FD * FD + (double)LDIM * FD);
     const double by = 4.0 * ((double)FD * LDIM + 2.0 * FDEPTH * FD * FD + (double)LDIM * FD) +
-                      4.0 * lsd_ * B * ((double)FDEPTH * 3 * FD + 2 * FD);
+                      4.0 * lsd_run * B * ((double)FDEPTH * 3 * FD + 2 * FD);
     // isolated replays: re-empty the regions and recompute x0 (the adaLN reduce's side jobs)
     float* hx = hx_;
-    const size_t nhx = hx_floats(B);
+    const size_t nhx = hx_floats(B, lsd_run);
     const float *cur = cur_, *iw = fh_inw_t_, *ib = W(L_.inproj_b);
     Op op{"head.chain", [f](hipStream_t s) { flow_head(f, s); }, fl, by};
     op.prep = [hx, nhx, cur, iw, ib, B](hipStream_t s) {
@@ -1121,7 +1126,7 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
     };
     ops.push_back(op);
   }
-  for (int st = 0; st < lsd_ && !use_head_chain(B); ++st) {
+  for (int st = 0; st < lsd_run && !use_head_chain(B); ++st) {
     const float* mods = mods_ + (size_t)st * B * NADA;
     const std::string p = "head.s" + std::to_string(st);
     linear_split(ops, p + ".inproj_gemm", cur_, LDIM, B, W(L_.inproj_w), FD, LDIM, &S);
@@ -1200,7 +1205,8 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb) {
       a.N = LDIM;
       a.bias = W(L_.fin_b);
       a.euler = cur_;
-      a.euler_scale = 1.0f / (float)lsd_;
+      a.euler_st = st_;
+      a.euler_step = st;
       push_rr(ops, p + ".euler", a);
     }
   }
@@ -1555,7 +1561,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
 // The whole step in plan order (front then back, buffer 0): plan listing and per-op timing.
 std::vector<Op> Engine::build_step(int B) {
   std::vector<Op> ops;
-  build_front(ops, B, 0);
+  build_front(ops, B, 0, lsd_run_for(B));
   build_back(ops, B, 0, nfr_, 0, nfr_);
   return ops;
 }
@@ -1616,13 +1622,14 @@ void Engine::copy_out(int B, int hb, hipStream_t s) {
   }
 }
 
-hipGraphExec_t Engine::part_graph(int part, int B, int hb, int qp, int nfr) {
+hipGraphExec_t Engine::part_graph(int part, int B, int hb, int qp, int nfr, int lsd_run) {
   if (part == 0) qp = nfr = 0;  // the front part does not use the quantizer history
-  const int key = (((B * 2 + part) * NHB + hb) * 2 + qp) * (NFR_MAX + 1) + nfr;
+  else lsd_run = 0;             // nor the back part the Euler step count
+  const int key = ((((B * 2 + part) * NHB + hb) * 2 + qp) * (NFR_MAX + 1) + nfr) * (LSD_MAX + 1) + lsd_run;
   auto it = graphs_.find(key);
   if (it != graphs_.end()) return it->second;
   std::vector<Op> ops;
-  if (part == 0) build_front(ops, B, hb);
+  if (part == 0) build_front(ops, B, hb, lsd_run);
   else build_back(ops, B, hb, nfr, qp, nfr_);
   hipGraph_t g = nullptr;
   // captured on the stream it is launched on (the back part of a pipelined step: stream_be_)
@@ -1729,7 +1736,10 @@ void Engine::call_async(int B, bool run_front) {
   prev_k_ = out_k_;
   const int hb = (int)(k_ % nhb_), qp = (int)(k_ & 1);
   // the front part of this call, or (a flush) its hand-off buffer marked frame-less
-  hipGraphExec_t front = B > 0 ? part_graph(0, B, hb, 0, 0) : nullptr;
+  // its Euler step count: the largest count among the call's rows that are still open
+  const int lsd_run = B > 0 ? lsd_run_for(B) : 0;
+  if (B > 0) lsd_last_run_ = lsd_run;
+  hipGraphExec_t front = B > 0 ? part_graph(0, B, hb, 0, 0, lsd_run) : nullptr;
   auto run_front_part = [&]() {
     if (pv_read_pending_[hb]) {  // a preview still gathers from this hand-off buffer
       PTTS_HIP(hipStreamWaitEvent(stream_, ev_pv_read_[hb], 0));
@@ -1871,7 +1881,7 @@ void Engine::fetch(int B, float* pcm, uint8_t* valid, uint8_t* last, float* eos,
     // after that frame's call (a driver that admits the next utterance before fetching the last
     // frame of the previous one, as bench.py does): then the frame is the previous utterance's and
     // the new one's back passes are still to come
-    if (ok && hf[b].last && fk >= admit_call_[b]) drained_[b] = 1;
+    if (ok && hf[b].last && fk >= admit_call_[b]) drained_[b] = 1;  // (lsd_run_for: the row counts no more)
     if (valid) valid[b] = ok;
     if (last) last[b] = ok && hf[b].last;
     if (pcm) {
@@ -2527,8 +2537,20 @@ ptts_voice* Engine::voice_from_audio(const float* pcm_in, int n_in, int sr, int 
   return v;
 }
 
-void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p) {
-  slots_open(1, &slot, &v, ids, &n, &p);
+void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
+                       int lsd_steps) {
+  slots_open(1, &slot, &v, ids, &n, &p, &lsd_steps);
+}
+
+// Euler steps of a front part over rows [0, B): the largest per-row count among the rows the
+// host still holds open (admitted, and neither closed nor seen finished by fetch()). A row that has
+// finished on the device but is not yet drained here only costs time; a row that may still be
+// active is never given fewer steps than its own count. No open row: the engine's default.
+int Engine::lsd_run_for(int B) const {
+  int run = 0;
+  for (int b = 0; b < B; ++b)
+    if (!drained_[b]) run = std::max(run, slot_lsd_[b]);
+  return run > 0 ? run : lsd_;
 }
 
 // Batched admission: the per-segment prologue of generate_stream_segment (tts_model.rs:938-1004)
@@ -2537,7 +2559,7 @@ void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n,
 // per slot, padded to 16-row groups (the 16-query attention tiles), and mapped to (slot, position)
 // through a row table.
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
-                        const int* n_ids, const ptts_gen_params* params) {
+                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
@@ -2553,6 +2575,9 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     const ptts_gen_params& p = params[i];
     PTTS_REQUIRE(n_ids[i] >= 0 && (n_ids[i] == 0 || ids != nullptr), "bad token ids");
     PTTS_REQUIRE(p.max_frames >= 1, "max_frames must be >= 1");
+    // 0: the engine's default (its cap)
+    PTTS_REQUIRE(!lsd_steps || lsd_steps[i] == 0 || (lsd_steps[i] >= 1 && lsd_steps[i] <= lsd_),
+                 "lsd_steps must be 0 (the default) or in [1, " + std::to_string(lsd_) + "] (the engine's lsd_decode_steps)");
     PTTS_REQUIRE(p.frames_after_eos >= 0, "frames_after_eos must be >= 0");
     PTTS_REQUIRE((long)v->F + n_ids[i] + p.max_frames <= max_ctx_, "voice + text + max_frames exceeds max_ctx");
     for (int j = 0; j < n_ids[i]; ++j)
@@ -2673,6 +2698,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   for (int i = 0; i < n; ++i) {
     drained_[slots[i]] = 0;
     admit_call_[slots[i]] = k_;
+    slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
   }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
@@ -2690,6 +2716,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     s.eos_threshold = p.eos_threshold;
     s.noise_clamp = p.noise_clamp;
     s.seed = p.seed;
+    s.lsd = slot_lsd_[slots[i]];
     fp[i] = voices[i]->F + n_ids[i];
   }
   // staged through pinned buffers so the copies are truly asynchronous: admission returns with

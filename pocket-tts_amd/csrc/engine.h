@@ -61,9 +61,14 @@ class Engine {
   ptts_voice* voice_from_audio(const float* x, int n, int sample_rate, int chunk_frames,
                                int resampler = PTTS_RESAMPLE_POLY);
   void resample_host(const float* x, int n, int sr_from, int sr_to, float* y, int resampler = PTTS_RESAMPLE_POLY);
-  void slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p);
+  // lsd_steps: the utterance's own Euler step count in [1, cap], or 0 (nullptr: every entry 0) for
+  // the engine's default, the cap (cfg.lsd_decode_steps)
+  void slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
+                 int lsd_steps = 0);
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
-                  const ptts_gen_params* params);
+                  const ptts_gen_params* params, const int* lsd_steps = nullptr);
+  int lsd_cap() const { return lsd_; }
+  int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
   void set_latent(int slot, const float* lat);
   void decode_latents(int slot, const float* lat, int n, float* pcm, float* quant, float* up, float* tr);
@@ -110,14 +115,15 @@ class Engine {
   std::vector<Op> build_step(int B);
   // hb: front -> back hand-off buffer (frame index mod NHB); qp: parity of the back part's
   // quantizer history (frame index mod 2; the back part reads the previous frame's half)
-  void build_front(std::vector<Op>& ops, int B, int hb);
+  void build_front(std::vector<Op>& ops, int B, int hb, int lsd_run);
   // back part over nfr consecutive frames from hand-off buffers hb, hb + 1, .. hb + nfr - 1; the
   // PCM goes to the pass block of hb (pcm_frames frames per row, pcmp_) or, with pcm_frames 1, to
   // pcm_[hb]
   void build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, int pcm_frames);
   // multi-frame passes: a pass whose later calls were all flushes decodes only the frames its
   // calls started (nfr in part_graph's key)
-  hipGraphExec_t part_graph(int part, int B, int hb, int qp, int nfr);
+  // (front parts: lsd_run, the Euler steps the graph runs, is part of the key too)
+  hipGraphExec_t part_graph(int part, int B, int hb, int qp, int nfr, int lsd_run = 0);
   void wait_unless_done(hipStream_t s, hipEvent_t e);
   void copy_out(int B, int hb, hipStream_t s);
   void push_rr(std::vector<Op>& ops, const std::string& name, const RowReduceArgs& r);
@@ -135,7 +141,12 @@ class Engine {
                            float* ring);
 
   // configuration
+  // lsd_: cfg.lsd_decode_steps, the cap on (and default of) the per-row Euler step counts
+  static constexpr int LSD_MAX = 64;
   int dev_ = 0, max_slots_ = 0, max_ctx_ = 0, lsd_ = 1;
+  std::vector<int> slot_lsd_;  // per slot: the count of its current utterance (0: never admitted)
+  int lsd_last_run_ = 0;
+  int lsd_run_for(int B) const;
   int wq_ = 0;  // weight_quant mode (QuantMode)
   // int8 code matrices of the quantized FlowLM step GEMMs: f32 weight pointer -> (codes, row scales)
   std::map<const float*, std::pair<const int8_t*, const float*>> q8map_;
@@ -216,10 +227,11 @@ class Engine {
   bool head_uniform_stride() const;  // ResBlock tensors at one stride (k_flow_head, its packing)
   bool use_head_chain(int B) const;
   float* fhw_ = nullptr;  // the chain's matrices in fragment order (pack_flow_head, at finalize)
-  float* hx_ = nullptr;   // flow-head hand-off regions [lsd * 13][roundup(B, 16)][512] (k_flow_head)
+  float* hx_ = nullptr;   // flow-head hand-off regions [cap * 13][roundup(B, 16)][512] (k_flow_head)
   float* fhm_ = nullptr;  // adaLN shift / scale in k_flow_head's fragment order (FlowHeadArgs::fhm)
   float* fh_inw_t_ = nullptr;  // flow-head input projection transposed [32][512] (x0 side job)
-  size_t hx_floats(int B) const { return (size_t)lsd_ * 13 * ((B + 15) / 16 * 16) * FD; }
+  size_t hx_floats(int B) const { return hx_floats(B, lsd_); }
+  size_t hx_floats(int B, int lsd) const { return (size_t)lsd * 13 * ((B + 15) / 16 * 16) * FD; }
   float* inw_t_ = nullptr;  // input_linear weight transposed, [32][1024] (k_input_ln)
   int *hctr_ = nullptr, *herr_ = nullptr;
   float *mx_ = nullptr, *mh_ = nullptr, *mq_ = nullptr, *mo_ = nullptr, *mqkv_ = nullptr, *mu_ = nullptr;

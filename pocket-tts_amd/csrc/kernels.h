@@ -21,8 +21,9 @@ enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_ELU = 3 };
 // ---------------------------------------------------------------------------------------------
 // Row reduce / epilogue of a split-K GEMM, fused with residual, gate, LayerNorm and modulate:
 //   v = sum_z P[z][m][n] (+bias[n]) ; v = act(v) ; v *= gate[m][n] ; v += R[m][n] ;
-//   Y[m][n] = v ; (euler) cur[m][n] += v*euler_scale
+//   Y[m][n] = v ; (euler) cur[m][n] += v / n_m while euler_step < n_m (n_m: row m's lsd count)
 //   if ln: h = LN(v)*w+b (or non-affine) ; h = h*(1+mscale[m][n]) + mshift[m][n] ; H[m][n] = h
+struct SlotState;
 struct RowReduceArgs {
   const float* P;
   int S, M, N;
@@ -35,8 +36,11 @@ struct RowReduceArgs {
   float* Y;  // [M][ldy] or nullptr
   long ldy;
   float* Y2;  // also store elu(v) here ([M][ldy]), or nullptr (SEANet dual raw / ELU'd output)
-  float* euler;  // cur [M][32]: cur += v * euler_scale (N must be 32)
-  float euler_scale;
+  // cur [M][32] (N must be 32): Euler step euler_step of the flow head. Row m takes euler_st[m].lsd
+  // steps of size 1 / lsd: cur += v / lsd while euler_step < lsd, cur kept (a select) from then on
+  float* euler;
+  const SlotState* euler_st;
+  int euler_step;
   // LayerNorm of the final row (N <= 1024)
   int ln;
   const float* ln_w;
@@ -279,6 +283,8 @@ struct SlotState {
   int frames_after_eos, max_frames;
   float temp, eos_threshold, noise_clamp;
   unsigned long long seed;
+  // the row's LSD Euler step count, 1 .. the engine's cap (0: a closed row; read as 1)
+  int lsd;
 };
 struct FrameFlags {
   int valid;  // the front produced a frame for this row at this step
@@ -286,22 +292,28 @@ struct FrameFlags {
 };
 
 // After the cond_embed|out_eos split-K GEMM: c = sum + b, eos logit -> eos_out,
-// y_s = silu(temb[s] + c) for each lsd step, x0 noise -> cur (reads SlotState only).
+// y_s = silu(temb_n[min(s, n - 1)] + c) for each of the launch's lsd_run Euler steps, n = the
+// row's own step count (SlotState::lsd, clamped to [1, lsd_cap]); x0 noise -> cur (reads SlotState
+// only). temb holds the time embeddings of every count 1 .. lsd_cap, triangular: the rows of
+// count n start at row temb_row0(n).
 constexpr int FLOW_COND_MAX_SLABS = 16;  // k_flow_cond's unrolled slab loads
-void flow_cond(const float* P, int S, int B, const float* bias, const float* temb, int lsd_steps,
+constexpr int temb_row0(int n) { return n * (n - 1) / 2; }
+void flow_cond(const float* P, int S, int B, const float* bias, const float* temb, int lsd_run, int lsd_cap,
                const SlotState* st, float* ysilu, float* cur, float* eos_out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Flow-head chain (mlp.rs:146-213,370-383; flow_lm.rs:7-22) in one persistent launch: per lsd
 // step, x = cur W_in^T + b_in; 6 ResBlocks x += gate * (silu(mod(LN(x)) W0^T + b0) W2^T + b2);
-// cur += (mod(LN_noaffine(x)) W_f^T + b_f) / lsd. mods [lsd][B][ldm] holds the adaLN shift |
+// cur += (mod(LN_noaffine(x)) W_f^T + b_f) / n_row while the step index < n_row, the row's own
+// count (st[row].lsd <= lsd; every row runs all lsd steps of the launch, a finished row keeps its
+// cur). mods [lsd][B][ldm] holds the adaLN shift |
 // scale | gate of each block and the final shift | scale (mlp.rs:322-368). xp/up: [B][512]
 // hand-off buffers; ctr: 4*ceil(B/16)+1 ints, zero before the first launch (the kernel re-arms
 // them); err: set to 1 if a hand-off wait timed out. Requires 1 <= B <= 128 (flow_head_fits).
 constexpr int FH_D = 512, FH_L = 32, FH_DEPTH = 6;
 struct FlowHeadArgs {
-  int B, lsd;
-  float euler_scale;
+  int B, lsd;  // lsd: Euler steps of this launch (launch-uniform; >= every row's own count)
+  const SlotState* st;  // per row: its own count (SlotState::lsd)
   float* cur;
   const float* mods;
   long ldm;

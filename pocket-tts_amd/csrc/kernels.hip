@@ -2357,9 +2357,11 @@ __device__ __forceinline__ void rr_store(const RowReduceArgs& a, int m, int n, f
   if (a.Y2) *reinterpret_cast<float4*>(a.Y2 + (long)m * a.ldy + n) = make_float4(elu1(v.x), elu1(v.y), elu1(v.z), elu1(v.w));
   if (a.euler) {
     float4* e = reinterpret_cast<float4*>(a.euler + (long)m * 32 + n);
-    const float sc = a.euler_scale;
-    float4 c = *e;
-    *e = make_float4(c.x + v.x * sc, c.y + v.y * sc, c.z + v.z * sc, c.w + v.w * sc);
+    const int nr = max(a.euler_st[m].lsd, 1);
+    const float sc = 1.0f / (float)nr;
+    const float4 c = *e;
+    const float4 nx = make_float4(c.x + v.x * sc, c.y + v.y * sc, c.z + v.z * sc, c.w + v.w * sc);
+    *e = a.euler_step < nr ? nx : c;  // a row past its own count keeps its latent
   }
 }
 // LayerNorm (+affine) (+modulate) of one row value quad, given the row mean and 1/den
@@ -3186,8 +3188,8 @@ __device__ float normal_at(unsigned long long seed, int step, int k, int attempt
 }
 
 __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B, const float* bias, const float* temb,
-                                                   int lsd, const SlotState* st, float* ysilu, float* cur,
-                                                   float* eos_out) {
+                                                   int lsd, int lsd_cap, const SlotState* st, float* ysilu,
+                                                   float* cur, float* eos_out) {
   front_prio();
   const int b = blockIdx.x, tid = threadIdx.x;
   const int NC = 513;  // cond_embed (512) | out_eos (1)
@@ -3206,6 +3208,9 @@ __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B,
   const float temp = ss.temp, clamp = ss.noise_clamp;
   const unsigned long long seed = ss.seed;
   const int step = ss.step;
+  // the row's own Euler step count: its time embeddings are rows temb_row0(n) .. + n - 1
+  const int nrow = min(max(ss.lsd, 1), lsd_cap);
+  const float* tn = temb + (long)temb_row0(nrow) * 512;
   const float b0 = bias[tid], b1 = bias[tid + 256], be = bias[512];
   float c0 = 0.f, c1 = 0.f, e = 0.f;
 #pragma unroll
@@ -3217,9 +3222,10 @@ __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B,
     }
   c0 += b0;
   c1 += b1;
-  for (int s = 0; s < lsd; ++s) {
-    ysilu[((long)s * B + b) * 512 + tid] = silu(temb[s * 512 + tid] + c0);
-    ysilu[((long)s * B + b) * 512 + tid + 256] = silu(temb[s * 512 + tid + 256] + c1);
+  for (int s = 0; s < lsd; ++s) {  // steps past the row's count repeat its last (finite, unused)
+    const int ts = min(s, nrow - 1);
+    ysilu[((long)s * B + b) * 512 + tid] = silu(tn[ts * 512 + tid] + c0);
+    ysilu[((long)s * B + b) * 512 + tid + 256] = silu(tn[ts * 512 + tid + 256] + c1);
   }
   if (tid == 0) eos_out[b] = e + be;  // out_eos logit (flow_lm.rs:139-145); the EOS rule runs in front_commit
   if (tid < 32) {
@@ -3237,10 +3243,12 @@ __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B,
   }
 }
 
-void flow_cond(const float* P, int S, int B, const float* bias, const float* temb, int lsd_steps,
+void flow_cond(const float* P, int S, int B, const float* bias, const float* temb, int lsd_run, int lsd_cap,
                const SlotState* st, float* ysilu, float* cur, float* eos_out, hipStream_t s) {
   if (S < 1 || S > FLOW_COND_MAX_SLABS) throw std::runtime_error("flow_cond: 1..16 split-K slabs");
-  hipLaunchKernelGGL(k_flow_cond, dim3(B), dim3(256), 0, s, P, S, B, bias, temb, lsd_steps, st, ysilu, cur, eos_out);
+  if (lsd_run < 1 || lsd_run > lsd_cap) throw std::runtime_error("flow_cond: lsd_run outside [1, cap]");
+  hipLaunchKernelGGL(k_flow_cond, dim3(B), dim3(256), 0, s, P, S, B, bias, temb, lsd_run, lsd_cap, st, ysilu, cur,
+                     eos_out);
 }
 
 // =============================================================================================
@@ -4177,6 +4185,11 @@ __global__ __launch_bounds__(64 * FH_WAVES) void k_flow_head(FlowHeadArgs a) {
   const int crow = min(orow, a.B - 1);
   const bool ostore = orow < a.B;
   const bool fin = cg < FH_L / 16;  // column groups 0 and 1 own the 32 latent columns
+  // the epilogue row's own Euler step count and step size (wave 0 of the latent column groups),
+  // loaded here with the launch's first operands: nothing of it waits behind a sweep. The step
+  // loop's trip count stays a.lsd for every row (the hand-offs need every workgroup in every phase).
+  const int n_row = fin && wave == 0 ? max(a.st[crow].lsd, 1) : 1;
+  const float e_row = 1.0f / (float)n_row;
   const __amdgpu_buffer_rsrc_t hr = fh_rsrc(a.hx), cr = fh_rsrc(a.cur);
   int* cc = a.ctr + 4 * rg + 2;  // cur published (lsd > 1)
   const int rstride = RG * 16 * FH_D * 4;  // bytes per hand-off region
@@ -4304,9 +4317,11 @@ __global__ __launch_bounds__(64 * FH_WAVES) void k_flow_head(FlowHeadArgs a) {
       const float4 r = fh_gemm(v, p0.w, s_red2[gi++ & 1], wave, c, G, lane);
       if (wave != 0 && more) load_ln_ops(p0, nmods, 0, st + 1);
       if (wave == 0) {
-        const float e = a.euler_scale;
+        const float e = e_row;
         const float4 o = f4add(r, p0.e0);
-        if (ostore) fh_st(cr, off, make_float4(cv.x + o.x * e, cv.y + o.y * e, cv.z + o.z * e, cv.w + o.w * e));
+        const float4 nx = make_float4(cv.x + o.x * e, cv.y + o.y * e, cv.z + o.z * e, cv.w + o.w * e);
+        // a row past its own count keeps its latent (a select: the discarded update may be non-finite)
+        if (ostore) fh_st(cr, off, st < n_row ? nx : cv);
         if (more) fh_publish(cc);
         FH_STAMP();
         if (more) {

@@ -21,6 +21,10 @@ class GenerationParams:
     frames_after_eos: int = 3
     max_frames: int = 250
     seed: int = 0
+    # the utterance's own LSD Euler step count (TTSModel.lsd_decode_steps, the server's lsd_steps),
+    # 1 .. the engine's cap; None: the engine's lsd_decode_steps. Not part of ptts_gen_params: the
+    # admission passes it beside the struct (ptts_slot_open_ex).
+    lsd_steps: int | None = None
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
@@ -79,8 +83,12 @@ class Engine:
                  seed: int = 0x5EED, weights_path: str | None = None, weight_blob: int | None = None,
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
-                 back_mfma: int | None = None):
-        """pipeline=True: overlapped stepping, each step() returns the frame produced by the
+                 back_mfma: int | None = None, max_lsd_steps: int | None = None):
+        """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
+        max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
+        ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
+        counts share one batched step (lsd_steps()).
+        pipeline=True: overlapped stepping, each step() returns the frame produced by the
         previous call (see ptts_engine_config.pipeline). weight_quant: QUANT_NONE / QUANT_FLOW_LM /
         QUANT_ALL, the reference's simulated int8 weight quantization (quantize.rs), with the
         FlowLM step GEMMs streaming int8 codes. fp8_gemm=True: the large FlowLM step GEMMs run as
@@ -95,7 +103,10 @@ class Engine:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
             raise ValueError("back_bf16=True contradicts back_mfma=%d (pass one of them)" % back_mfma)
-        cfg = EngineConfig(device, max_slots, max_ctx, lsd_decode_steps, seed,
+        cap = int(lsd_decode_steps if max_lsd_steps is None else max_lsd_steps)
+        if not 1 <= int(lsd_decode_steps) <= cap:
+            raise ValueError(f"lsd_decode_steps {lsd_decode_steps} outside [1, max_lsd_steps = {cap}]")
+        cfg = EngineConfig(device, max_slots, max_ctx, cap, seed,
                            weights_path.encode() if weights_path else None,
                            weight_blob or None, int(defer_weights), int(pipeline), int(weight_quant),
                            int(fp8_gemm), cfg_yaml.encode() if cfg_yaml else None, int(back_frames),
@@ -106,7 +117,8 @@ class Engine:
         self.weight_quant = int(weight_quant)
         self.max_slots = max_slots
         self.max_ctx = max_ctx
-        self.lsd_decode_steps = lsd_decode_steps
+        self.lsd_decode_steps = int(lsd_decode_steps)
+        self.max_lsd_steps = cap
         self.pipeline = bool(pipeline)
         self.back_frames = int(back_frames) if pipeline else 1
         self.back_mfma = int(back_mfma)
@@ -122,6 +134,16 @@ class Engine:
         y = np.empty((splits, m, n) if splits > 1 else (m, n), np.float32)
         check(lib().ptts_test_gemm(self.handle, layout, m, n, k, splits, tail_slices, fptr(x), fptr(w), fptr(y)))
         return y
+
+    def lsd_steps(self) -> tuple[int, int]:
+        """(cap, last_run): the cap on the per-utterance Euler step counts, and the steps the most
+        recent step call ran: the largest count among its rows still open (ptts_lsd_steps)."""
+        cap, run = C.c_int(0), C.c_int(0)
+        check(lib().ptts_lsd_steps(self.handle, C.byref(cap), C.byref(run)))
+        return int(cap.value), int(run.value)
+
+    def _row_lsd(self, params: GenerationParams) -> int:
+        return int(self.lsd_decode_steps if params.lsd_steps is None else params.lsd_steps)
 
     def frame_lag(self) -> tuple[int, int]:
         """(lag, admit_delay): a frame arrives `lag` calls after the call that computed it; the
@@ -232,11 +254,11 @@ class Engine:
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
-        check(lib().ptts_slot_open(self.handle, slot, voice.handle, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
-                                   C.byref(cp)))
+        check(lib().ptts_slot_open_ex(self.handle, slot, voice.handle, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
+                                      C.byref(cp), self._row_lsd(params)))
 
     def open_many(self, slots, voices, ids_list, params_list):
-        """Batched admission (ptts_slots_open): row slots[i] <- (voices[i], ids_list[i], params_list[i])."""
+        """Batched admission (ptts_slots_open_ex): row slots[i] <- (voices[i], ids_list[i], params_list[i])."""
         n = len(slots)
         sl = np.ascontiguousarray(np.asarray(slots, np.int32))
         arrs = [np.asarray(x, np.int32).reshape(-1) for x in ids_list]
@@ -244,9 +266,10 @@ class Engine:
         cat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int32))
         vh = (C.c_void_p * n)(*[v.handle for v in voices])
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
+        lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
-        check(lib().ptts_slots_open(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                    nid.ctypes.data_as(i32), ps))
+        check(lib().ptts_slots_open_ex(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                       nid.ctypes.data_as(i32), ps, lsd.ctypes.data_as(i32)))
 
     def close_slot(self, slot: int):
         check(lib().ptts_slot_close(self.handle, slot))
@@ -330,6 +353,21 @@ class Engine:
         return [(int(self._pv_slots[i]), self._pv_pcm[i].copy()) for i in range(n.value)]
 
     def generate(self, slot: int, voice: Voice, ids, params: GenerationParams) -> np.ndarray:
+        if self._row_lsd(params) != self.max_lsd_steps:
+            # ptts_generate admits at the engine's cap: its loop here, over an admission at the row's count
+            self.open(slot, voice, ids, params)
+            lag, delay = self.frame_lag()
+            frames = []
+            for it in range(params.max_frames + lag + delay):
+                r = self.step(slot + 1)
+                if not r.valid[slot]:
+                    if it < lag + delay:
+                        continue
+                    break
+                frames.append(r.pcm[slot].copy())
+                if r.last[slot]:
+                    break
+            return np.concatenate(frames) if frames else np.zeros(0, np.float32)
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cap = params.max_frames * FRAME
         out = np.zeros(cap, np.float32)

@@ -20,7 +20,9 @@ packed once and broadcast over RCCL at load time).
 HTTP (`create_app`, FastAPI; routes of pocket-tts-cli/src/server/routes.rs:20-30):
   GET  /health             {"status": "healthy", "version": ...}
   POST /generate           JSON {text | token_ids, voice?, temperature?, eos_threshold?,
-                           noise_clamp?, lsd_steps?} -> audio/wav (handlers.rs:128-213)
+                           noise_clamp?, lsd_steps?} -> audio/wav (handlers.rs:128-213);
+                           lsd_steps: this request's own Euler step count, 1 .. --max-lsd-steps
+                           (requests with different counts share the batch)
   POST /stream             same body -> chunked 16-bit PCM LE (handlers.rs:215-310): the first
                            frame as soon as it exists, later frames coalesced to at most one
                            chunk per 20 ms per stream
@@ -476,13 +478,18 @@ class TTSService:
 
     def __init__(self, scheduler, voices: dict[str, Voice | Sequence[Voice]], default_voice: str,
                  tokenizer: Callable[[str], Sequence[int]] | None = None, temp: float = 0.7,
-                 eos_threshold: float = -4.0, noise_clamp: float | None = None, lsd_decode_steps: int = 1):
+                 eos_threshold: float = -4.0, noise_clamp: float | None = None, lsd_decode_steps: int = 1,
+                 max_lsd_steps: int | None = None):
+        """lsd_decode_steps: the Euler step count of a request that names none (the engine's own
+        default). max_lsd_steps: the largest `lsd_steps` a request may ask for, the engine's cap
+        (None: lsd_decode_steps, so any other value is refused)."""
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
         self.tokenizer = tokenizer
         self.temp, self.eos_threshold, self.noise_clamp = temp, eos_threshold, noise_clamp
         self.lsd_decode_steps = lsd_decode_steps
+        self.max_lsd_steps = lsd_decode_steps if max_lsd_steps is None else max_lsd_steps
         self._seed = 0
         self._lock = threading.Lock()
 
@@ -490,8 +497,9 @@ class TTSService:
                 temperature: float | None = None, eos_threshold: float | None = None,
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None) -> Request:
-        if lsd_steps is not None and lsd_steps != self.lsd_decode_steps:
-            raise ValueError(f"lsd_steps is fixed at engine creation ({self.lsd_decode_steps})")
+        if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
+            raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
+                             f"the default is {self.lsd_decode_steps}")
         if token_ids is not None:  # extension: ids carry no word count, the client states it
             ids = np.asarray(token_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
@@ -515,7 +523,8 @@ class TTSService:
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
                              eos_threshold=self.eos_threshold if eos_threshold is None else eos_threshold,
                              noise_clamp=self.noise_clamp if noise_clamp is None else noise_clamp,
-                             frames_after_eos=fae, max_frames=mgl, seed=seed)
+                             frames_after_eos=fae, max_frames=mgl, seed=seed,
+                             lsd_steps=None if lsd_steps is None else int(lsd_steps))
         return self.scheduler.submit(ids, self.voices[name], p)  # MultiGpuScheduler: one voice per GPU
 
 
@@ -764,7 +773,7 @@ def _worker_engine(args, Engine):
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     kw = dict(max_slots=args.slots, max_ctx=args.max_ctx, weights_path=args.weights, pipeline=True,
-              back_frames=args.back_frames)
+              back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -821,6 +830,11 @@ def main(argv=None):
     ap.add_argument("--back-frames", type=int, default=2, choices=(1, 2, 4, 8),
                     help="frames per Mimi decode pass (ptts_engine_config.back_frames): 2, the throughput "
                          "configuration bench.py measures (two more calls of frame lag, ~1.2 ms at B = 32)")
+    ap.add_argument("--lsd-steps", type=int, default=1,
+                    help="LSD Euler steps of a request that names none (TTSModel.lsd_decode_steps)")
+    ap.add_argument("--max-lsd-steps", type=int, default=None,
+                    help="largest per-request lsd_steps (the engine's cap; default: --lsd-steps). Requests with "
+                         "different counts share the batch; a step costs the largest count among its open rows")
     ap.add_argument("--preview-rows", type=int, default=8,
                     help="first-frame previews: rows per call whose first frame is decoded at once (0: off)")
     ap.add_argument("--stand-in-engine", action="store_true",
@@ -870,7 +884,8 @@ def main(argv=None):
         raise SystemExit("at least one --voice NAME=path is required")
     scheduler = BatchScheduler(engine, preview_rows=args.preview_rows)
     service = TTSService(scheduler, voices, default_voice=next(iter(voices)),
-                         tokenizer=load_tokenizer(args.tokenizer) if args.tokenizer else None)
+                         tokenizer=load_tokenizer(args.tokenizer) if args.tokenizer else None,
+                         lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps)
     service.worker = {"rank": rank, "world": world, "pid": os.getpid(), "weights_checksum": checksum}
     socks = [_listen_socket(args.host, args.port)]
     board = None

@@ -3,7 +3,9 @@ running the generation hot path through the HIP engine.
 
 Reference surface kept:
   * `TTSModel.load / load_with_params`, public fields `temp`, `lsd_decode_steps`,
-    `eos_threshold`, `noise_clamp`, `sample_rate`, `voice_prompt_chunk_frames` (:22-49, :417);
+    `eos_threshold`, `noise_clamp`, `sample_rate`, `voice_prompt_chunk_frames` (:22-49, :417), all
+    live: each segment is generated with the values the fields hold when it starts
+    (`lsd_decode_steps` up to the engine's cap, `max_lsd_decode_steps` at load);
   * voices: `get_voice_state` (:446-463), `get_voice_state_from_bytes` (:428-444),
     `get_voice_state_from_tensor` (:504-577), `get_voice_state_from_prompt_file / _bytes /
     _tensor` (:465-501). WAV decode on the host (audio.py), resampling and the Mimi encoder on
@@ -68,15 +70,17 @@ class TTSModel:
                          eos_threshold: float = -4.0, noise_clamp: float | None = None, *,
                          weights_path: str | None = None, tokenizer_path: str | None = None, seed: int = 0x5EED,
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
-                         weight_quant: int = QUANT_NONE) -> "TTSModel":
-        """weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
+                         weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None) -> "TTSModel":
+        """max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
+        (the engine's cap; None: lsd_decode_steps itself, the field can then only be lowered).
+        weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
         from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
             tokenizer = load_tokenizer(tokenizer_path)
         eng = Engine(device=device, max_slots=1, max_ctx=max_ctx, lsd_decode_steps=lsd_decode_steps, seed=seed,
-                     weights_path=weights_path, weight_quant=weight_quant)
+                     weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -163,9 +167,13 @@ class TTSModel:
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int
                  ) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0."""
-        if self.lsd_decode_steps != self.engine.lsd_decode_steps:
-            raise ValueError("lsd_decode_steps is fixed at engine creation")
-        self.engine.open(0, voice_state, ids, self._params(max_frames, frames_after_eos))
+        cap = self.engine.max_lsd_steps
+        if not 1 <= int(self.lsd_decode_steps) <= cap:
+            raise ValueError(f"lsd_decode_steps {self.lsd_decode_steps} outside [1, {cap}], the engine's cap "
+                             "(max_lsd_decode_steps at load)")
+        params = self._params(max_frames, frames_after_eos)
+        params.lsd_steps = int(self.lsd_decode_steps)
+        self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
         while True:
