@@ -220,6 +220,31 @@ int ptts_resample_ex(ptts_engine* e, const float* x, int n_samples, int sr_from,
  * ptts_voice_from_audio_ex(..., PTTS_RESAMPLE_POLY, out). */
 int ptts_voice_from_audio_ex(ptts_engine* e, const float* samples, int n_samples, int sample_rate, int chunk_frames,
                              int resampler, ptts_voice** out);
+/* Voice jobs: the clones above without draining the step pipeline. A job runs on a
+ * stream of the engine's own (lowest priority) with a workspace of its own, in submission order;
+ * admission is ordered behind it on the GPU by an event, with no host wait. */
+#define PTTS_SAMPLES_F32 0
+#define PTTS_SAMPLES_S16 1
+/* Enqueue a clone of a mono clip on the engine's voice stream and return at once. *out is usable in
+ * ptts_slot_open / ptts_slots_open[_ex] immediately (the admission is ordered behind the job on the
+ * GPU). Same conditioning as ptts_voice_from_audio_ex on the same samples (int16 samples: v / 32768), bit
+ * for bit; the K/V prefix is equal up to the reduction order of the prefill's GEMMs (the job's
+ * split-K slabs and tail scratch are sized for its workspace, not for the engine's batch).
+ * Does not drain the step pipeline nor touch its buffers. `samples` is read before the call returns. All
+ * arguments are checked before anything is enqueued: a rejected job leaves *out NULL. */
+int ptts_voice_job_start(ptts_engine* e, const void* samples, int n_samples, int sample_format,
+                         int sample_rate, int chunk_frames, int resampler, ptts_voice** out);
+/* The same for a precomputed audio_prompt [n_frames x 1024] (get_voice_state_from_prompt_tensor). */
+int ptts_voice_job_start_prompt(ptts_engine* e, const float* prompt, int n_frames, ptts_voice** out);
+/* *ready = 1 once the voice's job has run (always 1 for a synchronously made voice and for a NULL
+ * voice, which has no job); wait = 1 blocks until then. A NULL `ready` is PTTS_ERR_INVALID.
+ * ptts_voice_len is valid as soon as the job is started; ptts_voice_conditioning and
+ * ptts_voice_destroy wait for the job. */
+int ptts_voice_ready(const ptts_voice* v, int wait, int* ready);
+/* Pre-size the voice workspace for clips of up to max_frames frames (< max_ctx). Without it the
+ * workspace is allocated at the first job and grows when a longer clip arrives (the voice stream,
+ * never the step pipeline, is synchronized then). */
+int ptts_voice_jobs_reserve(ptts_engine* e, int max_frames);
 /* Conditioning rows the voice holds (frames). */
 int ptts_voice_len(const ptts_voice* v);
 /* The [n_frames x 1024] conditioning a PCM voice was built from (host copy); for tests. */

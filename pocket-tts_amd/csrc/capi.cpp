@@ -217,13 +217,54 @@ int ptts_test_gemm(ptts_engine* e, int layout, int m, int n, int k, int splits, 
   return guard([&] { eng(e).test_gemm(layout, m, n, k, splits, tail_slices, x, w, y); });
 }
 
+int ptts_voice_job_start(ptts_engine* e, const void* samples, int n_samples, int sample_format, int sample_rate,
+                         int chunk_frames, int resampler, ptts_voice** out) {
+  return guard([&] {
+    if (!out) throw ptts::Error(PTTS_ERR_INVALID, "null out");
+    *out = nullptr;
+    *out = eng(e).voice_job_audio(samples, n_samples, sample_format, sample_rate, chunk_frames, resampler);
+  });
+}
+
+int ptts_voice_job_start_prompt(ptts_engine* e, const float* prompt, int n_frames, ptts_voice** out) {
+  return guard([&] {
+    if (!out) throw ptts::Error(PTTS_ERR_INVALID, "null out");
+    *out = nullptr;
+    *out = eng(e).voice_job_prompt(prompt, n_frames);
+  });
+}
+
+int ptts_voice_ready(const ptts_voice* v, int wait, int* ready) {
+  return guard([&] {
+    if (!ready) throw ptts::Error(PTTS_ERR_INVALID, "null argument");
+    *ready = 1;  // no voice, or a synchronously made one: no job is pending
+    if (!v || !v->ev) return;
+    if (wait) {
+      PTTS_HIP(hipEventSynchronize(v->ev));
+      return;
+    }
+    const hipError_t q = hipEventQuery(v->ev);
+    if (q == hipErrorNotReady) *ready = 0;
+    else PTTS_HIP(q);
+  });
+}
+
+int ptts_voice_jobs_reserve(ptts_engine* e, int max_frames) {
+  return guard([&] { eng(e).voice_jobs_reserve(max_frames); });
+}
+
 int ptts_voice_len(const ptts_voice* v) { return v ? v->F : 0; }
 
 int ptts_voice_conditioning(const ptts_voice* v, float* out, int max_rows) {
   return guard([&] {
     if (!v || !out) throw ptts::Error(PTTS_ERR_INVALID, "null argument");
-    if (v->cond.empty()) throw ptts::Error(PTTS_ERR_STATE, "voice was not built from PCM");
+    if (v->cond.empty() && !v->h_cond) throw ptts::Error(PTTS_ERR_STATE, "voice was not built from PCM");
     const int rows = std::min(max_rows, v->F);
+    if (v->h_cond) {  // a voice job's: its event covers the copy into the pinned rows
+      PTTS_HIP(hipEventSynchronize(v->ev));
+      memcpy(out, v->h_cond, sizeof(float) * rows * ptts::D);
+      return;
+    }
     memcpy(out, v->cond.data(), sizeof(float) * rows * ptts::D);
   });
 }

@@ -177,6 +177,10 @@ Engine::Engine(const ptts_engine_config& cfg) {
   partial_ = dalloc(pcap_);
   tslab_ = dalloc(TAIL_CAP);
   tickets_ = (int*)dalloc(TICKETS);  // zero; every split-tail launch leaves them zero
+  fbm_.x = x_, fbm_.h = h_, fbm_.q = q_, fbm_.o = o_, fbm_.u = u_, fbm_.partial = partial_;
+  fbm_.pcap = pcap_, fbm_.tslab = tslab_, fbm_.tail_cap = (long)TAIL_CAP, fbm_.tickets = tickets_;
+  fbm_.kv = KvStore{kv_, kv_slot_, max_ctx_};
+  fbm_.kv_layer = kv_layer_;
   ids_dev_ = (int*)dalloc(PREFILL);
   rowtab_dev_ = (int*)dalloc(PREFILL);
   ctab_dev_ = (int*)dalloc(PREFILL);
@@ -295,6 +299,7 @@ Engine::~Engine() {
   if (stream_) (void)hipStreamSynchronize(stream_);
   if (stream_be_) (void)hipStreamSynchronize(stream_be_);
   if (stream_pv_) (void)hipStreamSynchronize(stream_pv_);
+  if (stream_vc_) (void)hipStreamSynchronize(stream_vc_);  // pending voice jobs write their voices
 #ifdef PTTS_PROBES
   if (stamp_ring_) {  // tag (part << 8 | buffer << 1 | end), then the 100-MHz realtime count
     unsigned n = 0;
@@ -332,6 +337,13 @@ Engine::~Engine() {
   for (hipEvent_t e : ev_call_)
     if (e) (void)hipEventDestroy(e);
   if (stream_be_) (void)hipStreamDestroy(stream_be_);
+  vws_free();
+  if (vws_.up) (void)hipFree(vws_.up);
+  for (char* h : vws_.h_up)
+    if (h) (void)hipHostFree(h);
+  for (hipEvent_t e : vws_.ev_up)
+    if (e) (void)hipEventDestroy(e);
+  if (stream_vc_) (void)hipStreamDestroy(stream_vc_);
   for (void* p : allocs_) (void)hipFree(p);
   for (int q = 0; q < NHB; ++q) {
     if (h_pcm_[q]) (void)hipHostFree(h_pcm_[q]);
@@ -602,8 +614,12 @@ void Engine::finalize() {
 
 void Engine::run_ops(const std::vector<Op>& ops) {
   xh_dirty_ = true;  // eager passes (prefills, encoder) use x_ / h_ as scratch
+  run_ops_on(ops, stream_);
+}
+
+void Engine::run_ops_on(const std::vector<Op>& ops, hipStream_t s) {
   for (const Op& op : ops) {
-    op.fn(stream_);
+    op.fn(s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) throw Error(PTTS_ERR_HIP, "launch of " + op.name + " failed: " + hipGetErrorString(e));
   }
@@ -678,8 +694,9 @@ void Engine::derive_fp8() {
 
 // ------------------------------------------------------------------ op builders
 void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M,
-                          const float* Wt, int N, int K, int* S_out) {
+                          const float* Wt, int N, int K, int* S_out, const FlowBufs* fbp) {
   PTTS_REQUIRE(K % 32 == 0, "GEMM K must be a multiple of 32");
+  const FlowBufs& fb = fbp ? *fbp : fbm_;  // the slabs and the tail scratch the launch writes
   int S = pick_splits(M, N, K);
   int layout = 0, tail = 0;
   // wide skinny GEMMs (FlowLM qkv/ff1, flow-head adaLN): 32x128 LDS-DMA tiles, 8-way split-K
@@ -713,8 +730,8 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
     const uint32_t* q8 = gv->second.q8;
     const float* sc = gv->second.scale;
     const int Sg = K / g.ks();
-    PTTS_REQUIRE((size_t)Sg * M * N <= pcap_, "split-K partial buffer too small");
-    float* part = partial_;
+    PTTS_REQUIRE((size_t)Sg * M * N <= fb.pcap, "split-K partial buffer too small");
+    float* part = fb.partial;
     const bool f8 = fp8_ && q8;
     ops.push_back({name, [=](hipStream_t s) { gemv_splitk(X, ldx, M, N, K, P, g, part, s, q8, sc, f8); }, 2.0 * M * N * K,
                    (q8 ? 1.0 * N * K + 4.0 * N : 4.0 * N * K) + 4.0 * ((double)M * K + (double)Sg * M * N)});
@@ -739,8 +756,8 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
     while (S < 16 && tiles * S < 256 && (K / 32) / (2 * S) >= 4) S *= 2;
   }
   if (!w8 && !wf8) tile_override(name, layout, S);
-  while (S > 1 && (size_t)S * M * N > pcap_) --S;
-  PTTS_REQUIRE((size_t)S * M * N <= pcap_, "split-K partial buffer too small");
+  while (S > 1 && (size_t)S * M * N > fb.pcap) --S;
+  PTTS_REQUIRE((size_t)S * M * N <= fb.pcap, "split-K partial buffer too small");
   GemmArgs a{};
   if (w8) {
     a.Wq = q8->second.first;
@@ -761,12 +778,12 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
   a.ldx = ldx;
   a.W = Wt;
   a.S = S;
-  a.partial = partial_;
+  a.partial = fb.partial;
   if (tail > 0 && S == 1 && !w8 && !wf8) {
     a.tail_S = tail;
-    a.tail_slab = tslab_;
-    a.tail_cap = (long)TAIL_CAP;
-    a.tickets = tickets_;
+    a.tail_slab = fb.tslab;
+    a.tail_cap = fb.tail_cap;
+    a.tickets = fb.tickets;
     a.tickets_cap = TICKETS;
   }
   // FlowLM / flow-head step weights are read once per step: non-temporal loads on the LDS-DMA
@@ -886,18 +903,26 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
 
 // FlowLM transformer layers over M rows (x_ holds the residual stream, h_ = norm1_0(x_)).
 // StreamingTransformerLayer::forward (transformer.rs:66-90).
-void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag) {
+void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag,
+                         const FlowBufs* fbp) {
+  // the engine's own buffers (step and admission graphs), or a voice job's: the names below shadow
+  // the members on purpose, so every access in this function goes through the struct
+  const FlowBufs& fb = fbp ? *fbp : fbm_;
+  float *const x_ = fb.x, *const h_ = fb.h, *const q_ = fb.q, *const o_ = fb.o, *const u_ = fb.u,
+               *const partial_ = fb.partial;
+  PTTS_REQUIRE(!fbp || qg != 1, "step passes run on the engine's own buffers");
   for (int l = 0; l < NL; ++l) {
     const Layout::TL& t = L_.fl[l];
     const std::string p = tag + ".l" + std::to_string(l);
-    KvStore kv{kv_ + (long)l * kv_layer_, kv_slot_, max_ctx_};
-    if (share_voice_) {  // positions below a slot's voice length read the voice's own cache
+    KvStore kv = fb.kv;
+    kv.base += (long)l * fb.kv_layer;
+    if (!fbp && share_voice_) {  // positions below a slot's voice length read the voice's own cache
       kv.pre = vpre_;
       kv.pre_len = vlen_;
       kv.layer = l;
     }
     int S = 1;
-    linear_split(ops, p + ".qkv_gemm", h_, D, M, W(t.in_proj), 3 * D, D, &S);
+    linear_split(ops, p + ".qkv_gemm", h_, D, M, W(t.in_proj), 3 * D, D, &S, fbp);
     if (qg == 1) {  // step: slab sum + RoPE + KV append fused into the attention kernel
       const float* P = partial_;
       float* O = o_;
@@ -950,7 +975,7 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
       a.ldh = N;
       push_rr(ops, name, a);
     };
-    linear_split(ops, p + ".out_gemm", o_, D, M, W(t.out_proj), D, D, &S);
+    linear_split(ops, p + ".out_gemm", o_, D, M, W(t.out_proj), D, D, &S, fbp);
     // step passes with the whole-K linear1 (gemv_fk): the out reduce also stores norm2's output in
     // its A-fragment order, and linear1 applies GELU in its own epilogue (no slabs, no reduce)
     auto fk = qg == 1 && gemv_fk_supported(M, FF, D) ? fkmap_.find(W(t.l1)) : fkmap_.end();
@@ -992,10 +1017,10 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
         ops.push_back({p + ".ff1_gemm", [=](hipStream_t s) { gemv_fk(A, M, FF, Pk, nullptr, ACT_GELU, U, FF, s); },
                        2.0 * M * FF * D, 4.0 * ((double)FF * D + (double)M * D + (double)M * FF)});
       } else {
-        linear_split(ops, p + ".ff1_gemm", h_, D, M, W(t.l1), FF, D, &S);
+        linear_split(ops, p + ".ff1_gemm", h_, D, M, W(t.l1), FF, D, &S, fbp);
         rr(p + ".ff1_reduce_gelu", S, FF, ACT_GELU, false, u_, nullptr, nullptr, false, nullptr);
       }
-      linear_split(ops, p + ".ff2_gemm", u_, FF, M, W(t.l2), D, FF, &S);
+      linear_split(ops, p + ".ff2_gemm", u_, FF, M, W(t.l2), D, FF, &S, fbp);
     }
     if (l + 1 < NL)
       rr(p + ".ff2_reduce_ln1", S, D, ACT_NONE, true, x_, W(L_.fl[l + 1].n1w), W(L_.fl[l + 1].n1b), true, h_);
@@ -1005,16 +1030,16 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
 }
 
 // Prefill T rows already in x_ into slot `slot` at positions p0.. (tts_model.rs:580-599, 958-964).
-void Engine::prefill_rows(std::vector<Op>& ops, int slot, int T, int p0) {
+void Engine::prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs* fbp) {
   {
-    float* x = x_;
-    float* h = h_;
+    float* x = fbp ? fbp->x : x_;
+    float* h = fbp ? fbp->h : h_;
     const float* w = W(L_.fl[0].n1w);
     const float* b = W(L_.fl[0].n1b);
     ops.push_back({"prefill.ln1", [=](hipStream_t s) { layernorm(x, D, h, D, T, D, w, b, 1e-5f, s); }});
   }
   RowMap map{slot, T, p0, nullptr};
-  flow_layers(ops, T, map, 16, false, "prefill");
+  flow_layers(ops, T, map, 16, false, "prefill", fbp);
 }
 
 // The persistent flow-head launch needs <= 128 rows and ResBlock tensors at one uniform stride
@@ -2537,6 +2562,266 @@ ptts_voice* Engine::voice_from_audio(const float* pcm_in, int n_in, int sr, int 
   return v;
 }
 
+// ------------------------------------------------------------------ voice jobs
+// The same clone as voice_from_audio / voice_from_prompt, enqueued on stream_vc_ (lowest priority,
+// plain launches of non-persistent kernels) with a workspace of its own, so it neither drains nor
+// touches the step pipeline: no sync(), no allocation but the voice's own, nothing written outside
+// VoiceWs and the voice. The prompt prefill appends K/V straight into the voice's compact cache.
+// slots_open orders the front stream behind the job's event.
+namespace {
+size_t al16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+void free_voice(ptts_voice* v) {
+  if (v->ev) {  // a pending job still writes the cache and the pinned conditioning
+    (void)hipEventSynchronize(v->ev);
+    (void)hipEventDestroy(v->ev);
+  }
+  if (v->h_cond) (void)hipHostFree(v->h_cond);
+  if (v->kv) (void)hipFree(v->kv);
+  delete v;
+}
+}  // namespace
+
+void Engine::vws_free() {
+  VoiceWs& w = vws_;
+  for (void* p : w.allocs) (void)hipFree(p);
+  w.allocs.clear();
+  w.frames = 0;
+}
+
+// Grow-only. A longer clip (or a larger upload) than any before re-allocates, after the jobs
+// already queued have run: the only point at which the voice stream is synchronized.
+void Engine::vws_reserve(int frames, size_t host_bytes, size_t up_bytes) {
+  VoiceWs& w = vws_;
+  if (!stream_vc_) {
+    int least = 0, greatest = 0;
+    PTTS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    PTTS_HIP(hipStreamCreateWithPriority(&stream_vc_, hipStreamNonBlocking, least));
+    for (hipEvent_t& e : w.ev_up) PTTS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (frames <= w.frames && host_bytes <= w.h_bytes && up_bytes <= w.up_bytes) return;
+  PTTS_HIP(hipStreamSynchronize(stream_vc_));
+  if (host_bytes > w.h_bytes) {  // the two pinned staging blocks
+    for (char*& h : w.h_up)
+      if (h) (void)hipHostFree(h), h = nullptr;
+    w.h_bytes = 0;
+    for (char*& h : w.h_up) PTTS_HIP(hipHostMalloc((void**)&h, host_bytes, hipHostMallocDefault));
+    w.h_bytes = host_bytes;
+  }
+  if (up_bytes > w.up_bytes) {  // the device block: the upload, then the converted clip (rubato rule)
+    if (w.up) (void)hipFree(w.up);
+    w.up = nullptr;
+    w.up_bytes = 0;
+    PTTS_HIP(hipMalloc((void**)&w.up, up_bytes));
+    w.up_bytes = up_bytes;
+  }
+  if (frames <= w.frames) return;
+  vws_free();
+  auto alloc = [&](size_t cnt) {
+    void* p = nullptr;
+    PTTS_HIP(hipMalloc(&p, std::max<size_t>(cnt, 1) * sizeof(float)));
+    w.allocs.push_back(p);
+    return (float*)p;
+  };
+  try {
+    const size_t Fc = (size_t)frames, Np = Fc * FRAME, Te = Fc * 16;
+    w.pcm = alloc(Np);
+    w.A = alloc(Np * 64);
+    w.Bf = alloc(Np * 64);
+    w.V = alloc(Np * 32);
+    w.zeros = alloc(16 * 512);
+    w.eh = alloc(Te * MD);
+    w.eqkv = alloc(Te * 3 * MD);
+    w.eq = alloc(Te * MD);
+    w.eo = alloc(Te * MD);
+    w.eu = alloc(Te * MFF);
+    w.ering = alloc((size_t)MNL * 2 * MNH * Te * 64);
+    w.Hd = alloc(Fc * 16 * 512);  // one replicated row block per chunk, chunks of >= 1 frame
+    w.lat = alloc(Fc * 512);
+    const size_t R = (Fc + 15) / 16 * 16, Rp = std::min<size_t>(R, PREFILL);
+    FlowBufs& b = w.fb;
+    b.x = alloc(R * D);  // the conditioning rows (the speaker projection's output), then the residual stream
+    w.cond = b.x;
+    b.h = alloc(Rp * D);
+    b.q = alloc(Rp * D);
+    b.o = alloc(Rp * D);
+    b.u = alloc(Rp * FF);
+    // the slabs of a pass of < 256 rows, or the one [rows][FF] block of a longer one (linear_split)
+    b.pcap = std::max((size_t)4 << 20, Rp * FF);
+    b.partial = alloc(b.pcap);
+    // split-tail scratch of the passes of >= 256 rows: at most 64 N tiles per 128 rows, 4 slices
+    b.tail_cap = Fc < 256 ? 0 : (long)std::min<size_t>(TAIL_CAP, (Fc + 127) / 128 * 64 * 4 * 128 * 64);
+    b.tslab = alloc((size_t)b.tail_cap);
+    b.tickets = (int*)alloc(TICKETS);
+    PTTS_HIP(hipMemsetAsync(w.zeros, 0, sizeof(float) * 16 * 512, stream_vc_));
+    PTTS_HIP(hipMemsetAsync(b.tickets, 0, sizeof(int) * TICKETS, stream_vc_));  // every launch leaves them zero
+    w.frames = frames;
+  } catch (...) {
+    vws_free();
+    throw;
+  }
+}
+
+void Engine::voice_jobs_reserve(int max_frames) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(max_frames >= 1 && max_frames < max_ctx_, "max_frames must be in [1, max_ctx)");
+  PTTS_HIP(hipSetDevice(dev_));
+  // uploads of float32 clips at up to twice the model's rate, plus the resampler's tables
+  const size_t up = al16((size_t)max_frames * FRAME * 2 * sizeof(float)) + (64 << 10);
+  vws_reserve(max_frames, up, up);
+}
+
+ptts_voice* Engine::voice_job_new(int F, bool pcm) {
+  ptts_voice* v = new ptts_voice();
+  v->F = F;
+  v->owner = this;
+  try {
+    PTTS_HIP(hipMalloc(&v->kv, sizeof(float) * (size_t)NL * 2 * NH * F * 64));
+    if (pcm) PTTS_HIP(hipHostMalloc((void**)&v->h_cond, sizeof(float) * (size_t)F * D, hipHostMallocDefault));
+    PTTS_HIP(hipEventCreateWithFlags(&v->ev, hipEventDisableTiming));
+  } catch (...) {
+    free_voice(v);
+    throw;
+  }
+  return v;
+}
+
+void Engine::voice_job_finish(ptts_voice* v, bool copy_cond) {
+  const VoiceWs& w = vws_;
+  const int F = v->F;
+  if (copy_cond)  // ahead of the prefill, which turns the rows into the residual stream in place
+    PTTS_HIP(hipMemcpyAsync(v->h_cond, w.cond, sizeof(float) * (size_t)F * D, hipMemcpyDeviceToHost, stream_vc_));
+  for (int c0 = 0; c0 < F; c0 += PREFILL) {
+    const int T = std::min(PREFILL, F - c0);
+    FlowBufs b = w.fb;
+    b.x = w.fb.x + (size_t)c0 * D;
+    b.kv = KvStore{v->kv, 0, F};  // the voice's own compact cache [NL][2][NH][F][64]
+    b.kv_layer = (long)2 * NH * F * 64;
+    std::vector<Op> ops;
+    prefill_rows(ops, 0, T, c0, &b);
+    run_ops_on(ops, stream_vc_);
+  }
+  PTTS_HIP(hipEventRecord(v->ev, stream_vc_));
+}
+
+ptts_voice* Engine::voice_job_prompt(const float* prompt, int F) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(prompt != nullptr && F >= 1, "empty prompt");
+  PTTS_REQUIRE(F < max_ctx_, "prompt longer than max_ctx");
+  PTTS_HIP(hipSetDevice(dev_));
+  const size_t bytes = sizeof(float) * (size_t)F * D;
+  vws_reserve(std::max(F, vws_.frames), bytes, 0);  // staged in pinned memory, uploaded straight into x
+  ptts_voice* v = voice_job_new(F, false);
+  try {
+    VoiceWs& w = vws_;
+    const int par = (int)(vjobs_ & 1);
+    PTTS_HIP(hipEventSynchronize(w.ev_up[par]));  // the staging block's previous upload (two jobs back)
+    memcpy(w.h_up[par], prompt, bytes);
+    PTTS_HIP(hipMemcpyAsync(w.fb.x, w.h_up[par], bytes, hipMemcpyHostToDevice, stream_vc_));
+    PTTS_HIP(hipEventRecord(w.ev_up[par], stream_vc_));
+    ++vjobs_;
+    voice_job_finish(v, false);
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_vc_);
+    free_voice(v);
+    throw;
+  }
+  return v;
+}
+
+ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int sr, int chunk_frames, int resampler) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(samples != nullptr && n_in >= 1, "empty PCM");
+  PTTS_REQUIRE(fmt == PTTS_SAMPLES_F32 || fmt == PTTS_SAMPLES_S16, "unknown sample format");
+  PTTS_REQUIRE(sr > 0, "sample rate must be positive");
+  PTTS_REQUIRE(resampler == PTTS_RESAMPLE_POLY || resampler == PTTS_RESAMPLE_RUBATO_SEPTIC, "unknown resampler");
+  const ResamplePlan rp = resample_plan(sr, PTTS_SAMPLE_RATE);
+  const bool septic = resampler == PTTS_RESAMPLE_RUBATO_SEPTIC && !rp.identity();
+  std::vector<int> sst;
+  std::vector<float> sfr;
+  const long n_long = rp.identity() ? n_in : septic ? septic_schedule(n_in, sr, PTTS_SAMPLE_RATE, &sst, &sfr)
+                                                    : rp.out_len(n_in);
+  PTTS_REQUIRE(n_long >= 1 && n_long < (1L << 28) && rp.L <= (1 << 22), "voice prompt length or rate out of range");
+  const int n = (int)n_long;
+  const int Np = (n + FRAME - 1) / FRAME * FRAME;
+  const int F = Np / FRAME, Te = Np / 120;
+  PTTS_REQUIRE(F < max_ctx_, "voice prompt longer than max_ctx");
+  const int cf = voice_chunk_frames(F, chunk_frames);
+  std::vector<float> taps;
+  if (!septic && !rp.identity()) taps = resample_taps(rp);
+  // the job's single upload: samples | taps | rubato start | rubato frac
+  const size_t bps = fmt == PTTS_SAMPLES_S16 ? 2 : 4;
+  const size_t o_taps = al16((size_t)n_in * bps), o_st = o_taps + al16(taps.size() * sizeof(float)),
+               o_fr = o_st + al16(sst.size() * sizeof(int)), up_bytes = o_fr + al16(sfr.size() * sizeof(float)),
+               o_fx = up_bytes, dev_bytes = up_bytes + (septic ? al16((size_t)n_in * sizeof(float)) : 0);
+  PTTS_HIP(hipSetDevice(dev_));
+  vws_reserve(std::max(F, vws_.frames), up_bytes, dev_bytes);
+  ptts_voice* v = voice_job_new(F, true);
+  try {
+    VoiceWs& w = vws_;
+    const int par = (int)(vjobs_ & 1);
+    PTTS_HIP(hipEventSynchronize(w.ev_up[par]));  // the staging block's previous upload (two jobs back)
+    char* hs = w.h_up[par];
+    memcpy(hs, samples, (size_t)n_in * bps);
+    if (!taps.empty()) memcpy(hs + o_taps, taps.data(), taps.size() * sizeof(float));
+    if (!sst.empty()) memcpy(hs + o_st, sst.data(), sst.size() * sizeof(int));
+    if (!sfr.empty()) memcpy(hs + o_fr, sfr.data(), sfr.size() * sizeof(float));
+    PTTS_HIP(hipMemcpyAsync(w.up, hs, up_bytes, hipMemcpyHostToDevice, stream_vc_));
+    PTTS_HIP(hipEventRecord(w.ev_up[par], stream_vc_));
+    ++vjobs_;
+    const int s16 = fmt == PTTS_SAMPLES_S16 ? 1 : 0;
+    float* dpcm = w.pcm;
+    if (septic) {  // the rubato rule keeps its kernel, fed by a converting copy
+      float* fx = (float*)(w.up + o_fx);  // behind the upload, in the same device block
+      voice_ingest(w.up, s16, n_in, nullptr, ResamplePlan{}, n_in, n_in, fx, stream_vc_);
+      resample_septic(fx, n_in, (const int*)(w.up + o_st), (const float*)(w.up + o_fr), n, Np, dpcm, stream_vc_);
+    } else {  // convert + polyphase rule + zero padding in one launch
+      voice_ingest(w.up, s16, n_in, (const float*)(w.up + o_taps), rp, n, Np, dpcm, stream_vc_);
+    }
+    PTTS_HIP(hipGetLastError());
+    std::vector<Op> ops;
+    float *A = w.A, *Bf = w.Bf, *V = w.V, *zeros = w.zeros;
+    {
+      const float *wt = W(L_.ec0_w), *b = W(L_.ec0_b);
+      ops.push_back({"enc.conv0", [=](hipStream_t s) { conv_cin1(dpcm, Np, 64, 7, wt, b, A, s); }});
+    }
+    int T = Np, ch = 64;
+    for (int i = 0; i < 3; ++i) {
+      const int r = RATIOS[2 - i];
+      conv_op(ops, "enc.res_conv3", A, 1, T, ch, zeros, 2, 1, 1, W(L_.era_w[i]), ch / 2, 3, 1, W(L_.era_b[i]),
+              nullptr, V, T, 1);
+      conv_op(ops, "enc.res_conv1", V, 1, T, ch / 2, nullptr, 0, 1, 1, W(L_.erb_w[i]), ch, 1, 1, W(L_.erb_b[i]), A,
+              Bf, T, 1);
+      conv_op(ops, "enc.down", Bf, 1, T, ch, zeros, r, r, 1, W(L_.edn_w[i]), 2 * ch, 2 * r, 1, W(L_.edn_b[i]),
+              nullptr, A, T / r, 1);
+      T /= r;
+      ch *= 2;
+    }
+    conv_op(ops, "enc.conv_final", A, 1, T, 512, zeros, 2, 1, 1, W(L_.efin_w), 512, 3, 1, W(L_.efin_b), nullptr, Bf,
+            T, 1);
+    encoder_transformer(ops, Bf, Te, w.eh, w.eqkv, w.eq, w.eo, w.eu, w.ering);
+    // ConvDownsample1d per chunk of cf frames (voice_from_audio), the chunks' replicated first rows
+    // written by ONE launch
+    const int nfull = F / cf, rem = F - nfull * cf, nch = nfull + (rem ? 1 : 0);
+    float *Hd = w.Hd, *lat = w.lat;
+    ops.push_back({"enc.replicate", [=](hipStream_t s) { replicate_chunks(Bf, (long)cf * 16 * 512, Hd, nch, 16, 512, s); }});
+    if (nfull)
+      conv_op(ops, "enc.downsample", Bf, nfull, cf * 16, 512, Hd, 16, 16, 0, W(L_.down_w), 512, 32, 1, nullptr,
+              nullptr, lat, cf, 1);
+    if (rem)
+      conv_op(ops, "enc.downsample", Bf + (size_t)nfull * cf * 16 * 512, 1, rem * 16, 512,
+              Hd + (size_t)nfull * 16 * 512, 16, 16, 0, W(L_.down_w), 512, 32, 1, nullptr, nullptr,
+              lat + (size_t)nfull * cf * 512, rem, 1);
+    dense_op(ops, "enc.speaker_proj", lat, F, W(L_.speaker_proj), D, MD, nullptr, ACT_NONE, nullptr, nullptr, w.cond);
+    run_ops_on(ops, stream_vc_);
+    voice_job_finish(v, true);
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_vc_);
+    free_voice(v);
+    throw;
+  }
+  return v;
+}
+
 void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
                        int lsd_steps) {
   slots_open(1, &slot, &v, ids, &n, &p, &lsd_steps);
@@ -2592,6 +2877,14 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   // of that state, after the text prefill.
   PTTS_HIP(hipEventSynchronize(ev_admit_));
   PTTS_HIP(hipEventSynchronize(ev_act_));  // pending start-of-utterance copies read h_act_
+  // voices whose job (voice_job_*) may still run: the front stream waits for the job's event on the
+  // GPU, ahead of everything below that reads the prefix; the host does not wait
+  for (int i = 0; i < n; ++i) {
+    const ptts_voice* v = voices[i];
+    if (!v->ev || v->ordered) continue;
+    if (hipEventQuery(v->ev) != hipSuccess) PTTS_HIP(hipStreamWaitEvent(stream_, v->ev, 0));
+    v->ordered = true;
+  }
   if (share_voice_) {
     // shared voice prefixes: each slot's positions < F read the voice's own cache (no copy; the
     // reference copies the prompt's ModelState per utterance, tts_model.rs:940: same values)
@@ -2895,9 +3188,7 @@ void Engine::voice_release(int slot, bool drained) {
   }
   if (!free_now) return;
   if (!drained) PTTS_HIP(hipStreamSynchronize(stream_));  // queued steps may still read it
-  ptts_voice* w = const_cast<ptts_voice*>(v);
-  if (w->kv) (void)hipFree(w->kv);
-  delete w;
+  free_voice(const_cast<ptts_voice*>(v));
 }
 
 void voice_destroy(ptts_voice* v) {
@@ -2909,8 +3200,7 @@ void voice_destroy(ptts_voice* v) {
       return;
     }
   }
-  if (v->kv) (void)hipFree(v->kv);
-  delete v;
+  free_voice(v);  // waits for a pending job of the voice first
 }
 
 void Engine::set_latent(int slot, const float* lat) {

@@ -21,6 +21,12 @@ struct ptts_voice {
   const void* owner = nullptr;
   mutable int refs = 0;
   mutable bool dead = false;
+  // voice jobs (Engine::voice_job_*): the event recorded on the voice stream behind the job (null:
+  // made synchronously), the pinned host copy of the conditioning the job's last copy fills (PCM
+  // jobs), and whether the front stream has already been ordered behind the event
+  hipEvent_t ev = nullptr;
+  float* h_cond = nullptr;
+  mutable bool ordered = false;
 };
 
 namespace ptts {
@@ -61,6 +67,13 @@ class Engine {
   ptts_voice* voice_from_audio(const float* x, int n, int sample_rate, int chunk_frames,
                                int resampler = PTTS_RESAMPLE_POLY);
   void resample_host(const float* x, int n, int sr_from, int sr_to, float* y, int resampler = PTTS_RESAMPLE_POLY);
+  // Voice jobs: the same clone enqueued on the engine's voice stream with a workspace of its own
+  // (VoiceWs); returns at once, the voice is admissible immediately (slots_open orders the front
+  // stream behind the job's event). sample_format: PTTS_SAMPLES_F32 / PTTS_SAMPLES_S16 (mono).
+  ptts_voice* voice_job_audio(const void* samples, int n, int sample_format, int sample_rate, int chunk_frames,
+                              int resampler);
+  ptts_voice* voice_job_prompt(const float* prompt, int F);
+  void voice_jobs_reserve(int max_frames);
   // lsd_steps: the utterance's own Euler step count in [1, cap], or 0 (nullptr: every entry 0) for
   // the engine's default, the cap (cfg.lsd_decode_steps)
   void slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
@@ -110,8 +123,21 @@ class Engine {
   void upload_weights(TensorSource* src);
   void derive_int8();
   void derive_fp8();
-  void prefill_rows(std::vector<Op>& ops, int slot, int T, int p0);
+  // The buffers flow_layers / linear_split write: the engine's own (fbm_, the step and admission
+  // graphs) or a voice job's (VoiceWs). kv is layer 0's store; layer l's base is kv.base + l * kv_layer.
+  struct FlowBufs {
+    float *x = nullptr, *h = nullptr, *q = nullptr, *o = nullptr, *u = nullptr, *partial = nullptr;
+    size_t pcap = 0;
+    float* tslab = nullptr;
+    long tail_cap = 0;
+    int* tickets = nullptr;
+    KvStore kv{};
+    long kv_layer = 0;
+  };
+  FlowBufs fbm_{};
+  void prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs* fb = nullptr);
   void run_ops(const std::vector<Op>& ops);
+  void run_ops_on(const std::vector<Op>& ops, hipStream_t s);
   std::vector<Op> build_step(int B);
   // hb: front -> back hand-off buffer (frame index mod NHB); qp: parity of the back part's
   // quantizer history (frame index mod 2; the back part reads the previous frame's half)
@@ -127,9 +153,10 @@ class Engine {
   void wait_unless_done(hipStream_t s, hipEvent_t e);
   void copy_out(int B, int hb, hipStream_t s);
   void push_rr(std::vector<Op>& ops, const std::string& name, const RowReduceArgs& r);
-  void flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag);
+  void flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag,
+                   const FlowBufs* fb = nullptr);
   void linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M, const float* Wt,
-                    int N, int K, int* S_out);
+                    int N, int K, int* S_out, const FlowBufs* fb = nullptr);
   void conv_op(std::vector<Op>& ops, const std::string& name, const float* X, int B, int T_in, int cin, const float* H,
                int P, int stride, int elu, const float* Wt, int cout, int ktaps, int phases, const float* bias,
                const float* R, float* Y, int T_out, int tstride, int layout = 0, int elu_out = 0,
@@ -366,6 +393,35 @@ class Engine {
   void launch_previews(int B, int hb);
   hipGraphExec_t pv_graph(int P);
   void pv_forget(int slot);  // drop the slot's pending / unfetched previews (re-admitted or closed)
+
+  // ---- voice jobs (voice_job_audio / voice_job_prompt): everything a clone writes lives here, so a
+  // job shares only read-only weights and tables with the step pipeline
+  struct VoiceWs {
+    int frames = 0;         // capacity in frames of everything below but `up`
+    size_t up_bytes = 0;    // capacity of the device block `up` (the upload, then the converted clip)
+    size_t h_bytes = 0;     // capacity of each pinned staging block
+    // one upload per job: raw samples | resampler taps | rubato start / frac tables (behind them on
+    // the device, rubato rule only: the converted samples [n_in]); a prompt job uploads its rows
+    // straight into fb.x. Staged in one of two pinned host blocks (h_up; ev_up: that block's latest upload has run)
+    char* up = nullptr;
+    char* h_up[2] = {};
+    hipEvent_t ev_up[2] = {};
+    float *pcm = nullptr;                      // frame-padded 24 kHz input [Np]
+    float *A = nullptr, *Bf = nullptr, *V = nullptr, *zeros = nullptr;  // SEANet encoder ping-pong, zero history
+    float *eh = nullptr, *eqkv = nullptr, *eq = nullptr, *eo = nullptr, *eu = nullptr, *ering = nullptr;
+    float *Hd = nullptr, *lat = nullptr, *cond = nullptr;
+    FlowBufs fb{};                             // the prompt prefill's x, h, q, o, u, slabs, tail scratch
+    std::vector<void*> allocs;
+  };
+  VoiceWs vws_{};
+  hipStream_t stream_vc_ = nullptr;  // lowest priority; plain launches of non-persistent kernels only
+  long long vjobs_ = 0;              // jobs started (upload block parity)
+  void vws_free();
+  void vws_reserve(int frames, size_t host_bytes, size_t up_bytes);
+  // the prompt prefill of F conditioning rows in vws_.fb.x straight into v->kv, the conditioning
+  // copy (PCM jobs) and the job's event, all on stream_vc_
+  void voice_job_finish(ptts_voice* v, bool copy_cond);
+  ptts_voice* voice_job_new(int F, bool pcm);
 };
 
 }  // namespace ptts

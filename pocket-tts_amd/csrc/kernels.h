@@ -535,6 +535,17 @@ std::vector<float> resample_taps(const ResamplePlan& p);  // host FIR design (f3
 void resample(const float* x, int n_in, const float* taps, const ResamplePlan& p, int n_out, int n_pad, float* y,
               hipStream_t s);
 
+// Voice-job ingest: the clip in its wire format (mono f32, or mono int16 little-endian when
+// fmt_s16: v / 32768, exact in f32) -> y [n_pad] in one launch: the kernel resample() runs,
+// instantiated on the sample type (bit-equal to resample() on the converted samples by
+// construction), zeros for n_out <= m < n_pad.
+// An identity plan converts and pads (taps unused, may be null).
+void voice_ingest(const void* x, int fmt_s16, int n_in, const float* taps, const ResamplePlan& p, int n_out,
+                  int n_pad, float* y, hipStream_t s);
+// dst [nch][rows][cols]: row r of chunk c = src[c * chunk_stride .. + cols) (each encoder chunk's
+// first row replicated: the history of the chunked ConvDownsample1d), one launch over all chunks
+void replicate_chunks(const float* src, long chunk_stride, float* dst, int nch, int rows, int cols, hipStream_t s);
+
 // The Rust driver's resampler instead (audio.rs:197-255): rubato 0.14.1 FastFixedIn with
 // PolynomialDegree::Septic, one process() call over the whole input (chunk = n). Its source is not
 // in the reference; the published algorithm restated here: a read position idx starts at -4

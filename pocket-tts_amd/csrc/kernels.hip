@@ -3870,31 +3870,45 @@ void conv_cin1(const float* X, int T, int cout, int k, const float* w, const flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// Polyphase resampler (see kernels.h). One lane per output sample: lanes of a wave walk
-// consecutive outputs, so their input windows overlap and the x reads coalesce in L1/L2; the
-// taps (L floats, <= 64 KB) are staged once per workgroup in LDS. Each output touches only the
-// ~L/up taps of its phase, accumulated in f64 (scipy's f32 upfirdn differs by f32 rounding only).
-__global__ __launch_bounds__(256) void k_resample(const float* __restrict__ x, int n_in,
-                                                  const float* __restrict__ taps, int L, int up, int down,
-                                                  int half, int n_out, int n_pad, int use_lds, float* y) {
+// Polyphase resampler (see kernels.h), the one copy of the rule: resample() runs it on f32 samples,
+// voice_ingest() on a clip in its wire format (f32, or int16: v / 32768, exact in f32), so the two
+// agree bit for bit by construction. One workgroup per tile of 256 consecutive outputs, one lane
+// per output: lanes of a wave walk consecutive outputs, so their input windows overlap and the x
+// reads coalesce (2 or 4 B per sample); the taps (L floats, <= 64 KB) are staged once per
+// workgroup in LDS. Each output touches only the ~L/up taps of its phase, accumulated in f64
+// (scipy's f32 upfirdn differs by f32 rounding only). Zeros for n_out <= m < n_pad.
+// up == down == 1 (launch-uniform; voice_ingest only): convert and pad, no taps.
+__device__ __forceinline__ float ingest_load(const float* x, long j) { return x[j]; }
+__device__ __forceinline__ float ingest_load(const short* x, long j) { return (float)x[j] * (1.0f / 32768.0f); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_voice_ingest(const T* __restrict__ x, int n_in,
+                                                      const float* __restrict__ taps, int L, int up, int down,
+                                                      int half, int n_out, int n_pad, int use_lds,
+                                                      float* __restrict__ y) {
   extern __shared__ float sh_taps[];
-  if (use_lds) {
+  const bool identity = up == 1 && down == 1;
+  if (!identity && use_lds) {
     for (int i = threadIdx.x; i < L; i += blockDim.x) sh_taps[i] = taps[i];
     __syncthreads();
   }
-  const float* h = use_lds ? sh_taps : taps;
   const long m = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= n_pad) return;
   if (m >= n_out) {
     y[m] = 0.f;
     return;
   }
+  if (identity) {
+    y[m] = m < n_in ? ingest_load(x, m) : 0.f;
+    return;
+  }
+  const float* h = use_lds ? sh_taps : taps;
   const long a = m * down + half;  // h index of x[0]; x[j] pairs with h[a - j*up]
   const long jhi = min(a / up, (long)n_in - 1);
   const long lo = a - (L - 1);
   const long jlo = lo <= 0 ? 0 : (lo + up - 1) / up;
   double acc = 0.0;
-  for (long j = jlo; j <= jhi; ++j) acc += (double)x[j] * (double)h[a - j * up];
+  for (long j = jlo; j <= jhi; ++j) acc += (double)ingest_load(x, j) * (double)h[a - j * up];
   y[m] = (float)acc;
 }
 
@@ -3951,8 +3965,41 @@ void resample(const float* x, int n_in, const float* taps, const ResamplePlan& p
   if (n_pad <= 0) return;
   const int use_lds = p.L <= 16384 ? 1 : 0;
   const size_t lds = use_lds ? sizeof(float) * (size_t)p.L : 0;
-  hipLaunchKernelGGL(k_resample, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), lds, s, x, n_in, taps, p.L, p.up,
-                     p.down, p.half, n_out, n_pad, use_lds, y);
+  // never with an identity plan here (the callers copy equal-rate input): the FIR branch
+  hipLaunchKernelGGL(k_voice_ingest<float>, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), lds, s, x, n_in, taps, p.L,
+                     p.up, p.down, p.half, n_out, n_pad, use_lds, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Voice-job ingest (see kernels.h): k_voice_ingest above on the clip's wire format.
+void voice_ingest(const void* x, int fmt_s16, int n_in, const float* taps, const ResamplePlan& p, int n_out,
+                  int n_pad, float* y, hipStream_t s) {
+  if (n_pad <= 0) return;
+  const int use_lds = !p.identity() && p.L <= 16384 ? 1 : 0;
+  const size_t lds = use_lds ? sizeof(float) * (size_t)p.L : 0;
+  const dim3 grid((unsigned)((n_pad + 255) / 256));
+  if (fmt_s16)
+    hipLaunchKernelGGL(k_voice_ingest<short>, grid, dim3(256), lds, s, (const short*)x, n_in, taps, p.L, p.up, p.down,
+                       p.half, n_out, n_pad, use_lds, y);
+  else
+    hipLaunchKernelGGL(k_voice_ingest<float>, grid, dim3(256), lds, s, (const float*)x, n_in, taps, p.L, p.up, p.down,
+                       p.half, n_out, n_pad, use_lds, y);
+}
+
+// dst[c][r][:] = src[c * chunk_stride + :] for c < nch, r < rows: the replicate padding of every
+// encoder chunk's first row in one launch (ConvDownsample1d, conv.rs:116-123).
+__global__ __launch_bounds__(256) void k_replicate_chunks(const float* __restrict__ src, long chunk_stride,
+                                                          float* __restrict__ dst, int nch, int rows, int cols) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)nch * rows * cols) return;
+  const int col = (int)(idx % cols), c = (int)(idx / ((long)rows * cols));
+  dst[idx] = src[(long)c * chunk_stride + col];
+}
+void replicate_chunks(const float* src, long chunk_stride, float* dst, int nch, int rows, int cols, hipStream_t s) {
+  const long total = (long)nch * rows * cols;
+  if (total > 0)
+    hipLaunchKernelGGL(k_replicate_chunks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, chunk_stride,
+                       dst, nch, rows, cols);
 }
 
 // ---------------------------------------------------------------------------------------------

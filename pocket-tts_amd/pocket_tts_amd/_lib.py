@@ -19,6 +19,7 @@ DIM = 1024
 SAMPLE_RATE = 24000
 QUANT_NONE, QUANT_FLOW_LM, QUANT_ALL = 0, 1, 2
 BACK_F32, BACK_BF16, BACK_F32X6 = 0, 1, 2  # ptts_engine_config.back_mfma (PTTS_BACK_*)
+SAMPLES_F32, SAMPLES_S16 = 0, 1  # sample_format of ptts_voice_job_start (PTTS_SAMPLES_*)
 ABI_VERSION = 6  # PTTS_ABI_VERSION of include/pocket_tts.h that the structs below mirror
 
 F32P = C.POINTER(C.c_float)
@@ -84,6 +85,11 @@ SIGNATURES = [
     ("ptts_resample_ex", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, C.c_int, F32P]),
     ("ptts_voice_from_audio_ex", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_void_p)]),
+    ("ptts_voice_job_start", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p)]),
+    ("ptts_voice_job_start_prompt", C.c_int, [C.c_void_p, F32P, C.c_int, C.POINTER(C.c_void_p)]),
+    ("ptts_voice_ready", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    ("ptts_voice_jobs_reserve", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_flush_async", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_test_gemm", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F32P, F32P, F32P]),
     ("ptts_voice_len", C.c_int, [C.c_void_p]),

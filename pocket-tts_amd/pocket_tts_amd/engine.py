@@ -7,8 +7,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, EngineConfig, GenParams, check, fptr, lib,
-                   u8ptr)
+from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, EngineConfig,
+                   GenParams, check, fptr, lib, u8ptr)
 
 
 @dataclass
@@ -48,7 +48,15 @@ class Voice:
         check(lib().ptts_voice_conditioning(self.handle, fptr(out), out.shape[0]))
         return out
 
+    def ready(self, wait: bool = False) -> bool:
+        """The voice's job has run (ptts_voice_ready); always True for a synchronously made voice.
+        wait=True blocks until it has. Admission never needs this: it is ordered on the GPU."""
+        r = C.c_int(0)
+        check(lib().ptts_voice_ready(self.handle, int(wait), C.byref(r)))
+        return bool(r.value)
+
     def close(self):
+        """Destroy the voice (waits for a pending job of it; slots still reading it keep it alive)."""
         if self.handle:
             lib().ptts_voice_destroy(self.handle)
             self.handle = None
@@ -240,6 +248,32 @@ class Engine:
         check(lib().ptts_voice_from_audio_ex(self.handle, fptr(x), x.size, int(sample_rate), int(chunk_frames),
                                              resampler_code(resampler), C.byref(h)))
         return Voice(self, h.value)
+
+    # -- voice jobs: the same clones on the engine's voice stream, beside the step pipeline
+    def voice_job(self, samples: np.ndarray, sample_rate: int, chunk_frames: int = 0,
+                  resampler: str = "poly") -> Voice:
+        """voice_from_audio as a job (ptts_voice_job_start): returns at once, the voice can be
+        admitted immediately, and the step pipeline is not drained. A mono float32
+        or int16 array selects the sample format (int16: v / 32768, converted on the GPU); any
+        other dtype is converted to float32 first."""
+        x = np.asarray(samples)
+        fmt = SAMPLES_S16 if x.dtype == np.int16 else SAMPLES_F32
+        x = np.ascontiguousarray(x, np.int16 if fmt == SAMPLES_S16 else np.float32).reshape(-1)
+        h = C.c_void_p()
+        check(lib().ptts_voice_job_start(self.handle, x.ctypes.data_as(C.c_void_p), x.size, fmt, int(sample_rate),
+                                         int(chunk_frames), resampler_code(resampler), C.byref(h)))
+        return Voice(self, h.value)
+
+    def voice_job_prompt(self, prompt: np.ndarray) -> Voice:
+        """voice_from_prompt as a job (ptts_voice_job_start_prompt)."""
+        p = np.ascontiguousarray(prompt, np.float32).reshape(-1, DIM)
+        h = C.c_void_p()
+        check(lib().ptts_voice_job_start_prompt(self.handle, fptr(p), p.shape[0], C.byref(h)))
+        return Voice(self, h.value)
+
+    def reserve_voice_jobs(self, max_frames: int):
+        """Pre-size the voice workspace for clips of up to max_frames frames (ptts_voice_jobs_reserve)."""
+        check(lib().ptts_voice_jobs_reserve(self.handle, int(max_frames)))
 
     def resample(self, x: np.ndarray, sr_from: int, sr_to: int = 24000, resampler: str = "poly") -> np.ndarray:
         """The GPU resampler on its own (ptts_resample_ex)."""

@@ -28,18 +28,41 @@ HTTP (`create_app`, FastAPI; routes of pocket-tts-cli/src/server/routes.rs:20-30
                            chunk per 20 ms per stream
   POST /v1/audio/speech    OpenAI body {model, input, voice?, response_format?} -> wav / pcm
                            (handlers.rs:380-398)
+  POST /voices/{name}      body: a mono RIFF/WAVE clip, or a safetensors file holding `audio_prompt`
+                           [F x 1024]: registers (or replaces) a named voice at run time
+  GET  /voices             {"voices": [names], "default": name}
 Wire formats follow crates/pocket-tts/src/audio.rs:110-185 (clamp to [-1, 1], x 32767,
 truncate to i16; 16-bit mono RIFF/WAVE).
+
+Per-request voices (pocket-tts-cli/src/voice.rs:67-222): the `voice` field is first a registered
+name; else base64 WAV audio, as a `data:audio/...;base64,` URL or as raw base64 (voice.rs:172-189:
+longer than 100 characters, base64 alphabet only); else the request is refused (400). The clip is
+cloned as a voice job (Engine.voice_job) started by the scheduler thread between two engine calls
+and admitted in the same pass, so cloning never drains the pipeline of the streams being generated
+(what a clone and a cache eviction still cost them: DESIGN.md section 16). Each
+engine keeps its clones in an LRU cache (`--voice-cache N`, the reference's VoiceCache,
+handlers.rs:99-126) keyed by the blake2b hash of the WAV bytes and the clone settings; requests
+that bring the same new clip share one job. Clips must be mono and at most `--max-voice-seconds`.
+
+Deliberate divergence from the reference: file paths and `hf://` specs in the `voice` field are NOT
+accepted from the network (the reference resolves both, voice.rs:93-102): a request must not make
+the server read its own file system or fetch from outside. Such specs get the 400 of an unknown
+voice. The reference's multipart /tts route is not implemented.
 """
 
 from __future__ import annotations
 
+import base64
+import binascii
+import hashlib
+import math
 import os
 import queue
+import re
 import struct
 import threading
 import time
-from collections import deque
+from collections import OrderedDict, deque
 from dataclasses import dataclass, field
 from typing import Callable, Iterator, Sequence
 
@@ -104,10 +127,96 @@ class FrameChannel:
 
 # ---------------------------------------------------------------------------------------------
 @dataclass
+class VoiceClip:
+    """A voice still to be cloned, on whichever engine its request is routed to: a mono clip in its
+    wire format (int16 or float32) with the clone settings, or a precomputed audio_prompt. `key`
+    identifies it in that engine's VoiceCache; n_frames is computed on the host (as the engine does)."""
+
+    key: bytes
+    n_frames: int
+    samples: np.ndarray | None = None
+    sample_rate: int = SAMPLE_RATE
+    chunk_frames: int = 0
+    resampler: str = "poly"
+    prompt: np.ndarray | None = None
+
+    def start(self, engine) -> Voice:
+        """Start the clone as a voice job; the returned voice can be admitted at once."""
+        if self.prompt is not None:
+            return engine.voice_job_prompt(self.prompt)
+        return engine.voice_job(self.samples, self.sample_rate, self.chunk_frames, self.resampler)
+
+
+def clip_frames(n_samples: int, sample_rate: int, resampler: str = "poly") -> int:
+    """Conditioning frames of a clip: its length at 24 kHz (the engine's host-side rule) in whole
+    1920-sample frames."""
+    if sample_rate == SAMPLE_RATE:
+        n = n_samples
+    elif resampler == "rubato":
+        from ._lib import lib
+        from .engine import resampler_code
+
+        n = lib().ptts_resample_len_ex(int(n_samples), int(sample_rate), SAMPLE_RATE, resampler_code(resampler))
+    else:
+        g = math.gcd(int(sample_rate), SAMPLE_RATE)
+        up, down = SAMPLE_RATE // g, int(sample_rate) // g
+        n = (n_samples * up + down - 1) // down
+    return (n + FRAME - 1) // FRAME
+
+
+class VoiceCache:
+    """LRU of the voices an engine cloned for its requests (the reference's VoiceCache,
+    handlers.rs:99-126), used by the scheduler thread only. A voice enters when its job is
+    started, so later requests with the same clip share that job. trim() drops the least recently
+    used entries past the capacity: only the cache's reference goes, a voice that slots still read
+    lives on until the last of them lets go (ptts_voice_destroy)."""
+
+    def __init__(self, capacity: int = 64):
+        self.capacity = max(int(capacity), 0)
+        self._d: OrderedDict[bytes, Voice] = OrderedDict()
+        self.jobs = 0  # clones started
+        self.hits = 0
+
+    def __len__(self):
+        return len(self._d)
+
+    def keys(self):
+        return list(self._d)
+
+    def get_or_start(self, clip: VoiceClip, engine) -> Voice:
+        v = self._d.get(clip.key)
+        if v is not None:
+            self._d.move_to_end(clip.key)
+            self.hits += 1
+            return v
+        v = clip.start(engine)
+        self.jobs += 1
+        self._d[clip.key] = v
+        return v
+
+    def trim(self, keep: int | None = None):
+        while len(self._d) > (self.capacity if keep is None else keep):
+            self._d.popitem(last=False)[1].close()
+
+
+class _Call:
+    def __init__(self, fn):
+        self.fn, self.done, self.result, self.error = fn, threading.Event(), None, None
+
+    def run(self):
+        try:
+            self.result = self.fn()
+        except BaseException as e:  # handed to the caller
+            self.error = e
+        self.done.set()
+
+
+@dataclass
 class Request:
     ids: np.ndarray
-    voice: Voice
+    voice: Voice | None
     params: GenerationParams
+    clip: VoiceClip | None = None  # voice still to be cloned (resolved by the scheduler thread at admission)
     out: FrameChannel = field(default_factory=FrameChannel)  # np.ndarray frames, then None
     slot: int = -1
     frames: int = 0
@@ -173,8 +282,11 @@ class BatchScheduler:
     comes (the two agree within float rounding: the regular pass decodes it from the same fresh
     state), or, if the regular frame comes first, drops the preview."""
 
-    def __init__(self, engine, max_rows: int | None = None, preview_rows: int = 8):
+    def __init__(self, engine, max_rows: int | None = None, preview_rows: int = 8, voice_cache: int = 64):
         self.engine = engine
+        self.voices = VoiceCache(voice_cache)  # per-request clones of this engine
+        self.calls: deque[_Call] = deque()     # engine work handed to the scheduler thread (call())
+        self.retired: list = []                # replaced voices, closed once no queued request holds them
         self.max_rows = min(max_rows or engine.max_slots, engine.max_slots)
         self.preview = bool(preview_rows) and getattr(engine, "pipeline", False) and hasattr(engine, "enable_preview")
         if self.preview:
@@ -196,8 +308,12 @@ class BatchScheduler:
         self.thread.start()
 
     # -- client side
-    def submit(self, ids, voice: Voice, params: GenerationParams) -> Request:
+    def submit(self, ids, voice: Voice | VoiceClip, params: GenerationParams) -> Request:
+        """voice: a Voice of this engine, or a VoiceClip: cloned (or found in the cache) by the
+        scheduler thread right before the request's admission, in the same pass."""
         req = Request(np.asarray(ids, np.int32).reshape(-1), voice, params)
+        if isinstance(voice, VoiceClip):
+            req.voice, req.clip = None, voice
         req.times["submit"] = time.time()
         if voice.n_frames + req.ids.size + params.max_frames > self.engine.max_ctx:
             raise ValueError("voice + text + max_frames exceeds the engine's max_ctx")
@@ -214,11 +330,51 @@ class BatchScheduler:
         with self.cv:
             return len(self.active) + len(self.waiting)
 
+    def call(self, fn):
+        """Run fn() on the scheduler thread between two engine calls (engine calls stay on one
+        thread) and return its result; its exception is raised here."""
+        c = _Call(fn)
+        with self.cv:
+            if not self.running:
+                raise RuntimeError("scheduler stopped")
+            self.calls.append(c)
+            self.cv.notify()
+        c.done.wait()
+        if c.error is not None:
+            raise c.error
+        return c.result
+
+    def retire(self, voice):
+        """Close a voice of this engine that the caller no longer hands out, once no waiting
+        request holds it (an admitted row keeps its voice alive by itself, ptts_voice_destroy). A
+        caller that resolves a name and submits under one lock, and swaps the name under the same
+        lock before retiring, cannot queue a request with a closed voice."""
+        try:
+            self.call(lambda: (self.retired.append(voice), self._close_retired()))
+        except RuntimeError:  # scheduler stopped: nothing is queued any more
+            voice.close()
+
+    def _close_retired(self):
+        """(scheduler thread, after the pass's admission)"""
+        if not self.retired:
+            return
+        with self.cv:
+            held = {id(r.voice) for r in self.waiting}
+        keep = [v for v in self.retired if id(v) in held]
+        for v in self.retired:
+            if id(v) not in held:
+                v.close()
+        self.retired = keep
+
     def close(self):
         with self.cv:
             self.running = False
             self.cv.notify()
         self.thread.join()
+        self.voices.trim(0)
+        for v in self.retired:
+            v.close()
+        self.retired = []
 
     # -- driver thread
     def _take(self) -> list[Request]:
@@ -232,11 +388,43 @@ class BatchScheduler:
             batch.append(req)
         return batch
 
+    def _refuse(self, batch: list[Request], reqs: list[Request], err: BaseException):
+        """Fail `reqs` of the taken batch with err and free their slots."""
+        with self.cv:
+            for r in reqs:
+                batch.remove(r)
+                del self.active[r.slot]
+            if self.on_load is not None:
+                self.on_load(len(self.active) + len(self.waiting))
+        for r in reqs:
+            r.put(err)
+            r.put(None)
+
     def _admit(self, batch: list[Request]):
         """(outside self.cv: submit() runs on the HTTP event loop and must never wait for an
         admission's engine call) one batched admission of the taken requests"""
-        self.engine.open_many([r.slot for r in batch], [r.voice for r in batch], [r.ids for r in batch],
-                              [r.params for r in batch])
+        for r in list(batch):  # per-request voices: found in the cache, or their job started here
+            if r.voice is None:
+                try:
+                    r.voice = self.voices.get_or_start(r.clip, self.engine)
+                except Exception as e:  # the engine refused the clip: this request fails, the rest go on
+                    self._refuse(batch, [r], e)
+            elif getattr(r.voice, "handle", True) is None:  # closed under the request: it alone fails
+                self._refuse(batch, [r], RuntimeError("the request's voice was closed before its admission"))
+        if not batch:
+            return
+        try:
+            self.engine.open_many([r.slot for r in batch], [r.voice for r in batch], [r.ids for r in batch],
+                                  [r.params for r in batch])
+        except Exception as e:
+            # an argument the engine refused (PTTS_ERR_INVALID: checked before anything is enqueued)
+            # fails the admission's own requests and the streams being generated go on; any other
+            # failure (HIP, state) still stops the scheduler
+            if getattr(e, "code", 1) != 1:
+                raise
+            self._refuse(batch, list(batch), e)
+            return
+        self.voices.trim()  # after the admission: the slots hold their voices now
         now = time.time()
         # the rows start at the step issued admit_delay calls after the next one (ptts_frame_lag)
         delay = self.engine.frame_lag()[1] if hasattr(self.engine, "frame_lag") else 0
@@ -294,13 +482,16 @@ class BatchScheduler:
         # released when its last frame is delivered (later calls compute it as inactive:
         # frame_valid = 0).
         issued: deque[int] = deque()  # rows of the calls issued and not fetched yet (<= 2)
+        calls: list[_Call] = []       # this pass's share of self.calls
         try:
             while True:
                 with self.cv:
-                    while self.running and not self.waiting and not self.active and not issued:
+                    while self.running and not self.waiting and not self.active and not issued and not self.calls:
                         self.cv.wait()
                     if not self.running:
                         break
+                    calls = list(self.calls)
+                    self.calls.clear()
                     batch = self._take()
                     rows = max(self.active) + 1 if self.active else 0
                 # A pipelined engine lets the host run calls ahead of the GPU (the fetch below waits
@@ -312,6 +503,13 @@ class BatchScheduler:
                     self.engine.front_done(1, wait=True)
                 if batch:
                     self._admit(batch)
+                    rows = max(self.active) + 1 if self.active else 0  # a refused request freed its slot
+                # after the admission: every request this pass took holds its voice in the engine
+                # by now, so a retired voice is kept for the requests still waiting only
+                for c in calls:
+                    c.run()
+                calls = []
+                self._close_retired()
                 if rows:
                     self.engine.step_async(rows)
                     issued.append(rows)
@@ -350,8 +548,14 @@ class BatchScheduler:
                 self.waiting.clear()
         finally:
             with self.cv:
+                self.running = False
                 for req in list(self.active.values()) + list(self.waiting):
                     req.put(None)
+                for c in list(calls) + list(self.calls):  # also those this pass took and never ran
+                    if not c.done.is_set():
+                        c.error = RuntimeError("scheduler stopped")
+                        c.done.set()
+                self.calls.clear()
 
 
 class MultiGpuScheduler:
@@ -360,9 +564,11 @@ class MultiGpuScheduler:
     def __init__(self, schedulers: Sequence[BatchScheduler]):
         self.schedulers = list(schedulers)
 
-    def submit(self, ids, voices: Sequence[Voice], params: GenerationParams) -> Request:
+    def submit(self, ids, voices: Sequence[Voice] | VoiceClip, params: GenerationParams) -> Request:
+        """voices: one Voice per GPU, or a VoiceClip: cloned on the engine the request is routed to
+        (each engine has its own cache)."""
         i = min(range(len(self.schedulers)), key=lambda k: self.schedulers[k].load())
-        return self.schedulers[i].submit(ids, voices[i], params)
+        return self.schedulers[i].submit(ids, voices if isinstance(voices, VoiceClip) else voices[i], params)
 
     def close(self):
         for s in self.schedulers:
@@ -473,16 +679,65 @@ def load_tokenizer(path: str) -> Callable[[str], list[int]]:
     return Tokenizer.from_file(path, native=True)
 
 
+_B64_ALPHABET = re.compile(r"[A-Za-z0-9+/=]+")
+_DATA_URL = re.compile(r"data:audio/[^;,]*;base64,", re.ASCII)
+_VOICE_NAME = re.compile(r"[A-Za-z0-9_.-]{1,64}")
+
+
+def voice_spec_audio(spec: str) -> bytes | None:
+    """The audio bytes of a base64 voice spec, by the reference's rule (voice.rs:172-222): a
+    `data:audio/...;base64,` URL, or raw base64 (longer than 100 characters, base64 alphabet only);
+    None for anything else. Nothing here touches the file system or the network."""
+    spec = spec.strip()
+    m = _DATA_URL.match(spec)
+    if m:
+        payload = spec[m.end():]
+    elif len(spec) > 100 and _B64_ALPHABET.fullmatch(spec):
+        payload = spec
+    else:
+        return None
+    try:
+        return base64.b64decode(payload, validate=True)
+    except (binascii.Error, ValueError) as e:
+        raise ValueError(f"voice: base64 audio does not decode ({e})") from e
+
+
+def wav_wire_samples(data: bytes) -> tuple[np.ndarray, int]:
+    """A mono RIFF/WAVE clip -> (samples in their wire format, sample rate): int16 where every
+    sample is an int16 value / 32768 (8- and 16-bit PCM: the engine converts them on the GPU, the
+    same numbers exactly), float32 otherwise. Raises ValueError (WavError) for anything else."""
+    from .audio import read_wav_from_bytes
+
+    x, sr = read_wav_from_bytes(data)
+    if x.shape[0] != 1:
+        raise ValueError(f"voice prompt must be mono, got {x.shape[0]} channels")
+    if x.shape[1] < 1 or sr <= 0:
+        raise ValueError("voice prompt holds no samples")
+    y = x[0] * np.float32(32768.0)  # exact (a power of two)
+    yi = y.astype(np.int16)
+    if np.array_equal(yi, y):
+        return yi, sr
+    return np.ascontiguousarray(x[0], np.float32), sr
+
+
 class TTSService:
     """Request-level logic shared by the HTTP routes: text -> ids, voice lookup, params."""
 
     def __init__(self, scheduler, voices: dict[str, Voice | Sequence[Voice]], default_voice: str,
                  tokenizer: Callable[[str], Sequence[int]] | None = None, temp: float = 0.7,
                  eos_threshold: float = -4.0, noise_clamp: float | None = None, lsd_decode_steps: int = 1,
-                 max_lsd_steps: int | None = None):
+                 max_lsd_steps: int | None = None, max_voice_seconds: float = 30.0, voice_chunk_frames: int = 0,
+                 voice_resampler: str = "poly", max_ctx: int | None = None):
         """lsd_decode_steps: the Euler step count of a request that names none (the engine's own
         default). max_lsd_steps: the largest `lsd_steps` a request may ask for, the engine's cap
-        (None: lsd_decode_steps, so any other value is refused)."""
+        (None: lsd_decode_steps, so any other value is refused). max_voice_seconds: longest clip a
+        request (or POST /voices) may bring. voice_chunk_frames / voice_resampler: the clone
+        settings of such clips (Engine.voice_job). max_ctx: the engines' context (a voice must be
+        shorter), read from the scheduler's engine when not given."""
+        self.max_voice_seconds = float(max_voice_seconds)
+        self.voice_chunk_frames, self.voice_resampler = int(voice_chunk_frames), voice_resampler
+        eng = getattr(scheduler, "engine", None) or getattr(getattr(scheduler, "schedulers", [None])[0], "engine", None)
+        self.max_ctx = max_ctx if max_ctx is not None else getattr(eng, "max_ctx", None)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -515,17 +770,89 @@ class TTSService:
         else:
             raise ValueError("text or token_ids required")
         name = voice or self.default_voice
-        if name not in self.voices:
-            raise ValueError(f"unknown voice {name!r}")
+        # not a registered name: base64 audio (decoded outside the lock), or refused
+        clip = None if name in self.voices else self.voice_clip(name)
+        # the name is resolved and the request queued under the lock register_voice swaps the name
+        # under: a replaced voice is retired only after every request that got it is queued, and
+        # the scheduler closes it only once none of them is still waiting (BatchScheduler.retire)
         with self._lock:
-            self._seed += 1
-            seed = self._seed
+            return self._submit_locked(ids, clip if clip is not None else self.voices[name], temperature,
+                                       eos_threshold, noise_clamp, fae, mgl, lsd_steps)
+
+    def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps) -> Request:
+        self._seed += 1
+        seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
                              eos_threshold=self.eos_threshold if eos_threshold is None else eos_threshold,
                              noise_clamp=self.noise_clamp if noise_clamp is None else noise_clamp,
                              frames_after_eos=fae, max_frames=mgl, seed=seed,
                              lsd_steps=None if lsd_steps is None else int(lsd_steps))
-        return self.scheduler.submit(ids, self.voices[name], p)  # MultiGpuScheduler: one voice per GPU
+        return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
+
+    # -- per-request and run-time voices
+    def voice_clip(self, spec: str) -> VoiceClip:
+        """The `voice` field of a request that names no registered voice -> the clip to clone.
+        ValueError (HTTP 400) for anything but base64 WAV audio: unknown names, and the file paths
+        and hf:// specs the reference would resolve (deliberately not accepted from the network)."""
+        data = voice_spec_audio(spec)
+        if data is None:
+            shown = spec if len(spec) <= 64 else spec[:61] + "..."
+            raise ValueError(f"unknown voice {shown!r} (a registered name or base64 WAV audio; file paths and "
+                             "hf:// specs are not accepted)")
+        return self.wav_clip(data)
+
+    def wav_clip(self, data: bytes) -> VoiceClip:
+        samples, sr = wav_wire_samples(data)
+        if samples.size > self.max_voice_seconds * sr:
+            raise ValueError(f"voice prompt is {samples.size / sr:.1f} s long, the limit is "
+                             f"{self.max_voice_seconds:g} s (--max-voice-seconds)")
+        frames = clip_frames(samples.size, sr, self.voice_resampler)
+        if frames < 1 or (self.max_ctx is not None and frames >= self.max_ctx):
+            raise ValueError(f"voice prompt of {frames} frames does not fit the engine's context")
+        h = hashlib.blake2b(data, digest_size=16)
+        h.update(f"|chunk={self.voice_chunk_frames}|resampler={self.voice_resampler}".encode())
+        return VoiceClip(h.digest(), frames, samples, sr, self.voice_chunk_frames, self.voice_resampler)
+
+    def prompt_clip(self, data: bytes) -> VoiceClip:
+        """A safetensors file holding `audio_prompt` [.. x F x 1024] (the reference's voice embeddings)."""
+        from safetensors.numpy import load as st_load
+
+        try:
+            t = st_load(data)
+        except Exception as e:
+            raise ValueError(f"body is neither RIFF/WAVE nor safetensors ({e})") from e
+        if "audio_prompt" not in t or t["audio_prompt"].size == 0 or t["audio_prompt"].shape[-1] != 1024:
+            raise ValueError("safetensors body needs an `audio_prompt` tensor [F x 1024]")
+        prompt = np.ascontiguousarray(t["audio_prompt"], np.float32).reshape(-1, 1024)
+        if self.max_ctx is not None and prompt.shape[0] >= self.max_ctx:
+            raise ValueError(f"audio_prompt of {prompt.shape[0]} frames does not fit the engine's context")
+        return VoiceClip(hashlib.blake2b(data, digest_size=16).digest(), prompt.shape[0], prompt=prompt)
+
+    def register_voice(self, name: str, data: bytes) -> int:
+        """POST /voices/{name}: clone `data` (WAV clip or safetensors audio_prompt) on every engine,
+        each on its scheduler thread, and register (or replace) the named voice. The registry owns
+        these voices: they are outside the LRU cache. Returns the voice's frames."""
+        if not _VOICE_NAME.fullmatch(name):
+            raise ValueError("voice name must be 1-64 characters of [A-Za-z0-9_.-]")
+        clip = self.wav_clip(data) if data[:4] == b"RIFF" else self.prompt_clip(data)
+        scheds = getattr(self.scheduler, "schedulers", None)
+        if scheds is None:
+            new = self.scheduler.call(lambda: clip.start(self.scheduler.engine))
+        else:
+            new = [s.call(lambda s=s: clip.start(s.engine)) for s in scheds]
+        with self._lock:
+            old, self.voices[name] = self.voices.get(name), new
+        if old is not None:  # closed once no queued request holds it; rows reading it keep it alive
+            if scheds is None:
+                self.scheduler.retire(old)
+            else:
+                for s, v in zip(scheds, old):
+                    s.retire(v)
+        return clip.n_frames
+
+    def voice_names(self) -> list[str]:
+        with self._lock:
+            return sorted(self.voices)
 
 
 from pydantic import BaseModel  # noqa: E402  (request bodies; module level so FastAPI resolves them)
@@ -646,6 +973,21 @@ def create_app(service: TTSService):
         stats = {"steps": sch.steps, "frames": sch.row_frames} if isinstance(sch, BatchScheduler) else {}
         return JSONResponse({"status": "healthy", "version": VERSION, "worker": worker, **stats}, headers=hdr)
 
+    @app.get("/voices")
+    def list_voices():
+        return JSONResponse({"voices": service.voice_names(), "default": service.default_voice}, headers=hdr)
+
+    @app.post("/voices/{name}")
+    async def register_voice(name: str, request: StarletteRequest):
+        from starlette.concurrency import run_in_threadpool
+
+        body = await request.body()
+        try:
+            frames = await run_in_threadpool(service.register_voice, name, body)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e)) from e
+        return JSONResponse({"voice": name, "frames": frames}, headers=hdr)
+
     @app.post("/generate")
     def generate(req: GenerateRequest, request: StarletteRequest):
         redirect = overflow(request)
@@ -707,6 +1049,34 @@ class StandInEngine:
         from types import SimpleNamespace
 
         return SimpleNamespace(n_frames=int(np.asarray(prompt).shape[0]))
+
+    class _Voice:
+        def __init__(self, n_frames):
+            self.n_frames, self.closed = int(n_frames), False
+
+        def ready(self, wait=False):
+            return True
+
+        def close(self):
+            self.closed = True
+
+    def voice_job(self, samples, sample_rate, chunk_frames=0, resampler="poly"):
+        """Counts the clones (voice_jobs) and checks what the engine checks on the host."""
+        x = np.asarray(samples)
+        if x.ndim != 1 or x.size < 1 or x.dtype not in (np.int16, np.float32) or sample_rate <= 0:
+            raise ValueError("voice_job: a mono int16 / float32 clip at a positive rate")
+        frames = clip_frames(x.size, sample_rate, "poly")
+        if frames >= self.max_ctx:
+            raise ValueError("voice prompt longer than max_ctx")
+        self.voice_jobs = getattr(self, "voice_jobs", 0) + 1
+        return self._Voice(frames)
+
+    def voice_job_prompt(self, prompt):
+        self.voice_jobs = getattr(self, "voice_jobs", 0) + 1
+        return self._Voice(np.asarray(prompt).reshape(-1, 1024).shape[0])
+
+    def reserve_voice_jobs(self, max_frames):
+        self.voice_frames_reserved = int(max_frames)
 
     def open_many(self, slots, voices, ids_list, params_list):
         for s, ids, p in zip(slots, ids_list, params_list):
@@ -837,6 +1207,10 @@ def main(argv=None):
                          "different counts share the batch; a step costs the largest count among its open rows")
     ap.add_argument("--preview-rows", type=int, default=8,
                     help="first-frame previews: rows per call whose first frame is decoded at once (0: off)")
+    ap.add_argument("--voice-cache", type=int, default=64,
+                    help="per-request voices (base64 WAV in the `voice` field) kept per engine, least recently used out")
+    ap.add_argument("--max-voice-seconds", type=float, default=30.0,
+                    help="longest voice clip a request or POST /voices may bring (also sizes the clone workspace)")
     ap.add_argument("--stand-in-engine", action="store_true",
                     help="CPU self-test of the launcher and routing: a stand-in engine that computes nothing")
     ap.add_argument("--stand-in-step-ms", type=float, default=0.0, help="--stand-in-engine: time per step")
@@ -882,10 +1256,13 @@ def main(argv=None):
             voices[name] = engine.voice_from_audio(audio[0], sr)
     if not voices:
         raise SystemExit("at least one --voice NAME=path is required")
-    scheduler = BatchScheduler(engine, preview_rows=args.preview_rows)
+    # the clone workspace of per-request voices, sized once for the longest clip accepted
+    engine.reserve_voice_jobs(max(1, min(args.max_ctx - 1, math.ceil(args.max_voice_seconds * SAMPLE_RATE / FRAME) + 1)))
+    scheduler = BatchScheduler(engine, preview_rows=args.preview_rows, voice_cache=args.voice_cache)
     service = TTSService(scheduler, voices, default_voice=next(iter(voices)),
                          tokenizer=load_tokenizer(args.tokenizer) if args.tokenizer else None,
-                         lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps)
+                         lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
+                         max_voice_seconds=args.max_voice_seconds)
     service.worker = {"rank": rank, "world": world, "pid": os.getpid(), "weights_checksum": checksum}
     socks = [_listen_socket(args.host, args.port)]
     board = None
