@@ -227,9 +227,8 @@ int ptts_voice_from_audio_ex(ptts_engine* e, const float* samples, int n_samples
 #define PTTS_SAMPLES_S16 1
 /* Enqueue a clone of a mono clip on the engine's voice stream and return at once. *out is usable in
  * ptts_slot_open / ptts_slots_open[_ex] immediately (the admission is ordered behind the job on the
- * GPU). Same conditioning as ptts_voice_from_audio_ex on the same samples (int16 samples: v / 32768), bit
- * for bit; the K/V prefix is equal up to the reduction order of the prefill's GEMMs (the job's
- * split-K slabs and tail scratch are sized for its workspace, not for the engine's batch).
+ * GPU). It is the clone ptts_voice_from_audio_ex makes, the same launches on another stream and
+ * workspace: the same conditioning on the same samples (int16 samples: v / 32768), bit for bit.
  * Does not drain the step pipeline nor touch its buffers. `samples` is read before the call returns. All
  * arguments are checked before anything is enqueued: a rejected job leaves *out NULL. */
 int ptts_voice_job_start(ptts_engine* e, const void* samples, int n_samples, int sample_format,

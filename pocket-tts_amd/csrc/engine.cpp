@@ -114,12 +114,12 @@ Engine::Engine(const ptts_engine_config& cfg) {
   const int B = max_slots_;
   kv_layer_ = (long)2 * NH * max_ctx_ * 64;
   kv_slot_ = kv_layer_ * NL;
-  kv_ = dalloc((size_t)kv_slot_ * (B + 1));
+  kv_ = dalloc((size_t)kv_slot_ * B);
   ring_layer_ = (long)2 * MNH * RING * 64;
   ring_slot_ = ring_layer_ * MNL;
   ring_ = dalloc((size_t)ring_slot_ * B);
-  fpos_ = (int*)dalloc(B + 1);
-  mpos_ = (int*)dalloc(B + 1);
+  fpos_ = (int*)dalloc(B);
+  mpos_ = (int*)dalloc(B);
   st_ = (SlotState*)dalloc((sizeof(SlotState) * B + 3) / 4);
   lat_in_ = dalloc((size_t)B * LDIM);
   cur_ = dalloc((size_t)B * LDIM);
@@ -189,8 +189,8 @@ Engine::Engine(const ptts_engine_config& cfg) {
   admit_slots_ = (int*)dalloc(B);
   admit_st_ = (SlotState*)dalloc((sizeof(SlotState) * B + 3) / 4);
   admit_fpos_ = (int*)dalloc(B);
-  vpre_ = (const float**)dalloc((sizeof(float*) * (B + 1) + 3) / 4);  // zero: no slot has a prefix
-  vlen_ = (int*)dalloc(B + 1);
+  vpre_ = (const float**)dalloc((sizeof(float*) * B + 3) / 4);  // zero: no slot has a prefix
+  vlen_ = (int*)dalloc(B);
   slot_voice_.assign(B, nullptr);
   drained_.assign(B, 1);
   admit_call_.assign(B, -1);
@@ -264,10 +264,10 @@ Engine::Engine(const ptts_engine_config& cfg) {
   PTTS_HIP(hipHostMalloc((void**)&h_fp_, sizeof(int) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_ids_, sizeof(int) * PREFILL, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_tab_, sizeof(int) * 4 * PREFILL, hipHostMallocDefault));  // ptab | ctab | qrow | orow
-  PTTS_HIP(hipHostMalloc((void**)&h_vpre_, sizeof(float*) * (B + 1), hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_vlen_, sizeof(int) * (B + 1), hipHostMallocDefault));
-  memset(h_vpre_, 0, sizeof(float*) * (B + 1));
-  memset(h_vlen_, 0, sizeof(int) * (B + 1));
+  PTTS_HIP(hipHostMalloc((void**)&h_vpre_, sizeof(float*) * B, hipHostMallocDefault));
+  PTTS_HIP(hipHostMalloc((void**)&h_vlen_, sizeof(int) * B, hipHostMallocDefault));
+  memset(h_vpre_, 0, sizeof(float*) * B);
+  memset(h_vlen_, 0, sizeof(int) * B);
   PTTS_HIP(hipStreamCreateWithFlags(&stream_be_, hipStreamNonBlocking));
   for (int q = 0; q < NHB; ++q) {
     PTTS_HIP(hipEventCreateWithFlags(&ev_front_[q], hipEventDisableTiming));
@@ -337,10 +337,7 @@ Engine::~Engine() {
   for (hipEvent_t e : ev_call_)
     if (e) (void)hipEventDestroy(e);
   if (stream_be_) (void)hipStreamDestroy(stream_be_);
-  vws_free();
-  if (vws_.up) (void)hipFree(vws_.up);
-  for (char* h : vws_.h_up)
-    if (h) (void)hipHostFree(h);
+  vws_free(vws_);
   for (hipEvent_t e : vws_.ev_up)
     if (e) (void)hipEventDestroy(e);
   if (stream_vc_) (void)hipStreamDestroy(stream_vc_);
@@ -613,7 +610,7 @@ void Engine::finalize() {
 }
 
 void Engine::run_ops(const std::vector<Op>& ops) {
-  xh_dirty_ = true;  // eager passes (prefills, encoder) use x_ / h_ as scratch
+  xh_dirty_ = true;  // the admission's text prefill uses x_ / h_ as scratch
   run_ops_on(ops, stream_);
 }
 
@@ -2322,36 +2319,6 @@ void Engine::overlap_probe(int B, int reps, double* us) {
 }
 
 // ------------------------------------------------------------------ voices and slots
-ptts_voice* Engine::voice_from_prompt(const float* prompt, int F) {
-  PTTS_REQUIRE(ready_, "engine weights not finalized");
-  PTTS_REQUIRE(prompt != nullptr && F >= 1, "empty prompt");
-  PTTS_REQUIRE(F < max_ctx_, "prompt longer than max_ctx");
-  sync();
-  const int scratch = max_slots_;
-  for (int c0 = 0; c0 < F; c0 += PREFILL) {
-    const int T = std::min(PREFILL, F - c0);
-    PTTS_HIP(hipMemcpyAsync(x_, prompt + (size_t)c0 * D, sizeof(float) * T * D, hipMemcpyHostToDevice, stream_));
-    std::vector<Op> ops;
-    prefill_rows(ops, scratch, T, c0);
-    run_ops(ops);
-  }
-  ptts_voice* v = new ptts_voice();
-  v->F = F;
-  v->owner = this;
-  try {
-    PTTS_HIP(hipMalloc(&v->kv, sizeof(float) * (size_t)NL * 2 * NH * F * 64));
-    PTTS_HIP(hipMemcpy2DAsync(v->kv, sizeof(float) * F * 64, kv_ + (size_t)scratch * kv_slot_,
-                              sizeof(float) * max_ctx_ * 64, sizeof(float) * F * 64, NL * 2 * NH,
-                              hipMemcpyDeviceToDevice, stream_));
-    PTTS_HIP(hipStreamSynchronize(stream_));
-  } catch (...) {
-    if (v->kv) (void)hipFree(v->kv);
-    delete v;
-    throw;
-  }
-  return v;
-}
-
 void Engine::encoder_transformer(std::vector<Op>& ops, float* x, int T, float* h, float* qkv, float* q, float* o,
                                  float* u, float* ring) {
   RowMap map{0, T, 0, nullptr};
@@ -2387,6 +2354,50 @@ int voice_chunk_frames(int F, int override_frames) {
   if (F <= 600) return 120;
   if (F <= 1800) return 180;
   return 240;
+}
+size_t al16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+}  // namespace
+
+// What the host works out about a clip before a clone is enqueued
+struct VoicePlan {
+  int n_in = 0, s16 = 0;
+  ResamplePlan rp{};
+  bool septic = false;       // the rubato rule (identity rates take neither resampler)
+  std::vector<float> taps;   // polyphase rule
+  std::vector<int> sst;      // rubato position schedule
+  std::vector<float> sfr;
+  int n = 0, Np = 0, F = 0, Te = 0, cf = 0;  // 24 kHz samples, frame-padded samples, frames, encoder rows, chunk frames
+  // the upload (VoiceWs::up): samples | taps | rubato start | rubato frac | on the device: o_fx
+  size_t o_taps = 0, o_st = 0, o_fr = 0, o_fx = 0, up_bytes = 0, dev_bytes = 0;
+};
+
+namespace {
+VoicePlan voice_plan(int n_in, int fmt, int sr, int chunk_frames, int resampler, int max_ctx) {
+  PTTS_REQUIRE(n_in >= 1, "empty PCM");
+  PTTS_REQUIRE(fmt == PTTS_SAMPLES_F32 || fmt == PTTS_SAMPLES_S16, "unknown sample format");
+  PTTS_REQUIRE(sr > 0, "sample rate must be positive");
+  PTTS_REQUIRE(resampler == PTTS_RESAMPLE_POLY || resampler == PTTS_RESAMPLE_RUBATO_SEPTIC, "unknown resampler");
+  VoicePlan p;
+  p.n_in = n_in;
+  p.s16 = fmt == PTTS_SAMPLES_S16 ? 1 : 0;
+  p.rp = resample_plan(sr, PTTS_SAMPLE_RATE);
+  p.septic = resampler == PTTS_RESAMPLE_RUBATO_SEPTIC && !p.rp.identity();
+  const long n_long = p.rp.identity() ? n_in : p.septic ? septic_schedule(n_in, sr, PTTS_SAMPLE_RATE, &p.sst, &p.sfr)
+                                                        : p.rp.out_len(n_in);
+  PTTS_REQUIRE(n_long >= 1 && n_long < (1L << 28) && p.rp.L <= (1 << 22), "voice prompt length or rate out of range");
+  p.n = (int)n_long;
+  p.Np = (p.n + FRAME - 1) / FRAME * FRAME;  // zero-pad to whole frames (mimi.py:103)
+  p.F = p.Np / FRAME, p.Te = p.Np / 120;
+  PTTS_REQUIRE(p.F < max_ctx, "voice prompt longer than max_ctx");
+  p.cf = voice_chunk_frames(p.F, chunk_frames);
+  if (!p.septic && !p.rp.identity()) p.taps = resample_taps(p.rp);
+  p.o_taps = al16((size_t)n_in * (p.s16 ? 2 : 4));
+  p.o_st = p.o_taps + al16(p.taps.size() * sizeof(float));
+  p.o_fr = p.o_st + al16(p.sst.size() * sizeof(int));
+  p.up_bytes = p.o_fr + al16(p.sfr.size() * sizeof(float));
+  p.o_fx = p.up_bytes;
+  p.dev_bytes = p.up_bytes + (p.septic ? al16((size_t)n_in * sizeof(float)) : 0);
+  return p;
 }
 }  // namespace
 
@@ -2437,139 +2448,15 @@ void Engine::resample_host(const float* x, int n, int sr_from, int sr_to, float*
   (void)hipFree(dx), (void)hipFree(dh), (void)hipFree(dy), (void)hipFree(ds);
 }
 
-// Voice cloning (tts_model.rs:428-577): samples at `sr` -> resampled to 24 kHz on the GPU
-// (resample_poly rule, kernels.h) -> zero-padded to whole frames (tts_model.rs:515-527) -> Mimi
-// encoder (mimi.rs:113-141) -> speaker projection (:543-553) -> FlowLM prompt prefill (:580-599).
-// The reference encodes chunk by chunk (adaptive chunk length, :530-541) with step=0 for every
-// chunk: the streaming convs and the encoder transformer carry their state, which equals the
-// single pass below, but ConvDownsample1d re-applies its replicate padding at each chunk's first
-// frame (conv.rs:116-123); the downsample conv is therefore run per chunk.
-ptts_voice* Engine::voice_from_audio(const float* pcm_in, int n_in, int sr, int chunk_frames, int resampler) {
-  PTTS_REQUIRE(ready_, "engine weights not finalized");
-  PTTS_REQUIRE(pcm_in != nullptr && n_in >= 1, "empty PCM");
-  PTTS_REQUIRE(sr > 0, "sample rate must be positive");
-  PTTS_REQUIRE(resampler == PTTS_RESAMPLE_POLY || resampler == PTTS_RESAMPLE_RUBATO_SEPTIC, "unknown resampler");
-  const ResamplePlan rp = resample_plan(sr, PTTS_SAMPLE_RATE);
-  const bool septic = resampler == PTTS_RESAMPLE_RUBATO_SEPTIC && !rp.identity();
-  std::vector<int> sst;  // rubato position schedule (host copies outlive the async uploads)
-  std::vector<float> sfr;
-  const long n_long = rp.identity() ? n_in : septic ? septic_schedule(n_in, sr, PTTS_SAMPLE_RATE, &sst, &sfr)
-                                                    : rp.out_len(n_in);
-  PTTS_REQUIRE(n_long >= 1 && n_long < (1L << 28) && rp.L <= (1 << 22), "voice prompt length or rate out of range");
-  const int n = (int)n_long;
-  sync();
-  const int Np = (n + FRAME - 1) / FRAME * FRAME;  // zero-pad to whole frames (mimi.py:103)
-  const int F = Np / FRAME, Te = Np / 120;
-  PTTS_REQUIRE(F < max_ctx_, "voice prompt longer than max_ctx");
-  const int cf = voice_chunk_frames(F, chunk_frames);
-  std::vector<void*> tmp;
-  auto talloc = [&](size_t cnt) {
-    void* p = nullptr;
-    PTTS_HIP(hipMalloc(&p, std::max<size_t>(cnt, 1) * sizeof(float)));
-    tmp.push_back(p);
-    return (float*)p;
-  };
-  ptts_voice* v = nullptr;
-  try {
-    float* dpcm = talloc(Np);
-    float* A = talloc((size_t)Np * 64);
-    float* Bf = talloc((size_t)Np * 64);
-    float* V = talloc((size_t)Np * 32);
-    float* zeros = talloc(16 * 512);
-    PTTS_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * 16 * 512, stream_));
-    std::vector<float> taps;  // host copy must outlive the async upload
-    if (rp.identity()) {
-      PTTS_HIP(hipMemsetAsync(dpcm, 0, sizeof(float) * Np, stream_));
-      PTTS_HIP(hipMemcpyAsync(dpcm, pcm_in, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
-    } else if (septic) {  // the Rust driver's resampler, straight into the frame-padded input
-      float* dx = talloc(n_in);
-      int* ds = (int*)talloc(n);
-      float* df = talloc(n);
-      PTTS_HIP(hipMemcpyAsync(dx, pcm_in, sizeof(float) * n_in, hipMemcpyHostToDevice, stream_));
-      PTTS_HIP(hipMemcpyAsync(ds, sst.data(), sizeof(int) * n, hipMemcpyHostToDevice, stream_));
-      PTTS_HIP(hipMemcpyAsync(df, sfr.data(), sizeof(float) * n, hipMemcpyHostToDevice, stream_));
-      resample_septic(dx, n_in, ds, df, n, Np, dpcm, stream_);
-      PTTS_HIP(hipGetLastError());
-    } else {  // resample straight into the frame-padded encoder input (zeros past n)
-      taps = resample_taps(rp);
-      float* dx = talloc(n_in);
-      float* dh = talloc(taps.size());
-      PTTS_HIP(hipMemcpyAsync(dx, pcm_in, sizeof(float) * n_in, hipMemcpyHostToDevice, stream_));
-      PTTS_HIP(hipMemcpyAsync(dh, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice, stream_));
-      resample(dx, n_in, dh, rp, n, Np, dpcm, stream_);
-      PTTS_HIP(hipGetLastError());
-    }
-    std::vector<Op> ops;
-    {
-      const float *w = W(L_.ec0_w), *b = W(L_.ec0_b);
-      ops.push_back({"enc.conv0", [=](hipStream_t s) { conv_cin1(dpcm, Np, 64, 7, w, b, A, s); }});
-    }
-    int T = Np, ch = 64;
-    for (int i = 0; i < 3; ++i) {
-      const int r = RATIOS[2 - i];
-      conv_op(ops, "enc.res_conv3", A, 1, T, ch, zeros, 2, 1, 1, W(L_.era_w[i]), ch / 2, 3, 1, W(L_.era_b[i]),
-              nullptr, V, T, 1);
-      conv_op(ops, "enc.res_conv1", V, 1, T, ch / 2, nullptr, 0, 1, 1, W(L_.erb_w[i]), ch, 1, 1, W(L_.erb_b[i]), A,
-              Bf, T, 1);
-      conv_op(ops, "enc.down", Bf, 1, T, ch, zeros, r, r, 1, W(L_.edn_w[i]), 2 * ch, 2 * r, 1, W(L_.edn_b[i]),
-              nullptr, A, T / r, 1);
-      T /= r;
-      ch *= 2;
-    }
-    conv_op(ops, "enc.conv_final", A, 1, T, 512, zeros, 2, 1, 1, W(L_.efin_w), 512, 3, 1, W(L_.efin_b), nullptr, Bf,
-            T, 1);
-    // encoder transformer on Bf rows [Te][512]
-    float* h = talloc((size_t)Te * MD);
-    float* qkv = talloc((size_t)Te * 3 * MD);
-    float* q = talloc((size_t)Te * MD);
-    float* o = talloc((size_t)Te * MD);
-    float* u = talloc((size_t)Te * MFF);
-    float* ring = talloc((size_t)MNL * 2 * MNH * Te * 64);
-    encoder_transformer(ops, Bf, Te, h, qkv, q, o, u, ring);
-    // ConvDownsample1d k32 s16 per chunk of cf frames, each with the replicate padding of its first
-    // frame (conv.rs:116-123): full chunks run as one batched implicit GEMM (chunk = batch row,
-    // history = that chunk's replicated first row), a shorter last chunk as a second launch.
-    const int nfull = F / cf, rem = F - nfull * cf, nch = nfull + (rem ? 1 : 0);
-    float* Hd = talloc((size_t)nch * 16 * 512);
-    for (int c = 0; c < nch; ++c) {
-      const float* src = Bf + (size_t)c * cf * 16 * 512;
-      float* dst = Hd + (size_t)c * 16 * 512;
-      ops.push_back({"enc.replicate", [=](hipStream_t s) { copy2d(src, 0, dst, 512, 16, 512, s); }});
-    }
-    float* lat = talloc((size_t)F * 512);
-    if (nfull)
-      conv_op(ops, "enc.downsample", Bf, nfull, cf * 16, 512, Hd, 16, 16, 0, W(L_.down_w), 512, 32, 1, nullptr,
-              nullptr, lat, cf, 1);
-    if (rem)
-      conv_op(ops, "enc.downsample", Bf + (size_t)nfull * cf * 16 * 512, 1, rem * 16, 512,
-              Hd + (size_t)nfull * 16 * 512, 16, 16, 0, W(L_.down_w), 512, 32, 1, nullptr, nullptr,
-              lat + (size_t)nfull * cf * 512, rem, 1);
-    float* cond = talloc((size_t)F * D);
-    dense_op(ops, "enc.speaker_proj", lat, F, W(L_.speaker_proj), D, MD, nullptr, ACT_NONE, nullptr, nullptr, cond);
-    run_ops(ops);
-    std::vector<float> hcond((size_t)F * D);
-    PTTS_HIP(hipMemcpyAsync(hcond.data(), cond, sizeof(float) * hcond.size(), hipMemcpyDeviceToHost, stream_));
-    PTTS_HIP(hipStreamSynchronize(stream_));
-    for (void* p : tmp) (void)hipFree(p);
-    tmp.clear();
-    v = voice_from_prompt(hcond.data(), F);
-    v->cond = std::move(hcond);
-  } catch (...) {
-    (void)hipStreamSynchronize(stream_);
-    for (void* p : tmp) (void)hipFree(p);
-    throw;
-  }
-  return v;
-}
-
-// ------------------------------------------------------------------ voice jobs
-// The same clone as voice_from_audio / voice_from_prompt, enqueued on stream_vc_ (lowest priority,
-// plain launches of non-persistent kernels) with a workspace of its own, so it neither drains nor
-// touches the step pipeline: no sync(), no allocation but the voice's own, nothing written outside
-// VoiceWs and the voice. The prompt prefill appends K/V straight into the voice's compact cache.
-// slots_open orders the front stream behind the job's event.
+// ------------------------------------------------------------------ voice cloning
+// One clone, two ways of calling it: samples at `sr` -> resampled to 24 kHz
+// on the GPU -> zero-padded to whole frames (tts_model.rs:515-527) -> Mimi encoder (mimi.rs:113-141)
+// -> speaker projection (:543-553) -> FlowLM prompt prefill (:580-599) into the voice's compact
+// cache. voice_clone enqueues it on the stream, in the VoiceWs, it is given. voice_from_* drain the
+// pipeline, run it on stream_ in a transient workspace and wait; voice_job_* run it on stream_vc_
+// in the grow-only vws_, staged through pinned memory, with no sync() and no allocation but the
+// voice's own (slots_open orders the front stream behind the job's event).
 namespace {
-size_t al16(size_t bytes) { return (bytes + 15) / 16 * 16; }
 void free_voice(ptts_voice* v) {
   if (v->ev) {  // a pending job still writes the cache and the pinned conditioning
     (void)hipEventSynchronize(v->ev);
@@ -2581,103 +2468,88 @@ void free_voice(ptts_voice* v) {
 }
 }  // namespace
 
-void Engine::vws_free() {
-  VoiceWs& w = vws_;
-  for (void* p : w.allocs) (void)hipFree(p);
-  w.allocs.clear();
-  w.frames = 0;
+void Engine::vws_free(VoiceWs& w) {
+  if (w.block) (void)hipFree(w.block);
+  if (w.up) (void)hipFree(w.up);
+  for (char*& h : w.h_up)
+    if (h) (void)hipHostFree(h), h = nullptr;
+  w.block = nullptr, w.up = nullptr;
+  w.frames = 0, w.up_bytes = 0, w.h_bytes = 0;
 }
 
-// Grow-only. A longer clip (or a larger upload) than any before re-allocates, after the jobs
-// already queued have run: the only point at which the voice stream is synchronized.
-void Engine::vws_reserve(int frames, size_t host_bytes, size_t up_bytes) {
-  VoiceWs& w = vws_;
-  if (!stream_vc_) {
-    int least = 0, greatest = 0;
-    PTTS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    PTTS_HIP(hipStreamCreateWithPriority(&stream_vc_, hipStreamNonBlocking, least));
-    for (hipEvent_t& e : w.ev_up) PTTS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+// Grow-only. A longer clip (or a larger upload) than any before re-allocates the workspace at the
+// larger sizes, after the work already queued on `st` (the stream that uses the workspace) has
+// run: the only point at which a voice job synchronizes its stream. host_bytes 0 (synchronous
+// clones): no pinned staging blocks.
+void Engine::vws_reserve(VoiceWs& w, hipStream_t st, int frames, size_t host_bytes, size_t up_bytes) {
   if (frames <= w.frames && host_bytes <= w.h_bytes && up_bytes <= w.up_bytes) return;
-  PTTS_HIP(hipStreamSynchronize(stream_vc_));
-  if (host_bytes > w.h_bytes) {  // the two pinned staging blocks
-    for (char*& h : w.h_up)
-      if (h) (void)hipHostFree(h), h = nullptr;
-    w.h_bytes = 0;
+  PTTS_HIP(hipStreamSynchronize(st));
+  frames = std::max(frames, w.frames), host_bytes = std::max(host_bytes, w.h_bytes);
+  up_bytes = std::max(up_bytes, w.up_bytes);
+  vws_free(w);
+  if (host_bytes)  // the two pinned staging blocks
     for (char*& h : w.h_up) PTTS_HIP(hipHostMalloc((void**)&h, host_bytes, hipHostMallocDefault));
-    w.h_bytes = host_bytes;
-  }
-  if (up_bytes > w.up_bytes) {  // the device block: the upload, then the converted clip (rubato rule)
-    if (w.up) (void)hipFree(w.up);
-    w.up = nullptr;
-    w.up_bytes = 0;
-    PTTS_HIP(hipMalloc((void**)&w.up, up_bytes));
-    w.up_bytes = up_bytes;
-  }
-  if (frames <= w.frames) return;
-  vws_free();
-  auto alloc = [&](size_t cnt) {
-    void* p = nullptr;
-    PTTS_HIP(hipMalloc(&p, std::max<size_t>(cnt, 1) * sizeof(float)));
-    w.allocs.push_back(p);
-    return (float*)p;
+  w.h_bytes = host_bytes;
+  // the device block: the upload, then the converted clip (rubato rule)
+  if (up_bytes) PTTS_HIP(hipMalloc((void**)&w.up, up_bytes));
+  w.up_bytes = up_bytes;
+  // one allocation, carved in 256-byte steps: first pass sizes it, second pass hands out the pointers
+  size_t off = 0;
+  auto take = [&](size_t cnt) {
+    float* p = w.block ? w.block + off : nullptr;
+    off += (std::max<size_t>(cnt, 1) + 63) / 64 * 64;
+    return p;
   };
-  try {
+  FlowBufs& b = w.fb;
+  auto carve = [&] {
     const size_t Fc = (size_t)frames, Np = Fc * FRAME, Te = Fc * 16;
-    w.pcm = alloc(Np);
-    w.A = alloc(Np * 64);
-    w.Bf = alloc(Np * 64);
-    w.V = alloc(Np * 32);
-    w.zeros = alloc(16 * 512);
-    w.eh = alloc(Te * MD);
-    w.eqkv = alloc(Te * 3 * MD);
-    w.eq = alloc(Te * MD);
-    w.eo = alloc(Te * MD);
-    w.eu = alloc(Te * MFF);
-    w.ering = alloc((size_t)MNL * 2 * MNH * Te * 64);
-    w.Hd = alloc(Fc * 16 * 512);  // one replicated row block per chunk, chunks of >= 1 frame
-    w.lat = alloc(Fc * 512);
+    w.pcm = take(Np);
+    w.A = take(Np * 64);
+    w.Bf = take(Np * 64);
+    w.V = take(Np * 32);
+    w.zeros = take(16 * 512);
+    w.eh = take(Te * MD);
+    w.eqkv = take(Te * 3 * MD);
+    w.eq = take(Te * MD);
+    w.eo = take(Te * MD);
+    w.eu = take(Te * MFF);
+    w.ering = take((size_t)MNL * 2 * MNH * Te * 64);
+    w.Hd = take(Fc * 16 * 512);  // one replicated row block per chunk, chunks of >= 1 frame
+    w.lat = take(Fc * 512);
     const size_t R = (Fc + 15) / 16 * 16, Rp = std::min<size_t>(R, PREFILL);
-    FlowBufs& b = w.fb;
-    b.x = alloc(R * D);  // the conditioning rows (the speaker projection's output), then the residual stream
+    b.x = take(R * D);  // the conditioning rows (the speaker projection's output), then the residual stream
     w.cond = b.x;
-    b.h = alloc(Rp * D);
-    b.q = alloc(Rp * D);
-    b.o = alloc(Rp * D);
-    b.u = alloc(Rp * FF);
+    b.h = take(Rp * D);
+    b.q = take(Rp * D);
+    b.o = take(Rp * D);
+    b.u = take(Rp * FF);
     // the slabs of a pass of < 256 rows, or the one [rows][FF] block of a longer one (linear_split)
     b.pcap = std::max((size_t)4 << 20, Rp * FF);
-    b.partial = alloc(b.pcap);
+    b.partial = take(b.pcap);
     // split-tail scratch of the passes of >= 256 rows: at most 64 N tiles per 128 rows, 4 slices
     b.tail_cap = Fc < 256 ? 0 : (long)std::min<size_t>(TAIL_CAP, (Fc + 127) / 128 * 64 * 4 * 128 * 64);
-    b.tslab = alloc((size_t)b.tail_cap);
-    b.tickets = (int*)alloc(TICKETS);
-    PTTS_HIP(hipMemsetAsync(w.zeros, 0, sizeof(float) * 16 * 512, stream_vc_));
-    PTTS_HIP(hipMemsetAsync(b.tickets, 0, sizeof(int) * TICKETS, stream_vc_));  // every launch leaves them zero
-    w.frames = frames;
-  } catch (...) {
-    vws_free();
-    throw;
-  }
+    b.tslab = take((size_t)b.tail_cap);
+    b.tickets = (int*)take(TICKETS);
+  };
+  carve();
+  PTTS_HIP(hipMalloc((void**)&w.block, off * sizeof(float)));
+  off = 0;
+  carve();
+  PTTS_HIP(hipMemsetAsync(w.zeros, 0, sizeof(float) * 16 * 512, st));
+  PTTS_HIP(hipMemsetAsync(b.tickets, 0, sizeof(int) * TICKETS, st));  // every launch leaves them zero
+  w.frames = frames;
 }
 
-void Engine::voice_jobs_reserve(int max_frames) {
-  PTTS_REQUIRE(ready_, "engine weights not finalized");
-  PTTS_REQUIRE(max_frames >= 1 && max_frames < max_ctx_, "max_frames must be in [1, max_ctx)");
-  PTTS_HIP(hipSetDevice(dev_));
-  // uploads of float32 clips at up to twice the model's rate, plus the resampler's tables
-  const size_t up = al16((size_t)max_frames * FRAME * 2 * sizeof(float)) + (64 << 10);
-  vws_reserve(max_frames, up, up);
-}
-
-ptts_voice* Engine::voice_job_new(int F, bool pcm) {
+// The voice's own allocations (a job's: its event, and pinned memory for a PCM voice's conditioning)
+ptts_voice* Engine::voice_new(int F, bool pcm, bool job) {
   ptts_voice* v = new ptts_voice();
   v->F = F;
   v->owner = this;
   try {
     PTTS_HIP(hipMalloc(&v->kv, sizeof(float) * (size_t)NL * 2 * NH * F * 64));
-    if (pcm) PTTS_HIP(hipHostMalloc((void**)&v->h_cond, sizeof(float) * (size_t)F * D, hipHostMallocDefault));
-    PTTS_HIP(hipEventCreateWithFlags(&v->ev, hipEventDisableTiming));
+    if (pcm && job) PTTS_HIP(hipHostMalloc((void**)&v->h_cond, sizeof(float) * (size_t)F * D, hipHostMallocDefault));
+    if (pcm && !job) v->cond.resize((size_t)F * D);
+    if (job) PTTS_HIP(hipEventCreateWithFlags(&v->ev, hipEventDisableTiming));
   } catch (...) {
     free_voice(v);
     throw;
@@ -2685,97 +2557,24 @@ ptts_voice* Engine::voice_job_new(int F, bool pcm) {
   return v;
 }
 
-void Engine::voice_job_finish(ptts_voice* v, bool copy_cond) {
-  const VoiceWs& w = vws_;
+// The clone of the clip uploaded to w.up (plan p), or with p == nullptr only the prompt prefill of
+// the v->F conditioning rows already in w.fb.x; everything on `st`. h_cond: where the conditioning
+// rows are copied (nullptr: nowhere). Records v->ev behind it all when the voice has one.
+// The reference encodes chunk by chunk (adaptive chunk length, tts_model.rs:530-541) with step=0
+// for every chunk: the streaming convs and the encoder transformer carry their state, which equals
+// the single pass below, but ConvDownsample1d re-applies its replicate padding at each chunk's
+// first frame (conv.rs:116-123); the downsample conv is therefore run per chunk.
+void Engine::voice_clone(const VoicePlan* p, const VoiceWs& w, hipStream_t st, ptts_voice* v, float* h_cond) {
   const int F = v->F;
-  if (copy_cond)  // ahead of the prefill, which turns the rows into the residual stream in place
-    PTTS_HIP(hipMemcpyAsync(v->h_cond, w.cond, sizeof(float) * (size_t)F * D, hipMemcpyDeviceToHost, stream_vc_));
-  for (int c0 = 0; c0 < F; c0 += PREFILL) {
-    const int T = std::min(PREFILL, F - c0);
-    FlowBufs b = w.fb;
-    b.x = w.fb.x + (size_t)c0 * D;
-    b.kv = KvStore{v->kv, 0, F};  // the voice's own compact cache [NL][2][NH][F][64]
-    b.kv_layer = (long)2 * NH * F * 64;
-    std::vector<Op> ops;
-    prefill_rows(ops, 0, T, c0, &b);
-    run_ops_on(ops, stream_vc_);
-  }
-  PTTS_HIP(hipEventRecord(v->ev, stream_vc_));
-}
-
-ptts_voice* Engine::voice_job_prompt(const float* prompt, int F) {
-  PTTS_REQUIRE(ready_, "engine weights not finalized");
-  PTTS_REQUIRE(prompt != nullptr && F >= 1, "empty prompt");
-  PTTS_REQUIRE(F < max_ctx_, "prompt longer than max_ctx");
-  PTTS_HIP(hipSetDevice(dev_));
-  const size_t bytes = sizeof(float) * (size_t)F * D;
-  vws_reserve(std::max(F, vws_.frames), bytes, 0);  // staged in pinned memory, uploaded straight into x
-  ptts_voice* v = voice_job_new(F, false);
-  try {
-    VoiceWs& w = vws_;
-    const int par = (int)(vjobs_ & 1);
-    PTTS_HIP(hipEventSynchronize(w.ev_up[par]));  // the staging block's previous upload (two jobs back)
-    memcpy(w.h_up[par], prompt, bytes);
-    PTTS_HIP(hipMemcpyAsync(w.fb.x, w.h_up[par], bytes, hipMemcpyHostToDevice, stream_vc_));
-    PTTS_HIP(hipEventRecord(w.ev_up[par], stream_vc_));
-    ++vjobs_;
-    voice_job_finish(v, false);
-  } catch (...) {
-    (void)hipStreamSynchronize(stream_vc_);
-    free_voice(v);
-    throw;
-  }
-  return v;
-}
-
-ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int sr, int chunk_frames, int resampler) {
-  PTTS_REQUIRE(ready_, "engine weights not finalized");
-  PTTS_REQUIRE(samples != nullptr && n_in >= 1, "empty PCM");
-  PTTS_REQUIRE(fmt == PTTS_SAMPLES_F32 || fmt == PTTS_SAMPLES_S16, "unknown sample format");
-  PTTS_REQUIRE(sr > 0, "sample rate must be positive");
-  PTTS_REQUIRE(resampler == PTTS_RESAMPLE_POLY || resampler == PTTS_RESAMPLE_RUBATO_SEPTIC, "unknown resampler");
-  const ResamplePlan rp = resample_plan(sr, PTTS_SAMPLE_RATE);
-  const bool septic = resampler == PTTS_RESAMPLE_RUBATO_SEPTIC && !rp.identity();
-  std::vector<int> sst;
-  std::vector<float> sfr;
-  const long n_long = rp.identity() ? n_in : septic ? septic_schedule(n_in, sr, PTTS_SAMPLE_RATE, &sst, &sfr)
-                                                    : rp.out_len(n_in);
-  PTTS_REQUIRE(n_long >= 1 && n_long < (1L << 28) && rp.L <= (1 << 22), "voice prompt length or rate out of range");
-  const int n = (int)n_long;
-  const int Np = (n + FRAME - 1) / FRAME * FRAME;
-  const int F = Np / FRAME, Te = Np / 120;
-  PTTS_REQUIRE(F < max_ctx_, "voice prompt longer than max_ctx");
-  const int cf = voice_chunk_frames(F, chunk_frames);
-  std::vector<float> taps;
-  if (!septic && !rp.identity()) taps = resample_taps(rp);
-  // the job's single upload: samples | taps | rubato start | rubato frac
-  const size_t bps = fmt == PTTS_SAMPLES_S16 ? 2 : 4;
-  const size_t o_taps = al16((size_t)n_in * bps), o_st = o_taps + al16(taps.size() * sizeof(float)),
-               o_fr = o_st + al16(sst.size() * sizeof(int)), up_bytes = o_fr + al16(sfr.size() * sizeof(float)),
-               o_fx = up_bytes, dev_bytes = up_bytes + (septic ? al16((size_t)n_in * sizeof(float)) : 0);
-  PTTS_HIP(hipSetDevice(dev_));
-  vws_reserve(std::max(F, vws_.frames), up_bytes, dev_bytes);
-  ptts_voice* v = voice_job_new(F, true);
-  try {
-    VoiceWs& w = vws_;
-    const int par = (int)(vjobs_ & 1);
-    PTTS_HIP(hipEventSynchronize(w.ev_up[par]));  // the staging block's previous upload (two jobs back)
-    char* hs = w.h_up[par];
-    memcpy(hs, samples, (size_t)n_in * bps);
-    if (!taps.empty()) memcpy(hs + o_taps, taps.data(), taps.size() * sizeof(float));
-    if (!sst.empty()) memcpy(hs + o_st, sst.data(), sst.size() * sizeof(int));
-    if (!sfr.empty()) memcpy(hs + o_fr, sfr.data(), sfr.size() * sizeof(float));
-    PTTS_HIP(hipMemcpyAsync(w.up, hs, up_bytes, hipMemcpyHostToDevice, stream_vc_));
-    PTTS_HIP(hipEventRecord(w.ev_up[par], stream_vc_));
-    ++vjobs_;
-    const int s16 = fmt == PTTS_SAMPLES_S16 ? 1 : 0;
+  if (p) {
+    const int n_in = p->n_in, n = p->n, Np = p->Np, Te = p->Te, cf = p->cf;
     float* dpcm = w.pcm;
-    if (septic) {  // the rubato rule keeps its kernel, fed by a converting copy
-      float* fx = (float*)(w.up + o_fx);  // behind the upload, in the same device block
-      voice_ingest(w.up, s16, n_in, nullptr, ResamplePlan{}, n_in, n_in, fx, stream_vc_);
-      resample_septic(fx, n_in, (const int*)(w.up + o_st), (const float*)(w.up + o_fr), n, Np, dpcm, stream_vc_);
+    if (p->septic) {  // the rubato rule keeps its kernel, fed by a converting copy
+      float* fx = (float*)(w.up + p->o_fx);  // behind the upload, in the same device block
+      voice_ingest(w.up, p->s16, n_in, nullptr, ResamplePlan{}, n_in, n_in, fx, st);
+      resample_septic(fx, n_in, (const int*)(w.up + p->o_st), (const float*)(w.up + p->o_fr), n, Np, dpcm, st);
     } else {  // convert + polyphase rule + zero padding in one launch
-      voice_ingest(w.up, s16, n_in, (const float*)(w.up + o_taps), rp, n, Np, dpcm, stream_vc_);
+      voice_ingest(w.up, p->s16, n_in, (const float*)(w.up + p->o_taps), p->rp, n, Np, dpcm, st);
     }
     PTTS_HIP(hipGetLastError());
     std::vector<Op> ops;
@@ -2798,9 +2597,11 @@ ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int 
     }
     conv_op(ops, "enc.conv_final", A, 1, T, 512, zeros, 2, 1, 1, W(L_.efin_w), 512, 3, 1, W(L_.efin_b), nullptr, Bf,
             T, 1);
-    encoder_transformer(ops, Bf, Te, w.eh, w.eqkv, w.eq, w.eo, w.eu, w.ering);
-    // ConvDownsample1d per chunk of cf frames (voice_from_audio), the chunks' replicated first rows
-    // written by ONE launch
+    encoder_transformer(ops, Bf, Te, w.eh, w.eqkv, w.eq, w.eo, w.eu, w.ering);  // on Bf rows [Te][512]
+    // ConvDownsample1d k32 s16 per chunk of cf frames, each with the replicate padding of its first
+    // frame: one launch writes every chunk's replicated first row, full chunks run as one batched
+    // implicit GEMM (chunk = batch row, history = that chunk's rows), a shorter last chunk as a
+    // second launch.
     const int nfull = F / cf, rem = F - nfull * cf, nch = nfull + (rem ? 1 : 0);
     float *Hd = w.Hd, *lat = w.lat;
     ops.push_back({"enc.replicate", [=](hipStream_t s) { replicate_chunks(Bf, (long)cf * 16 * 512, Hd, nch, 16, 512, s); }});
@@ -2812,14 +2613,127 @@ ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int 
               Hd + (size_t)nfull * 16 * 512, 16, 16, 0, W(L_.down_w), 512, 32, 1, nullptr, nullptr,
               lat + (size_t)nfull * cf * 512, rem, 1);
     dense_op(ops, "enc.speaker_proj", lat, F, W(L_.speaker_proj), D, MD, nullptr, ACT_NONE, nullptr, nullptr, w.cond);
-    run_ops_on(ops, stream_vc_);
-    voice_job_finish(v, true);
+    run_ops_on(ops, st);
+    if (h_cond)  // ahead of the prefill, which turns the rows into the residual stream in place
+      PTTS_HIP(hipMemcpyAsync(h_cond, w.cond, sizeof(float) * (size_t)F * D, hipMemcpyDeviceToHost, st));
+  }
+  for (int c0 = 0; c0 < F; c0 += PREFILL) {
+    const int T = std::min(PREFILL, F - c0);
+    FlowBufs b = w.fb;
+    b.x = w.fb.x + (size_t)c0 * D;
+    b.kv = KvStore{v->kv, 0, F};  // the voice's own compact cache [NL][2][NH][F][64]
+    b.kv_layer = (long)2 * NH * F * 64;
+    std::vector<Op> ops;
+    prefill_rows(ops, 0, T, c0, &b);
+    run_ops_on(ops, st);
+  }
+  if (v->ev) PTTS_HIP(hipEventRecord(v->ev, st));
+}
+
+// The synchronous call: p (and the caller's samples `src`), or p == nullptr and F prompt rows `src`.
+ptts_voice* Engine::voice_sync(const VoicePlan* p, const void* src, int F) {
+  sync();
+  VoiceWs w;  // transient, sized to this clip; vws_ and its pending jobs are not touched
+  ptts_voice* v = nullptr;
+  try {
+    vws_reserve(w, stream_, F, 0, p ? p->dev_bytes : 0);
+    v = voice_new(F, p != nullptr, false);
+    auto up = [&](void* dst, const void* from, size_t bytes) {
+      if (bytes) PTTS_HIP(hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, stream_));
+    };
+    if (p) {  // the pieces of a job's single upload, from the caller's memory and the plan's
+      up(w.up, src, (size_t)p->n_in * (p->s16 ? 2 : 4));
+      up(w.up + p->o_taps, p->taps.data(), p->taps.size() * sizeof(float));
+      up(w.up + p->o_st, p->sst.data(), p->sst.size() * sizeof(int));
+      up(w.up + p->o_fr, p->sfr.data(), p->sfr.size() * sizeof(float));
+    } else {
+      up(w.fb.x, src, sizeof(float) * (size_t)F * D);
+    }
+    voice_clone(p, w, stream_, v, p ? v->cond.data() : nullptr);
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    vws_free(w);
+    if (v) free_voice(v);
+    throw;
+  }
+  vws_free(w);
+  return v;
+}
+
+ptts_voice* Engine::voice_from_prompt(const float* prompt, int F) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(prompt != nullptr && F >= 1, "empty prompt");
+  PTTS_REQUIRE(F < max_ctx_, "prompt longer than max_ctx");
+  return voice_sync(nullptr, prompt, F);
+}
+
+ptts_voice* Engine::voice_from_audio(const float* pcm_in, int n_in, int sr, int chunk_frames, int resampler) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(pcm_in != nullptr, "empty PCM");
+  const VoicePlan p = voice_plan(n_in, PTTS_SAMPLES_F32, sr, chunk_frames, resampler, max_ctx_);
+  return voice_sync(&p, pcm_in, p.F);
+}
+
+// The job: p and the samples, or p == nullptr and F prompt rows, uploaded through a pinned block
+ptts_voice* Engine::voice_job(const VoicePlan* p, const void* src, int F) {
+  const size_t bytes = p ? p->up_bytes : sizeof(float) * (size_t)F * D;
+  vjob_reserve(F, bytes, p ? p->dev_bytes : 0);
+  ptts_voice* v = voice_new(F, p != nullptr, true);
+  try {
+    VoiceWs& w = vws_;
+    const int par = (int)(vjobs_ & 1);
+    PTTS_HIP(hipEventSynchronize(w.ev_up[par]));  // the staging block's previous upload (two jobs back)
+    char* hs = w.h_up[par];
+    memcpy(hs, src, p ? (size_t)p->n_in * (p->s16 ? 2 : 4) : bytes);
+    if (p && !p->taps.empty()) memcpy(hs + p->o_taps, p->taps.data(), p->taps.size() * sizeof(float));
+    if (p && !p->sst.empty()) memcpy(hs + p->o_st, p->sst.data(), p->sst.size() * sizeof(int));
+    if (p && !p->sfr.empty()) memcpy(hs + p->o_fr, p->sfr.data(), p->sfr.size() * sizeof(float));
+    // a prompt's rows go straight into x
+    PTTS_HIP(hipMemcpyAsync(p ? (void*)w.up : (void*)w.fb.x, hs, bytes, hipMemcpyHostToDevice, stream_vc_));
+    PTTS_HIP(hipEventRecord(w.ev_up[par], stream_vc_));
+    ++vjobs_;
+    voice_clone(p, w, stream_vc_, v, v->h_cond);
   } catch (...) {
     (void)hipStreamSynchronize(stream_vc_);
     free_voice(v);
     throw;
   }
   return v;
+}
+
+// vws_ holds `frames` frames and the two block sizes; the voice stream exists
+void Engine::vjob_reserve(int frames, size_t host_bytes, size_t up_bytes) {
+  PTTS_HIP(hipSetDevice(dev_));
+  if (!stream_vc_) {
+    int least = 0, greatest = 0;
+    PTTS_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    PTTS_HIP(hipStreamCreateWithPriority(&stream_vc_, hipStreamNonBlocking, least));
+    for (hipEvent_t& e : vws_.ev_up) PTTS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  vws_reserve(vws_, stream_vc_, std::max(frames, vws_.frames), host_bytes, up_bytes);
+}
+
+void Engine::voice_jobs_reserve(int max_frames) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(max_frames >= 1 && max_frames < max_ctx_, "max_frames must be in [1, max_ctx)");
+  // uploads of float32 clips at up to twice the model's rate, plus the resampler's tables
+  const size_t up = al16((size_t)max_frames * FRAME * 2 * sizeof(float)) + (64 << 10);
+  vjob_reserve(max_frames, up, up);
+}
+
+ptts_voice* Engine::voice_job_prompt(const float* prompt, int F) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(prompt != nullptr && F >= 1, "empty prompt");
+  PTTS_REQUIRE(F < max_ctx_, "prompt longer than max_ctx");
+  return voice_job(nullptr, prompt, F);
+}
+
+ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int sr, int chunk_frames, int resampler) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(samples != nullptr, "empty PCM");
+  const VoicePlan p = voice_plan(n_in, fmt, sr, chunk_frames, resampler, max_ctx_);
+  return voice_job(&p, samples, p.F);
 }
 
 void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,

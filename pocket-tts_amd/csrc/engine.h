@@ -31,6 +31,8 @@ struct ptts_voice {
 
 namespace ptts {
 
+struct VoicePlan;  // engine.cpp: what the host works out about a clip before a clone is enqueued
+
 // ptts_voice_destroy: frees the voice now, or (while slots still read its prefix) marks it for
 // the last of them to free
 void voice_destroy(ptts_voice* v);
@@ -61,15 +63,15 @@ class Engine {
   int frame_lag() const { return !pipeline_ ? 0 : 2 * nfr_ - 1; }
   int admit_delay() const { return admit_delay_; }
 
+  // One clone (voice_clone), called synchronously: drains the pipeline, returns the finished voice
   ptts_voice* voice_from_prompt(const float* prompt, int F);
   ptts_voice* voice_from_pcm(const float* pcm, int n) { return voice_from_audio(pcm, n, PTTS_SAMPLE_RATE, 0); }
   // resampler: PTTS_RESAMPLE_POLY (resample_poly rule) or PTTS_RESAMPLE_RUBATO_SEPTIC (the Rust driver's)
   ptts_voice* voice_from_audio(const float* x, int n, int sample_rate, int chunk_frames,
                                int resampler = PTTS_RESAMPLE_POLY);
   void resample_host(const float* x, int n, int sr_from, int sr_to, float* y, int resampler = PTTS_RESAMPLE_POLY);
-  // Voice jobs: the same clone enqueued on the engine's voice stream with a workspace of its own
-  // (VoiceWs); returns at once, the voice is admissible immediately (slots_open orders the front
-  // stream behind the job's event). sample_format: PTTS_SAMPLES_F32 / PTTS_SAMPLES_S16 (mono).
+  // or as a job on the engine's voice stream: returns at once, the voice is admissible immediately
+  // (slots_open orders the front stream behind the job's event). sample_format: PTTS_SAMPLES_F32 / _S16
   ptts_voice* voice_job_audio(const void* samples, int n, int sample_format, int sample_rate, int chunk_frames,
                               int resampler);
   ptts_voice* voice_job_prompt(const float* prompt, int F);
@@ -124,7 +126,7 @@ class Engine {
   void derive_int8();
   void derive_fp8();
   // The buffers flow_layers / linear_split write: the engine's own (fbm_, the step and admission
-  // graphs) or a voice job's (VoiceWs). kv is layer 0's store; layer l's base is kv.base + l * kv_layer.
+  // graphs) or a voice clone's (VoiceWs). kv is layer 0's store; layer l's base is kv.base + l * kv_layer.
   struct FlowBufs {
     float *x = nullptr, *h = nullptr, *q = nullptr, *o = nullptr, *u = nullptr, *partial = nullptr;
     size_t pcap = 0;
@@ -211,14 +213,14 @@ class Engine {
   std::vector<void*> allocs_;
 
   // per-slot streaming state
-  float* kv_ = nullptr;  // [(max_slots+1)][NL][2][NH][max_ctx][64] (last slot = prefill scratch)
+  float* kv_ = nullptr;  // [max_slots][NL][2][NH][max_ctx][64]
   long kv_slot_ = 0, kv_layer_ = 0;
   float* ring_ = nullptr;  // [max_slots][MNL][2][MNH][RING][64]
   long ring_slot_ = 0, ring_layer_ = 0;
   int* fpos_ = nullptr;
   int* mpos_ = nullptr;
   // shared voice prefixes (KvStore::pre): per slot, the voice cache its positions < F read from
-  // and F (0: the slot's own rows, as for the prefill scratch slot); pinned host mirrors; the
+  // and F (0: the slot's own rows); pinned host mirrors; the
   // voice each slot references. PTTS_NO_SHARED_VOICE (probe builds) copies the prefix in instead.
   bool share_voice_ = true;
   const float** vpre_ = nullptr;
@@ -394,34 +396,35 @@ class Engine {
   hipGraphExec_t pv_graph(int P);
   void pv_forget(int slot);  // drop the slot's pending / unfetched previews (re-admitted or closed)
 
-  // ---- voice jobs (voice_job_audio / voice_job_prompt): everything a clone writes lives here, so a
-  // job shares only read-only weights and tables with the step pipeline
+  // ---- voice cloning: everything a clone writes but the voice itself lives in a VoiceWs, so a
+  // clone shares only read-only weights and tables with the step pipeline
   struct VoiceWs {
-    int frames = 0;         // capacity in frames of everything below but `up`
+    int frames = 0;         // capacity in frames of `block`
     size_t up_bytes = 0;    // capacity of the device block `up` (the upload, then the converted clip)
-    size_t h_bytes = 0;     // capacity of each pinned staging block
-    // one upload per job: raw samples | resampler taps | rubato start / frac tables (behind them on
-    // the device, rubato rule only: the converted samples [n_in]); a prompt job uploads its rows
-    // straight into fb.x. Staged in one of two pinned host blocks (h_up; ev_up: that block's latest upload has run)
+    size_t h_bytes = 0;     // capacity of each pinned staging block (0: none, synchronous clones)
+    // one upload per clone: raw samples | resampler taps | rubato start / frac tables (behind them on
+    // the device, rubato rule only: the converted samples [n_in]); a prompt's rows go straight into
+    // fb.x. Jobs stage it in one of two pinned host blocks (h_up; ev_up: that block's latest upload has run)
     char* up = nullptr;
     char* h_up[2] = {};
     hipEvent_t ev_up[2] = {};
+    float* block = nullptr;                    // one allocation holding everything below
     float *pcm = nullptr;                      // frame-padded 24 kHz input [Np]
     float *A = nullptr, *Bf = nullptr, *V = nullptr, *zeros = nullptr;  // SEANet encoder ping-pong, zero history
     float *eh = nullptr, *eqkv = nullptr, *eq = nullptr, *eo = nullptr, *eu = nullptr, *ering = nullptr;
     float *Hd = nullptr, *lat = nullptr, *cond = nullptr;
     FlowBufs fb{};                             // the prompt prefill's x, h, q, o, u, slabs, tail scratch
-    std::vector<void*> allocs;
   };
-  VoiceWs vws_{};
+  static void vws_free(VoiceWs& w);  // everything vws_reserve allocated
+  static void vws_reserve(VoiceWs& w, hipStream_t st, int frames, size_t host_bytes, size_t up_bytes);
+  ptts_voice* voice_new(int F, bool pcm, bool job);
+  void voice_clone(const VoicePlan* p, const VoiceWs& w, hipStream_t st, ptts_voice* v, float* h_cond);
+  ptts_voice* voice_sync(const VoicePlan* p, const void* src, int F);
+  VoiceWs vws_{};                    // the jobs' grow-only workspace
   hipStream_t stream_vc_ = nullptr;  // lowest priority; plain launches of non-persistent kernels only
   long long vjobs_ = 0;              // jobs started (upload block parity)
-  void vws_free();
-  void vws_reserve(int frames, size_t host_bytes, size_t up_bytes);
-  // the prompt prefill of F conditioning rows in vws_.fb.x straight into v->kv, the conditioning
-  // copy (PCM jobs) and the job's event, all on stream_vc_
-  void voice_job_finish(ptts_voice* v, bool copy_cond);
-  ptts_voice* voice_job_new(int F, bool pcm);
+  void vjob_reserve(int frames, size_t host_bytes, size_t up_bytes);
+  ptts_voice* voice_job(const VoicePlan* p, const void* src, int F);
 };
 
 }  // namespace ptts

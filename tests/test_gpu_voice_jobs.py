@@ -77,7 +77,31 @@ def _cases():
         "ref_wav_i16_48k": (_ref13(), 48000, 0, "poly", -1, 13),
         "chunked_5f": (d["pcm"], 24000, int(d["meta"][2]), "poly", int(d["meta"][2]), 5),
         "rubato_48k": (0.2 * rng.standard_normal(2 * 3840 + 77).astype(np.float32), 48000, -1, "rubato", -1, 3),
+        "five_frames_48k": (0.1 * rng.standard_normal(5 * 3840 - 100).astype(np.float32), 48000, 2, "poly", 2, 5),
     }
+
+
+def test_sync_clone_between_jobs_leaves_job_workspace_alone(gpu_engine, oracle):
+    """A synchronous clone runs the jobs' code in a transient workspace of its own. First in this
+    file, so the engine's job workspace is the 2 frames reserved here: the 5-frame synchronous clone
+    (two full chunks of 2 frames and a one-frame remainder) between two jobs, none of them waited
+    for, is larger than it and must neither alias, free nor resize it."""
+    cases = _cases()
+    gpu_engine.reserve_voice_jobs(2)
+    a = gpu_engine.voice_job(*cases["one_frame_24k"][:2])
+    x, sr, chunk, rule, ochunk, frames = cases["five_frames_48k"]
+    b = gpu_engine.voice_from_audio(x, sr, chunk, resampler=rule)
+    assert b.ready() and b.n_frames == frames
+    c = gpu_engine.voice_job(*cases["padded_last_frame"][:2])
+    conds = [_oracle_cond(oracle, *cases["one_frame_24k"][:2]), _oracle_cond(oracle, x, sr, ochunk),
+             _oracle_cond(oracle, *cases["padded_last_frame"][:2])]
+    for name, v, cond in zip("abc", (a, b, c), conds):
+        err = float(np.abs(v.conditioning() - cond).max())
+        print(f"{name}: {v.n_frames} frames, conditioning max |d| {err:.3g}")
+        assert err <= 1e-5, (name, err)
+    for v, cond in zip((a, b, c), conds):
+        _check_generation(gpu_engine, oracle, v, cond)
+        v.close()
 
 
 @pytest.mark.parametrize("case", ["one_frame_24k", "padded_last_frame", "ref_wav_i16_48k", "chunked_5f", "rubato_48k"])
