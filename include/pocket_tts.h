@@ -272,6 +272,47 @@ int ptts_slot_open_ex(ptts_engine* e, int slot, const ptts_voice* v, const int32
                       const ptts_gen_params* p, int lsd_steps);
 int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps);
+/* Wire-format output (no reference counterpart: the reference emits f32 at 24 kHz and its server
+ * converts on the host, audio.rs:110-185). A row admitted with a wire format also gets, per frame,
+ * the bytes a client reads: its PCM resampled to wire_rate by the resample_poly rule of
+ * ptts_resample (streaming: the chunks of a row concatenate to the whole-signal resample of its
+ * PCM, bit for bit; 24000 is the identity) and encoded as 16-bit little-endian integers by the wire
+ * rule trunc(clamp(x, -1, 1) * 32767), or as the G.711 mu-law / A-law code of that 16-bit value.
+ * The conversion runs on the GPU at the end of the back part; rows of every format and rows with
+ * none share a batch, and the f32 PCM of ptts_fetch is unchanged for all of them. Chunk sizes in
+ * samples (first / middle / last frame of an utterance): 8 kHz 630 / 640 / 650, 16 kHz 1270 /
+ * 1280 / 1290, 44.1 kHz 3510 / 3528 / 3546, 48 kHz 3820 / 3840 / 3860, 24 kHz 1920; an
+ * utterance of one frame emits 1920 * rate / 24000 at once. */
+#define PTTS_WIRE_NONE 0
+#define PTTS_WIRE_S16 1
+#define PTTS_WIRE_ULAW 2
+#define PTTS_WIRE_ALAW 3
+#define PTTS_WIRE_CHUNK_MAX 8192 /* bytes: the largest chunk of one frame (3860 16-bit samples) fits */
+/* on = 1: the engine's back passes end in the wire stage and one more device-to-host copy; 0: as
+ * created (the same graphs and copies as an engine that never called this). Valid on an idle engine
+ * before its first step, as ptts_preview_enable is; PTTS_ERR_INVALID later. */
+int ptts_wire_enable(ptts_engine* e, int on);
+/* Per-row admission options. size = sizeof(ptts_slot_opts) of the caller's header (0 is read as
+ * that of this one): the stride of the array, and fields past it read as 0, so the struct can grow
+ * without an ABI bump. Zero fields are the defaults: lsd_steps as in ptts_slots_open_ex; wire_rate
+ * 0 and wire_encoding 0: no wire format; one of them 0: 24000 / PTTS_WIRE_S16. */
+typedef struct ptts_slot_opts {
+  size_t size;
+  int lsd_steps;
+  int wire_rate;     /* 8000, 16000, 24000, 44100 or 48000 */
+  int wire_encoding; /* PTTS_WIRE_* */
+} ptts_slot_opts;
+/* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
+ * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
+ * engine without ptts_wire_enable, is PTTS_ERR_INVALID and admits nothing. */
+int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
+                         const int* n_ids, const ptts_gen_params* params, const ptts_slot_opts* opts);
+/* The wire seam alone, like ptts_resample: bytes of n_samples at 24 kHz in the format (0 if the
+ * arguments are invalid; host only), and the whole-signal conversion on the GPU (the kernel
+ * ptts_resample runs, then the encoder of the streaming stage); out receives ptts_wire_len bytes. */
+long ptts_wire_len(long n_samples, int sample_rate, int encoding);
+int ptts_wire_encode(ptts_engine* e, const float* pcm, int n_samples, int sample_rate, int encoding, uint8_t* out);
+
 /* *cap: cfg.lsd_decode_steps. *last_run: the Euler steps the most recent step call ran (0 before
  * the first): the largest count among that call's rows still open (admitted, not closed, last
  * frame not yet fetched), so a call whose open rows all use one step pays for one. Either pointer
@@ -312,6 +353,11 @@ int ptts_frame_lag(const ptts_engine* e, int* admit_delay);
  * GPU always has the next step queued while the host hands out frames. calls_back <= 1. */
 int ptts_fetch_prev(ptts_engine* e, int calls_back, int n_rows, float* pcm, uint8_t* frame_valid, uint8_t* last,
                     float* eos_logits, float* latents);
+/* The wire chunks of the same call's frame (the companion of ptts_fetch / ptts_fetch_prev: the same
+ * event, no bookkeeping of its own, so call it beside them in either order): row b's n_bytes[b]
+ * bytes at out + b * row_stride (row_stride >= PTTS_WIRE_CHUNK_MAX); n_bytes[b] = 0 for a row with no
+ * wire format or no frame. out may be NULL (sizes only). Wire-enabled engines only. */
+int ptts_fetch_wire(ptts_engine* e, int calls_back, int n_rows, uint8_t* out, size_t row_stride, int* n_bytes);
 /* *ready = 1 if ptts_fetch_prev(e, calls_back, ..) would return without waiting (the call's frame
  * is complete), else 0; never blocks. A driver that also serves previews polls this and
  * ptts_preview_fetch instead of blocking in the fetch. */

@@ -294,6 +294,44 @@ int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice
   return guard([&] { eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd_steps); });
 }
 
+int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
+                         const int* n_ids, const ptts_gen_params* params, const ptts_slot_opts* opts) {
+  return guard([&] {
+    if (!opts) return eng(e).slots_open(n, slots, voices, ids, n_ids, params, nullptr);
+    if (n < 1) throw ptts::Error(PTTS_ERR_INVALID, "number of admissions out of range");
+    // entries are `size` bytes apart (the caller's struct); fields past it read as 0 (checked ahead
+    // of everything else: a caller with another header learns so whatever the engine's state)
+    const size_t size = opts[0].size ? opts[0].size : sizeof(ptts_slot_opts);
+    if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
+      throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
+    std::vector<int> lsd(n), rate(n), enc(n);
+    for (int i = 0; i < n; ++i) {
+      ptts_slot_opts o{};
+      std::memcpy(&o, (const char*)opts + (size_t)i * size, std::min(size, sizeof o));
+      if (o.size != opts[0].size) throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size differs between entries");
+      lsd[i] = o.lsd_steps;
+      rate[i] = o.wire_rate;
+      enc[i] = o.wire_encoding;
+    }
+    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data());
+  });
+}
+
+int ptts_wire_enable(ptts_engine* e, int on) { return guard([&] { eng(e).wire_enable(on != 0); }); }
+
+int ptts_fetch_wire(ptts_engine* e, int calls_back, int n_rows, uint8_t* out, size_t row_stride, int* n_bytes) {
+  return guard([&] { eng(e).fetch_wire(calls_back, n_rows, out, row_stride, n_bytes); });
+}
+
+long ptts_wire_len(long n_samples, int sample_rate, int encoding) {
+  const long n = ptts::Engine::wire_len(n_samples, sample_rate, encoding);
+  return n > 0 ? n : 0;
+}
+
+int ptts_wire_encode(ptts_engine* e, const float* pcm, int n_samples, int sample_rate, int encoding, uint8_t* out) {
+  return guard([&] { eng(e).wire_encode_host(pcm, n_samples, sample_rate, encoding, out); });
+}
+
 int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run) {
   return guard([&] {
     if (!e || !e->impl) throw ptts::Error(PTTS_ERR_INVALID, "null engine");

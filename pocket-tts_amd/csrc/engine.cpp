@@ -349,6 +349,9 @@ Engine::~Engine() {
   for (int p = 0; p < NHB / 2; ++p)
     if (h_pcmp_[p]) (void)hipHostFree(h_pcmp_[p]);
   if (h_act_) (void)hipHostFree(h_act_);
+  if (h_wire_) (void)hipHostFree(h_wire_);
+  for (unsigned char* hp : h_wireb_)
+    if (hp) (void)hipHostFree(hp);
   if (h_err_) (void)hipHostFree(h_err_);
   for (void* hp : {(void*)h_slots_, (void*)h_st_, (void*)h_fp_, (void*)h_ids_, (void*)h_tab_, (void*)h_vpre_,
                    (void*)h_vlen_})
@@ -1578,6 +1581,27 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     for (int i = 0; i < 8; ++i) hb_bytes += 8.0 * B * hist_P_[i] * hist_C_[i];
     ops.push_back({"commit", [c](hipStream_t s) { step_commit(c, s); }, 0.0, hb_bytes + 16.0 * B});
   }
+  // ---- wire stage (wire-enabled engines): after the commit, which still adds the fused final
+  // conv's tile-boundary shares into the PCM
+  if (wire_ && !wire_skip_) {
+    WireArgs w{};
+    w.B = B;
+    w.nfr = nfr;
+    w.pcm_frames = pcm_frames;
+    w.out_frames = nfr_;
+    w.pcm = pcm_out;
+    for (int f = 0; f < NFR_MAX; ++f) w.flags[f] = flags_[hbs[f]];
+    w.fmt = wire_fmt_;
+    w.frames = wire_frames_;
+    w.tail = wire_tail_;
+    w.taps = wire_taps_;
+    for (int r = 0; r < WIRE_RATES; ++r) w.plan[r] = wire_plan_[r];
+    unsigned char* blk = wireb_[nfr_ > 1 ? hb / nfr_ : hb];
+    w.counts = (int*)blk;
+    w.out = blk + wire_head_bytes();
+    ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
+                   (double)B * nfr * (4.0 * FRAME + WIRE_CHUNK_MAX)});
+  }
 }
 
 // The whole step in plan order (front then back, buffer 0): plan listing and per-op timing.
@@ -1641,6 +1665,13 @@ void Engine::copy_out(int B, int hb, hipStream_t s) {
   } else {
     PTTS_HIP(hipMemcpyAsync(h_pcm_[hb], pcm_[hb], sizeof(float) * B * FRAME, hipMemcpyDeviceToHost, s));
     PTTS_HIP(hipMemcpyAsync(h_meta_[hb], meta_[hb], sizeof(float) * meta_floats_, hipMemcpyDeviceToHost, s));
+  }
+  if (wire_) {  // the pass's byte counts, and the chunk slots of its rows when one of them has a format
+    const int p = nfr_ > 1 ? hb / nfr_ : hb;
+    bool any = false;  // (a slot's format changes only at its admission, whose reset drops its pending frames)
+    for (int b = 0; b < B; ++b) any = any || slot_wire_[b];
+    PTTS_HIP(hipMemcpyAsync(h_wireb_[p], wireb_[p], any ? wire_block_bytes(B) : wire_head_bytes(),
+                            hipMemcpyDeviceToHost, s));
   }
 }
 
@@ -2758,13 +2789,23 @@ int Engine::lsd_run_for(int B) const {
 // per slot, padded to 16-row groups (the 16-query attention tiles), and mapped to (slot, position)
 // through a row table.
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
-                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps) {
+                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
+                        const int* wire_enc) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
   std::vector<char> seen(max_slots_, 0);
+  std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
   long total_ids = 0;
   for (int i = 0; i < n; ++i) {
+    const int wr = wire_rate ? wire_rate[i] : 0, we = wire_enc ? wire_enc[i] : 0;
+    if (wr || we) {
+      PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
+      const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
+      PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
+      PTTS_REQUIRE(we >= 0 && we <= WIRE_ALAW, "wire_encoding must be 0 (s16) or PTTS_WIRE_S16 / _ULAW / _ALAW");
+      wfmt[i] = (we ? we : WIRE_S16) | ri << 8;
+    }
     const int slot = slots[i];
     PTTS_REQUIRE(slot >= 0 && slot < max_slots_, "slot out of range");
     PTTS_REQUIRE(!seen[slot], "slot admitted twice in one call");
@@ -2906,6 +2947,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     drained_[slots[i]] = 0;
     admit_call_[slots[i]] = k_;
     slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
+    if (wire_) slot_wire_[slots[i]] = wfmt[i];
   }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
@@ -2947,6 +2989,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   memcpy(h_slots_, slots, sizeof(int) * n);
   memcpy(h_st_, st.data(), sizeof(SlotState) * n);
   memcpy(h_fp_, fp.data(), sizeof(int) * n);
+  if (wire_) {
+    memcpy(h_wire_, wfmt.data(), sizeof(int) * n);
+    PTTS_HIP(hipMemcpyAsync(admit_wire_, h_wire_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  }
   PTTS_HIP(hipMemcpyAsync(admit_slots_, h_slots_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_st_, h_st_, sizeof(SlotState) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_fpos_, h_fp_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
@@ -2969,11 +3015,117 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     r.fpos = fpos_;
     r.mpos = mpos_;
     for (int q = 0; q < NHB; ++q) r.flags[q] = flags_[q];
+    if (wire_) {  // the wire state is back-owned too: same reset, same ordering
+      r.wire_src = admit_wire_;
+      r.wire_fmt = wire_fmt_;
+      r.wire_frames = wire_frames_;
+    }
     slot_reset(r, stream_);
     PTTS_HIP(hipGetLastError());
   }
   mark_admission();
   admitted_since_call_ = true;
+}
+
+// ------------------------------------------------------------------ wire stage
+int Engine::wire_rate_index(int rate) {
+  for (int r = 0; r < WIRE_RATES; ++r)
+    if (WIRE_RATE_HZ[r] == rate) return r;
+  return -1;
+}
+
+long Engine::wire_len(long n_samples, int rate, int enc) {
+  if (n_samples < 0 || wire_rate_index(rate) < 0 || enc < WIRE_S16 || enc > WIRE_ALAW) return -1;
+  return resample_plan(PTTS_SAMPLE_RATE, rate).out_len(n_samples) * (enc == WIRE_S16 ? 2 : 1);
+}
+
+void Engine::wire_enable(bool on) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "wire output is chosen on an idle engine before its first step");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !wire_fmt_) {
+    const size_t B = max_slots_;
+    wire_fmt_ = (int*)dalloc(B);
+    slot_wire_.assign(B, 0);
+    wire_frames_ = (int*)dalloc(B);
+    admit_wire_ = (int*)dalloc(B);
+    wire_tail_ = dalloc(B * WIRE_TAIL);
+    PTTS_HIP(hipHostMalloc((void**)&h_wire_, sizeof(int) * B, hipHostMallocDefault));
+    std::vector<float> taps;
+    for (int r = 0; r < WIRE_RATES; ++r) {
+      const ResamplePlan rp = resample_plan(PTTS_SAMPLE_RATE, WIRE_RATE_HZ[r]);
+      wire_plan_[r] = WirePlan{rp.up, rp.down, rp.half, rp.L, (int)taps.size()};
+      if (rp.identity()) continue;
+      PTTS_REQUIRE(rp.L <= WIRE_TAPS_MAX && 2 * rp.half <= WIRE_TAIL * rp.up, "wire rate outside the stage's window");
+      const std::vector<float> h = resample_taps(rp);
+      taps.insert(taps.end(), h.begin(), h.end());
+    }
+    wire_taps_ = dalloc(taps.size());
+    PTTS_HIP(hipMemcpy(wire_taps_, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice));
+    const size_t bytes = wire_block_bytes(max_slots_);
+    for (int p = 0; p < WIRE_BLOCKS; ++p) {
+      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
+      PTTS_HIP(hipHostMalloc((void**)&h_wireb_[p], bytes, hipHostMallocDefault));
+      memset(h_wireb_[p], 0, wire_head_bytes());
+    }
+  }
+  wire_ = on;
+}
+
+void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_stride, int* n_bytes) {
+  PTTS_REQUIRE(wire_, "fetch_wire: the engine has no wire output (ptts_wire_enable)");
+  PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
+  PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
+  PTTS_REQUIRE(n_bytes != nullptr, "null argument");
+  PTTS_REQUIRE(!out || row_stride >= (size_t)WIRE_CHUNK_MAX, "row_stride must be >= PTTS_WIRE_CHUNK_MAX");
+  // the same frame, rows and event as fetch() of that call; no bookkeeping of its own
+  const int q = calls_back ? prev_hb_ : out_hb_;
+  const int rows = calls_back ? prev_rows_ : out_rows_;
+  if (pipeline_) PTTS_HIP(hipEventSynchronize(ev_back_[q - q % nfr_]));
+  else sync();
+  const int n = std::min(B, rows);
+  const unsigned char* blk = h_wireb_[nfr_ > 1 ? q / nfr_ : q];
+  const int* cnt = (const int*)blk;
+  for (int b = 0; b < B; ++b) {
+    const int f = q % nfr_;
+    int c = b < n ? cnt[(size_t)b * nfr_ + f] : 0;
+    if (c < 0 || c > WIRE_CHUNK_MAX) throw Error(PTTS_ERR_STATE, "fetch_wire: corrupt chunk size");
+    if (c && out) memcpy(out + b * row_stride, blk + wire_head_bytes() + ((size_t)b * nfr_ + f) * WIRE_CHUNK_MAX, c);
+    n_bytes[b] = c;
+  }
+}
+
+void Engine::wire_encode_host(const float* pcm, int n, int rate, int enc, unsigned char* out) {
+  PTTS_REQUIRE(pcm && out && n >= 1, "empty input");
+  const long bytes = wire_len(n, rate, enc);
+  PTTS_REQUIRE(bytes >= 1, "unknown wire rate or encoding");
+  const ResamplePlan rp = resample_plan(PTTS_SAMPLE_RATE, rate);
+  const long n_out = rp.out_len(n);
+  PTTS_REQUIRE(n_out < (1L << 30), "input too long");
+  sync();
+  void *dx = nullptr, *dh = nullptr, *dy = nullptr, *dw = nullptr;
+  try {
+    PTTS_HIP(hipMalloc(&dx, sizeof(float) * n));
+    PTTS_HIP(hipMalloc(&dw, (size_t)(bytes + 7) / 8 * 8));
+    PTTS_HIP(hipMemcpyAsync(dx, pcm, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    const float* src = (const float*)dx;
+    if (!rp.identity()) {  // the whole-signal kernel ptts_resample runs
+      const std::vector<float> taps = resample_taps(rp);
+      PTTS_HIP(hipMalloc(&dh, sizeof(float) * taps.size()));
+      PTTS_HIP(hipMalloc(&dy, sizeof(float) * n_out));
+      PTTS_HIP(hipMemcpy(dh, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice));
+      resample((const float*)dx, n, (const float*)dh, rp, (int)n_out, (int)n_out, (float*)dy, stream_);
+      src = (const float*)dy;
+    }
+    wire_encode(src, n_out, enc, (unsigned char*)dw, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(out, dw, (size_t)bytes, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(dh), (void)hipFree(dy), (void)hipFree(dw);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(dh), (void)hipFree(dy), (void)hipFree(dw);
 }
 
 void Engine::mark_admission() {
@@ -3045,7 +3197,14 @@ void Engine::decode_latents(int slot, const float* lat, int n, float* pcm, float
                             hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(flags_[par] + slot, &on, sizeof on, hipMemcpyHostToDevice, stream_));
     std::vector<Op> ops;
-    build_back(ops, slot + 1, par, 1, par, 1);
+    wire_skip_ = true;  // the seam decodes to f32 only
+    try {
+      build_back(ops, slot + 1, par, 1, par, 1);
+    } catch (...) {
+      wire_skip_ = false;
+      throw;
+    }
+    wire_skip_ = false;
     size_t j = 0;
     for (; j < ops.size(); ++j) {
       if (ops[j].name == "seanet.conv0" && tr) rows16(tr + (size_t)i * UP * MD, mx_);
@@ -3231,12 +3390,15 @@ hipGraphExec_t Engine::pv_graph(int P) {
   if (it != pv_graphs_.end()) return it->second;
   std::vector<Op> ops;
   swap_back(pv_);  // build_back over the preview buffers (its lambdas capture the pointers)
+  wire_skip_ = true;  // previews stay f32 at 24 kHz
   try {
     build_back(ops, P, 0, 1, 0, 1);
   } catch (...) {
+    wire_skip_ = false;
     swap_back(pv_);
     throw;
   }
+  wire_skip_ = false;
   swap_back(pv_);
   // The preview state must stay the fresh one (zero conv and overlap-add histories, Mimi position
   // 0): the pass's closing commit, the only op that writes it, is left out, so the buffers keep

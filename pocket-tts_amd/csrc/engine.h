@@ -80,8 +80,11 @@ class Engine {
   // the engine's default, the cap (cfg.lsd_decode_steps)
   void slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
                  int lsd_steps = 0);
+  // wire_rate / wire_enc (wire-enabled engines): the row's output format, per row; 0 in both (or null
+  // arrays) = none, 0 in one = its default (24000 Hz, PTTS_WIRE_S16)
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
-                  const ptts_gen_params* params, const int* lsd_steps = nullptr);
+                  const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
+                  const int* wire_enc = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -110,6 +113,18 @@ class Engine {
   // the caller delivers whichever arrives first.
   void preview_enable(int max_rows);
   int preview_fetch(int wait, int max_n, int* slots, float* pcm);
+
+  // Wire stage (ptts_wire_enable / ptts_fetch_wire): with it on, every back
+  // pass ends in one more launch that turns the f32 PCM of the rows that asked for a format into
+  // their wire bytes (kernels.h wire_stage), and one more copy carries them to pinned host memory.
+  // Valid before the engine's first call only (the back graphs are captured with or without it).
+  void wire_enable(bool on);
+  bool wire() const { return wire_; }
+  // the wire chunks of the frame fetch(.., calls_back) returns: n_bytes[b] bytes at out + b * row_stride
+  void fetch_wire(int calls_back, int B, unsigned char* out, size_t row_stride, int* n_bytes);
+  // the seam alone: whole-signal f32 at 24 kHz -> wire bytes (wire_len of them)
+  static long wire_len(long n_samples, int rate, int enc);  // -1: unknown rate or encoding
+  void wire_encode_host(const float* pcm, int n, int rate, int enc, unsigned char* out);
 
   double time_op(int B, const std::string& name, int reps);
   // GEMM-core test hook (ptts_test_gemm): Y = X W^T on tile `layout` (host buffers)
@@ -395,6 +410,26 @@ class Engine {
   void launch_previews(int B, int hb);
   hipGraphExec_t pv_graph(int P);
   void pv_forget(int slot);  // drop the slot's pending / unfetched previews (re-admitted or closed)
+
+  // ---- wire stage (wire_enable)
+  bool wire_ = false;
+  bool wire_skip_ = false;  // build_back for a preview pass: no wire op
+  int* wire_fmt_ = nullptr;     // [max_slots] encoding | rate index << 8 (0: none)
+  std::vector<int> slot_wire_;  // its host mirror (copy_out: no chunk copy while no row has a format)
+  int* wire_frames_ = nullptr;  // [max_slots] frames received
+  float* wire_tail_ = nullptr;  // [max_slots][WIRE_TAIL]
+  float* wire_taps_ = nullptr;
+  WirePlan wire_plan_[WIRE_RATES] = {};
+  int* admit_wire_ = nullptr;   // staged formats of an admission (device), h_wire_ (pinned)
+  int* h_wire_ = nullptr;
+  // per pass (index: hand-off buffer / frames per pass): counts [max_slots][nfr] | chunks
+  // [max_slots][nfr][WIRE_CHUNK_MAX], and its pinned host copy
+  static constexpr int WIRE_BLOCKS = 3;
+  unsigned char* wireb_[WIRE_BLOCKS] = {};
+  unsigned char* h_wireb_[WIRE_BLOCKS] = {};
+  size_t wire_head_bytes() const { return ((size_t)max_slots_ * nfr_ * sizeof(int) + 127) / 128 * 128; }
+  size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * WIRE_CHUNK_MAX; }
+  static int wire_rate_index(int rate);
 
   // ---- voice cloning: everything a clone writes but the voice itself lives in a VoiceWs, so a
   // clone shares only read-only weights and tables with the step pipeline

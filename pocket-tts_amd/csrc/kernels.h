@@ -459,6 +459,11 @@ struct ResetArgs {
   SlotState* st;
   int* fpos;
   int* mpos;
+  // wire stage (null on an engine without it): the row's format from the staged array, no frames
+  // received yet
+  const int* wire_src = nullptr;
+  int* wire_fmt = nullptr;
+  int* wire_frames = nullptr;
 };
 void slot_reset(const ResetArgs& a, hipStream_t s);
 // The first-frame preview pass's inputs, one launch: row i < n gets the latent and frame flags of
@@ -542,6 +547,45 @@ void resample(const float* x, int n_in, const float* taps, const ResamplePlan& p
 // An identity plan converts and pads (taps unused, may be null).
 void voice_ingest(const void* x, int fmt_s16, int n_in, const float* taps, const ResamplePlan& p, int n_out,
                   int n_pad, float* y, hipStream_t s);
+// ---------------------------------------------------------------------------------------------
+// Wire stage: a row's f32 PCM at 24 kHz -> the bytes a client reads, inside the back part. Per row
+// a format (encoding | rate index << 8; 0: none): 16-bit integer samples by the project's wire rule
+// (audio.rs:110-185: trunc(clamp(x, -1, 1) * 32767) in f32), or the G.711 mu-law / A-law code of
+// that 16-bit value, at one of WIRE_RATE_HZ. Rates other than 24 kHz resample by the rule above
+// (the same tap loop as k_voice_ingest: one device function), streaming: after N samples of a row
+// every output whose filter support is complete has been emitted, emitted(N) = floor((N up - 1 -
+// half) / down) + 1, and the frame flagged `last` emits the rest up to N up / down, so a row's
+// chunks concatenate to the whole-signal resample of its PCM, bit for bit. Per-row state: the
+// frames received and the last WIRE_TAIL input samples; the admission reset (k_slot_reset) zeroes
+// the count and writes the format.
+constexpr int WIRE_NONE = 0, WIRE_S16 = 1, WIRE_ULAW = 2, WIRE_ALAW = 3;
+constexpr int WIRE_RATES = 5;
+constexpr int WIRE_RATE_HZ[WIRE_RATES] = {8000, 16000, 24000, 44100, 48000};
+constexpr int WIRE_CHUNK_MAX = 8192;  // bytes per (row, frame) slot: 3860 16-bit samples at most
+constexpr int WIRE_TAIL = 64;         // >= 2 half / up of every rate (60 at 8 kHz)
+constexpr int WIRE_TAPS_MAX = 2944;   // >= L of every rate (2941 at 44.1 kHz)
+struct WirePlan {
+  int up, down, half, L, tap_off;  // tap_off: the rate's taps within WireArgs::taps
+};
+struct WireArgs {
+  int B, nfr;               // rows, frames this pass decodes
+  int pcm_frames;           // frames per row of the PCM block
+  int out_frames;           // frames per row of `out` / `counts` (slots past nfr get count 0)
+  const float* pcm;         // [B][pcm_frames][1920], after the commit
+  const FrameFlags* flags[NFR_MAX];
+  const int* fmt;           // [B]
+  int* frames;              // [B] frames of the row's utterance received so far
+  float* tail;              // [B][WIRE_TAIL]
+  const float* taps;
+  WirePlan plan[WIRE_RATES];
+  unsigned char* out;       // [B][out_frames][WIRE_CHUNK_MAX]
+  int* counts;              // [B][out_frames] bytes of each chunk (0: no wire format or no frame)
+};
+void wire_stage(const WireArgs& a, hipStream_t s);
+// n samples already at the wire rate -> n (G.711) or 2 n (16-bit) bytes; `out` holds the byte count
+// rounded up to a multiple of 8
+void wire_encode(const float* x, long n, int enc, unsigned char* out, hipStream_t s);
+
 // dst [nch][rows][cols]: row r of chunk c = src[c * chunk_stride .. + cols) (each encoder chunk's
 // first row replicated: the history of the chunked ConvDownsample1d), one launch over all chunks
 void replicate_chunks(const float* src, long chunk_stride, float* dst, int nch, int rows, int cols, hipStream_t s);

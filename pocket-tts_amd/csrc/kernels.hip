@@ -3510,6 +3510,10 @@ __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
     a.mpos[slot] = 0;
     for (int q = 0; q < NHB_MAX; ++q)
       if (a.flags[q]) a.flags[q][slot] = FrameFlags{0, 0};
+    if (a.wire_fmt) {
+      a.wire_fmt[slot] = a.wire_src[i];
+      a.wire_frames[slot] = 0;
+    }
   }
 }
 
@@ -3881,6 +3885,21 @@ void conv_cin1(const float* X, int T, int cout, int k, const float* w, const flo
 __device__ __forceinline__ float ingest_load(const float* x, long j) { return x[j]; }
 __device__ __forceinline__ float ingest_load(const short* x, long j) { return (float)x[j] * (1.0f / 32768.0f); }
 
+// Output m of the rule: x[j] is read as x[j - xoff] (xoff = 0 for a whole signal; the wire stage
+// holds a window of the signal in LDS), n_in = samples of the signal so far. The one tap loop of
+// k_voice_ingest and k_wire: ascending j, f64 accumulation, rounded to f32 once.
+template <typename T>
+__device__ __forceinline__ float resample_out(const T* x, long xoff, long n_in, const float* h, int L, int up, int down,
+                                              int half, long m) {
+  const long a = m * down + half;  // h index of x[0]; x[j] pairs with h[a - j*up]
+  const long jhi = min(a / up, n_in - 1);
+  const long lo = a - (L - 1);
+  const long jlo = max(lo <= 0 ? 0 : (lo + up - 1) / up, xoff);
+  double acc = 0.0;
+  for (long j = jlo; j <= jhi; ++j) acc += (double)ingest_load(x, j - xoff) * (double)h[a - j * up];
+  return (float)acc;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_voice_ingest(const T* __restrict__ x, int n_in,
                                                       const float* __restrict__ taps, int L, int up, int down,
@@ -3903,13 +3922,7 @@ __global__ __launch_bounds__(256) void k_voice_ingest(const T* __restrict__ x, i
     return;
   }
   const float* h = use_lds ? sh_taps : taps;
-  const long a = m * down + half;  // h index of x[0]; x[j] pairs with h[a - j*up]
-  const long jhi = min(a / up, (long)n_in - 1);
-  const long lo = a - (L - 1);
-  const long jlo = lo <= 0 ? 0 : (lo + up - 1) / up;
-  double acc = 0.0;
-  for (long j = jlo; j <= jhi; ++j) acc += (double)ingest_load(x, j) * (double)h[a - j * up];
-  y[m] = (float)acc;
+  y[m] = resample_out(x, 0, (long)n_in, h, L, up, down, half, m);
 }
 
 namespace {
@@ -3984,6 +3997,142 @@ void voice_ingest(const void* x, int fmt_s16, int n_in, const float* taps, const
   else
     hipLaunchKernelGGL(k_voice_ingest<float>, grid, dim3(256), lds, s, (const float*)x, n_in, taps, p.L, p.up, p.down,
                        p.half, n_out, n_pad, use_lds, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Wire stage (see kernels.h): the encodings, then the streaming kernel and the whole-signal one.
+__device__ __forceinline__ int wire_s16(float x) {  // audio.rs:110-146: clamp, x 32767, truncate
+  return (int)(fminf(fmaxf(x, -1.0f), 1.0f) * 32767.0f);
+}
+__device__ __forceinline__ unsigned wire_ulaw(int s) {
+  int v = s >> 2;
+  const unsigned mask = v < 0 ? 0x7Fu : 0xFFu;
+  v = min(v < 0 ? -v : v, 8159) + 33;
+  int seg = 0;
+  while (seg < 8 && v > (0x3F << seg | ((1 << seg) - 1))) ++seg;  // 0x3F, 0x7F, .. 0x1FFF
+  if (seg == 8) return 0x7Fu ^ mask;
+  return (unsigned)((seg << 4) | ((v >> (seg + 1)) & 15)) ^ mask;
+}
+__device__ __forceinline__ unsigned wire_alaw(int s) {
+  const unsigned mask = s >= 0 ? 0xD5u : 0x55u;
+  const int v = s >= 0 ? s >> 3 : (-s - 1) >> 3;  // <= 0xFFF: a segment always exists
+  int seg = 0;
+  while (seg < 7 && v > (0x1F << seg | ((1 << seg) - 1))) ++seg;  // 0x1F, 0x3F, .. 0xFFF
+  return (unsigned)((seg << 4) | ((v >> (seg < 2 ? 1 : seg)) & 15)) ^ mask;
+}
+// four consecutive samples -> 8 bytes (s16) or 4 bytes (G.711) at byte offset bytes_per * 4 g of
+// dst, as dword stores; samples past the chunk's end arrive as 0.f (padding inside the chunk slot)
+__device__ __forceinline__ void wire_store4(unsigned char* dst, long g, int enc, const float v[4]) {
+  int s[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s[q] = wire_s16(v[q]);
+  if (enc == WIRE_S16) {
+    const unsigned lo = ((unsigned)s[0] & 0xFFFFu) | ((unsigned)s[1] << 16);
+    const unsigned hi = ((unsigned)s[2] & 0xFFFFu) | ((unsigned)s[3] << 16);
+    reinterpret_cast<uint2*>(dst)[g] = make_uint2(lo, hi);
+    return;
+  }
+  unsigned w = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) w |= (enc == WIRE_ULAW ? wire_ulaw(s[q]) : wire_alaw(s[q])) << (8 * q);
+  reinterpret_cast<unsigned*>(dst)[g] = w;
+}
+
+// One workgroup per row walks the frames of the pass in order, so the row's history is read and
+// written by this workgroup alone. LDS: the row's taps, and a window of the row's signal: the
+// WIRE_TAIL samples before the frame | the frame. Output m needs x[j] for j >= (m down - half) /
+// up, and the first output not yet emitted after N samples has m down + half >= N up: at most
+// 2 half / up = 60 samples (8 kHz) before the frame. Two phases per frame: one output per lane
+// into LDS (1,024 lanes: at most four tap chains in a row per lane and frame), then four outputs
+// per lane encoded and stored as dwords. (With 256 lanes computing four outputs each, the launch
+// took 59 / 85 us per four-frame pass of 32 rows at 8 / 48 kHz: the tap chain is latency bound.)
+constexpr int WIRE_THREADS = 1024;
+constexpr int WIRE_OUT_MAX = 3864;  // >= the largest chunk, 3860 samples, and a multiple of 4
+__global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
+  __shared__ float s_taps[WIRE_TAPS_MAX];
+  __shared__ __attribute__((aligned(16))) float s_x[WIRE_TAIL + 1920];
+  __shared__ __attribute__((aligned(16))) float s_y[WIRE_OUT_MAX];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int fmt = a.fmt[b];
+  const int enc = fmt & 0xFF, ri = fmt >> 8;
+  int* cnt = a.counts + (long)b * a.out_frames;
+  if (enc == WIRE_NONE || ri < 0 || ri >= WIRE_RATES) {  // uniform
+    if (t < a.out_frames) cnt[t] = 0;
+    return;
+  }
+  const WirePlan p = a.plan[ri];
+  const bool identity = p.up == 1 && p.down == 1;
+  if (!identity)
+    for (int i = t; i < p.L; i += WIRE_THREADS) s_taps[i] = a.taps[p.tap_off + i];
+  long nf = a.frames[b];  // frames of the row received so far
+  if (t < WIRE_TAIL) s_x[t] = nf > 0 ? a.tail[(long)b * WIRE_TAIL + t] : 0.f;
+  bool any = false;
+  for (int f = 0; f < a.out_frames; ++f) {
+    const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
+    if (!fl.valid) {  // uniform
+      if (t == 0) cnt[f] = 0;
+      continue;
+    }
+    any = true;
+    __syncthreads();  // the previous frame's tail is in place
+    const float4* src = reinterpret_cast<const float4*>(a.pcm + ((long)b * a.pcm_frames + f) * 1920);
+    for (int i = t; i < 480; i += WIRE_THREADS) reinterpret_cast<float4*>(s_x + WIRE_TAIL)[i] = src[i];
+    __syncthreads();
+    const long N0 = nf * 1920, N1 = N0 + 1920;
+    long m0 = N0, m1 = N1;
+    if (!identity) {  // emitted(N) = floor((N up - 1 - half) / down) + 1 (0 before the first sample)
+      m0 = N0 == 0 ? 0 : (N0 * p.up - 1 - p.half) / p.down + 1;
+      m1 = fl.last ? (N1 * p.up + p.down - 1) / p.down : (N1 * p.up - 1 - p.half) / p.down + 1;
+    }
+    const long count = min(m1 - m0, (long)WIRE_OUT_MAX);  // (never more: the chunk sizes of kernels.h)
+    unsigned char* dst = a.out + ((long)b * a.out_frames + f) * WIRE_CHUNK_MAX;
+    for (long i = t; i < (count + 3) / 4 * 4; i += WIRE_THREADS) {  // zeros pad the last dword
+      const long m = m0 + i;
+      float v = 0.f;
+      if (i < count)
+        v = identity ? s_x[WIRE_TAIL + (m - N0)]
+                     : resample_out(s_x, N0 - WIRE_TAIL, N1, s_taps, p.L, p.up, p.down, p.half, m);
+      s_y[i] = v;
+    }
+    __syncthreads();
+    for (long g = t; 4 * g < count; g += WIRE_THREADS) {
+      const float4 y4 = reinterpret_cast<const float4*>(s_y)[g];
+      const float v[4] = {y4.x, y4.y, y4.z, y4.w};
+      wire_store4(dst, g, enc, v);
+    }
+    if (t == 0) cnt[f] = (int)count * (enc == WIRE_S16 ? 2 : 1);
+    nf += 1;
+    __syncthreads();  // every lane has read the window
+    if (t < WIRE_TAIL) s_x[t] = s_x[1920 + t];
+  }
+  if (!any) return;  // uniform
+  if (t < WIRE_TAIL) a.tail[(long)b * WIRE_TAIL + t] = s_x[t];  // each lane wrote its own entry
+  if (t == 0) a.frames[b] = (int)nf;
+}
+
+void wire_stage(const WireArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
+    throw std::runtime_error("wire_stage: bad pass shape");
+  for (int r = 0; r < WIRE_RATES; ++r)
+    if (a.plan[r].L > WIRE_TAPS_MAX || a.plan[r].L < 1 || 2 * a.plan[r].half > WIRE_TAIL * a.plan[r].up)
+      throw std::runtime_error("wire_stage: plan outside the kernel's LDS window");
+  hipLaunchKernelGGL(k_wire, dim3(a.B), dim3(WIRE_THREADS), 0, s, a);
+}
+
+// whole-signal encode of n samples (already at the wire rate), four per lane
+__global__ __launch_bounds__(256) void k_wire_encode(const float* __restrict__ x, long n, int enc,
+                                                     unsigned char* __restrict__ out) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (4 * g >= n) return;
+  float v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = 4 * g + q < n ? x[4 * g + q] : 0.f;
+  wire_store4(out, g, enc, v);
+}
+void wire_encode(const float* x, long n, int enc, unsigned char* out, hipStream_t s) {
+  if (n <= 0) return;
+  if (enc != WIRE_S16 && enc != WIRE_ULAW && enc != WIRE_ALAW) throw std::runtime_error("wire_encode: encoding");
+  hipLaunchKernelGGL(k_wire_encode, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, s, x, n, enc, out);
 }
 
 // dst[c][r][:] = src[c * chunk_stride + :] for c < nch, r < rows: the replicate padding of every

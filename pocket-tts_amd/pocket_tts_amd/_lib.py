@@ -20,6 +20,9 @@ SAMPLE_RATE = 24000
 QUANT_NONE, QUANT_FLOW_LM, QUANT_ALL = 0, 1, 2
 BACK_F32, BACK_BF16, BACK_F32X6 = 0, 1, 2  # ptts_engine_config.back_mfma (PTTS_BACK_*)
 SAMPLES_F32, SAMPLES_S16 = 0, 1  # sample_format of ptts_voice_job_start (PTTS_SAMPLES_*)
+WIRE_NONE, WIRE_S16, WIRE_ULAW, WIRE_ALAW = 0, 1, 2, 3  # PTTS_WIRE_*
+WIRE_CHUNK_MAX = 8192  # PTTS_WIRE_CHUNK_MAX
+WIRE_RATES = (8000, 16000, 24000, 44100, 48000)
 ABI_VERSION = 6  # PTTS_ABI_VERSION of include/pocket_tts.h that the structs below mirror
 
 F32P = C.POINTER(C.c_float)
@@ -54,6 +57,15 @@ class GenParams(C.Structure):
         ("frames_after_eos", C.c_int),
         ("max_frames", C.c_int),
         ("seed", C.c_uint64),
+    ]
+
+
+class SlotOpts(C.Structure):
+    _fields_ = [
+        ("size", C.c_size_t),
+        ("lsd_steps", C.c_int),
+        ("wire_rate", C.c_int),
+        ("wire_encoding", C.c_int),
     ]
 
 
@@ -101,6 +113,12 @@ SIGNATURES = [
     ("ptts_slot_open_ex", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, I32P, C.c_int, C.POINTER(GenParams), C.c_int]),
     ("ptts_slots_open_ex", C.c_int, [C.c_void_p, C.c_int, I32P, C.POINTER(C.c_void_p), I32P, I32P,
                                      C.POINTER(GenParams), I32P]),
+    ("ptts_slots_open_opts", C.c_int, [C.c_void_p, C.c_int, I32P, C.POINTER(C.c_void_p), I32P, I32P,
+                                       C.POINTER(GenParams), C.c_void_p]),
+    ("ptts_wire_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_fetch_wire", C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_size_t, C.POINTER(C.c_int)]),
+    ("ptts_wire_len", C.c_long, [C.c_long, C.c_int, C.c_int]),
+    ("ptts_wire_encode", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, U8P]),
     ("ptts_lsd_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ptts_probe_overlap", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("ptts_slot_close", C.c_int, [C.c_void_p, C.c_int]),

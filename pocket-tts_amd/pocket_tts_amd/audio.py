@@ -7,7 +7,11 @@ Mirrors crates/pocket-tts/src/audio.rs:
     keeps the whole samples read so far (the reference accepts truncated files, audio.rs:33-49).
   * `pcm_i16_le_bytes` (audio.rs:110-146): clamp to [-1, 1], x 32767, truncate toward zero,
     channels interleaved.
-  * `write_wav` / `wav_bytes` (audio.rs:148-185): 16-bit integer PCM RIFF/WAVE.
+  * `write_wav` / `wav_bytes` (audio.rs:148-185): 16-bit integer PCM RIFF/WAVE; with an encoding,
+    also G.711 mu-law / A-law files (8 bits per sample, an 18-byte fmt chunk and a fact chunk).
+  * `lin2ulaw` / `lin2alaw` / `wire_bytes`: the host restatement of the engine's wire stage
+    encodings (include/pocket_tts.h, PTTS_WIRE_*): what the GPU writes, for tests and for rows
+    that did not go through it.
   * `normalize_peak` (audio.rs:187-194).
 Resampling to 24 kHz is not here: it runs on the GPU inside `ptts_voice_from_audio`
 (the polyphase resampler of pocket-tts_amd/csrc/kernels.hip).
@@ -22,7 +26,10 @@ import numpy as np
 
 WAVE_FORMAT_PCM = 0x0001
 WAVE_FORMAT_IEEE_FLOAT = 0x0003
+WAVE_FORMAT_ALAW = 0x0006
+WAVE_FORMAT_MULAW = 0x0007
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
+ENCODINGS = ("pcm_s16le", "ulaw", "alaw")
 
 
 class WavError(ValueError):
@@ -94,14 +101,77 @@ def pcm_i16_le_bytes(audio: np.ndarray) -> bytes:
     return x.astype(np.int16).astype("<i2").tobytes()  # float -> int casts truncate toward zero
 
 
-def wav_bytes(audio: np.ndarray, sample_rate: int = 24000) -> bytes:
-    a = np.asarray(audio, np.float32)
-    ch = 1 if a.ndim == 1 else a.shape[0]
-    data = pcm_i16_le_bytes(a)
-    hdr = b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE"
-    hdr += b"fmt " + struct.pack("<IHHIIHH", 16, WAVE_FORMAT_PCM, ch, sample_rate, sample_rate * 2 * ch, 2 * ch, 16)
-    hdr += b"data" + struct.pack("<I", len(data))
-    return hdr + data
+def pcm_i16(audio: np.ndarray) -> np.ndarray:
+    """The 16-bit wire value of every sample: trunc(clip(x, -1, 1) * 32767) in float32."""
+    x = np.clip(np.asarray(audio, np.float32), -1.0, 1.0) * np.float32(32767.0)
+    return x.astype(np.int16)
+
+
+def lin2ulaw(s: np.ndarray) -> np.ndarray:
+    """G.711 mu-law code (uint8) of 16-bit samples: the rule of the engine's wire stage, equal to
+    CPython's audioop.lin2ulaw(.., 2) on all 65,536 inputs."""
+    v = np.asarray(s, np.int16).astype(np.int32) >> 2
+    mask = np.where(v < 0, 0x7F, 0xFF)
+    v = np.minimum(np.abs(v), 8159) + 33
+    seg = np.searchsorted(np.array([0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF]), v, side="left")
+    code = np.where(seg >= 8, 0x7F, (np.minimum(seg, 7) << 4) | ((v >> (np.minimum(seg, 7) + 1)) & 15))
+    return (code ^ mask).astype(np.uint8)
+
+
+def lin2alaw(s: np.ndarray) -> np.ndarray:
+    """G.711 A-law code (uint8) of 16-bit samples; equal to audioop.lin2alaw(.., 2) on all inputs."""
+    s = np.asarray(s, np.int16).astype(np.int32)
+    mask = np.where(s >= 0, 0xD5, 0x55)
+    v = np.where(s >= 0, s >> 3, (-s - 1) >> 3)
+    seg = np.searchsorted(np.array([0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF]), v, side="left")
+    code = (seg << 4) | ((v >> np.where(seg < 2, 1, seg)) & 15)
+    return (code ^ mask).astype(np.uint8)
+
+
+def wire_bytes(audio: np.ndarray, encoding: str = "pcm_s16le") -> bytes:
+    """Mono float32 samples (already at the wire rate) -> the bytes of `encoding`."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"encoding must be one of {list(ENCODINGS)}, got {encoding!r}")
+    s = pcm_i16(np.asarray(audio, np.float32).reshape(-1))
+    if encoding == "pcm_s16le":
+        return s.astype("<i2").tobytes()
+    return (lin2ulaw(s) if encoding == "ulaw" else lin2alaw(s)).tobytes()
+
+
+def wav_header(n_data: int, sample_rate: int = 24000, encoding: str = "pcm_s16le", channels: int = 1) -> bytes:
+    """RIFF/WAVE header in front of n_data bytes of `encoding`: format tag 1 (16-bit PCM, a 16-byte
+    fmt chunk), or 7 (mu-law) / 6 (A-law) with 8 bits per sample, an 18-byte fmt chunk (cbSize 0)
+    and a fact chunk holding the sample count per channel, as non-PCM formats require."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"encoding must be one of {list(ENCODINGS)}, got {encoding!r}")
+    ch = channels
+    if encoding == "pcm_s16le":
+        fmt = b"fmt " + struct.pack("<IHHIIHH", 16, WAVE_FORMAT_PCM, ch, sample_rate, sample_rate * 2 * ch, 2 * ch, 16)
+        fact = b""
+    else:
+        tag = WAVE_FORMAT_MULAW if encoding == "ulaw" else WAVE_FORMAT_ALAW
+        fmt = b"fmt " + struct.pack("<IHHIIHHH", 18, tag, ch, sample_rate, sample_rate * ch, ch, 8, 0)
+        fact = b"fact" + struct.pack("<II", 4, n_data // ch)
+    body = fmt + fact + b"data" + struct.pack("<I", n_data)
+    return b"RIFF" + struct.pack("<I", 4 + len(body) + n_data + (n_data & 1)) + b"WAVE" + body
+
+
+def wav_bytes(audio, sample_rate: int = 24000, encoding: str = "pcm_s16le") -> bytes:
+    """A WAV file of `audio`: float32 samples [channels, n] or [n] (encoded here: 16-bit by
+    pcm_i16_le_bytes, G.711 mono by wire_bytes), or bytes already in `encoding` (mono; what
+    Engine.fetch_wire returned)."""
+    if isinstance(audio, (bytes, bytearray, memoryview)):
+        data, ch = bytes(audio), 1
+    else:
+        a = np.asarray(audio, np.float32)
+        ch = 1 if a.ndim == 1 else a.shape[0]
+        if encoding == "pcm_s16le":
+            data = pcm_i16_le_bytes(a)
+        else:
+            if ch != 1:
+                raise ValueError("G.711 output is mono")
+            data = wire_bytes(a, encoding)
+    return wav_header(len(data), sample_rate, encoding, ch) + data + (b"\0" if len(data) & 1 else b"")
 
 
 def write_wav(path, audio: np.ndarray, sample_rate: int = 24000) -> None:

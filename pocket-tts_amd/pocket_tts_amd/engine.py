@@ -7,8 +7,23 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, EngineConfig,
-                   GenParams, check, fptr, lib, u8ptr)
+from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
+                   WIRE_ALAW, WIRE_CHUNK_MAX, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
+                   SlotOpts, check, fptr, lib, u8ptr)
+
+# wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
+WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW}
+
+
+def wire_encoding_code(encoding) -> int:
+    """PTTS_WIRE_* of an encoding given by name (WIRE_ENCODINGS), by code, or None (WIRE_NONE)."""
+    if encoding is None:
+        return WIRE_NONE
+    if isinstance(encoding, str):
+        if encoding not in WIRE_ENCODINGS:
+            raise ValueError(f"encoding must be one of {sorted(WIRE_ENCODINGS)}, got {encoding!r}")
+        return WIRE_ENCODINGS[encoding]
+    return int(encoding)
 
 
 @dataclass
@@ -25,6 +40,15 @@ class GenerationParams:
     # 1 .. the engine's cap; None: the engine's lsd_decode_steps. Not part of ptts_gen_params: the
     # admission passes it beside the struct (ptts_slot_open_ex).
     lsd_steps: int | None = None
+    # wire format of the row (wire-enabled engines; Engine.fetch_wire returns its bytes): sample_rate
+    # one of WIRE_RATES, encoding "pcm_s16le" / "ulaw" / "alaw" (or a PTTS_WIRE_* code). None in both:
+    # no wire output; None in one: 24000 / 16-bit. Passed beside the struct too (ptts_slots_open_opts).
+    sample_rate: int | None = None
+    encoding: str | int | None = None
+
+    def wire(self) -> tuple[int, int]:
+        """(wire_rate, wire_encoding) of ptts_slot_opts; (0, 0): none."""
+        return int(self.sample_rate or 0), wire_encoding_code(self.encoding)
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
@@ -91,7 +115,7 @@ class Engine:
                  seed: int = 0x5EED, weights_path: str | None = None, weight_blob: int | None = None,
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
-                 back_mfma: int | None = None, max_lsd_steps: int | None = None):
+                 back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -106,7 +130,9 @@ class Engine:
         frame computed 2 n - 1 calls earlier (`frame_lag`). back_mfma (ptts_engine_config.back_mfma): how the
         Mimi decode's GEMMs and convs use the matrix cores, BACK_F32 (exact f32 FMA chain), BACK_F32X6
         (f32 products as six bf16 piece products, f32 accuracy) or BACK_BF16 (operands rounded to
-        bf16: a variant gated on PCM accuracy); back_bf16=True is BACK_BF16."""
+        bf16: a variant gated on PCM accuracy); back_bf16=True is BACK_BF16.
+        wire=True (ptts_wire_enable): rows admitted with GenerationParams.sample_rate / encoding also
+        get their wire bytes, converted on the GPU (fetch_wire)."""
         if back_mfma is None:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
@@ -131,6 +157,14 @@ class Engine:
         self.back_frames = int(back_frames) if pipeline else 1
         self.back_mfma = int(back_mfma)
         self.back_bf16 = self.back_mfma == BACK_BF16
+        self.wire = bool(wire)
+        if wire:
+            try:
+                check(lib().ptts_wire_enable(self.handle, 1))
+            except Exception:
+                self.close()
+                raise
+        self._wire_buf = self._wire_n = None
 
     def test_gemm(self, layout: int, x: np.ndarray, w: np.ndarray, splits: int = 1, tail_slices: int = 0) -> np.ndarray:
         """GEMM-core test hook (ptts_test_gemm): x [m][k] @ w [n][k]^T on tile `layout`; splits > 1
@@ -286,6 +320,8 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
+        if params.wire() != (0, 0):
+            return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
         check(lib().ptts_slot_open_ex(self.handle, slot, voice.handle, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
@@ -302,6 +338,12 @@ class Engine:
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
+        if any(p.wire() != (0, 0) for p in params_list):  # a row with a wire format: ptts_slots_open_opts
+            opts = (SlotOpts * n)(*[SlotOpts(C.sizeof(SlotOpts), int(lsd[i]), *p.wire())
+                                    for i, p in enumerate(params_list)])
+            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
+            return
         check(lib().ptts_slots_open_ex(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
                                        nid.ctypes.data_as(i32), ps, lsd.ctypes.data_as(i32)))
 
@@ -355,6 +397,26 @@ class Engine:
         r.valid = r.valid.astype(bool)
         r.last = r.last.astype(bool)
         return r
+
+    def fetch_wire(self, n_rows: int, calls_back: int = 0) -> list[bytes]:
+        """The wire chunks of the frame fetch(n_rows, calls_back) returns (ptts_fetch_wire): one
+        bytes object per row, empty for a row with no wire format or no frame."""
+        if self._wire_buf is None:
+            self._wire_buf = np.zeros((self.max_slots, WIRE_CHUNK_MAX), np.uint8)
+            self._wire_n = np.zeros(self.max_slots, np.int32)
+        check(lib().ptts_fetch_wire(self.handle, calls_back, n_rows, u8ptr(self._wire_buf), WIRE_CHUNK_MAX,
+                                    self._wire_n.ctypes.data_as(C.POINTER(C.c_int))))
+        return [self._wire_buf[b, : self._wire_n[b]].tobytes() for b in range(n_rows)]
+
+    def encode_wire(self, pcm: np.ndarray, sample_rate: int = 24000, encoding="pcm_s16le") -> bytes:
+        """Whole-signal f32 PCM at 24 kHz -> wire bytes on the GPU (ptts_wire_encode): the resampler
+        of resample(), then the encoder of the streaming stage."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        enc = wire_encoding_code(encoding)
+        n = int(lib().ptts_wire_len(x.size, int(sample_rate), enc))
+        out = np.zeros(max(n, 1), np.uint8)
+        check(lib().ptts_wire_encode(self.handle, fptr(x), x.size, int(sample_rate), enc, out.ctypes.data_as(U8P)))
+        return out[:n].tobytes()
 
     def fetch_ready(self, calls_back: int = 0) -> bool:
         """fetch(calls_back=...) would not block (ptts_fetch_ready)."""

@@ -34,6 +34,17 @@ HTTP (`create_app`, FastAPI; routes of pocket-tts-cli/src/server/routes.rs:20-30
 Wire formats follow crates/pocket-tts/src/audio.rs:110-185 (clamp to [-1, 1], x 32767,
 truncate to i16; 16-bit mono RIFF/WAVE).
 
+Per-request output format (`--wire`, the default; no reference counterpart: the reference emits
+24 kHz only): /generate, /stream and /v1/audio/speech also take `sample_rate` (8000, 16000, 24000,
+44100, 48000) and `encoding` (`pcm_s16le`, `ulaw`, `alaw`); one of them alone defaults the other
+to 24000 / pcm_s16le, and /v1/audio/speech's `response_format` also takes `ulaw` / `alaw` (raw
+G.711, 8 kHz unless `sample_rate` says otherwise). Such a row is resampled and encoded on the GPU
+at the end of the Mimi decode and the scheduler hands its bytes on
+untouched; requests with different formats, and with none, share a batch. /generate answers with a
+WAV file of that encoding (G.711: format tag 7 / 6, 8 bits, a `fact` chunk), /stream with the raw
+bytes. A request that names neither field gets today's bytes by today's code path. Unknown values,
+or either field on a `--no-wire` server, get 400.
+
 Per-request voices (pocket-tts-cli/src/voice.rs:67-222): the `voice` field is first a registered
 name; else base64 WAV audio, as a `data:audio/...;base64,` URL or as raw base64 (voice.rs:172-189:
 longer than 100 characters, base64 alphabet only); else the request is refused (400). The clip is
@@ -68,8 +79,8 @@ from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
-from ._lib import FRAME, SAMPLE_RATE
-from .audio import pcm_i16_le_bytes, wav_bytes  # noqa: F401 (re-exported wire formats)
+from ._lib import FRAME, SAMPLE_RATE, WIRE_RATES
+from .audio import ENCODINGS, pcm_i16_le_bytes, wav_bytes, wire_bytes  # noqa: F401 (re-exported wire formats)
 from .engine import GenerationParams, Voice
 from .text import estimate_frames_after_eos, max_gen_len, prepare_text_prompt
 
@@ -227,6 +238,15 @@ class Request:
     preview: int = 0
     start_step: int = 0  # the scheduler's step that starts the row (trace)
 
+    # (sample_rate, encoding name) of a request with a wire format: its items are bytes the engine
+    # converted (Engine.fetch_wire), not float32 frames; None: today's float32 frames
+    wire: tuple[int, str] | None = None
+
+    def __post_init__(self):
+        rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
+        if rate or enc:
+            self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
+
     def put(self, item):
         """Driver side: hand over a frame (np.ndarray), the end marker (None) or an error."""
         self.out.put(item)
@@ -270,6 +290,10 @@ class Request:
     def audio(self, timeout: float | None = None) -> np.ndarray:
         frames = list(self.stream(timeout))
         return np.concatenate(frames) if frames else np.zeros(0, np.float32)
+
+    def wire_audio(self, timeout: float | None = None) -> bytes:
+        """A wire request's whole output: its chunks joined, untouched."""
+        return b"".join(self.stream(timeout))
 
 
 class BatchScheduler:
@@ -439,6 +463,13 @@ class BatchScheduler:
             req = self.active.get(slot)
             if req is None or req.frames or req.preview:  # the regular frame 0 came first
                 continue
+            fmt = req.wire
+            if fmt is not None:
+                # a resampled row's first chunk is shorter than its preview's frame (the filter's
+                # delay): it waits for its regular first chunk; a 24 kHz row's preview is encoded here
+                if fmt[0] != SAMPLE_RATE:
+                    continue
+                pcm = wire_bytes(pcm, fmt[1])
             req.preview = 1
             req.frames = 1
             self.row_frames += 1
@@ -446,7 +477,9 @@ class BatchScheduler:
             req.times["first"] = time.time()
             req.put(pcm)
 
-    def _deliver(self, res, rows) -> list[int]:
+    def _deliver(self, res, rows, wire=None) -> list[int]:
+        """wire: the call's Engine.fetch_wire chunks (a call with wire rows): those rows get their
+        bytes untouched; numpy is called for rows without a format only (by their consumers)."""
         done = []
         for slot, req in list(self.active.items()):
             if slot < rows and res.valid[slot]:
@@ -457,7 +490,8 @@ class BatchScheduler:
                     self.row_frames += 1
                     if req.frames == 1:
                         req.times["first"] = time.time()
-                    req.put(res.pcm[slot])  # a view: fetch() returns fresh arrays every step
+                    # a view: fetch() returns fresh arrays every step
+                    req.put(res.pcm[slot] if req.wire is None else wire[slot])
                 if res.last[slot]:
                     req.times["last"] = time.time()
                     if self.trace:
@@ -530,8 +564,11 @@ class BatchScheduler:
                             self._deliver_previews()
                             time.sleep(self.poll_s)
                     res = self.engine.fetch(issued[0], calls_back=cb)
+                    wire = None
+                    if any(r.wire is not None for r in self.active.values()):
+                        wire = self.engine.fetch_wire(issued[0], calls_back=cb)
                     self._deliver_previews()  # those that completed while fetch() waited: ahead of it
-                    done = self._deliver(res, issued.popleft())
+                    done = self._deliver(res, issued.popleft(), wire)
                     if done:
                         with self.cv:
                             for slot in done:
@@ -738,6 +775,7 @@ class TTSService:
         self.voice_chunk_frames, self.voice_resampler = int(voice_chunk_frames), voice_resampler
         eng = getattr(scheduler, "engine", None) or getattr(getattr(scheduler, "schedulers", [None])[0], "engine", None)
         self.max_ctx = max_ctx if max_ctx is not None else getattr(eng, "max_ctx", None)
+        self.wire = bool(getattr(eng, "wire", False))  # the engines convert to wire formats (--wire)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -751,7 +789,16 @@ class TTSService:
     def request(self, text: str | None = None, token_ids=None, voice: str | None = None,
                 temperature: float | None = None, eos_threshold: float | None = None,
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
-                max_frames: int | None = None) -> Request:
+                max_frames: int | None = None, sample_rate: int | None = None,
+                encoding: str | None = None) -> Request:
+        if sample_rate is not None or encoding is not None:
+            if sample_rate is not None and sample_rate not in WIRE_RATES:
+                raise ValueError(f"sample_rate must be one of {list(WIRE_RATES)}")
+            if encoding is not None and encoding not in ENCODINGS:
+                raise ValueError(f"encoding must be one of {list(ENCODINGS)}")
+            if not self.wire:
+                raise ValueError("this server runs without wire output (--no-wire): sample_rate / encoding "
+                                 "are not available")
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
@@ -777,9 +824,10 @@ class TTSService:
         # the scheduler closes it only once none of them is still waiting (BatchScheduler.retire)
         with self._lock:
             return self._submit_locked(ids, clip if clip is not None else self.voices[name], temperature,
-                                       eos_threshold, noise_clamp, fae, mgl, lsd_steps)
+                                       eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding)
 
-    def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps) -> Request:
+    def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
+                       sample_rate=None, encoding=None) -> Request:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -787,6 +835,8 @@ class TTSService:
                              noise_clamp=self.noise_clamp if noise_clamp is None else noise_clamp,
                              frames_after_eos=fae, max_frames=mgl, seed=seed,
                              lsd_steps=None if lsd_steps is None else int(lsd_steps))
+        if sample_rate is not None or encoding is not None:  # a request that names neither: as before
+            p.sample_rate, p.encoding = sample_rate, encoding
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     # -- per-request and run-time voices
@@ -871,6 +921,10 @@ class GenerateRequest(BaseModel):
     lsd_steps: int | None = None
     eos_threshold: float | None = None
     noise_clamp: float | None = None
+    # wire format (converted on the GPU): 8000 / 16000 / 24000 / 44100 / 48000 and pcm_s16le / ulaw /
+    # alaw; one of them alone defaults the other to 24000 / pcm_s16le; neither: today's output
+    sample_rate: int | None = None
+    encoding: str | None = None
 
 
 class OpenAIRequest(BaseModel):
@@ -879,9 +933,11 @@ class OpenAIRequest(BaseModel):
     model: str = "pocket-tts"
     input: str | None = None
     voice: str | None = None
-    response_format: str | None = None
+    response_format: str | None = None  # wav (default), pcm, ulaw, alaw (raw G.711, 8 kHz unless sample_rate)
     token_ids: list[int] | None = None
     words: int | None = None
+    sample_rate: int | None = None
+    encoding: str | None = None
 
 
 # /stream: at most one chunk per stream per 20 ms after the first (32 streams x 50 wakes/s keep the
@@ -927,7 +983,10 @@ async def pcm_chunks(r: Request):
         if batch:
             if "chunk0" not in r.times:
                 r.times["chunk0"] = time.time()
-            yield pcm_i16_le_bytes(batch[0] if len(batch) == 1 else np.concatenate(batch))
+            if isinstance(batch[0], bytes):  # a wire request: the engine's bytes, untouched
+                yield batch[0] if len(batch) == 1 else b"".join(batch)
+            else:
+                yield pcm_i16_le_bytes(batch[0] if len(batch) == 1 else np.concatenate(batch))
         if done:
             return
         if batch:
@@ -994,6 +1053,8 @@ def create_app(service: TTSService):
         if redirect is not None:
             return redirect
         r = submit(**req.model_dump())
+        if r.wire is not None:
+            return Response(wav_bytes(r.wire_audio(), *r.wire), media_type="audio/wav", headers=hdr)
         return Response(wav_bytes(r.audio()), media_type="audio/wav", headers=hdr)
 
     @app.post("/stream")
@@ -1004,7 +1065,8 @@ def create_app(service: TTSService):
             return redirect
         r = submit(**req.model_dump())
         r.times["route"] = t_route
-        return StreamingResponse(pcm_chunks(r), media_type="audio/pcm",
+        media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1] if r.wire else "", "audio/pcm")
+        return StreamingResponse(pcm_chunks(r), media_type=media,
                                  headers={**hdr, "X-PTTS-Route-Time": f"{t_route:.6f}"})
 
     @app.post("/v1/audio/speech")
@@ -1012,9 +1074,24 @@ def create_app(service: TTSService):
         redirect = overflow(request)
         if redirect is not None:
             return redirect
-        r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words)
+        fmt = req.response_format or "wav"
+        rate, enc = req.sample_rate, req.encoding
+        if fmt in ("ulaw", "alaw"):  # raw G.711: telephony's 8 kHz unless the request names a rate
+            if enc not in (None, fmt):
+                raise HTTPException(status_code=400, detail=f"response_format {fmt} contradicts encoding {enc}")
+            rate, enc = rate or 8000, fmt
+        elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
+            raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
+        r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
+                   encoding=enc)
+        if r.wire is not None:
+            data = r.wire_audio()
+            if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
+                return Response(wav_bytes(data, *r.wire), media_type="audio/wav", headers=hdr)
+            media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1], "audio/pcm")
+            return Response(data, media_type=media, headers=hdr)
         audio = r.audio()
-        if (req.response_format or "wav") == "pcm":
+        if fmt == "pcm":
             return Response(pcm_i16_le_bytes(audio), media_type="audio/pcm", headers=hdr)
         return Response(wav_bytes(audio), media_type="audio/wav", headers=hdr)
 
@@ -1143,7 +1220,8 @@ def _worker_engine(args, Engine):
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     kw = dict(max_slots=args.slots, max_ctx=args.max_ctx, weights_path=args.weights, pipeline=True,
-              back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps)
+              back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
+              wire=args.wire)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1205,6 +1283,9 @@ def main(argv=None):
     ap.add_argument("--max-lsd-steps", type=int, default=None,
                     help="largest per-request lsd_steps (the engine's cap; default: --lsd-steps). Requests with "
                          "different counts share the batch; a step costs the largest count among its open rows")
+    ap.add_argument("--wire", action=argparse.BooleanOptionalAction, default=True,
+                    help="wire formats converted on the GPU (requests' sample_rate / encoding); --no-wire: the "
+                         "engine as before, such requests get 400")
     ap.add_argument("--preview-rows", type=int, default=8,
                     help="first-frame previews: rows per call whose first frame is decoded at once (0: off)")
     ap.add_argument("--voice-cache", type=int, default=64,

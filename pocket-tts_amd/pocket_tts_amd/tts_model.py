@@ -70,17 +70,20 @@ class TTSModel:
                          eos_threshold: float = -4.0, noise_clamp: float | None = None, *,
                          weights_path: str | None = None, tokenizer_path: str | None = None, seed: int = 0x5EED,
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
-                         weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None) -> "TTSModel":
+                         weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
+                         wire: bool = False) -> "TTSModel":
         """max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
         (the engine's cap; None: lsd_decode_steps itself, the field can then only be lowered).
         weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
-        from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json."""
+        from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json.
+        wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=)."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
             tokenizer = load_tokenizer(tokenizer_path)
         eng = Engine(device=device, max_slots=1, max_ctx=max_ctx, lsd_decode_steps=lsd_decode_steps, seed=seed,
-                     weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps)
+                     weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
+                     wire=wire)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -164,15 +167,19 @@ class TTSModel:
         return GenerationParams(temp=self.temp, eos_threshold=self.eos_threshold, noise_clamp=self.noise_clamp,
                                 frames_after_eos=frames_after_eos, max_frames=max_frames, seed=self._seed)
 
-    def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int
-                 ) -> Iterator[np.ndarray]:
-        """generate_stream_segment (tts_model.rs:935-1071) on engine row 0."""
+    def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
+                 sample_rate: int | None = None, encoding=None) -> Iterator[np.ndarray]:
+        """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
+        (sample_rate / encoding; a wire-enabled engine) the items are the row's wire chunks, bytes
+        converted on the GPU (Engine.fetch_wire), instead of f32 frames."""
         cap = self.engine.max_lsd_steps
         if not 1 <= int(self.lsd_decode_steps) <= cap:
             raise ValueError(f"lsd_decode_steps {self.lsd_decode_steps} outside [1, {cap}], the engine's cap "
                              "(max_lsd_decode_steps at load)")
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
+        params.sample_rate, params.encoding = sample_rate, encoding
+        wire = params.wire() != (0, 0)
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
@@ -184,37 +191,44 @@ class TTSModel:
                     continue
                 return
             lead = 0
-            yield r.pcm[0].reshape(1, 1, FRAME).copy()
+            yield self.engine.fetch_wire(1)[0] if wire else r.pcm[0].reshape(1, 1, FRAME).copy()
             if r.last[0]:
                 return
 
     def generate_stream(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
-                        words: int | None = None) -> Iterator[np.ndarray]:
+                        words: int | None = None, sample_rate: int | None = None, encoding=None
+                        ) -> Iterator[np.ndarray]:
         """tts_model.rs:894-913. Text: one segment per sentence chunk; max_gen_len and the EOS tail
         from each chunk (:968-969). Token ids (an extension for callers with their own tokenizer):
         one segment; ids carry no word count, so the caller passes `words` (the reference's rules
         then apply: max_gen_len = (words + 2) * 13, tail 5 frames up to 4 words else 3) or an
-        explicit max_frames (tail 3)."""
+        explicit max_frames (tail 3).
+        sample_rate (8000, 16000, 24000, 44100, 48000) and / or encoding ("pcm_s16le", "ulaw",
+        "alaw"): the items are bytes in that wire format, one chunk per frame (every segment is
+        resampled on its own: its chunks are the whole-signal resample of the segment)."""
         if not isinstance(text_or_ids, str):
             ids = np.asarray(text_or_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
-            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae)
+            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk))
+                                     estimate_frames_after_eos(chunk), sample_rate, encoding)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
-                 words: int | None = None) -> np.ndarray:
-        """tts_model.rs:687-703: all frames concatenated, [1, N*1920]."""
-        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words))
+                 words: int | None = None, sample_rate: int | None = None, encoding=None):
+        """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding,
+        the wire bytes of generate_stream concatenated."""
+        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding))
         if not frames:
             raise RuntimeError("No audio generated")
+        if sample_rate is not None or encoding is not None:
+            return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
 
     def generate_stream_long(self, text: str, voice_state: Voice) -> Iterator[np.ndarray]:
