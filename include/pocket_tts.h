@@ -319,6 +319,16 @@ int ptts_wire_encode(ptts_engine* e, const float* pcm, int n_samples, int sample
  * may be NULL. */
 int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run);
 int ptts_slot_close(ptts_engine* e, int slot);
+/* Stop the utterances of n distinct slots without draining the pipeline (ptts_slot_close waits for
+ * every queued call; this call waits for nothing on the GPU). It is stream-ordered like an
+ * admission: the slots go idle behind the step calls already issued, and the other rows are not
+ * touched. From its return, ptts_fetch / ptts_fetch_prev / ptts_fetch_wire / ptts_preview_fetch
+ * report no frame of a cancelled utterance (frame_valid 0, n_bytes 0, never `last`): frames of it
+ * still in flight are dropped by their call index, frames of the slot's previous or next utterance
+ * are not. A cancelled slot may be admitted again at once. Cancelling an idle, finished or
+ * never-admitted slot is a no-op. A slot out of range or named twice is PTTS_ERR_INVALID and
+ * cancels nothing. */
+int ptts_slots_cancel(ptts_engine* e, int n, const int* slots);
 
 /* THE batched hot path: one iteration of the loop body of generate_stream_segment
  * (tts_model.rs:1006-1070) for rows [0, n_rows): FlowLM step -> EOS -> flow sampling ->

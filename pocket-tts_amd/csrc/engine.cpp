@@ -195,6 +195,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
   drained_.assign(B, 1);
   admit_call_.assign(B, -1);
   slot_lsd_.assign(B, 0);
+  cancelled_.assign(B, 0);
   share_voice_ = probe_env("PTTS_NO_SHARED_VOICE") == nullptr;
 #ifdef PTTS_PROBES
   if (probe_env("PTTS_STAMPS")) {
@@ -261,6 +262,9 @@ Engine::Engine(const ptts_engine_config& cfg) {
   *h_err_ = 0;
   PTTS_HIP(hipHostMalloc((void**)&h_slots_, sizeof(int) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_st_, sizeof(SlotState) * B, hipHostMallocDefault));
+  PTTS_HIP(hipHostMalloc((void**)&h_idle_, sizeof(SlotState), hipHostMallocDefault));
+  *h_idle_ = SlotState{};
+  h_idle_->eos_step = -1;
   PTTS_HIP(hipHostMalloc((void**)&h_fp_, sizeof(int) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_ids_, sizeof(int) * PREFILL, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_tab_, sizeof(int) * 4 * PREFILL, hipHostMallocDefault));  // ptab | ctab | qrow | orow
@@ -349,6 +353,7 @@ Engine::~Engine() {
   for (int p = 0; p < NHB / 2; ++p)
     if (h_pcmp_[p]) (void)hipHostFree(h_pcmp_[p]);
   if (h_act_) (void)hipHostFree(h_act_);
+  if (h_idle_) (void)hipHostFree(h_idle_);
   if (h_wire_) (void)hipHostFree(h_wire_);
   for (unsigned char* hp : h_wireb_)
     if (hp) (void)hipHostFree(hp);
@@ -1787,6 +1792,10 @@ void Engine::call_async(int B, bool run_front) {
   prev_hb_ = out_hb_;
   prev_rows_ = out_rows_;
   prev_k_ = out_k_;
+  if (!cancel_wins_.empty())  // windows wholly before the oldest frame a fetch can still return
+    cancel_wins_.erase(std::remove_if(cancel_wins_.begin(), cancel_wins_.end(),
+                                      [this](const CancelWin& w) { return w.to <= prev_k_; }),
+                       cancel_wins_.end());
   const int hb = (int)(k_ % nhb_), qp = (int)(k_ & 1);
   // the front part of this call, or (a flush) its hand-off buffer marked frame-less
   // its Euler step count: the largest count among the call's rows that are still open
@@ -1929,7 +1938,8 @@ void Engine::fetch(int B, float* pcm, uint8_t* valid, uint8_t* last, float* eos,
     return nfr_ > 1 ? h_pcmp_[q / nfr_] + ((size_t)b * nfr_ + q % nfr_) * FRAME : h_pcm_[q] + (size_t)b * FRAME;
   };
   for (int b = 0; b < B; ++b) {
-    const bool ok = b < n && hf[b].valid;
+    // (a frame of an utterance slots_cancel stopped is not reported: it never drains the slot either)
+    const bool ok = b < n && hf[b].valid && (cancel_wins_.empty() || !frame_cancelled(b, fk));
     // its last frame's pass has completed (waited above) - unless the slot was admitted again
     // after that frame's call (a driver that admits the next utterance before fetching the last
     // frame of the previous one, as bench.py does): then the frame is the previous utterance's and
@@ -2945,6 +2955,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   }
   for (int i = 0; i < n; ++i) {
     drained_[slots[i]] = 0;
+    cancelled_[slots[i]] = 0;
     admit_call_[slots[i]] = k_;
     slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
     if (wire_) slot_wire_[slots[i]] = wfmt[i];
@@ -3080,6 +3091,7 @@ void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_st
   // the same frame, rows and event as fetch() of that call; no bookkeeping of its own
   const int q = calls_back ? prev_hb_ : out_hb_;
   const int rows = calls_back ? prev_rows_ : out_rows_;
+  const long long fk = calls_back ? prev_k_ : out_k_;
   if (pipeline_) PTTS_HIP(hipEventSynchronize(ev_back_[q - q % nfr_]));
   else sync();
   const int n = std::min(B, rows);
@@ -3088,6 +3100,7 @@ void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_st
   for (int b = 0; b < B; ++b) {
     const int f = q % nfr_;
     int c = b < n ? cnt[(size_t)b * nfr_ + f] : 0;
+    if (c && !cancel_wins_.empty() && frame_cancelled(b, fk)) c = 0;  // slots_cancel: no byte of that utterance
     if (c < 0 || c > WIRE_CHUNK_MAX) throw Error(PTTS_ERR_STATE, "fetch_wire: corrupt chunk size");
     if (c && out) memcpy(out + b * row_stride, blk + wire_head_bytes() + ((size_t)b * nfr_ + f) * WIRE_CHUNK_MAX, c);
     n_bytes[b] = c;
@@ -3246,8 +3259,39 @@ void Engine::slot_close(int slot) {
   mark_admission();
   PTTS_HIP(hipStreamSynchronize(stream_));
   drained_[slot] = 1;
+  cancelled_[slot] = 0;
   pv_forget(slot);
   voice_release(slot, true);
+}
+
+// Stream-ordered cancel: nothing here waits for the GPU. The idle state lands on the front stream
+// behind the front parts already issued (SlotState is front-owned: no back part reads it), from a
+// pinned constant, so no staging has to come free first. The rows' frames still in flight are
+// decoded as queued (other rows' passes are untouched) and masked on the host by their call
+// index. drained_ stays 0: a queued back pass may still write the slot's histories, so the slot's
+// next admission takes the ev_be_tail_ wait; the voice reference is kept until then as well (the
+// idle row is still stepped and reads its prefix).
+void Engine::slots_cancel(int n, const int* slots) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(n >= 0 && n <= max_slots_ && (n == 0 || slots != nullptr), "number of slots out of range");
+  std::vector<char> seen(max_slots_, 0);
+  for (int i = 0; i < n; ++i) {
+    PTTS_REQUIRE(slots[i] >= 0 && slots[i] < max_slots_, "slot out of range");
+    PTTS_REQUIRE(!seen[slots[i]], "slot cancelled twice in one call");
+    seen[slots[i]] = 1;
+  }
+  PTTS_HIP(hipSetDevice(dev_));
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i];
+    if (drained_[slot] || cancelled_[slot]) continue;  // idle, finished or never admitted: nothing to stop
+    PTTS_HIP(hipMemcpyAsync(st_ + slot, h_idle_, sizeof(SlotState), hipMemcpyHostToDevice, stream_));
+    // admitted inside a multi-frame pass and not started yet: it never starts
+    act_slots_.erase(std::remove(act_slots_.begin(), act_slots_.end(), slot), act_slots_.end());
+    cancelled_[slot] = 1;
+    slot_lsd_[slot] = 0;  // lsd_run_for: the row counts no more
+    if (k_ > admit_call_[slot]) cancel_wins_.push_back({slot, admit_call_[slot], k_});
+    pv_forget(slot);
+  }
 }
 
 void Engine::voice_release(int slot, bool drained) {

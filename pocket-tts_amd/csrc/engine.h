@@ -88,6 +88,10 @@ class Engine {
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
+  // Stop the utterances of n distinct slots without draining the pipeline (ptts_slots_cancel;
+  // DESIGN.md section 18): stream-ordered like slots_open, no host wait. Frames of the cancelled
+  // utterances still in flight are masked in the fetch path.
+  void slots_cancel(int n, const int* slots);
   void set_latent(int slot, const float* lat);
   void decode_latents(int slot, const float* lat, int n, float* pcm, float* quant, float* up, float* tr);
 
@@ -340,6 +344,21 @@ class Engine {
   // per slot: the index of the first call of its current utterance (the admission's k_): a fetched
   // frame of an earlier call belongs to the slot's previous utterance and does not drain the slot
   std::vector<long long> admit_call_;
+  // slots_cancel: slots whose current utterance was cancelled (until their next admission), and
+  // the frames still to mask: calls [from, to) of `slot` belong to a cancelled utterance (from: its
+  // admission's call index, to: the cancel's). Entries leave once no fetch can reach their calls.
+  std::vector<char> cancelled_;
+  struct CancelWin {
+    int slot;
+    long long from, to;
+  };
+  std::vector<CancelWin> cancel_wins_;
+  bool frame_cancelled(int b, long long fk) const {
+    for (const CancelWin& w : cancel_wins_)
+      if (w.slot == b && fk >= w.from && fk < w.to) return true;
+    return false;
+  }
+  SlotState* h_idle_ = nullptr;  // pinned, constant: the idle state (active 0, eos_step -1) slots_cancel copies in
   int front_rows_ = 0;       // rows of the last front part (0: the call was a flush)
   bool admitted_since_call_ = false;  // an admission since the last step / flush call
   // x_ / h_ / lat_in_ written outside the step graphs since the last front part (refresh_xh)

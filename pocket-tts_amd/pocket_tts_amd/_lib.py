@@ -122,6 +122,7 @@ SIGNATURES = [
     ("ptts_lsd_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ptts_probe_overlap", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("ptts_slot_close", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_slots_cancel", C.c_int, [C.c_void_p, C.c_int, I32P]),
     ("ptts_step", C.c_int, [C.c_void_p, C.c_int, F32P, U8P, U8P, F32P, F32P]),
     ("ptts_step_async", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_sync", C.c_int, [C.c_void_p]),

@@ -350,6 +350,13 @@ class Engine:
     def close_slot(self, slot: int):
         check(lib().ptts_slot_close(self.handle, slot))
 
+    def cancel_slots(self, slots):
+        """Stop the utterances of these (distinct) slots without draining the pipeline
+        (ptts_slots_cancel): returns at once, the other rows keep stepping, and no later fetch
+        reports a frame of a cancelled utterance. The slots may be admitted again right away."""
+        sl = np.ascontiguousarray(np.asarray(list(slots), np.int32).reshape(-1))
+        check(lib().ptts_slots_cancel(self.handle, int(sl.size), sl.ctypes.data_as(C.POINTER(C.c_int32))))
+
     def set_latent(self, slot: int, latent: np.ndarray):
         v = np.ascontiguousarray(latent, np.float32).reshape(LDIM)
         check(lib().ptts_slot_set_latent(self.handle, slot, fptr(v)))

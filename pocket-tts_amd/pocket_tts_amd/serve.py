@@ -45,6 +45,14 @@ WAV file of that encoding (G.711: format tag 7 / 6, 8 bits, a `fact` chunk), /st
 bytes. A request that names neither field gets today's bytes by today's code path. Unknown values,
 or either field on a `--no-wire` server, get 400.
 
+Long-form requests (`long_form` in the three audio routes' bodies; `--long-form` sets the default,
+off): the text is cut as the reference's routes cut it (generate_stream_long, handlers.rs:165,260:
+pause markers and natural pauses become silence, each piece is cut into sentence chunks of at most
+50 tokens) and the chunks run as rows of the batch, at most `--segment-rows` of one request at a
+time, delivered in text order behind one Request-like RequestGroup. A
+/stream client that disconnects cancels its request: its rows stop without a drain of the engine
+(Request.cancel, Engine.cancel_slots).
+
 Per-request voices (pocket-tts-cli/src/voice.rs:67-222): the `voice` field is first a registered
 name; else base64 WAV audio, as a `data:audio/...;base64,` URL or as raw base64 (voice.rs:172-189:
 longer than 100 characters, base64 alphabet only); else the request is refused (400). The clip is
@@ -82,7 +90,8 @@ import numpy as np
 from ._lib import FRAME, SAMPLE_RATE, WIRE_RATES
 from .audio import ENCODINGS, pcm_i16_le_bytes, wav_bytes, wire_bytes  # noqa: F401 (re-exported wire formats)
 from .engine import GenerationParams, Voice
-from .text import estimate_frames_after_eos, max_gen_len, prepare_text_prompt
+from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
+                   silence_samples)
 
 VERSION = "0.1.0"
 
@@ -222,37 +231,8 @@ class _Call:
         self.done.set()
 
 
-@dataclass
-class Request:
-    ids: np.ndarray
-    voice: Voice | None
-    params: GenerationParams
-    clip: VoiceClip | None = None  # voice still to be cloned (resolved by the scheduler thread at admission)
-    out: FrameChannel = field(default_factory=FrameChannel)  # np.ndarray frames, then None
-    slot: int = -1
-    frames: int = 0
-    waker: Callable[[], None] | None = None  # set by an async consumer (HTTP /stream)
-    times: dict = field(default_factory=dict)  # submit / admit / first / last (time.time())
-    # first-frame preview: 1 = the preview was delivered as frame 0 and the regular frame 0 is still
-    # to come (it is dropped), 2 = that frame came
-    preview: int = 0
-    start_step: int = 0  # the scheduler's step that starts the row (trace)
-
-    # (sample_rate, encoding name) of a request with a wire format: its items are bytes the engine
-    # converted (Engine.fetch_wire), not float32 frames; None: today's float32 frames
-    wire: tuple[int, str] | None = None
-
-    def __post_init__(self):
-        rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
-        if rate or enc:
-            self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
-
-    def put(self, item):
-        """Driver side: hand over a frame (np.ndarray), the end marker (None) or an error."""
-        self.out.put(item)
-        w = self.waker
-        if w is not None:
-            w()
+class _Consumer:
+    """The consumer side of a Request or a RequestGroup: items from `out` until the end marker."""
 
     def stream(self, timeout: float | None = None) -> Iterator[np.ndarray]:
         """Frames [1920] float32 as they are produced; raises the driver's error if any."""
@@ -295,6 +275,128 @@ class Request:
         """A wire request's whole output: its chunks joined, untouched."""
         return b"".join(self.stream(timeout))
 
+    def cancel(self):
+        """Stop the request (its client went away): the scheduler thread drops what of it still
+        waits, stops its rows at its next pass without draining the engine (Engine.cancel_slots)
+        and ends the stream. Callable from any thread; a finished request is left alone."""
+        s = self.sched
+        if s is not None:
+            s._cancel(self)
+
+
+@dataclass
+class Request(_Consumer):
+    ids: np.ndarray
+    voice: Voice | None
+    params: GenerationParams
+    clip: VoiceClip | None = None  # voice still to be cloned (resolved by the scheduler thread at admission)
+    out: FrameChannel = field(default_factory=FrameChannel)  # np.ndarray frames, then None
+    slot: int = -1
+    frames: int = 0
+    waker: Callable[[], None] | None = None  # set by an async consumer (HTTP /stream)
+    times: dict = field(default_factory=dict)  # submit / admit / first / last (time.time())
+    # first-frame preview: 1 = the preview was delivered as frame 0 and the regular frame 0 is still
+    # to come (it is dropped), 2 = that frame came
+    preview: int = 0
+    start_step: int = 0  # the scheduler's step that starts the row (trace)
+
+    # (sample_rate, encoding name) of a request with a wire format: its items are bytes the engine
+    # converted (Engine.fetch_wire), not float32 frames; None: today's float32 frames
+    wire: tuple[int, str] | None = None
+    sched: object = None   # the scheduler that holds the request (cancel())
+    group: object = None   # the RequestGroup this request is a text segment of
+    ended: bool = False    # the end marker was put
+
+    def __post_init__(self):
+        rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
+        if rate or enc:
+            self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
+
+    def put(self, item):
+        """Driver side: hand over a frame (np.ndarray), the end marker (None) or an error."""
+        if item is None:
+            self.ended = True
+        g = self.group
+        if g is not None:  # a segment of a long-form request: its group puts the items in text order
+            g.deliver(self, item)
+            return
+        self.out.put(item)
+        w = self.waker
+        if w is not None:
+            w()
+
+    def _end(self):
+        if not self.ended:
+            self.put(None)
+
+
+class RequestGroup(_Consumer):
+    """A long-form request: the ordered segments of one text, pauses
+    (ready-made silence items) and text segments (Requests the scheduler runs as rows like any
+    other), behind the consumer surface of one Request. A segment's items are held back until every
+    earlier segment and pause has been handed over; at most `rows` text segments are waiting or
+    active at once, the next one joining the tail of the scheduler's queue when one finishes.
+    deliver() runs on the scheduler thread only."""
+
+    def __init__(self, sched, items, rows: int, wire):
+        self.sched, self.items, self.rows, self.wire = sched, items, max(1, int(rows)), wire
+        self.out = FrameChannel()
+        self.waker: Callable[[], None] | None = None
+        self.times: dict = {"submit": time.time()}
+        self.segments = [it for it in items if isinstance(it, Request)]
+        self.pending: deque[Request] = deque(self.segments)  # not yet handed to the scheduler
+        self.buf = {id(r): [] for r in self.segments}
+        self.head = 0
+        self.frames = 0
+        self.ended = False
+        for r in self.segments:
+            r.group = self
+
+    def _emit(self, item):
+        if item is not None and "first" not in self.times:
+            self.times["first"] = time.time()
+        self.out.put(item)
+        w = self.waker
+        if w is not None:
+            w()
+
+    def _end(self):
+        """The end marker, once; nothing of the group is handed over after it."""
+        if not self.ended:
+            self.ended = True
+            self.pending.clear()
+            self.times["last"] = time.time()
+            self._emit(None)
+
+    def _pump(self):
+        while not self.ended and self.head < len(self.items):
+            it = self.items[self.head]
+            if isinstance(it, Request):
+                buf = self.buf[id(it)]
+                for x in buf:
+                    self.frames += 1
+                    self._emit(x)
+                buf.clear()
+                if not it.ended:
+                    return
+            else:
+                self._emit(it)
+            self.head += 1
+        self._end()
+
+    def deliver(self, seg: Request, item):
+        if self.ended:
+            return
+        if isinstance(item, BaseException):  # a segment failed: the group fails once, the rest is torn down
+            self._emit(item)
+            self._end()
+            self.sched._cancel(self)
+            return
+        if item is not None:
+            self.buf[id(seg)].append(item)
+        if self.items[self.head] is seg:
+            self._pump()
+
 
 class BatchScheduler:
     """Continuous batching over one engine's slots (one GPU).
@@ -306,7 +408,11 @@ class BatchScheduler:
     comes (the two agree within float rounding: the regular pass decodes it from the same fresh
     state), or, if the regular frame comes first, drops the preview."""
 
-    def __init__(self, engine, max_rows: int | None = None, preview_rows: int = 8, voice_cache: int = 64):
+    def __init__(self, engine, max_rows: int | None = None, preview_rows: int = 8, voice_cache: int = 64,
+                 segment_rows: int = 4):
+        """segment_rows: how many text segments of one long-form request (submit_group) may be
+        waiting or active at once (a policy knob: more rows finish a long text sooner and leave
+        fewer to other requests)."""
         self.engine = engine
         self.voices = VoiceCache(voice_cache)  # per-request clones of this engine
         self.calls: deque[_Call] = deque()     # engine work handed to the scheduler thread (call())
@@ -318,8 +424,17 @@ class BatchScheduler:
         self.previews = 0  # first frames delivered from a preview
         self.poll_s = 50e-6
         self.shallow = getattr(engine, "pipeline", False) and hasattr(engine, "front_done")
+        self.segment_rows = max(1, min(int(segment_rows), self.max_rows))
         self.waiting: deque[Request] = deque()
         self.active: dict[int, Request] = {}
+        self.cancels: deque = deque()  # requests / groups to stop at the next pass (cancel())
+        # calls by which a fetched frame trails the step that computed it
+        self.lag = int(bool(getattr(engine, "pipeline", False)))  # (an engine without frame_lag: one call if pipelined)
+        if hasattr(engine, "frame_lag"):
+            self.lag = engine.frame_lag()[0]
+        # slots freed by a cancel on an engine without cancel_slots: the old row's frames are told
+        # from the next request's by the step that computed them (Request.start_step)
+        self.stale: set[int] = set()
         self.cv = threading.Condition()
         self.running = True
         self.steps = 0
@@ -335,12 +450,7 @@ class BatchScheduler:
     def submit(self, ids, voice: Voice | VoiceClip, params: GenerationParams) -> Request:
         """voice: a Voice of this engine, or a VoiceClip: cloned (or found in the cache) by the
         scheduler thread right before the request's admission, in the same pass."""
-        req = Request(np.asarray(ids, np.int32).reshape(-1), voice, params)
-        if isinstance(voice, VoiceClip):
-            req.voice, req.clip = None, voice
-        req.times["submit"] = time.time()
-        if voice.n_frames + req.ids.size + params.max_frames > self.engine.max_ctx:
-            raise ValueError("voice + text + max_frames exceeds the engine's max_ctx")
+        req = self._new_request(ids, voice, params)
         with self.cv:
             if not self.running:
                 raise RuntimeError("scheduler stopped")
@@ -350,9 +460,69 @@ class BatchScheduler:
             self.cv.notify()
         return req
 
+    def _new_request(self, ids, voice, params) -> Request:
+        req = Request(np.asarray(ids, np.int32).reshape(-1), voice, params, sched=self)
+        if isinstance(voice, VoiceClip):
+            req.voice, req.clip = None, voice
+        req.times["submit"] = time.time()
+        if voice.n_frames + req.ids.size + params.max_frames > self.engine.max_ctx:
+            raise ValueError("voice + text + max_frames exceeds the engine's max_ctx")
+        return req
+
+    def submit_group(self, segments, voice: Voice | VoiceClip, wire: tuple[int, str] | None = None,
+                     segment_rows: int | None = None) -> RequestGroup:
+        """A long-form request: segments in text order, ("text", ids, params) | ("pause", ms). Every
+        text segment is an utterance of its own (the max_ctx rule of submit() applies to each); a
+        pause becomes silence, in the group's wire format (`wire`: (rate, encoding)) if it has one."""
+        items = []
+        for seg in segments:
+            if seg[0] == "text":
+                items.append(self._new_request(seg[1], voice, seg[2]))
+            elif wire is not None:
+                items.append(wire_bytes(np.zeros(silence_samples(seg[1], wire[0]), np.float32), wire[1]))
+            else:
+                items.append(np.zeros(silence_samples(seg[1], SAMPLE_RATE), np.float32))
+        rows = self.segment_rows if segment_rows is None else max(1, min(int(segment_rows), self.max_rows))
+        g = RequestGroup(self, items, rows, wire)
+        with self.cv:
+            if not self.running:
+                raise RuntimeError("scheduler stopped")
+            g._pump()  # leading pauses (and a text of pauses only) need no row
+            for _ in range(min(g.rows, len(g.pending))):
+                self.waiting.append(g.pending.popleft())
+            if self.on_load is not None:
+                self.on_load(len(self.active) + len(self.waiting))
+            self.cv.notify()
+        return g
+
     def load(self) -> int:
         with self.cv:
             return len(self.active) + len(self.waiting)
+
+    def _cancel(self, target):
+        with self.cv:
+            if self.running:
+                self.cancels.append(target)
+                self.cv.notify()
+
+    def _reap(self) -> list[int]:
+        """(under self.cv, ahead of _take) drop what the cancelled requests and groups still have
+        waiting, free their rows' slots (admissible in this pass) and end their streams; returns
+        the slots whose rows the engine is to stop."""
+        slots = []
+        while self.cancels:
+            t = self.cancels.popleft()
+            mine = {id(r) for r in (t.segments if isinstance(t, RequestGroup) else [t])}
+            if any(id(r) in mine for r in self.waiting):
+                self.waiting = deque(r for r in self.waiting if id(r) not in mine)
+            for slot, r in list(self.active.items()):
+                if id(r) in mine:
+                    del self.active[slot]
+                    slots.append(slot)
+            t._end()
+        if self.on_load is not None:
+            self.on_load(len(self.active) + len(self.waiting))
+        return slots
 
     def call(self, fn):
         """Run fn() on the scheduler thread between two engine calls (engine calls stay on one
@@ -477,12 +647,17 @@ class BatchScheduler:
             req.times["first"] = time.time()
             req.put(pcm)
 
-    def _deliver(self, res, rows, wire=None) -> list[int]:
+    def _deliver(self, res, rows, wire=None, fstep: int = 0) -> list[int]:
         """wire: the call's Engine.fetch_wire chunks (a call with wire rows): those rows get their
-        bytes untouched; numpy is called for rows without a format only (by their consumers)."""
+        bytes untouched; numpy is called for rows without a format only (by their consumers).
+        fstep: the step that computed the call's frame."""
         done = []
         for slot, req in list(self.active.items()):
             if slot < rows and res.valid[slot]:
+                if self.stale and slot in self.stale:
+                    if fstep < req.start_step:  # still the cancelled row's frame
+                        continue
+                    self.stale.discard(slot)
                 if req.preview == 1:  # frame 0, already delivered from the preview
                     req.preview = 2
                 else:
@@ -520,12 +695,14 @@ class BatchScheduler:
         try:
             while True:
                 with self.cv:
-                    while self.running and not self.waiting and not self.active and not issued and not self.calls:
+                    while (self.running and not self.waiting and not self.active and not issued and not self.calls
+                           and not self.cancels):
                         self.cv.wait()
                     if not self.running:
                         break
                     calls = list(self.calls)
                     self.calls.clear()
+                    stop = self._reap() if self.cancels else []
                     batch = self._take()
                     rows = max(self.active) + 1 if self.active else 0
                 # A pipelined engine lets the host run calls ahead of the GPU (the fetch below waits
@@ -535,6 +712,11 @@ class BatchScheduler:
                 # GPU still always has the next step queued)
                 if self.shallow and issued:
                     self.engine.front_done(1, wait=True)
+                if stop:  # before the admission: a freed slot may be admitted again in this pass
+                    if hasattr(self.engine, "cancel_slots"):
+                        self.engine.cancel_slots(sorted(stop))  # no drain: the other rows keep stepping
+                    else:
+                        self.stale.update(stop)  # the rows run out; their frames are discarded
                 if batch:
                     self._admit(batch)
                     rows = max(self.active) + 1 if self.active else 0  # a refused request freed its slot
@@ -568,11 +750,15 @@ class BatchScheduler:
                     if any(r.wire is not None for r in self.active.values()):
                         wire = self.engine.fetch_wire(issued[0], calls_back=cb)
                     self._deliver_previews()  # those that completed while fetch() waited: ahead of it
-                    done = self._deliver(res, issued.popleft(), wire)
+                    fstep = self.steps - len(issued) - self.lag
+                    done = self._deliver(res, issued.popleft(), wire, fstep)
                     if done:
                         with self.cv:
                             for slot in done:
-                                del self.active[slot]
+                                g = self.active.pop(slot).group
+                                # a long-form request's next segment joins the tail of the queue
+                                if g is not None and g.pending and not g.ended:
+                                    self.waiting.append(g.pending.popleft())
                             if self.on_load is not None:
                                 self.on_load(len(self.active) + len(self.waiting))
         except BaseException as e:  # deliver the failure to every waiting client
@@ -587,7 +773,10 @@ class BatchScheduler:
             with self.cv:
                 self.running = False
                 for req in list(self.active.values()) + list(self.waiting):
-                    req.put(None)
+                    if req.group is not None:
+                        req.group._end()
+                    else:
+                        req.put(None)
                 for c in list(calls) + list(self.calls):  # also those this pass took and never ran
                     if not c.done.is_set():
                         c.error = RuntimeError("scheduler stopped")
@@ -606,6 +795,10 @@ class MultiGpuScheduler:
         (each engine has its own cache)."""
         i = min(range(len(self.schedulers)), key=lambda k: self.schedulers[k].load())
         return self.schedulers[i].submit(ids, voices if isinstance(voices, VoiceClip) else voices[i], params)
+
+    def submit_group(self, segments, voices: Sequence[Voice] | VoiceClip, wire=None) -> RequestGroup:
+        i = min(range(len(self.schedulers)), key=lambda k: self.schedulers[k].load())
+        return self.schedulers[i].submit_group(segments, voices if isinstance(voices, VoiceClip) else voices[i], wire)
 
     def close(self):
         for s in self.schedulers:
@@ -764,8 +957,10 @@ class TTSService:
                  tokenizer: Callable[[str], Sequence[int]] | None = None, temp: float = 0.7,
                  eos_threshold: float = -4.0, noise_clamp: float | None = None, lsd_decode_steps: int = 1,
                  max_lsd_steps: int | None = None, max_voice_seconds: float = 30.0, voice_chunk_frames: int = 0,
-                 voice_resampler: str = "poly", max_ctx: int | None = None):
-        """lsd_decode_steps: the Euler step count of a request that names none (the engine's own
+                 voice_resampler: str = "poly", max_ctx: int | None = None, long_form: bool = False):
+        """long_form: whether a text request that does not say is split into segments on parallel
+        rows (request(long_form=...)).
+        lsd_decode_steps: the Euler step count of a request that names none (the engine's own
         default). max_lsd_steps: the largest `lsd_steps` a request may ask for, the engine's cap
         (None: lsd_decode_steps, so any other value is refused). max_voice_seconds: longest clip a
         request (or POST /voices) may bring. voice_chunk_frames / voice_resampler: the clone
@@ -783,14 +978,26 @@ class TTSService:
         self.temp, self.eos_threshold, self.noise_clamp = temp, eos_threshold, noise_clamp
         self.lsd_decode_steps = lsd_decode_steps
         self.max_lsd_steps = lsd_decode_steps if max_lsd_steps is None else max_lsd_steps
+        self.long_form = bool(long_form)
         self._seed = 0
         self._lock = threading.Lock()
+
+    def _count_tokens(self, text: str) -> int:
+        tok = self.tokenizer
+        return tok.count_tokens(text) if hasattr(tok, "count_tokens") else len(tok(text))
 
     def request(self, text: str | None = None, token_ids=None, voice: str | None = None,
                 temperature: float | None = None, eos_threshold: float | None = None,
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None, sample_rate: int | None = None,
-                encoding: str | None = None) -> Request:
+                encoding: str | None = None, long_form: bool | None = None) -> Request:
+        """long_form (None: the server's default, --long-form): the text is split as the reference's
+        routes split it (generate_stream_long: pause markers and natural pauses become silence,
+        each text piece is cut into sentence chunks of at most 50 tokens) and the chunks run as
+        rows of the batch, delivered in text order behind one Request-like object (RequestGroup).
+        token_ids are never split."""
+        if long_form and token_ids is not None:
+            raise ValueError("long_form needs `text`: token_ids are never split")
         if sample_rate is not None or encoding is not None:
             if sample_rate is not None and sample_rate not in WIRE_RATES:
                 raise ValueError(f"sample_rate must be one of {list(WIRE_RATES)}")
@@ -802,6 +1009,7 @@ class TTSService:
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
+        segments = None
         if token_ids is not None:  # extension: ids carry no word count, the client states it
             ids = np.asarray(token_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
@@ -811,9 +1019,18 @@ class TTSService:
         elif text is not None:
             if self.tokenizer is None:
                 raise ValueError("no tokenizer configured: send token_ids")
-            prepared = prepare_text_prompt(text)
-            ids = np.asarray(self.tokenizer(prepared), np.int32)
-            mgl, fae = max_frames or max_gen_len(prepared), estimate_frames_after_eos(text)
+            if self.long_form if long_form is None else long_form:
+                segments = []  # ("text", ids, max_frames, frames_after_eos) | ("pause", ms), in text order
+                for kind, val in long_form_segments(text, self._count_tokens, pauses=True):
+                    if kind == "text":
+                        sid, mgl, fae = segment_request(val, self.tokenizer)
+                        segments.append(("text", np.asarray(sid, np.int32), max_frames or mgl, fae))
+                    else:
+                        segments.append((kind, val))
+            else:
+                prepared = prepare_text_prompt(text)
+                ids = np.asarray(self.tokenizer(prepared), np.int32)
+                mgl, fae = max_frames or max_gen_len(prepared), estimate_frames_after_eos(text)
         else:
             raise ValueError("text or token_ids required")
         name = voice or self.default_voice
@@ -823,11 +1040,25 @@ class TTSService:
         # under: a replaced voice is retired only after every request that got it is queued, and
         # the scheduler closes it only once none of them is still waiting (BatchScheduler.retire)
         with self._lock:
-            return self._submit_locked(ids, clip if clip is not None else self.voices[name], temperature,
-                                       eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding)
+            target = clip if clip is not None else self.voices[name]
+            if segments is not None:  # one seed per text segment, in text order
+                segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
+                                                            lsd_steps, sample_rate, encoding))
+                        if sg[0] == "text" else sg for sg in segments]
+                wire = None
+                if sample_rate is not None or encoding is not None:
+                    wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
+                return self.scheduler.submit_group(segs, target, wire)
+            return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
+                                       sample_rate, encoding)
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
                        sample_rate=None, encoding=None) -> Request:
+        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding)
+        return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
+
+    def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
+                       encoding=None) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -837,7 +1068,7 @@ class TTSService:
                              lsd_steps=None if lsd_steps is None else int(lsd_steps))
         if sample_rate is not None or encoding is not None:  # a request that names neither: as before
             p.sample_rate, p.encoding = sample_rate, encoding
-        return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
+        return p
 
     # -- per-request and run-time voices
     def voice_clip(self, spec: str) -> VoiceClip:
@@ -925,6 +1156,8 @@ class GenerateRequest(BaseModel):
     # alaw; one of them alone defaults the other to 24000 / pcm_s16le; neither: today's output
     sample_rate: int | None = None
     encoding: str | None = None
+    # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
+    long_form: bool | None = None
 
 
 class OpenAIRequest(BaseModel):
@@ -938,6 +1171,7 @@ class OpenAIRequest(BaseModel):
     words: int | None = None
     sample_rate: int | None = None
     encoding: str | None = None
+    long_form: bool | None = None
 
 
 # /stream: at most one chunk per stream per 20 ms after the first (32 streams x 50 wakes/s keep the
@@ -965,36 +1199,44 @@ async def pcm_chunks(r: Request):
             loop.call_soon_threadsafe(ev.set)
 
     r.waker = wake
-    while True:
-        items = []
+    done = False
+    try:
         while True:
-            try:
-                items.append(r.out.get_nowait())
-            except queue.Empty:
-                break
-        batch, done = [], False
-        for item in items:
-            if item is None:
-                done = True
-                break
-            if isinstance(item, BaseException):
-                raise item
-            batch.append(item)
-        if batch:
-            if "chunk0" not in r.times:
-                r.times["chunk0"] = time.time()
-            if isinstance(batch[0], bytes):  # a wire request: the engine's bytes, untouched
-                yield batch[0] if len(batch) == 1 else b"".join(batch)
-            else:
-                yield pcm_i16_le_bytes(batch[0] if len(batch) == 1 else np.concatenate(batch))
-        if done:
-            return
-        if batch:
-            await asyncio.sleep(CHUNK_INTERVAL_S)
-        ev.clear()
-        armed[0] = True
-        if r.out.empty():
-            await ev.wait()
+            items = []
+            while True:
+                try:
+                    items.append(r.out.get_nowait())
+                except queue.Empty:
+                    break
+            batch = []
+            for item in items:
+                if item is None:
+                    done = True
+                    break
+                if isinstance(item, BaseException):
+                    done = True  # the request has ended on the scheduler's side
+                    raise item
+                batch.append(item)
+            if batch:
+                if "chunk0" not in r.times:
+                    r.times["chunk0"] = time.time()
+                if isinstance(batch[0], bytes):  # a wire request: the engine's bytes, untouched
+                    yield batch[0] if len(batch) == 1 else b"".join(batch)
+                else:
+                    yield pcm_i16_le_bytes(batch[0] if len(batch) == 1 else np.concatenate(batch))
+            if done:
+                return
+            if batch:
+                await asyncio.sleep(CHUNK_INTERVAL_S)
+            ev.clear()
+            armed[0] = True
+            if r.out.empty():
+                await ev.wait()
+    finally:
+        # closed before the end marker (GeneratorExit / CancelledError): the client went away, so
+        # its rows stop now instead of running to EOS or max_frames
+        if not done and hasattr(r, "cancel"):
+            r.cancel()
 
 
 def create_app(service: TTSService):
@@ -1083,7 +1325,7 @@ def create_app(service: TTSService):
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
-                   encoding=enc)
+                   encoding=enc, long_form=req.long_form)
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
@@ -1160,6 +1402,15 @@ class StandInEngine:
             self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames]
             if self.pending is not None and s < self.pending[1].size:  # drop the slot's undrained frame
                 self.pending[1][s] = False
+
+    def cancel_slots(self, slots):
+        """Engine.cancel_slots: the rows stop and no frame of theirs is reported any more."""
+        self.cancelled = getattr(self, "cancelled", []) + [sorted(int(s) for s in slots)]
+        for s in slots:
+            self.rows.pop(s, None)
+            for held in (self.pending, getattr(self, "out", None), getattr(self, "prev_out", None)):
+                if held is not None and s < held[1].size:
+                    held[1][s] = False
 
     def step_async(self, n):
         if self.step_s:
@@ -1286,6 +1537,12 @@ def main(argv=None):
     ap.add_argument("--wire", action=argparse.BooleanOptionalAction, default=True,
                     help="wire formats converted on the GPU (requests' sample_rate / encoding); --no-wire: the "
                          "engine as before, such requests get 400")
+    ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
+                    help="default of requests that do not say `long_form`: split the text into pause and sentence "
+                         "segments (the reference's generate_stream_long) and run them on parallel rows")
+    ap.add_argument("--segment-rows", type=int, default=4,
+                    help="text segments of one long-form request that may be waiting or active at once "
+                         "(clamped to --slots)")
     ap.add_argument("--preview-rows", type=int, default=8,
                     help="first-frame previews: rows per call whose first frame is decoded at once (0: off)")
     ap.add_argument("--voice-cache", type=int, default=64,
@@ -1339,11 +1596,12 @@ def main(argv=None):
         raise SystemExit("at least one --voice NAME=path is required")
     # the clone workspace of per-request voices, sized once for the longest clip accepted
     engine.reserve_voice_jobs(max(1, min(args.max_ctx - 1, math.ceil(args.max_voice_seconds * SAMPLE_RATE / FRAME) + 1)))
-    scheduler = BatchScheduler(engine, preview_rows=args.preview_rows, voice_cache=args.voice_cache)
+    scheduler = BatchScheduler(engine, preview_rows=args.preview_rows, voice_cache=args.voice_cache,
+                               segment_rows=args.segment_rows)
     service = TTSService(scheduler, voices, default_voice=next(iter(voices)),
                          tokenizer=load_tokenizer(args.tokenizer) if args.tokenizer else None,
                          lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
-                         max_voice_seconds=args.max_voice_seconds)
+                         max_voice_seconds=args.max_voice_seconds, long_form=args.long_form)
     service.worker = {"rank": rank, "world": world, "pid": os.getpid(), "weights_checksum": checksum}
     socks = [_listen_socket(args.host, args.port)]
     board = None

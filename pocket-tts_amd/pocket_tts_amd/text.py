@@ -505,3 +505,26 @@ def split_into_best_sentences(text: str, count_tokens) -> list[str]:
     if cur:
         chunks.append(cur)
     return chunks
+
+
+def long_form_segments(text: str, count_tokens, pauses: bool = True) -> list[tuple[str, object]]:
+    """The ordered segment list of one long-form text, [("text", chunk) | ("pause", ms)]: what
+    generate_stream_long walks (pauses=True: long_text_segments, tts_model.rs:1080-1108, then
+    split_into_best_sentences on each text piece, :601-684) or what generate_stream walks
+    (pauses=False: the sentence chunks alone). Every ("text", chunk) is one utterance
+    (generate_stream_segment, :935-1004)."""
+    pieces = long_text_segments(text) if pauses else [("text", text)]
+    out: list[tuple[str, object]] = []
+    for kind, val in pieces:
+        if kind == "text":
+            out.extend(("text", c) for c in split_into_best_sentences(val, count_tokens))
+        else:
+            out.append((kind, val))
+    return out
+
+
+def segment_request(chunk: str, tokenize) -> tuple[list[int], int, int]:
+    """(ids, max_gen_len, frames_after_eos) of one sentence chunk, as generate_stream derives them
+    (tts_model.rs:947-969)."""
+    prepared = prepare_text_prompt(chunk)
+    return list(tokenize(prepared)), max_gen_len(prepared), estimate_frames_after_eos(chunk)

@@ -14,7 +14,9 @@ Reference surface kept:
     50 tokens, one segment each from a fresh copy of the voice state), `generate_stream_long`
     and `generate_with_pauses` (:856-883, 1074-1131: pause markers become silence), one
     [1, 1, 1920] frame per item; `split_into_best_sentences` (:601-684),
-    `estimate_generation_steps` (:1187-1190).
+    `estimate_generation_steps` (:1187-1190);
+  * `generate_parallel` / `generate_stream_parallel` (:705-854, commented out in the reference):
+    the same segments as rows of one batch, on an engine loaded with `max_slots` > 1.
 Text goes through the text front end (text.py: tokenizer, prompt preparation); token-id input
 is accepted too (one segment, no splitting).
 """
@@ -26,10 +28,10 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
-from .audio import read_wav, read_wav_from_bytes
+from .audio import read_wav, read_wav_from_bytes, wire_bytes
 from .engine import Engine, GenerationParams, Voice
-from .text import (estimate_frames_after_eos, load_tokenizer, long_text_segments, max_gen_len,
-                   prepare_text_prompt, silence_samples, split_into_best_sentences)
+from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
+                   prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
 
 DEFAULT_VARIANT = "b6369a24"
 
@@ -71,8 +73,11 @@ class TTSModel:
                          weights_path: str | None = None, tokenizer_path: str | None = None, seed: int = 0x5EED,
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
-                         wire: bool = False) -> "TTSModel":
-        """max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
+                         wire: bool = False, max_slots: int = 1, pipeline: bool = False,
+                         back_frames: int = 1) -> "TTSModel":
+        """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
+        other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
+        max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
         (the engine's cap; None: lsd_decode_steps itself, the field can then only be lowered).
         weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
         from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json.
@@ -81,7 +86,8 @@ class TTSModel:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
             tokenizer = load_tokenizer(tokenizer_path)
-        eng = Engine(device=device, max_slots=1, max_ctx=max_ctx, lsd_decode_steps=lsd_decode_steps, seed=seed,
+        eng = Engine(device=device, max_slots=int(max_slots), max_ctx=max_ctx, pipeline=pipeline,
+                     back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
                      wire=wire)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
@@ -167,15 +173,18 @@ class TTSModel:
         return GenerationParams(temp=self.temp, eos_threshold=self.eos_threshold, noise_clamp=self.noise_clamp,
                                 frames_after_eos=frames_after_eos, max_frames=max_frames, seed=self._seed)
 
+    def _check_lsd(self):
+        cap = self.engine.max_lsd_steps
+        if not 1 <= int(self.lsd_decode_steps) <= cap:
+            raise ValueError(f"lsd_decode_steps {self.lsd_decode_steps} outside [1, {cap}], the engine's cap "
+                             "(max_lsd_decode_steps at load)")
+
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
                  sample_rate: int | None = None, encoding=None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
         (sample_rate / encoding; a wire-enabled engine) the items are the row's wire chunks, bytes
         converted on the GPU (Engine.fetch_wire), instead of f32 frames."""
-        cap = self.engine.max_lsd_steps
-        if not 1 <= int(self.lsd_decode_steps) <= cap:
-            raise ValueError(f"lsd_decode_steps {self.lsd_decode_steps} outside [1, {cap}], the engine's cap "
-                             "(max_lsd_decode_steps at load)")
+        self._check_lsd()
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
         params.sample_rate, params.encoding = sample_rate, encoding
@@ -244,4 +253,101 @@ class TTSModel:
         chunks = list(self.generate_stream_long(text, voice_state))
         if not chunks:
             raise RuntimeError("No audio generated")
+        return np.concatenate(chunks, axis=2)[0]
+
+    # ---- the same segments on parallel rows
+    def generate_stream_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
+                                 sample_rate: int | None = None, encoding=None) -> Iterator:
+        """The items of generate_stream (pauses=False) or generate_stream_long (pauses=True), in text
+        order, with the text segments generated as rows of one batch: up to `rows` (default: the
+        engine's max_slots) are admitted at once (Engine.open_many: one shared text prefill, the
+        voice prefix shared) and rows are refilled as segments end. The segments are independent
+        utterances (each starts from the voice prefix with a fresh Mimi state, tts_model.rs:935-1004)
+        and the noise of an utterance depends on its seed alone, not on its row, so segment i is the
+        segment the sequential methods produce: it gets their seed (`_seed` advanced once per text
+        segment, in text order) and the field values read when this call starts.
+        sample_rate / encoding: wire bytes as generate_stream yields them, and each pause as the
+        encoded silence of silence_samples(ms, sample_rate) samples. Closing the generator early
+        cancels the rows it still holds (Engine.cancel_slots)."""
+        self._check_lsd()
+        tok = self._tok()
+        eng = self.engine
+        wire = sample_rate is not None or encoding is not None
+        n_rows = max(1, min(int(rows or eng.max_slots), eng.max_slots))
+        items = []  # per segment: ("pause", item) | ["text", ids, params, frames, done]
+        for kind, val in long_form_segments(text, self.count_tokens, pauses):
+            if kind == "text":
+                ids, mgl, fae = segment_request(val, tok)
+                params = self._params(mgl, fae)
+                params.lsd_steps = int(self.lsd_decode_steps)
+                params.sample_rate, params.encoding = sample_rate, encoding
+                items.append(["text", np.asarray(ids, np.int32), params, [], False])
+            elif wire:
+                n = silence_samples(val, int(sample_rate or SAMPLE_RATE))
+                items.append(("pause", wire_bytes(np.zeros(n, np.float32), encoding or "pcm_s16le")))
+            else:
+                items.append(("pause", np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)))
+        return self._run_parallel(items, voice_state, n_rows, wire)
+
+    def _run_parallel(self, items, voice_state: Voice, n_rows: int, wire: bool) -> Iterator:
+        eng = self.engine
+        todo = [it for it in items if it[0] == "text"]  # not yet admitted, text order
+        active: dict[int, list] = {}  # slot -> its segment
+        lead: dict[int, int] = {}     # slot -> calls its first frame may still be late (frame_lag)
+        head = 0
+        try:
+            while True:
+                while head < len(items):  # deliver, strictly in text order
+                    it = items[head]
+                    if it[0] == "pause":
+                        yield it[1]
+                    else:
+                        while it[3]:
+                            yield it[3].pop(0)
+                        if not it[4]:
+                            break
+                    head += 1
+                if head == len(items):
+                    return
+                free = [s for s in range(n_rows) if s not in active]
+                batch = [(s, todo.pop(0)) for s in free[:len(todo)]]
+                if batch:
+                    eng.open_many([s for s, _ in batch], [voice_state] * len(batch), [it[1] for _, it in batch],
+                                  [it[2] for _, it in batch])
+                    lag, delay = eng.frame_lag()
+                    for s, it in batch:
+                        active[s] = it
+                        lead[s] = lag + delay
+                B = max(active) + 1
+                r = eng.step(B)
+                chunks = eng.fetch_wire(B) if wire else None
+                for s in sorted(active):
+                    it = active[s]
+                    if not r.valid[s]:
+                        if lead[s] > 0:
+                            lead[s] -= 1
+                            continue
+                        it[4] = True
+                        del active[s]
+                        continue
+                    lead[s] = 0
+                    it[3].append(chunks[s] if wire else r.pcm[s].reshape(1, 1, FRAME).copy())
+                    if r.last[s]:
+                        it[4] = True
+                        del active[s]
+        finally:
+            if active:  # closed early (or failed): the rows still held stop now, without a drain
+                eng.cancel_slots(sorted(active))
+
+    def generate_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
+                          sample_rate: int | None = None, encoding=None):
+        """generate (pauses=False) or generate_with_pauses (pauses=True) with the text's segments on
+        parallel rows: the concatenation of generate_stream_parallel's items. The name is the
+        reference's own: its generate_parallel (tts_model.rs:705-854) is commented out there, "for
+        future exploration with GPU acceleration"."""
+        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding))
+        if not chunks:
+            raise RuntimeError("No audio generated")
+        if sample_rate is not None or encoding is not None:
+            return b"".join(chunks)
         return np.concatenate(chunks, axis=2)[0]
