@@ -295,12 +295,14 @@ int ptts_wire_enable(ptts_engine* e, int on);
 /* Per-row admission options. size = sizeof(ptts_slot_opts) of the caller's header (0 is read as
  * that of this one): the stride of the array, and fields past it read as 0, so the struct can grow
  * without an ABI bump. Zero fields are the defaults: lsd_steps as in ptts_slots_open_ex; wire_rate
- * 0 and wire_encoding 0: no wire format; one of them 0: 24000 / PTTS_WIRE_S16. */
+ * 0 and wire_encoding 0: no wire format; one of them 0: 24000 / PTTS_WIRE_S16; speed_permille 0:
+ * no speed (the field lies in what was the struct's tail padding: zero the struct before filling it). */
 typedef struct ptts_slot_opts {
   size_t size;
   int lsd_steps;
   int wire_rate;     /* 8000, 16000, 24000, 44100 or 48000 */
   int wire_encoding; /* PTTS_WIRE_* */
+  int speed_permille; /* speech speed, 500 .. 2000 (ptts_tempo_enable); 0 or 1000: none */
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
@@ -312,6 +314,25 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
  * ptts_resample runs, then the encoder of the streaming stage); out receives ptts_wire_len bytes. */
 long ptts_wire_len(long n_samples, int sample_rate, int encoding);
 int ptts_wire_encode(ptts_engine* e, const float* pcm, int n_samples, int sample_rate, int encoding, uint8_t* out);
+/* Speech speed (no reference counterpart; the model has no duration control). A row admitted with
+ * ptts_slot_opts.speed_permille = sp has its f32 PCM time-scaled at 24 kHz ahead of the wire
+ * conversion, by a streaming WSOLA whose rule DESIGN.md section 19 states: pitch is kept, an
+ * utterance of N samples becomes ceil(N * 1000 / sp), and the chunks of a row concatenate to the
+ * whole-signal rule (ptts_tempo) over its PCM, bit for bit. Only the wire bytes change: the PCM of
+ * ptts_fetch, the latents, the EOS logits and the stop frames do not depend on speed. A speed with
+ * no wire format implies 24000 / PTTS_WIRE_S16. A speed outside [500, 2000], or one asked of an
+ * engine without ptts_tempo_enable, is PTTS_ERR_INVALID and admits nothing.
+ * ptts_tempo_enable: valid on a wire-enabled idle engine before its first step (PTTS_ERR_INVALID
+ * otherwise); on = 0, or never called: the passes, graphs and copies of a wire-enabled engine. On a
+ * tempo-enabled engine chunks can be longer (a last frame at speed 500 and 48 kHz holds 11,058
+ * 16-bit samples at most), and ptts_fetch_wire requires row_stride >= PTTS_WIRE_CHUNK_MAX_TEMPO. */
+#define PTTS_WIRE_CHUNK_MAX_TEMPO 22528
+int ptts_tempo_enable(ptts_engine* e, int on);
+/* The tempo seam alone: samples of n at speed sp (0 if the arguments are invalid; host only), and
+ * the whole-signal rule on the GPU (the hop functions of the streaming stage); out receives
+ * ptts_tempo_len samples. */
+long ptts_tempo_len(long n, int speed_permille);
+int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, float* out);
 
 /* *cap: cfg.lsd_decode_steps. *last_run: the Euler steps the most recent step call ran (0 before
  * the first): the largest count among that call's rows still open (admitted, not closed, last
@@ -365,7 +386,8 @@ int ptts_fetch_prev(ptts_engine* e, int calls_back, int n_rows, float* pcm, uint
                     float* eos_logits, float* latents);
 /* The wire chunks of the same call's frame (the companion of ptts_fetch / ptts_fetch_prev: the same
  * event, no bookkeeping of its own, so call it beside them in either order): row b's n_bytes[b]
- * bytes at out + b * row_stride (row_stride >= PTTS_WIRE_CHUNK_MAX); n_bytes[b] = 0 for a row with no
+ * bytes at out + b * row_stride (row_stride >= PTTS_WIRE_CHUNK_MAX, or PTTS_WIRE_CHUNK_MAX_TEMPO on a
+ * tempo-enabled engine); n_bytes[b] = 0 for a row with no
  * wire format or no frame. out may be NULL (sizes only). Wire-enabled engines only. */
 int ptts_fetch_wire(ptts_engine* e, int calls_back, int n_rows, uint8_t* out, size_t row_stride, int* n_bytes);
 /* *ready = 1 if ptts_fetch_prev(e, calls_back, ..) would return without waiting (the call's frame

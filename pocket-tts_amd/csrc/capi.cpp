@@ -304,7 +304,7 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     const size_t size = opts[0].size ? opts[0].size : sizeof(ptts_slot_opts);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n);
+    std::vector<int> lsd(n), rate(n), enc(n), speed(n);
     for (int i = 0; i < n; ++i) {
       ptts_slot_opts o{};
       std::memcpy(&o, (const char*)opts + (size_t)i * size, std::min(size, sizeof o));
@@ -312,8 +312,9 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
       lsd[i] = o.lsd_steps;
       rate[i] = o.wire_rate;
       enc[i] = o.wire_encoding;
+      speed[i] = o.speed_permille;
     }
-    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data());
+    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data());
   });
 }
 
@@ -330,6 +331,17 @@ long ptts_wire_len(long n_samples, int sample_rate, int encoding) {
 
 int ptts_wire_encode(ptts_engine* e, const float* pcm, int n_samples, int sample_rate, int encoding, uint8_t* out) {
   return guard([&] { eng(e).wire_encode_host(pcm, n_samples, sample_rate, encoding, out); });
+}
+
+int ptts_tempo_enable(ptts_engine* e, int on) { return guard([&] { eng(e).tempo_enable(on != 0); }); }
+
+long ptts_tempo_len(long n, int speed_permille) {
+  if (n < 0 || speed_permille < ptts::TEMPO_SP_MIN || speed_permille > ptts::TEMPO_SP_MAX) return 0;
+  return ptts::tempo_len(n, speed_permille);
+}
+
+int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, float* out) {
+  return guard([&] { eng(e).tempo_host(pcm, n, speed_permille, out); });
 }
 
 int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run) {

@@ -355,6 +355,7 @@ Engine::~Engine() {
   if (h_act_) (void)hipHostFree(h_act_);
   if (h_idle_) (void)hipHostFree(h_idle_);
   if (h_wire_) (void)hipHostFree(h_wire_);
+  if (h_tempo_) (void)hipHostFree(h_tempo_);
   for (unsigned char* hp : h_wireb_)
     if (hp) (void)hipHostFree(hp);
   if (h_err_) (void)hipHostFree(h_err_);
@@ -1589,6 +1590,23 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   // ---- wire stage (wire-enabled engines): after the commit, which still adds the fused final
   // conv's tile-boundary shares into the PCM
   if (wire_ && !wire_skip_) {
+    if (tempo_) {  // the speed rows' chunks first: the wire stage reads them in place of the PCM
+      TempoArgs ta{};
+      ta.B = B;
+      ta.nfr = nfr;
+      ta.pcm_frames = pcm_frames;
+      ta.out_frames = nfr_;
+      ta.pcm = pcm_out;
+      for (int f = 0; f < NFR_MAX; ++f) ta.flags[f] = flags_[hbs[f]];
+      ta.sp = tempo_sp_;
+      ta.state = tempo_state_;
+      ta.hist = tempo_hist_;
+      ta.win = tempo_win_;
+      ta.out = tempo_out_;
+      ta.counts = tempo_cnt_;
+      ops.push_back({"tempo", [ta](hipStream_t s) { tempo_stage(ta, s); }, 0.0,
+                     (double)B * nfr * 4.0 * (FRAME + TEMPO_OUT_MAX)});
+    }
     WireArgs w{};
     w.B = B;
     w.nfr = nfr;
@@ -1604,8 +1622,14 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     unsigned char* blk = wireb_[nfr_ > 1 ? hb / nfr_ : hb];
     w.counts = (int*)blk;
     w.out = blk + wire_head_bytes();
+    w.chunk = wire_chunk_max();
+    if (tempo_) {
+      w.tempo_sp = tempo_sp_;
+      w.tin = tempo_out_;
+      w.tcnt = tempo_cnt_;
+    }
     ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
-                   (double)B * nfr * (4.0 * FRAME + WIRE_CHUNK_MAX)});
+                   (double)B * nfr * (4.0 * FRAME + wire_chunk_max())});
   }
 }
 
@@ -2800,16 +2824,23 @@ int Engine::lsd_run_for(int B) const {
 // through a row table.
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                         const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
-                        const int* wire_enc) {
+                        const int* wire_enc, const int* speed) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
   std::vector<char> seen(max_slots_, 0);
   std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
+  std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
   long total_ids = 0;
   for (int i = 0; i < n; ++i) {
     const int wr = wire_rate ? wire_rate[i] : 0, we = wire_enc ? wire_enc[i] : 0;
-    if (wr || we) {
+    const int sp = speed ? speed[i] : 0;
+    if (sp != 0 && sp != 1000) {  // 1000: no tempo stage for the row, like no speed at all
+      PTTS_REQUIRE(sp >= TEMPO_SP_MIN && sp <= TEMPO_SP_MAX, "speed_permille must be 0 or in [500, 2000]");
+      PTTS_REQUIRE(tempo_, "a speed needs a tempo-enabled engine (ptts_tempo_enable before the first step)");
+      wsp[i] = sp;
+    }
+    if (wr || we || wsp[i]) {  // a speed with no format: 24000 / 16 bit
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
@@ -2960,6 +2991,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
     if (wire_) slot_wire_[slots[i]] = wfmt[i];
   }
+  if (tempo_) {
+    memcpy(h_tempo_, wsp.data(), sizeof(int) * n);
+    PTTS_HIP(hipMemcpyAsync(admit_tempo_, h_tempo_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
   std::vector<int> fp(n);
@@ -3031,6 +3066,11 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       r.wire_fmt = wire_fmt_;
       r.wire_frames = wire_frames_;
     }
+    if (tempo_) {
+      r.tempo_src = admit_tempo_;
+      r.tempo_sp = tempo_sp_;
+      r.tempo_state = tempo_state_;
+    }
     slot_reset(r, stream_);
     PTTS_HIP(hipGetLastError());
   }
@@ -3087,7 +3127,9 @@ void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_st
   PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
   PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
   PTTS_REQUIRE(n_bytes != nullptr, "null argument");
-  PTTS_REQUIRE(!out || row_stride >= (size_t)WIRE_CHUNK_MAX, "row_stride must be >= PTTS_WIRE_CHUNK_MAX");
+  PTTS_REQUIRE(!out || row_stride >= (size_t)wire_chunk_max(),
+               tempo_ ? "row_stride must be >= PTTS_WIRE_CHUNK_MAX_TEMPO on a tempo-enabled engine"
+                      : "row_stride must be >= PTTS_WIRE_CHUNK_MAX");
   // the same frame, rows and event as fetch() of that call; no bookkeeping of its own
   const int q = calls_back ? prev_hb_ : out_hb_;
   const int rows = calls_back ? prev_rows_ : out_rows_;
@@ -3101,8 +3143,8 @@ void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_st
     const int f = q % nfr_;
     int c = b < n ? cnt[(size_t)b * nfr_ + f] : 0;
     if (c && !cancel_wins_.empty() && frame_cancelled(b, fk)) c = 0;  // slots_cancel: no byte of that utterance
-    if (c < 0 || c > WIRE_CHUNK_MAX) throw Error(PTTS_ERR_STATE, "fetch_wire: corrupt chunk size");
-    if (c && out) memcpy(out + b * row_stride, blk + wire_head_bytes() + ((size_t)b * nfr_ + f) * WIRE_CHUNK_MAX, c);
+    if (c < 0 || c > wire_chunk_max()) throw Error(PTTS_ERR_STATE, "fetch_wire: corrupt chunk size");
+    if (c && out) memcpy(out + b * row_stride, blk + wire_head_bytes() + ((size_t)b * nfr_ + f) * wire_chunk_max(), c);
     n_bytes[b] = c;
   }
 }
@@ -3139,6 +3181,71 @@ void Engine::wire_encode_host(const float* pcm, int n, int rate, int enc, unsign
     throw;
   }
   (void)hipFree(dx), (void)hipFree(dh), (void)hipFree(dy), (void)hipFree(dw);
+}
+
+// ------------------------------------------------------------------ tempo stage
+void Engine::tempo_enable(bool on) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the tempo stage is chosen on an idle engine before its first step");
+  PTTS_REQUIRE(!on || wire_, "the tempo stage needs a wire-enabled engine (ptts_wire_enable first)");
+  // section 19: a pending hop reads nothing older than TEMPO_HIST samples, a chunk fits its slots
+  static_assert(TEMPO_R == TEMPO_D + TEMPO_HS + TEMPO_W && 2 * TEMPO_HS == TEMPO_W, "tempo constants");
+  const int step_max = (TEMPO_HS * TEMPO_SP_MAX + 999) / 1000, step_min = TEMPO_HS * TEMPO_SP_MIN / 1000;
+  const long out_max = std::max<long>((long)(FRAME + TEMPO_R - 1) * 1000 / TEMPO_SP_MIN + 1,
+                                      (long)FRAME * 1000 / TEMPO_SP_MIN + TEMPO_HS);
+  PTTS_REQUIRE(step_min >= TEMPO_D && TEMPO_HIST >= TEMPO_R + step_max + TEMPO_D - TEMPO_HS && TEMPO_HIST <= FRAME &&
+                   out_max <= TEMPO_OUT_MAX && (2L * TEMPO_OUT_MAX + 21) * 2 <= WIRE_CHUNK_MAX_TEMPO,
+               "tempo constants violate the history or chunk bounds of DESIGN.md section 19");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !tempo_sp_) {
+    const size_t B = max_slots_;
+    tempo_sp_ = (int*)dalloc(B);
+    tempo_state_ = (int*)dalloc(B * TEMPO_STATE);
+    tempo_hist_ = dalloc(B * TEMPO_HIST);
+    tempo_out_ = dalloc(B * nfr_ * TEMPO_OUT_MAX);
+    tempo_cnt_ = (int*)dalloc(B * nfr_);
+    admit_tempo_ = (int*)dalloc(B);
+    PTTS_HIP(hipHostMalloc((void**)&h_tempo_, sizeof(int) * B, hipHostMallocDefault));
+    const std::vector<float> w = tempo_window();
+    tempo_win_ = dalloc(w.size());
+    PTTS_HIP(hipMemcpy(tempo_win_, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
+  }
+  if (on != tempo_) {  // the chunk slots change size: new pass blocks
+    tempo_ = on;
+    const size_t bytes = wire_block_bytes(max_slots_);
+    for (int p = 0; p < WIRE_BLOCKS; ++p) {
+      (void)hipHostFree(h_wireb_[p]);
+      h_wireb_[p] = nullptr;
+      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
+      PTTS_HIP(hipHostMalloc((void**)&h_wireb_[p], bytes, hipHostMallocDefault));
+      memset(h_wireb_[p], 0, wire_head_bytes());
+    }
+  }
+}
+
+void Engine::tempo_host(const float* pcm, int n, int sp, float* out) {
+  PTTS_REQUIRE(pcm && out && n >= 1, "empty input");
+  PTTS_REQUIRE(sp >= TEMPO_SP_MIN && sp <= TEMPO_SP_MAX, "speed_permille must be in [500, 2000]");
+  const long n_out = tempo_len(n, sp);
+  PTTS_REQUIRE(n_out < (1L << 30), "input too long");
+  sync();
+  void *dx = nullptr, *dw = nullptr, *dy = nullptr;
+  try {
+    const std::vector<float> w = tempo_window();
+    PTTS_HIP(hipMalloc(&dx, sizeof(float) * n));
+    PTTS_HIP(hipMalloc(&dw, sizeof(float) * w.size()));
+    PTTS_HIP(hipMalloc(&dy, sizeof(float) * n_out));
+    PTTS_HIP(hipMemcpyAsync(dx, pcm, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    PTTS_HIP(hipMemcpy(dw, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
+    ptts::tempo((const float*)dx, n, sp, (const float*)dw, (float*)dy, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(out, dy, sizeof(float) * n_out, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(dw), (void)hipFree(dy);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(dw), (void)hipFree(dy);
 }
 
 void Engine::mark_admission() {

@@ -84,7 +84,7 @@ class Engine {
   // arrays) = none, 0 in one = its default (24000 Hz, PTTS_WIRE_S16)
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
                   const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
-                  const int* wire_enc = nullptr);
+                  const int* wire_enc = nullptr, const int* speed = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -129,6 +129,13 @@ class Engine {
   // the seam alone: whole-signal f32 at 24 kHz -> wire bytes (wire_len of them)
   static long wire_len(long n_samples, int rate, int enc);  // -1: unknown rate or encoding
   void wire_encode_host(const float* pcm, int n, int rate, int enc, unsigned char* out);
+  // Tempo stage (ptts_tempo_enable): rows admitted with a speed have their PCM
+  // time-scaled (kernels.h tempo_stage) ahead of the wire stage; chunks grow to wire_chunk_max()
+  void tempo_enable(bool on);
+  bool tempo() const { return tempo_; }
+  int wire_chunk_max() const { return tempo_ ? WIRE_CHUNK_MAX_TEMPO : WIRE_CHUNK_MAX; }
+  // the seam alone: whole-signal f32 at 24 kHz -> tempo_len(n, sp) samples
+  void tempo_host(const float* pcm, int n, int sp, float* out);
 
   double time_op(int B, const std::string& name, int reps);
   // GEMM-core test hook (ptts_test_gemm): Y = X W^T on tile `layout` (host buffers)
@@ -441,13 +448,23 @@ class Engine {
   WirePlan wire_plan_[WIRE_RATES] = {};
   int* admit_wire_ = nullptr;   // staged formats of an admission (device), h_wire_ (pinned)
   int* h_wire_ = nullptr;
+  // ---- tempo stage (tempo_enable): per-row speed and state, back-owned like the wire state
+  bool tempo_ = false;
+  int* tempo_sp_ = nullptr;      // [max_slots] permille (0: none)
+  int* tempo_state_ = nullptr;   // [max_slots][TEMPO_STATE]
+  float* tempo_hist_ = nullptr;  // [max_slots][TEMPO_HIST]
+  float* tempo_win_ = nullptr;   // [TEMPO_W]
+  float* tempo_out_ = nullptr;   // [max_slots][nfr][TEMPO_OUT_MAX]: one pass's chunks (k_tempo -> k_wire)
+  int* tempo_cnt_ = nullptr;     // [max_slots][nfr]
+  int* admit_tempo_ = nullptr;   // staged speeds of an admission (device), h_tempo_ (pinned)
+  int* h_tempo_ = nullptr;
   // per pass (index: hand-off buffer / frames per pass): counts [max_slots][nfr] | chunks
   // [max_slots][nfr][WIRE_CHUNK_MAX], and its pinned host copy
   static constexpr int WIRE_BLOCKS = 3;
   unsigned char* wireb_[WIRE_BLOCKS] = {};
   unsigned char* h_wireb_[WIRE_BLOCKS] = {};
   size_t wire_head_bytes() const { return ((size_t)max_slots_ * nfr_ * sizeof(int) + 127) / 128 * 128; }
-  size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * WIRE_CHUNK_MAX; }
+  size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * wire_chunk_max(); }
   static int wire_rate_index(int rate);
 
   // ---- voice cloning: everything a clone writes but the voice itself lives in a VoiceWs, so a

@@ -464,6 +464,10 @@ struct ResetArgs {
   const int* wire_src = nullptr;
   int* wire_fmt = nullptr;
   int* wire_frames = nullptr;
+  // tempo stage (null without it): the row's speed from the staged array, no frame, no hop yet
+  const int* tempo_src = nullptr;
+  int* tempo_sp = nullptr;
+  int* tempo_state = nullptr;  // [max_slots][TEMPO_STATE]
 };
 void slot_reset(const ResetArgs& a, hipStream_t s);
 // The first-frame preview pass's inputs, one launch: row i < n gets the latent and frame flags of
@@ -567,6 +571,10 @@ constexpr int WIRE_TAPS_MAX = 2944;   // >= L of every rate (2941 at 44.1 kHz)
 struct WirePlan {
   int up, down, half, L, tap_off;  // tap_off: the rate's taps within WireArgs::taps
 };
+// On an engine with the tempo stage (below) a frame's input is the row's tempo chunk instead: `tin`
+// [B][out_frames][TEMPO_OUT_MAX] and its sample counts `tcnt` for the rows whose tempo_sp is not 0,
+// the PCM frame and 1920 for the others. The per-row state counts input samples, and a chunk longer
+// than 1920 samples is walked in pieces of 1920 (the LDS window), so the emitted(N) rule is the same.
 struct WireArgs {
   int B, nfr;               // rows, frames this pass decodes
   int pcm_frames;           // frames per row of the PCM block
@@ -574,17 +582,59 @@ struct WireArgs {
   const float* pcm;         // [B][pcm_frames][1920], after the commit
   const FrameFlags* flags[NFR_MAX];
   const int* fmt;           // [B]
-  int* frames;              // [B] frames of the row's utterance received so far
+  int* frames;              // [B] input samples of the row's utterance received so far
   float* tail;              // [B][WIRE_TAIL]
   const float* taps;
   WirePlan plan[WIRE_RATES];
   unsigned char* out;       // [B][out_frames][WIRE_CHUNK_MAX]
   int* counts;              // [B][out_frames] bytes of each chunk (0: no wire format or no frame)
+  int chunk;                // bytes per (row, frame) slot of `out`: WIRE_CHUNK_MAX, or _TEMPO
+  const int* tempo_sp = nullptr;  // [B] (null: no tempo stage)
+  const float* tin = nullptr;
+  const int* tcnt = nullptr;
 };
 void wire_stage(const WireArgs& a, hipStream_t s);
 // n samples already at the wire rate -> n (G.711) or 2 n (16-bit) bytes; `out` holds the byte count
 // rounded up to a multiple of 8
 void wire_encode(const float* x, long n, int enc, unsigned char* out, hipStream_t s);
+
+// Tempo stage: WSOLA time-scaling of a row's f32 PCM at 24 kHz by its speed
+// sp (permille, [TEMPO_SP_MIN, TEMPO_SP_MAX]; 0: none), ahead of the wire stage. Hop k writes
+// TEMPO_HS output samples from the segment at p_k = a_k + delta_k, a_k = floor(k Hs sp / 1000),
+// delta_k the shift in [-D, D] that correlates best (f64, four ordered quarters of 120 products)
+// with the continuation of the previous segment. Streaming: hop k runs in the first frame after
+// which the row has a_k + TEMPO_R samples, the frame flagged `last` runs the rest up to
+// tempo_len(N, sp), so a row's chunks concatenate to the whole-signal rule (tempo()) bit for bit.
+// Per-row state: frames received, next hop, p of the last hop (tempo_state), and the last TEMPO_HIST
+// input samples.
+constexpr int TEMPO_W = 480, TEMPO_HS = 240, TEMPO_D = 120, TEMPO_R = TEMPO_D + TEMPO_HS + TEMPO_W;
+constexpr int TEMPO_SP_MIN = 500, TEMPO_SP_MAX = 2000;
+// input history: a pending hop has a_k > N - R, and reads no sample before
+// min(a_k - D, p_{k-1} + Hs) >= a_k - (ceil(Hs SP_MAX / 1000) + D - Hs)
+constexpr int TEMPO_BACK = (TEMPO_HS * TEMPO_SP_MAX + 999) / 1000 + TEMPO_D - TEMPO_HS;  // 360
+constexpr int TEMPO_HIST = TEMPO_R + TEMPO_BACK;                                         // 1200
+// samples of one chunk: the hops run before a last frame cover every a_k <= N_prev - R, so that
+// frame emits < (1920 + R - 1) 1000 / sp + 1 <= 5519 (section 19); any other frame <= 3840 + Hs
+constexpr int TEMPO_OUT_MAX = 5528;
+constexpr int TEMPO_STATE = 4;  // ints per row: frames received, next hop k, p_{k-1}, unused
+// bytes per (row, frame) slot on a tempo-enabled engine: 2 TEMPO_OUT_MAX + 21 samples at 48 kHz, 16 bit
+constexpr int WIRE_CHUNK_MAX_TEMPO = 22528;
+long tempo_len(long n, int sp);            // ceil(n 1000 / sp)
+std::vector<float> tempo_window();         // [TEMPO_W] periodic Hann, f64 rounded to f32
+struct TempoArgs {
+  int B, nfr, pcm_frames, out_frames;      // as WireArgs
+  const float* pcm;
+  const FrameFlags* flags[NFR_MAX];
+  const int* sp;                           // [B] speed (0: none)
+  int* state;                              // [B][TEMPO_STATE]
+  float* hist;                             // [B][TEMPO_HIST]
+  const float* win;                        // [TEMPO_W]
+  float* out;                              // [B][out_frames][TEMPO_OUT_MAX]
+  int* counts;                             // [B][out_frames] samples of each chunk
+};
+void tempo_stage(const TempoArgs& a, hipStream_t s);
+// whole signal: x [n] -> y [tempo_len(n, sp)], one workgroup, the hop functions of the stage
+void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_t s);
 
 // dst [nch][rows][cols]: row r of chunk c = src[c * chunk_stride .. + cols) (each encoder chunk's
 // first row replicated: the history of the chunked ConvDownsample1d), one launch over all chunks

@@ -3514,6 +3514,10 @@ __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
       a.wire_fmt[slot] = a.wire_src[i];
       a.wire_frames[slot] = 0;
     }
+    if (a.tempo_sp) {
+      a.tempo_sp[slot] = a.tempo_src[i];
+      for (int q = 0; q < TEMPO_STATE; ++q) a.tempo_state[slot * TEMPO_STATE + q] = 0;
+    }
   }
 }
 
@@ -4047,7 +4051,10 @@ __device__ __forceinline__ void wire_store4(unsigned char* dst, long g, int enc,
 // per lane encoded and stored as dwords. (With 256 lanes computing four outputs each, the launch
 // took 59 / 85 us per four-frame pass of 32 rows at 8 / 48 kHz: the tap chain is latency bound.)
 constexpr int WIRE_THREADS = 1024;
-constexpr int WIRE_OUT_MAX = 3864;  // >= the largest chunk, 3860 samples, and a multiple of 4
+constexpr int WIRE_OUT_MAX = 3864;  // >= the largest piece's outputs, 3860 + 3 carried, and a multiple of 4
+// A frame's input is (pointer, count): the PCM frame and 1920, or the row's tempo chunk. It is walked
+// in pieces of at most 1920 samples (one piece for a PCM frame); a piece's outputs that do not fill
+// a group of four are carried in s_y to the next piece, so every store stays a whole dword.
 __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
   __shared__ float s_taps[WIRE_TAPS_MAX];
   __shared__ __attribute__((aligned(16))) float s_x[WIRE_TAIL + 1920];
@@ -4064,8 +4071,10 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
   const bool identity = p.up == 1 && p.down == 1;
   if (!identity)
     for (int i = t; i < p.L; i += WIRE_THREADS) s_taps[i] = a.taps[p.tap_off + i];
-  long nf = a.frames[b];  // frames of the row received so far
-  if (t < WIRE_TAIL) s_x[t] = nf > 0 ? a.tail[(long)b * WIRE_TAIL + t] : 0.f;
+  const int sp = a.tempo_sp ? a.tempo_sp[b] : 0;  // uniform: the row's input is its tempo chunk
+  const long cap = a.chunk / (enc == WIRE_S16 ? 2 : 1);  // samples a chunk slot holds
+  long n = a.frames[b];  // input samples of the row received so far
+  if (t < WIRE_TAIL) s_x[t] = n > 0 ? a.tail[(long)b * WIRE_TAIL + t] : 0.f;
   bool any = false;
   for (int f = 0; f < a.out_frames; ++f) {
     const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
@@ -4074,49 +4083,309 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
       continue;
     }
     any = true;
-    __syncthreads();  // the previous frame's tail is in place
-    const float4* src = reinterpret_cast<const float4*>(a.pcm + ((long)b * a.pcm_frames + f) * 1920);
-    for (int i = t; i < 480; i += WIRE_THREADS) reinterpret_cast<float4*>(s_x + WIRE_TAIL)[i] = src[i];
-    __syncthreads();
-    const long N0 = nf * 1920, N1 = N0 + 1920;
-    long m0 = N0, m1 = N1;
-    if (!identity) {  // emitted(N) = floor((N up - 1 - half) / down) + 1 (0 before the first sample)
-      m0 = N0 == 0 ? 0 : (N0 * p.up - 1 - p.half) / p.down + 1;
-      m1 = fl.last ? (N1 * p.up + p.down - 1) / p.down : (N1 * p.up - 1 - p.half) / p.down + 1;
-    }
-    const long count = min(m1 - m0, (long)WIRE_OUT_MAX);  // (never more: the chunk sizes of kernels.h)
-    unsigned char* dst = a.out + ((long)b * a.out_frames + f) * WIRE_CHUNK_MAX;
-    for (long i = t; i < (count + 3) / 4 * 4; i += WIRE_THREADS) {  // zeros pad the last dword
-      const long m = m0 + i;
-      float v = 0.f;
-      if (i < count)
-        v = identity ? s_x[WIRE_TAIL + (m - N0)]
-                     : resample_out(s_x, N0 - WIRE_TAIL, N1, s_taps, p.L, p.up, p.down, p.half, m);
-      s_y[i] = v;
-    }
-    __syncthreads();
-    for (long g = t; 4 * g < count; g += WIRE_THREADS) {
-      const float4 y4 = reinterpret_cast<const float4*>(s_y)[g];
-      const float v[4] = {y4.x, y4.y, y4.z, y4.w};
-      wire_store4(dst, g, enc, v);
-    }
-    if (t == 0) cnt[f] = (int)count * (enc == WIRE_S16 ? 2 : 1);
-    nf += 1;
-    __syncthreads();  // every lane has read the window
-    if (t < WIRE_TAIL) s_x[t] = s_x[1920 + t];
+    const float* in = sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
+                         : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
+    const int n_in = sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX) : 1920;
+    unsigned char* dst = a.out + ((long)b * a.out_frames + f) * a.chunk;
+    long gbase = 0, total = 0;  // groups of four stored, samples of the chunk
+    int rem = 0, done = 0;      // outputs carried in s_y[0, rem), inputs walked
+    do {
+      const int np = min(1920, n_in - done);
+      const bool fin = done + np == n_in;
+      __syncthreads();  // the previous piece's tail and carried outputs are in place
+      const float4* src = reinterpret_cast<const float4*>(in + done);
+      for (int i = t; 4 * i < np; i += WIRE_THREADS) reinterpret_cast<float4*>(s_x + WIRE_TAIL)[i] = src[i];
+      __syncthreads();
+      const long N0 = n, N1 = n + np;
+      long m0 = N0, m1 = N1;
+      if (!identity) {  // emitted(N) = floor((N up - 1 - half) / down) + 1 (0 before the first sample)
+        m0 = N0 == 0 ? 0 : (N0 * p.up - 1 - p.half) / p.down + 1;
+        m1 = fl.last && fin ? (N1 * p.up + p.down - 1) / p.down
+                            : (N1 == 0 ? 0 : (N1 * p.up - 1 - p.half) / p.down + 1);
+      }
+      // (never more: the chunk sizes of kernels.h)
+      const long count = max(min(min(m1 - m0, (long)WIRE_OUT_MAX - rem), cap - 4 * gbase - rem), 0L);
+      const long tot = rem + count;
+      const long ng = fin ? (tot + 3) / 4 : tot / 4;
+      for (long i = t; i < (fin ? 4 * ng : tot) - rem; i += WIRE_THREADS) {  // zeros pad the last dword
+        const long m = m0 + i;
+        float v = 0.f;
+        if (i < count)
+          v = identity ? s_x[WIRE_TAIL + (m - N0)]
+                       : resample_out(s_x, N0 - WIRE_TAIL, N1, s_taps, p.L, p.up, p.down, p.half, m);
+        s_y[rem + i] = v;
+      }
+      __syncthreads();
+      for (long g = t; g < ng; g += WIRE_THREADS) {
+        const float4 y4 = reinterpret_cast<const float4*>(s_y)[g];
+        const float v[4] = {y4.x, y4.y, y4.z, y4.w};
+        wire_store4(dst, gbase + g, enc, v);
+      }
+      if (fin) {
+        total = 4 * gbase + tot;
+      } else {  // uniform: the outputs past the last whole group move to the front of s_y
+        const int left = (int)(tot - 4 * ng);
+        const float v = t < left ? s_y[4 * ng + t] : 0.f;
+        __syncthreads();
+        if (t < left) s_y[t] = v;
+        rem = left;
+        gbase += ng;
+      }
+      n = N1;
+      done += np;
+      const float tv = t < WIRE_TAIL ? s_x[np + t] : 0.f;  // the last WIRE_TAIL samples of tail | piece
+      __syncthreads();  // every lane has read the window
+      if (t < WIRE_TAIL) s_x[t] = tv;
+    } while (done < n_in);
+    if (t == 0) cnt[f] = (int)total * (enc == WIRE_S16 ? 2 : 1);
   }
   if (!any) return;  // uniform
   if (t < WIRE_TAIL) a.tail[(long)b * WIRE_TAIL + t] = s_x[t];  // each lane wrote its own entry
-  if (t == 0) a.frames[b] = (int)nf;
+  if (t == 0) a.frames[b] = (int)n;
 }
 
 void wire_stage(const WireArgs& a, hipStream_t s) {
   if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
     throw std::runtime_error("wire_stage: bad pass shape");
+  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || (a.tempo_sp && (!a.tin || !a.tcnt || a.chunk < WIRE_CHUNK_MAX_TEMPO)))
+    throw std::runtime_error("wire_stage: bad chunk slot");
   for (int r = 0; r < WIRE_RATES; ++r)
     if (a.plan[r].L > WIRE_TAPS_MAX || a.plan[r].L < 1 || 2 * a.plan[r].half > WIRE_TAIL * a.plan[r].up)
       throw std::runtime_error("wire_stage: plan outside the kernel's LDS window");
   hipLaunchKernelGGL(k_wire, dim3(a.B), dim3(WIRE_THREADS), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tempo stage (see kernels.h; the rule is DESIGN.md section 19). The hop functions are templates on
+// how a sample is read: the streaming kernel's LDS window, or the whole signal in global memory.
+// The streaming window lives in LDS with its four index phases apart: sample u of the window is at
+// (u & 3) * TEMPO_WQ + (u >> 2), so lanes that read samples four apart (tempo_search: four shifts
+// per lane) read consecutive words. quad(j, p): p[r][m * STRIDE] is x[j + 4 m + r].
+constexpr int TEMPO_WQ = (TEMPO_HIST + 1920) / 4;  // 780 words per phase
+struct TempoWindow {  // sample u of s is x[base + u]; n samples received so far (x reads 0 from n on)
+  const float* s;
+  long base, n;
+  static constexpr int STRIDE = 1;
+  __device__ __forceinline__ static int pos(int u) { return (u & 3) * TEMPO_WQ + (u >> 2); }
+  __device__ __forceinline__ float raw(long j) const { return s[pos((int)(j - base))]; }
+  __device__ __forceinline__ float operator()(long j) const { return j >= base && j < n ? raw(j) : 0.f; }
+  __device__ __forceinline__ bool inside(long j, int len) const { return j >= base && j + len <= n; }
+  __device__ __forceinline__ void quad(long j, const float* p[4]) const {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = s + pos((int)(j - base) + r);
+  }
+};
+struct TempoSignal {
+  const float* x;
+  long n;
+  static constexpr int STRIDE = 4;
+  __device__ __forceinline__ float raw(long j) const { return x[j]; }
+  __device__ __forceinline__ float operator()(long j) const { return j >= 0 && j < n ? x[j] : 0.f; }
+  __device__ __forceinline__ bool inside(long j, int len) const { return j >= 0 && j + len <= n; }
+  __device__ __forceinline__ void quad(long j, const float* p[4]) const {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = x + j + r;
+  }
+};
+constexpr int TEMPO_THREADS = 1024;
+constexpr int TEMPO_CAND = 2 * TEMPO_D + 1;       // 241 shifts
+constexpr int TEMPO_QLEN = TEMPO_W / 4;           // 120 products per quarter
+constexpr int TEMPO_NG = (TEMPO_CAND + 3) / 4;    // 61 groups of four consecutive shifts
+static_assert(4 * TEMPO_NG <= TEMPO_THREADS && TEMPO_CAND <= 256 && TEMPO_QLEN % 4 == 0, "tempo_search's lanes");
+
+// p_k of hop k >= 1. Lane q * 61 + g runs quarter q of the four shifts 4 g - D .. 4 g - D + 3: four
+// independent 120-long f64 chains that share each template word and slide over one new signal
+// word per product (964 lanes with one chain each took 5 us a hop: two LDS reads and two
+// conversions per product, LDS bound; this takes a quarter of both). Each chain is still the
+// ascending sum of its quarter. The quarters are added in order, and the largest sum wins, the
+// earliest in the scan order 0, -1, +1, .. among equal ones. s_c [4 * TEMPO_CAND], s_v / s_r [256].
+template <class X>
+__device__ __forceinline__ long tempo_search(const X& x, long a, long pprev, double* s_c, double* s_v, int* s_r) {
+  const int t = threadIdx.x;
+  if (t < 4 * TEMPO_NG) {
+    const int q = t / TEMPO_NG, c0 = 4 * (t - q * TEMPO_NG);
+    const long xa = a + (c0 - TEMPO_D) + q * TEMPO_QLEN, ta = pprev + TEMPO_HS + q * TEMPO_QLEN;
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+    if (x.inside(xa, TEMPO_QLEN + 3) && x.inside(ta, TEMPO_QLEN)) {
+      const float *xp[4], *tp[4];
+      x.quad(xa + 3, xp);
+      x.quad(ta, tp);
+      double x0 = (double)x.raw(xa), x1 = (double)x.raw(xa + 1), x2 = (double)x.raw(xa + 2);
+#pragma unroll 5
+      for (int m = 0; m < TEMPO_QLEN / 4; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // product i = 4 m + r of the four chains
+          const double x3 = (double)xp[r][m * X::STRIDE], tv = (double)tp[r][m * X::STRIDE];
+          acc0 += x0 * tv;
+          acc1 += x1 * tv;
+          acc2 += x2 * tv;
+          acc3 += x3 * tv;
+          x0 = x1, x1 = x2, x2 = x3;
+        }
+      }
+    } else {  // a window that crosses the utterance's end (zeros) or its start
+      double x0 = (double)x(xa), x1 = (double)x(xa + 1), x2 = (double)x(xa + 2);
+      for (int i = 0; i < TEMPO_QLEN; ++i) {
+        const double x3 = (double)x(xa + 3 + i), tv = (double)x(ta + i);
+        acc0 += x0 * tv;
+        acc1 += x1 * tv;
+        acc2 += x2 * tv;
+        acc3 += x3 * tv;
+        x0 = x1, x1 = x2, x2 = x3;
+      }
+    }
+    double* c = s_c + q * TEMPO_CAND + c0;
+    c[0] = acc0;  // (c0 <= 240: the first shift of a group always exists)
+    if (c0 + 1 < TEMPO_CAND) c[1] = acc1;
+    if (c0 + 2 < TEMPO_CAND) c[2] = acc2;
+    if (c0 + 3 < TEMPO_CAND) c[3] = acc3;
+  }
+  __syncthreads();
+  if (t < 256) {
+    double v = -INFINITY;
+    int r = 1 << 30;
+    if (t < TEMPO_CAND) {
+      v = ((s_c[t] + s_c[TEMPO_CAND + t]) + s_c[2 * TEMPO_CAND + t]) + s_c[3 * TEMPO_CAND + t];
+      const int d = t - TEMPO_D;
+      r = d == 0 ? 0 : d < 0 ? -2 * d - 1 : 2 * d;  // place in the scan order
+    }
+    s_v[t] = v;
+    s_r[t] = r;
+  }
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) {
+      const double v2 = s_v[t + h];
+      const int r2 = s_r[t + h];
+      if (v2 > s_v[t] || (v2 == s_v[t] && r2 < s_r[t])) {
+        s_v[t] = v2;
+        s_r[t] = r2;
+      }
+    }
+    __syncthreads();
+  }
+  const int r = min(s_r[0], 2 * TEMPO_D);
+  return a + (r == 0 ? 0 : (r & 1) ? -(r + 1) / 2 : r / 2);
+}
+
+// `count` output samples of hop k (the products are exact in f64: one rounding, to f32)
+template <class X>
+__device__ __forceinline__ void tempo_ola(const X& x, const float* w, long k, long p, long pprev, int count,
+                                          float* out) {
+  const int i = threadIdx.x;
+  if (i >= count) return;
+  out[i] = k == 0 ? x(p + i)
+                  : (float)((double)w[i] * (double)x(p + i) +
+                            (double)w[TEMPO_HS + i] * (double)x(pprev + TEMPO_HS + i));
+}
+
+__global__ __launch_bounds__(TEMPO_THREADS) void k_tempo(TempoArgs a) {
+  __shared__ float s_x[4 * TEMPO_WQ];  // the window, by phase (TempoWindow)
+  __shared__ float s_w[TEMPO_W];
+  __shared__ double s_c[4 * TEMPO_CAND];
+  __shared__ double s_v[256];
+  __shared__ int s_r[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int sp = a.sp[b];
+  int* cnt = a.counts + (long)b * a.out_frames;
+  if (sp < TEMPO_SP_MIN || sp > TEMPO_SP_MAX) {  // uniform: a row without speed
+    if (t < a.out_frames) cnt[t] = 0;
+    return;
+  }
+  if (t < TEMPO_W) s_w[t] = a.win[t];
+  int* st = a.state + (long)b * TEMPO_STATE;
+  long nf = st[0], k = st[1], pprev = st[2];
+  for (int i = t; i < TEMPO_HIST; i += TEMPO_THREADS)
+    s_x[TempoWindow::pos(i)] = nf > 0 ? a.hist[(long)b * TEMPO_HIST + i] : 0.f;
+  bool any = false;
+  for (int f = 0; f < a.out_frames; ++f) {
+    const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
+    if (!fl.valid) {  // uniform
+      if (t == 0) cnt[f] = 0;
+      continue;
+    }
+    any = true;
+    __syncthreads();  // the history is in place
+    const float4* src = reinterpret_cast<const float4*>(a.pcm + ((long)b * a.pcm_frames + f) * 1920);
+    for (int i = t; i < 480; i += TEMPO_THREADS) {  // samples TEMPO_HIST + 4 i + r: word TEMPO_HIST / 4 + i of phase r
+      const float4 v = src[i];
+      s_x[0 * TEMPO_WQ + TEMPO_HIST / 4 + i] = v.x;
+      s_x[1 * TEMPO_WQ + TEMPO_HIST / 4 + i] = v.y;
+      s_x[2 * TEMPO_WQ + TEMPO_HIST / 4 + i] = v.z;
+      s_x[3 * TEMPO_WQ + TEMPO_HIST / 4 + i] = v.w;
+    }
+    __syncthreads();
+    const long N0 = nf * 1920, N = N0 + 1920;
+    const TempoWindow x{s_x, N0 - TEMPO_HIST, N};
+    const long L = (N * 1000 + sp - 1) / sp;
+    float* out = a.out + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX;
+    int emitted = 0;
+    for (;;) {  // uniform: the hops this frame completes
+      const long ak = k * TEMPO_HS * sp / 1000;
+      if (fl.last ? k * TEMPO_HS >= L : ak + TEMPO_R > N) break;
+      const int count = fl.last ? (int)min((long)TEMPO_HS, L - k * TEMPO_HS) : TEMPO_HS;
+      if (emitted + count > TEMPO_OUT_MAX) break;  // (never: the bound of kernels.h)
+      const long p = k > 0 ? tempo_search(x, ak, pprev, s_c, s_v, s_r) : 0;
+      tempo_ola(x, s_w, k, p, pprev, count, out + emitted);
+      emitted += count;
+      pprev = p;
+      ++k;
+    }
+    if (t == 0) cnt[f] = emitted;
+    nf += 1;
+    __syncthreads();  // every lane has read the window
+    // the window moves on by 1920 samples, 480 words of each phase (1920 >= TEMPO_HIST: disjoint)
+    for (int i = t; i < TEMPO_HIST; i += TEMPO_THREADS) s_x[TempoWindow::pos(i)] = s_x[TempoWindow::pos(i) + 480];
+  }
+  if (!any) return;  // uniform
+  for (int i = t; i < TEMPO_HIST; i += TEMPO_THREADS)  // own entries
+    a.hist[(long)b * TEMPO_HIST + i] = s_x[TempoWindow::pos(i)];
+  if (t == 0) {
+    st[0] = (int)nf;
+    st[1] = (int)k;
+    st[2] = (int)pprev;
+  }
+}
+
+void tempo_stage(const TempoArgs& a, hipStream_t s) {
+  static_assert(TEMPO_HIST <= 1920 && TEMPO_HIST % 4 == 0 && TEMPO_OUT_MAX % 4 == 0, "k_tempo's window");
+  if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
+    throw std::runtime_error("tempo_stage: bad pass shape");
+  hipLaunchKernelGGL(k_tempo, dim3(a.B), dim3(TEMPO_THREADS), 0, s, a);
+}
+
+__global__ __launch_bounds__(TEMPO_THREADS) void k_tempo_whole(const float* __restrict__ xs, long n, int sp,
+                                                              const float* __restrict__ win, float* __restrict__ y) {
+  __shared__ float s_w[TEMPO_W];
+  __shared__ double s_c[4 * TEMPO_CAND];
+  __shared__ double s_v[256];
+  __shared__ int s_r[256];
+  const int t = threadIdx.x;
+  if (t < TEMPO_W) s_w[t] = win[t];
+  __syncthreads();
+  const TempoSignal x{xs, n};
+  const long L = (n * 1000 + sp - 1) / sp;
+  long pprev = 0;
+  for (long k = 0; k * TEMPO_HS < L; ++k) {
+    const long ak = k * TEMPO_HS * sp / 1000;
+    const int count = (int)min((long)TEMPO_HS, L - k * TEMPO_HS);
+    const long p = k > 0 ? tempo_search(x, ak, pprev, s_c, s_v, s_r) : 0;
+    tempo_ola(x, s_w, k, p, pprev, count, y + k * TEMPO_HS);
+    pprev = p;
+  }
+}
+
+long tempo_len(long n, int sp) { return (n * 1000 + sp - 1) / sp; }
+
+std::vector<float> tempo_window() {
+  std::vector<float> w(TEMPO_W);
+  for (int i = 0; i < TEMPO_W; ++i) w[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / TEMPO_W));
+  return w;
+}
+
+void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_t s) {
+  if (n < 1 || sp < TEMPO_SP_MIN || sp > TEMPO_SP_MAX) throw std::runtime_error("tempo: bad arguments");
+  hipLaunchKernelGGL(k_tempo_whole, dim3(1), dim3(TEMPO_THREADS), 0, s, x, (long)n, sp, win, y);
 }
 
 // whole-signal encode of n samples (already at the wire rate), four per lane

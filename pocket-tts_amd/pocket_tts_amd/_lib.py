@@ -22,6 +22,7 @@ BACK_F32, BACK_BF16, BACK_F32X6 = 0, 1, 2  # ptts_engine_config.back_mfma (PTTS_
 SAMPLES_F32, SAMPLES_S16 = 0, 1  # sample_format of ptts_voice_job_start (PTTS_SAMPLES_*)
 WIRE_NONE, WIRE_S16, WIRE_ULAW, WIRE_ALAW = 0, 1, 2, 3  # PTTS_WIRE_*
 WIRE_CHUNK_MAX = 8192  # PTTS_WIRE_CHUNK_MAX
+WIRE_CHUNK_MAX_TEMPO = 22528  # PTTS_WIRE_CHUNK_MAX_TEMPO
 WIRE_RATES = (8000, 16000, 24000, 44100, 48000)
 ABI_VERSION = 6  # PTTS_ABI_VERSION of include/pocket_tts.h that the structs below mirror
 
@@ -66,6 +67,7 @@ class SlotOpts(C.Structure):
         ("lsd_steps", C.c_int),
         ("wire_rate", C.c_int),
         ("wire_encoding", C.c_int),
+        ("speed_permille", C.c_int),
     ]
 
 
@@ -119,6 +121,9 @@ SIGNATURES = [
     ("ptts_fetch_wire", C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_size_t, C.POINTER(C.c_int)]),
     ("ptts_wire_len", C.c_long, [C.c_long, C.c_int, C.c_int]),
     ("ptts_wire_encode", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, U8P]),
+    ("ptts_tempo_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_tempo_len", C.c_long, [C.c_long, C.c_int]),
+    ("ptts_tempo", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, F32P]),
     ("ptts_lsd_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ptts_probe_overlap", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("ptts_slot_close", C.c_int, [C.c_void_p, C.c_int]),

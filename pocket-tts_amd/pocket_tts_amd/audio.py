@@ -19,6 +19,7 @@ Resampling to 24 kHz is not here: it runs on the GPU inside `ptts_voice_from_aud
 
 from __future__ import annotations
 
+import math
 import struct
 from pathlib import Path
 
@@ -182,3 +183,99 @@ def normalize_peak(audio: np.ndarray) -> np.ndarray:
     a = np.asarray(audio, np.float32)
     m = float(np.abs(a).max()) if a.size else 0.0
     return (a * np.float32(1.0 / m)).astype(np.float32) if m > 0 else a.copy()
+
+
+# ---- speech speed: the host restatement of DESIGN.md section 19 (the GPU tempo stage's rule)
+TEMPO_W, TEMPO_HS, TEMPO_D = 480, 240, 120  # window, synthesis hop, search radius
+TEMPO_R = TEMPO_D + TEMPO_HS + TEMPO_W  # hop k runs once a_k + TEMPO_R samples are in
+TEMPO_SPEED_MIN, TEMPO_SPEED_MAX = 500, 2000  # permille
+
+
+def speed_permille(speed) -> int:
+    """A speed factor (1.0 = unchanged) as the integer permille the engine takes; 0 for None or 1.0.
+    ValueError outside [0.5, 2.0]."""
+    if speed is None:
+        return 0
+    f = float(speed)
+    sp = round(f * 1000) if math.isfinite(f) else -1
+    if not TEMPO_SPEED_MIN <= sp <= TEMPO_SPEED_MAX:
+        raise ValueError(f"speed must be in [0.5, 2.0], got {speed!r}")
+    return 0 if sp == 1000 else sp
+
+
+def tempo_len(n: int, sp: int) -> int:
+    """Samples of an n-sample utterance at speed sp (permille): ceil(n * 1000 / sp)."""
+    return (int(n) * 1000 + int(sp) - 1) // int(sp)
+
+
+def tempo_window() -> np.ndarray:
+    """w[i] = 0.5 - 0.5 cos(2 pi i / W) in f64, rounded to f32."""
+    return np.array([0.5 - 0.5 * math.cos(2.0 * math.pi * i / TEMPO_W) for i in range(TEMPO_W)], np.float32)
+
+
+def tempo_hops_ready(n: int, sp: int) -> int:
+    """Hops a stream has run after n samples (not its last frame): the k with a_k + TEMPO_R <= n."""
+    k = 0
+    while k * TEMPO_HS * sp // 1000 + TEMPO_R <= n:
+        k += 1
+    return k
+
+
+def tempo_chunk_samples(frame: int, sp: int, last: bool, frame_len: int = 1920) -> int:
+    """Samples the tempo stage emits in frame `frame` (0-based) of a row at speed sp: a pure function
+    of (frame, sp, last). The last frame emits the rest up to tempo_len of the utterance."""
+    n0, n1 = frame * frame_len, (frame + 1) * frame_len
+    before = tempo_hops_ready(n0, sp) * TEMPO_HS
+    return (tempo_len(n1, sp) if last else tempo_hops_ready(n1, sp) * TEMPO_HS) - before
+
+
+def tempo_wsola(x: np.ndarray, sp: int, frame_len: int | None = None):
+    """WSOLA time-scaling of mono f32 PCM at 24 kHz by sp permille: tempo_len(len(x), sp) samples.
+    Every product is f32 x f32 in f64 (exact), every sum runs in the stated order, so the GPU stage
+    agrees bit for bit. frame_len: run frame by frame as the stream does (hop k as soon as
+    a_k + TEMPO_R samples are in, the rest in the last frame) and return the list of chunks."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    sp = int(sp)
+    if not TEMPO_SPEED_MIN <= sp <= TEMPO_SPEED_MAX:
+        raise ValueError(f"speed must be in [{TEMPO_SPEED_MIN}, {TEMPO_SPEED_MAX}] permille, got {sp}")
+    n = x.size
+    W, HS, D = TEMPO_W, TEMPO_HS, TEMPO_D
+    L = tempo_len(n, sp)
+    hops = (L + HS - 1) // HS
+    # zeros past the end: the furthest read is a_k + D + W or p_{k-1} + HS + W
+    xd = np.concatenate([x.astype(np.float64), np.zeros(hops * HS * sp // 1000 + TEMPO_R + W + 1)])
+    w = tempo_window().astype(np.float64)
+    scan = [0] + [d for j in range(1, D + 1) for d in (-j, j)]
+    y = np.zeros(hops * HS, np.float32)
+    starts = np.arange(-D, D + 1)
+    p_prev = 0
+    for k in range(hops):
+        if k == 0:
+            p = 0
+            y[:HS] = x[:HS] if n >= HS else xd[:HS].astype(np.float32)
+        else:
+            a = k * HS * sp // 1000
+            t = xd[p_prev + HS: p_prev + HS + W]
+            c = np.zeros(2 * D + 1)
+            for q in range(4):
+                acc = np.zeros(2 * D + 1)
+                for i in range(120 * q, 120 * q + 120):  # ascending i, all shifts at once
+                    acc += xd[a + starts + i] * t[i]
+                c = acc if q == 0 else c + acc
+            best = 0
+            for d in scan[1:]:
+                if c[d + D] > c[best + D]:
+                    best = d
+            p = a + best
+            y[k * HS:(k + 1) * HS] = (w[:HS] * xd[p: p + HS] + w[HS:] * xd[p_prev + HS: p_prev + W]).astype(np.float32)
+        p_prev = p
+    y = y[:L]
+    if frame_len is None:
+        return y
+    chunks, done, nfr = [], 0, (n + frame_len - 1) // frame_len
+    for f in range(nfr):
+        end = L if f == nfr - 1 else tempo_hops_ready((f + 1) * frame_len, sp) * HS
+        chunks.append(y[done:end])
+        done = end
+    return chunks
+

@@ -8,8 +8,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
-                   WIRE_ALAW, WIRE_CHUNK_MAX, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
+                   WIRE_ALAW, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
                    SlotOpts, check, fptr, lib, u8ptr)
+from .audio import speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
 WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW}
@@ -45,10 +46,19 @@ class GenerationParams:
     # no wire output; None in one: 24000 / 16-bit. Passed beside the struct too (ptts_slots_open_opts).
     sample_rate: int | None = None
     encoding: str | int | None = None
+    # speech speed of the row's wire bytes (tempo-enabled engines), 0.5 .. 2.0; None or 1.0: unchanged.
+    # A speed with no wire format implies 24000 / 16-bit. The f32 PCM of fetch() never depends on it.
+    speed: float | None = None
 
     def wire(self) -> tuple[int, int]:
         """(wire_rate, wire_encoding) of ptts_slot_opts; (0, 0): none."""
         return int(self.sample_rate or 0), wire_encoding_code(self.encoding)
+
+    def opts(self) -> tuple[int, int, int]:
+        """(wire_rate, wire_encoding, speed_permille) of ptts_slot_opts; all 0: the defaults. A speed
+        out of range is passed on as it is (rounded to permille): the admission refuses it."""
+        sp = 0 if self.speed is None else round(float(self.speed) * 1000)
+        return (*self.wire(), 0 if sp == 1000 else sp)
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
@@ -115,7 +125,8 @@ class Engine:
                  seed: int = 0x5EED, weights_path: str | None = None, weight_blob: int | None = None,
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
-                 back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False):
+                 back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
+                 tempo: bool = False):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -132,7 +143,9 @@ class Engine:
         (f32 products as six bf16 piece products, f32 accuracy) or BACK_BF16 (operands rounded to
         bf16: a variant gated on PCM accuracy); back_bf16=True is BACK_BF16.
         wire=True (ptts_wire_enable): rows admitted with GenerationParams.sample_rate / encoding also
-        get their wire bytes, converted on the GPU (fetch_wire)."""
+        get their wire bytes, converted on the GPU (fetch_wire).
+        tempo=True (ptts_tempo_enable; needs wire): rows admitted with GenerationParams.speed have
+        their wire bytes time-scaled on the GPU."""
         if back_mfma is None:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
@@ -164,6 +177,14 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        self.tempo_enabled = bool(tempo)
+        if tempo:
+            try:
+                check(lib().ptts_tempo_enable(self.handle, 1))
+            except Exception:
+                self.close()
+                raise
+        self.wire_chunk_max = WIRE_CHUNK_MAX_TEMPO if tempo else WIRE_CHUNK_MAX
         self._wire_buf = self._wire_n = None
 
     def test_gemm(self, layout: int, x: np.ndarray, w: np.ndarray, splits: int = 1, tail_slices: int = 0) -> np.ndarray:
@@ -320,7 +341,7 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
-        if params.wire() != (0, 0):
+        if params.opts() != (0, 0, 0):
             return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
@@ -338,8 +359,8 @@ class Engine:
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
-        if any(p.wire() != (0, 0) for p in params_list):  # a row with a wire format: ptts_slots_open_opts
-            opts = (SlotOpts * n)(*[SlotOpts(C.sizeof(SlotOpts), int(lsd[i]), *p.wire())
+        if any(p.opts() != (0, 0, 0) for p in params_list):  # a wire format or a speed: ptts_slots_open_opts
+            opts = (SlotOpts * n)(*[SlotOpts(C.sizeof(SlotOpts), int(lsd[i]), *p.opts())
                                     for i, p in enumerate(params_list)])
             check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
                                              nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
@@ -409,9 +430,9 @@ class Engine:
         """The wire chunks of the frame fetch(n_rows, calls_back) returns (ptts_fetch_wire): one
         bytes object per row, empty for a row with no wire format or no frame."""
         if self._wire_buf is None:
-            self._wire_buf = np.zeros((self.max_slots, WIRE_CHUNK_MAX), np.uint8)
+            self._wire_buf = np.zeros((self.max_slots, self.wire_chunk_max), np.uint8)
             self._wire_n = np.zeros(self.max_slots, np.int32)
-        check(lib().ptts_fetch_wire(self.handle, calls_back, n_rows, u8ptr(self._wire_buf), WIRE_CHUNK_MAX,
+        check(lib().ptts_fetch_wire(self.handle, calls_back, n_rows, u8ptr(self._wire_buf), self.wire_chunk_max,
                                     self._wire_n.ctypes.data_as(C.POINTER(C.c_int))))
         return [self._wire_buf[b, : self._wire_n[b]].tobytes() for b in range(n_rows)]
 
@@ -424,6 +445,23 @@ class Engine:
         out = np.zeros(max(n, 1), np.uint8)
         check(lib().ptts_wire_encode(self.handle, fptr(x), x.size, int(sample_rate), enc, out.ctypes.data_as(U8P)))
         return out[:n].tobytes()
+
+    @staticmethod
+    def tempo_len(n: int, speed) -> int:
+        """Samples of an n-sample utterance at `speed` (ptts_tempo_len; host only)."""
+        return int(lib().ptts_tempo_len(int(n), speed_permille(speed) or 1000))
+
+    def tempo(self, pcm: np.ndarray, speed) -> np.ndarray:
+        """Whole-signal f32 PCM at 24 kHz time-scaled by `speed` on the GPU (ptts_tempo): the rule of
+        the streaming tempo stage (audio.tempo_wsola is its host restatement). Speed 1.0: a copy."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        sp = speed_permille(speed)
+        if sp == 0:
+            return x.copy()
+        n = int(lib().ptts_tempo_len(x.size, sp))
+        y = np.zeros(max(n, 1), np.float32)
+        check(lib().ptts_tempo(self.handle, fptr(x), x.size, sp, fptr(y)))
+        return y[:n]
 
     def fetch_ready(self, calls_back: int = 0) -> bool:
         """fetch(calls_back=...) would not block (ptts_fetch_ready)."""

@@ -45,6 +45,18 @@ WAV file of that encoding (G.711: format tag 7 / 6, 8 bits, a `fact` chunk), /st
 bytes. A request that names neither field gets today's bytes by today's code path. Unknown values,
 or either field on a `--no-wire` server, get 400.
 
+Per-request speech speed (`--tempo`, on with `--wire`; the `speed` of the API /v1/audio/speech
+imitates): the three audio routes also take `speed`, a factor in [0.5, 2.0]. The model has no
+duration control, so the row's PCM is time-scaled on the GPU, pitch kept, ahead of the wire
+conversion (a streaming WSOLA); the scheduler hands the bytes on untouched,
+and requests with different speeds, and with none, share a batch. A speed with no format answers in
+24000 / pcm_s16le. Unset or 1.0 changes nothing; a long-form request's every text segment carries
+the speed and its pause silences keep their stated duration. A value outside the range, or a speed
+on a server without the stage (`--no-tempo`, `--no-wire`), gets 400.
+
+    curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
+         -d '{"input": "Hello there.", "voice": "alba", "speed": 1.25}' -o fast.wav
+
 Long-form requests (`long_form` in the three audio routes' bodies; `--long-form` sets the default,
 off): the text is cut as the reference's routes cut it (generate_stream_long, handlers.rs:165,260:
 pause markers and natural pauses become silence, each piece is cut into sentence chunks of at most
@@ -88,7 +100,8 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, SAMPLE_RATE, WIRE_RATES
-from .audio import ENCODINGS, pcm_i16_le_bytes, wav_bytes, wire_bytes  # noqa: F401 (re-exported wire formats)
+from .audio import (ENCODINGS, pcm_i16_le_bytes, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
+                    wire_bytes)
 from .engine import GenerationParams, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
                    silence_samples)
@@ -303,13 +316,15 @@ class Request(_Consumer):
     # (sample_rate, encoding name) of a request with a wire format: its items are bytes the engine
     # converted (Engine.fetch_wire), not float32 frames; None: today's float32 frames
     wire: tuple[int, str] | None = None
+    speed: int = 0         # permille of a request with a speed (its wire bytes are time-scaled); 0: none
     sched: object = None   # the scheduler that holds the request (cancel())
     group: object = None   # the RequestGroup this request is a text segment of
     ended: bool = False    # the end marker was put
 
     def __post_init__(self):
         rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
-        if rate or enc:
+        self.speed = self.params.opts()[2] if hasattr(self.params, "opts") else 0
+        if rate or enc or self.speed:  # a speed alone: 24000 / pcm_s16le
             self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
 
     def put(self, item):
@@ -637,7 +652,8 @@ class BatchScheduler:
             if fmt is not None:
                 # a resampled row's first chunk is shorter than its preview's frame (the filter's
                 # delay): it waits for its regular first chunk; a 24 kHz row's preview is encoded here
-                if fmt[0] != SAMPLE_RATE:
+                # a speed row's first chunk is not its first frame either
+                if fmt[0] != SAMPLE_RATE or req.speed:
                     continue
                 pcm = wire_bytes(pcm, fmt[1])
             req.preview = 1
@@ -971,6 +987,7 @@ class TTSService:
         eng = getattr(scheduler, "engine", None) or getattr(getattr(scheduler, "schedulers", [None])[0], "engine", None)
         self.max_ctx = max_ctx if max_ctx is not None else getattr(eng, "max_ctx", None)
         self.wire = bool(getattr(eng, "wire", False))  # the engines convert to wire formats (--wire)
+        self.tempo = self.wire and bool(getattr(eng, "tempo_enabled", False))  # and time-scale (--tempo)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -990,8 +1007,9 @@ class TTSService:
                 temperature: float | None = None, eos_threshold: float | None = None,
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None, sample_rate: int | None = None,
-                encoding: str | None = None, long_form: bool | None = None) -> Request:
-        """long_form (None: the server's default, --long-form): the text is split as the reference's
+                encoding: str | None = None, long_form: bool | None = None, speed: float | None = None) -> Request:
+        """speed: 0.5 .. 2.0, the row's wire bytes time-scaled on the GPU (None or 1.0: unchanged).
+        long_form (None: the server's default, --long-form): the text is split as the reference's
         routes split it (generate_stream_long: pause markers and natural pauses become silence,
         each text piece is cut into sentence chunks of at most 50 tokens) and the chunks run as
         rows of the batch, delivered in text order behind one Request-like object (RequestGroup).
@@ -1006,6 +1024,11 @@ class TTSService:
             if not self.wire:
                 raise ValueError("this server runs without wire output (--no-wire): sample_rate / encoding "
                                  "are not available")
+        if speed_permille(speed) == 0:  # (ValueError outside [0.5, 2.0]); 1.0: the request without it
+            speed = None
+        elif not self.tempo:
+            raise ValueError("this server runs without the tempo stage (--no-tempo or --no-wire): speed is not "
+                             "available")
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
@@ -1043,22 +1066,23 @@ class TTSService:
             target = clip if clip is not None else self.voices[name]
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
-                                                            lsd_steps, sample_rate, encoding))
+                                                            lsd_steps, sample_rate, encoding, speed))
                         if sg[0] == "text" else sg for sg in segments]
-                wire = None
-                if sample_rate is not None or encoding is not None:
+                wire = None  # (pauses: silence of their stated duration, whatever the speed)
+                if sample_rate is not None or encoding is not None or speed is not None:
                     wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
                 return self.scheduler.submit_group(segs, target, wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       sample_rate, encoding)
+                                       sample_rate, encoding, speed)
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       sample_rate=None, encoding=None) -> Request:
-        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding)
+                       sample_rate=None, encoding=None, speed=None) -> Request:
+        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding,
+                                speed)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
-                       encoding=None) -> GenerationParams:
+                       encoding=None, speed=None) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -1068,6 +1092,8 @@ class TTSService:
                              lsd_steps=None if lsd_steps is None else int(lsd_steps))
         if sample_rate is not None or encoding is not None:  # a request that names neither: as before
             p.sample_rate, p.encoding = sample_rate, encoding
+        if speed is not None:
+            p.speed = float(speed)
         return p
 
     # -- per-request and run-time voices
@@ -1156,6 +1182,8 @@ class GenerateRequest(BaseModel):
     # alaw; one of them alone defaults the other to 24000 / pcm_s16le; neither: today's output
     sample_rate: int | None = None
     encoding: str | None = None
+    # speech speed, 0.5 .. 2.0 (time-scaled on the GPU, pitch kept); unset or 1.0: unchanged
+    speed: float | None = None
     # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
     long_form: bool | None = None
 
@@ -1171,6 +1199,7 @@ class OpenAIRequest(BaseModel):
     words: int | None = None
     sample_rate: int | None = None
     encoding: str | None = None
+    speed: float | None = None  # 0.5 .. 2.0, as in the API this route imitates (0.25 .. 4.0 there)
     long_form: bool | None = None
 
 
@@ -1325,7 +1354,7 @@ def create_app(service: TTSService):
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
-                   encoding=enc, long_form=req.long_form)
+                   encoding=enc, long_form=req.long_form, speed=req.speed)
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
@@ -1472,7 +1501,7 @@ def _worker_engine(args, Engine):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     kw = dict(max_slots=args.slots, max_ctx=args.max_ctx, weights_path=args.weights, pipeline=True,
               back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
-              wire=args.wire)
+              wire=args.wire, tempo=args.wire and args.tempo)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1537,6 +1566,9 @@ def main(argv=None):
     ap.add_argument("--wire", action=argparse.BooleanOptionalAction, default=True,
                     help="wire formats converted on the GPU (requests' sample_rate / encoding); --no-wire: the "
                          "engine as before, such requests get 400")
+    ap.add_argument("--tempo", action=argparse.BooleanOptionalAction, default=True,
+                    help="per-request speech speed (requests' speed) time-scaled on the GPU; needs --wire (off "
+                         "with --no-wire); --no-tempo: the wire-enabled engine as before, such requests get 400")
     ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
                     help="default of requests that do not say `long_form`: split the text into pause and sentence "
                          "segments (the reference's generate_stream_long) and run them on parallel rows")

@@ -28,7 +28,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
-from .audio import read_wav, read_wav_from_bytes, wire_bytes
+from .audio import read_wav, read_wav_from_bytes, speed_permille, wire_bytes
 from .engine import Engine, GenerationParams, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
@@ -74,14 +74,15 @@ class TTSModel:
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
-                         back_frames: int = 1) -> "TTSModel":
+                         back_frames: int = 1, tempo: bool = False) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
         (the engine's cap; None: lsd_decode_steps itself, the field can then only be lowered).
         weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
         from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json.
-        wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=)."""
+        wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=); tempo (with wire):
+        its tempo stage too, for generate(.., speed=)."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
@@ -89,7 +90,7 @@ class TTSModel:
         eng = Engine(device=device, max_slots=int(max_slots), max_ctx=max_ctx, pipeline=pipeline,
                      back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
-                     wire=wire)
+                     wire=wire, tempo=tempo)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -180,15 +181,16 @@ class TTSModel:
                              "(max_lsd_decode_steps at load)")
 
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
-                 sample_rate: int | None = None, encoding=None) -> Iterator[np.ndarray]:
+                 sample_rate: int | None = None, encoding=None, speed: float | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
-        (sample_rate / encoding; a wire-enabled engine) the items are the row's wire chunks, bytes
-        converted on the GPU (Engine.fetch_wire), instead of f32 frames."""
+        (sample_rate / encoding; a wire-enabled engine) or a speed (a tempo-enabled one; 24 kHz
+        16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
+        GPU (Engine.fetch_wire), instead of f32 frames."""
         self._check_lsd()
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
-        params.sample_rate, params.encoding = sample_rate, encoding
-        wire = params.wire() != (0, 0)
+        params.sample_rate, params.encoding, params.speed = sample_rate, encoding, speed
+        wire = params.opts() != (0, 0, 0)
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
@@ -205,8 +207,8 @@ class TTSModel:
                 return
 
     def generate_stream(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
-                        words: int | None = None, sample_rate: int | None = None, encoding=None
-                        ) -> Iterator[np.ndarray]:
+                        words: int | None = None, sample_rate: int | None = None, encoding=None,
+                        speed: float | None = None) -> Iterator[np.ndarray]:
         """tts_model.rs:894-913. Text: one segment per sentence chunk; max_gen_len and the EOS tail
         from each chunk (:968-969). Token ids (an extension for callers with their own tokenizer):
         one segment; ids carry no word count, so the caller passes `words` (the reference's rules
@@ -214,29 +216,36 @@ class TTSModel:
         explicit max_frames (tail 3).
         sample_rate (8000, 16000, 24000, 44100, 48000) and / or encoding ("pcm_s16le", "ulaw",
         "alaw"): the items are bytes in that wire format, one chunk per frame (every segment is
-        resampled on its own: its chunks are the whole-signal resample of the segment)."""
+        resampled on its own: its chunks are the whole-signal resample of the segment).
+        speed (0.5 .. 2.0; a tempo-enabled engine): the segments' audio is time-scaled on the GPU
+        ahead of that conversion, pitch kept; the items are wire bytes then
+        too, 24 kHz 16-bit unless a format is given. None or 1.0 changes nothing."""
+        if speed_permille(speed) == 0:
+            speed = None
         if not isinstance(text_or_ids, str):
             ids = np.asarray(text_or_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
-            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding)
+            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding,
+                                     speed)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), sample_rate, encoding)
+                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
-                 words: int | None = None, sample_rate: int | None = None, encoding=None):
-        """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding,
-        the wire bytes of generate_stream concatenated."""
-        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding))
+                 words: int | None = None, sample_rate: int | None = None, encoding=None,
+                 speed: float | None = None):
+        """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
+        speed, the wire bytes of generate_stream concatenated."""
+        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed))
         if not frames:
             raise RuntimeError("No audio generated")
-        if sample_rate is not None or encoding is not None:
+        if sample_rate is not None or encoding is not None or speed_permille(speed):
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
 
@@ -257,7 +266,8 @@ class TTSModel:
 
     # ---- the same segments on parallel rows
     def generate_stream_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
-                                 sample_rate: int | None = None, encoding=None) -> Iterator:
+                                 sample_rate: int | None = None, encoding=None,
+                                 speed: float | None = None) -> Iterator:
         """The items of generate_stream (pauses=False) or generate_stream_long (pauses=True), in text
         order, with the text segments generated as rows of one batch: up to `rows` (default: the
         engine's max_slots) are admitted at once (Engine.open_many: one shared text prefill, the
@@ -267,12 +277,14 @@ class TTSModel:
         segment the sequential methods produce: it gets their seed (`_seed` advanced once per text
         segment, in text order) and the field values read when this call starts.
         sample_rate / encoding: wire bytes as generate_stream yields them, and each pause as the
-        encoded silence of silence_samples(ms, sample_rate) samples. Closing the generator early
+        encoded silence of silence_samples(ms, sample_rate) samples. speed: every text segment's row
+        carries it (generate_stream); pauses keep their stated duration. Closing the generator early
         cancels the rows it still holds (Engine.cancel_slots)."""
         self._check_lsd()
         tok = self._tok()
         eng = self.engine
-        wire = sample_rate is not None or encoding is not None
+        speed = speed if speed_permille(speed) else None
+        wire = sample_rate is not None or encoding is not None or speed is not None
         n_rows = max(1, min(int(rows or eng.max_slots), eng.max_slots))
         items = []  # per segment: ("pause", item) | ["text", ids, params, frames, done]
         for kind, val in long_form_segments(text, self.count_tokens, pauses):
@@ -280,7 +292,7 @@ class TTSModel:
                 ids, mgl, fae = segment_request(val, tok)
                 params = self._params(mgl, fae)
                 params.lsd_steps = int(self.lsd_decode_steps)
-                params.sample_rate, params.encoding = sample_rate, encoding
+                params.sample_rate, params.encoding, params.speed = sample_rate, encoding, speed
                 items.append(["text", np.asarray(ids, np.int32), params, [], False])
             elif wire:
                 n = silence_samples(val, int(sample_rate or SAMPLE_RATE))
@@ -340,14 +352,14 @@ class TTSModel:
                 eng.cancel_slots(sorted(active))
 
     def generate_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
-                          sample_rate: int | None = None, encoding=None):
+                          sample_rate: int | None = None, encoding=None, speed: float | None = None):
         """generate (pauses=False) or generate_with_pauses (pauses=True) with the text's segments on
         parallel rows: the concatenation of generate_stream_parallel's items. The name is the
         reference's own: its generate_parallel (tts_model.rs:705-854) is commented out there, "for
         future exploration with GPU acceleration"."""
-        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding))
+        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding, speed))
         if not chunks:
             raise RuntimeError("No audio generated")
-        if sample_rate is not None or encoding is not None:
+        if sample_rate is not None or encoding is not None or speed_permille(speed):
             return b"".join(chunks)
         return np.concatenate(chunks, axis=2)[0]
