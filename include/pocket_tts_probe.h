@@ -3,7 +3,7 @@
  * Not part of the drop-in boundary (include/pocket_tts.h): nothing in the reference corresponds
  * to these, and a reference-side binding never declares them. bench.py, the
  * GPU tests and tools/ use them to time single kernels of the step plan, list the plan with its
- * algorithmic costs, probe front/back overlap and test the GEMM core on off-model shapes. Same
+ * algorithmic costs, probe front/back overlap and test the GEMM core and the attention path on off-model operands. Same
  * conventions as pocket_tts.h (status codes, the thread-local last-error message).
  */
 #ifndef POCKET_TTS_PROBE_H
@@ -22,6 +22,26 @@ extern "C" {
  * (layouts 34 / 35). The tests run every shipped layout on shapes the model never runs. */
 int ptts_test_gemm(ptts_engine* e, int layout, int m, int n, int k, int splits, int tail_slices, const float* x,
                    const float* w, float* y);
+/* Test hook of the attention path (no reference counterpart): the product launchers, unchanged, on
+ * host operands, so the tests can compare RoPE, the KV append and the softmax with fp64 on operands
+ * the model never produces. kind PTTS_ATTN_PREFILL: qkv_rope_append + attention(qg = 16) (FlowLM
+ * prefill, Mimi multi-frame pass); PTTS_ATTN_MIMI_STEP: attention16_qkv (RoPE and ring append fused,
+ * 16 rows per slot; cap < window + 16 is refused as in the product); PTTS_ATTN_FLOW_STEP:
+ * attention_step_qkv with the engine's rope_table (one row per slot, window 0).
+ *   qkv  [m][3 nh 64] dense rows (splits == 0) or [splits][m][3 nh 64] partial slabs;
+ *   kv   [n_slots][2][nh][cap][64], in: the store before the call, out: after it;
+ *   pre  optional shared prefixes, slot s's [2][nh][F_s][64] back to back, F_s = pre_len[s]
+ *        (positions < F_s of slot s are read from it; window 0, not the Mimi step);
+ *   rows -> (slot, position): uniform, slot = slot0 + row / rps at (pos ? pos[slot] : p0) + row % rps
+ *        (16-row groups must not straddle slots), or, PREFILL only, tab [m] = slot << 16 | position
+ *        with -1 padding rows closing a 16-row group; with ptab [mpad] as well, tab holds the tokens
+ *        only and ptab the padded groups (the compact batched admission: Q is [mpad] rows);
+ *   q    out, PREFILL only: the rotated queries [m or mpad][nh 64];  o  out [m][nh 64].
+ * Every position must lie inside the store unless it is a ring (cap a power of two, window > 0). */
+enum { PTTS_ATTN_PREFILL = 0, PTTS_ATTN_MIMI_STEP = 1, PTTS_ATTN_FLOW_STEP = 2 };
+int ptts_test_attention(ptts_engine* e, int kind, int m, int nh, int cap, int window, int n_slots, int splits,
+                        const float* qkv, float* kv, const float* pre, const int* pre_len, int slot0, int rps, int p0,
+                        const int* pos, const int* tab, const int* ptab, int mpad, float* q, float* o);
 /* Measurement: replay one named kernel of the step plan `reps` times between HIP events on
  * the engine stream; returns the average duration in microseconds. */
 int ptts_time_kernel(ptts_engine* e, int n_rows, const char* name, int reps, double* avg_us);

@@ -217,6 +217,15 @@ int ptts_test_gemm(ptts_engine* e, int layout, int m, int n, int k, int splits, 
   return guard([&] { eng(e).test_gemm(layout, m, n, k, splits, tail_slices, x, w, y); });
 }
 
+int ptts_test_attention(ptts_engine* e, int kind, int m, int nh, int cap, int window, int n_slots, int splits,
+                        const float* qkv, float* kv, const float* pre, const int* pre_len, int slot0, int rps, int p0,
+                        const int* pos, const int* tab, const int* ptab, int mpad, float* q, float* o) {
+  return guard([&] {
+    eng(e).test_attention(kind, m, nh, cap, window, n_slots, splits, qkv, kv, pre, pre_len, slot0, rps, p0, pos, tab,
+                          ptab, mpad, q, o);
+  });
+}
+
 int ptts_voice_job_start(ptts_engine* e, const void* samples, int n_samples, int sample_format, int sample_rate,
                          int chunk_frames, int resampler, ptts_voice** out) {
   return guard([&] {

@@ -2102,6 +2102,155 @@ void Engine::test_gemm(int layout, int M, int N, int K, int splits, int tail_S, 
   release();
 }
 
+// Attention-path test hook: the product launchers, unchanged, on host operands (the tests compare
+// with an fp64 softmax attention on operands the model never produces). kind 0: qkv_rope_append
+// (dense rows, S == 0, or S partial slabs) + attention(qg = 16); kind 1: attention16_qkv (the fused
+// Mimi step); kind 2: rope_table + attention_step_qkv. The KV store [n_slots][2][nh][cap][64] goes
+// in and comes back; pre (optional) holds each slot's shared prefix [2][nh][F][64], F =
+// pre_len[slot], back to back. Rows map to (slot, position) by the uniform RowMap {slot0, rps, p0,
+// pos} or, kind 0, by the table `tab` (-1: padding), with the compact form when `ptab` [mpad] is
+// given: tab holds the tokens only, ptab the padded 16-row groups, qrow / orow derived as the batched
+// admission derives them. Every index the kernels form is checked here first.
+void Engine::test_attention(int kind, int M, int nh, int cap, int window, int n_slots, int S, const float* qkv,
+                            float* kvh, const float* pre, const int* pre_len, int slot0, int rps, int p0,
+                            const int* pos, const int* tab, const int* ptab, int mpad, float* Qh, float* Oh) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(kind >= 0 && kind <= 2 && qkv && kvh && Oh && (kind != 0 || Qh), "test_attention: bad arguments");
+  PTTS_REQUIRE(M >= 1 && M <= 4096 && nh >= 1 && nh <= 16 && cap >= 1 && cap <= 65536 && window >= 0 &&
+                   n_slots >= 1 && n_slots <= 64 && S >= 0 && S <= 16,
+               "test_attention: bad shape");
+  PTTS_REQUIRE(kind == 0 || (!tab && !ptab), "test_attention: the table form belongs to kind 0");
+  PTTS_REQUIRE(kind != 1 || S == 0, "test_attention: the fused Mimi step takes dense rows");
+  PTTS_REQUIRE(kind != 2 || (S >= 1 && window == 0 && rps == 1), "test_attention: the step takes slabs, one row per slot");
+  PTTS_REQUIRE(!pre || (pre_len && kind != 1 && window == 0), "test_attention: a prefix needs the causal FlowLM kinds");
+  PTTS_REQUIRE(!ptab || tab, "test_attention: ptab needs the token table");
+  const bool pow2 = (cap & (cap - 1)) == 0;
+  const bool ring = pow2 && window > 0 && !pre && kind != 2;  // positions may wrap
+  auto group_ok = [](const int* t, int n0, int n1, int cap_, int slots_) {  // one 16-row group of a table
+    int nv = 0;
+    while (n0 + nv < n1 && t[n0 + nv] >= 0) ++nv;
+    for (int i = n0 + nv; i < n1; ++i)
+      if (t[i] != -1) return false;  // a slot's rows come first, padding after them
+    for (int i = 0; i < nv; ++i) {
+      const int v = t[n0 + i], sl = v >> 16, ps = v & 0xFFFF;
+      if (sl >= slots_ || ps >= cap_ || v != t[n0] + i) return false;  // one slot, consecutive positions
+    }
+    return true;
+  };
+  int Mq = M;  // rows of Q and of the attention launch
+  std::vector<int> qrow, orow;
+  if (tab) {
+    if (ptab) {
+      PTTS_REQUIRE(mpad >= M && mpad <= 4096 && mpad % 16 == 0, "test_attention: bad padded row count");
+      orow.assign(mpad, -1);
+      int tc = 0;
+      for (int r = 0; r < mpad; ++r) {
+        if (ptab[r] < 0) continue;
+        PTTS_REQUIRE(tc < M && tab[tc] == ptab[r], "test_attention: ptab's rows are not the tokens of tab");
+        orow[r] = tc;
+        qrow.push_back(r);
+        ++tc;
+      }
+      PTTS_REQUIRE(tc == M, "test_attention: ptab's rows are not the tokens of tab");
+      Mq = mpad;
+    }
+    const int* t = ptab ? ptab : tab;
+    for (int r0 = 0; r0 < Mq; r0 += 16)
+      PTTS_REQUIRE(group_ok(t, r0, std::min(r0 + 16, Mq), cap, n_slots), "test_attention: bad row table");
+  } else {
+    PTTS_REQUIRE(rps >= 1 && slot0 >= 0 && p0 >= 0 && slot0 + (M - 1) / rps < n_slots, "test_attention: bad row map");
+    PTTS_REQUIRE(kind == 2 || rps % 16 == 0 || rps >= M, "test_attention: a 16-row group would straddle slots");
+    for (int sl = slot0; sl <= slot0 + (M - 1) / rps; ++sl) {
+      const int base = pos ? pos[sl] : p0, n = std::min(rps, M - (sl - slot0) * rps);
+      PTTS_REQUIRE(base >= 0 && base < (1 << 30), "test_attention: bad position");
+      if (kind == 2) {
+        PTTS_REQUIRE(base <= cap, "test_attention: step position past the cache");
+      } else if (ring) {  // (kind 1: attention16_qkv's own check, cap >= window + 16, is left to throw)
+        PTTS_REQUIRE(kind == 1 || window + n - 1 <= cap, "test_attention: the pass would evict keys inside the window");
+      } else {
+        PTTS_REQUIRE(base + n <= cap, "test_attention: positions past the cache");
+      }
+    }
+  }
+  size_t pre_floats = 0;
+  std::vector<size_t> pre_off(n_slots, 0);
+  if (pre)
+    for (int sl = 0; sl < n_slots; ++sl) {
+      PTTS_REQUIRE(pre_len[sl] >= 0 && pre_len[sl] <= cap, "test_attention: bad prefix length");
+      pre_off[sl] = pre_floats;
+      pre_floats += (size_t)2 * nh * pre_len[sl] * 64;
+    }
+  sync();
+  const int d = nh * 64;
+  const size_t n_qkv = (size_t)std::max(S, 1) * M * 3 * d, n_kv = (size_t)n_slots * 2 * nh * cap * 64;
+  std::vector<void*> allocs;
+  std::vector<const float*> prep(n_slots, nullptr);
+  auto dalloc = [&](size_t bytes) {
+    void* p = nullptr;
+    PTTS_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    allocs.push_back(p);
+    return p;
+  };
+  auto release = [&]() {
+    for (void* p : allocs) (void)hipFree(p);
+  };
+  try {
+    auto up = [&](const void* src, size_t bytes) {
+      void* p = dalloc(bytes);
+      PTTS_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream_));
+      return p;
+    };
+    const float* dqkv = (const float*)up(qkv, sizeof(float) * n_qkv);
+    float* dkv = (float*)up(kvh, sizeof(float) * n_kv);
+    float* dq = (float*)dalloc(sizeof(float) * Mq * d);
+    float* dout = (float*)dalloc(sizeof(float) * M * d);
+    PTTS_HIP(hipMemsetAsync(dq, 0, sizeof(float) * Mq * d, stream_));
+    PTTS_HIP(hipMemsetAsync(dout, 0, sizeof(float) * M * d, stream_));
+    RowMap map{slot0, rps, p0, nullptr};
+    if (tab) {
+      map = RowMap{0, 1, 0, nullptr, (const int*)up(tab, sizeof(int) * M)};
+      if (ptab) {
+        map.ptab = (const int*)up(ptab, sizeof(int) * mpad);
+        map.mpad = mpad;
+        map.qrow = (const int*)up(qrow.data(), sizeof(int) * M);
+        map.orow = (const int*)up(orow.data(), sizeof(int) * mpad);
+      }
+    } else if (pos) {
+      map.pos_arr = (const int*)up(pos, sizeof(int) * n_slots);
+    }
+    KvStore kv{dkv, (long)2 * nh * cap * 64, cap};
+    if (pre) {
+      const float* dpre = (const float*)up(pre, sizeof(float) * pre_floats);
+      for (int sl = 0; sl < n_slots; ++sl) prep[sl] = dpre + pre_off[sl];
+      kv.pre = (const float* const*)up(prep.data(), sizeof(float*) * n_slots);
+      kv.pre_len = (const int*)up(pre_len, sizeof(int) * n_slots);
+      kv.layer = 0;
+    }
+    if (kind == 0) {
+      qkv_rope_append(S > 0 ? dqkv : nullptr, S, S > 0 ? nullptr : dqkv, M, nh, map, kv, dq, stream_);
+      RowMap am = map;  // as flow_layers: the attention runs on the padded 16-row groups
+      if (map.ptab) am.tab = map.ptab;
+      attention(dq, Mq, nh, am, kv, window, 16, dout, stream_);
+    } else if (kind == 1) {
+      attention16_qkv(dqkv, M, nh, map, kv, window, dout, stream_);
+    } else {
+      float* drope = (float*)dalloc(sizeof(float) * cap * 64);
+      rope_table(drope, cap, stream_);
+      attention_step_qkv(dqkv, S, M, nh, map, kv, drope, dout, stream_);
+    }
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(kvh, dkv, sizeof(float) * n_kv, hipMemcpyDeviceToHost, stream_));
+    if (kind == 0) PTTS_HIP(hipMemcpyAsync(Qh, dq, sizeof(float) * Mq * d, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipMemcpyAsync(Oh, dout, sizeof(float) * M * d, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
+}
+
 double Engine::time_op(int B, const std::string& name, int reps) {
   xh_dirty_ = true;  // replays write x_ / h_
   PTTS_REQUIRE(ready_, "engine weights not finalized");

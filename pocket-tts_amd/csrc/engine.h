@@ -140,6 +140,10 @@ class Engine {
   double time_op(int B, const std::string& name, int reps);
   // GEMM-core test hook (ptts_test_gemm): Y = X W^T on tile `layout` (host buffers)
   void test_gemm(int layout, int M, int N, int K, int splits, int tail_S, const float* X, const float* Wt, float* Y);
+  // Attention-path test hook (ptts_test_attention): the product launchers on host operands
+  void test_attention(int kind, int M, int nh, int cap, int window, int n_slots, int S, const float* qkv, float* kvh,
+                      const float* pre, const int* pre_len, int slot0, int rps, int p0, const int* pos, const int* tab,
+                      const int* ptab, int mpad, float* Qh, float* Oh);
   void overlap_probe(int B, int reps, double* us);
   std::vector<std::string> plan_names(int B);
   int int8_matrices() const { return (int)q8map_.size(); }

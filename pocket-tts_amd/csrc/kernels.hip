@@ -3039,7 +3039,11 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode_qkv(const float* __rest
     const float2 cssn = *reinterpret_cast<const float2*>(rope + (long)qp * 64 + 2 * i);  // table of rope_table()
     const float cs = cssn.x, sn = cssn.y;
     const float x0 = s_qkv[part][2 * i], x1 = s_qkv[part][2 * i + 1];
-    const float y0 = x0 * cs - x1 * sn, y1 = x0 * sn + x1 * cs;  // one wave: all reads precede the writes
+    // Spelled as the fused form k_qkv_rope compiles to (one product rounded, the other fused), so
+    // that a key rotates to the same bits whichever kernel appends it; left to the compiler, y1 fused
+    // the other product here and odd dims came out an ulp apart (tests/test_gpu_attention_core.py).
+    // One wave: all reads precede the writes.
+    const float y0 = fmaf(x0, cs, -(x1 * sn)), y1 = fmaf(x1, cs, x0 * sn);
     s_qkv[part][2 * i] = y0;
     s_qkv[part][2 * i + 1] = y1;
     if (part == 1 && append) {

@@ -198,6 +198,53 @@ class Engine:
         check(lib().ptts_test_gemm(self.handle, layout, m, n, k, splits, tail_slices, fptr(x), fptr(w), fptr(y)))
         return y
 
+    def test_attention(self, kind: int, qkv: np.ndarray, kv: np.ndarray, window: int = 0, *, slot0: int = 0,
+                       rps: int = 16, p0: int = 0, pos=None, tab=None, ptab=None, pre=None):
+        """Attention-path test hook (ptts_test_attention). kind 0: qkv_rope_append + attention(qg = 16),
+        1: the fused Mimi step attention16_qkv, 2: attention_step_qkv. qkv [m][3 nh 64] dense rows or
+        [S][m][3 nh 64] partial slabs; kv [slots][2][nh][cap][64], the store before the call; rows map
+        to (slot, position) by slot0 / rps / p0 / pos [slots] or by the table tab (with ptab: the
+        compact form, tab the tokens and ptab the padded 16-row groups); pre: one [2][nh][F][64]
+        prefix (or None) per slot. Returns (o, kv_after, q): q the rotated queries for kind 0, else
+        None."""
+        qkv = np.ascontiguousarray(qkv, np.float32)
+        kv_out = np.array(kv, np.float32, order="C")  # a copy: the call writes it
+        slots, two, nh, cap, hd = kv_out.shape
+        splits, m = (qkv.shape[0], qkv.shape[1]) if qkv.ndim == 3 else (0, qkv.shape[0])
+        if two != 2 or hd != 64 or qkv.shape[-1] != 3 * nh * 64:
+            raise ValueError("test_attention: qkv / kv shapes disagree")
+
+        def iarr(a, n):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.int32)
+            if a.shape != (n,):
+                raise ValueError(f"test_attention: expected {n} ints, got shape {a.shape}")
+            return a
+
+        def iptr(a):
+            return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+        pos, tab = iarr(pos, slots), iarr(tab, m)
+        mpad = 0 if ptab is None else len(ptab)
+        ptab = iarr(ptab, mpad)
+        pre_cat = pre_len = None
+        if pre is not None:
+            if len(pre) != slots:
+                raise ValueError("test_attention: one prefix (or None) per slot")
+            parts = [np.zeros((2, nh, 0, 64), np.float32) if p is None else np.ascontiguousarray(p, np.float32)
+                     for p in pre]
+            if any(p.ndim != 4 or p.shape[:2] != (2, nh) or p.shape[3] != 64 for p in parts):
+                raise ValueError("test_attention: a prefix is [2][nh][F][64]")
+            pre_len = np.array([p.shape[2] for p in parts], np.int32)
+            pre_cat = np.concatenate([p.ravel() for p in parts] + [np.zeros(4, np.float32)])
+        q = np.zeros((mpad if ptab is not None else m, nh * 64), np.float32) if kind == 0 else None
+        o = np.zeros((m, nh * 64), np.float32)
+        check(lib().ptts_test_attention(self.handle, kind, m, nh, cap, window, slots, splits, fptr(qkv), fptr(kv_out),
+                                        fptr(pre_cat), iptr(pre_len), slot0, rps, p0, iptr(pos), iptr(tab), iptr(ptab),
+                                        mpad, fptr(q), fptr(o)))
+        return o, kv_out, q
+
     def lsd_steps(self) -> tuple[int, int]:
         """(cap, last_run): the cap on the per-utterance Euler step counts, and the steps the most
         recent step call ran: the largest count among its rows still open (ptts_lsd_steps)."""
