@@ -16,15 +16,22 @@ extern "C" {
 #endif
 
 /* Test hook of the GEMM core (no reference counterpart): y = x w^T for x [m][k], w [n][k] (host
- * buffers, k % 32 == 0) on the engine's device, with the tile of kernel layout `layout`
- * (kernels.hip gemm_launch: the f32 tiles, and + 100 for their bf16-operand twins); splits > 1
- * writes the [splits][m][n] split-K partial slabs to y, tail_slices > 0 takes the split-tail path
- * (layouts 34 / 35). The tests run every shipped layout on shapes the model never runs. */
+ * buffers) on the engine's device, with the tile of id `layout` (the table PTTS_TILES of
+ * csrc/kernels.h: the f32 tiles, + 100 for their bf16-operand twins, + 200 for the bf16x6 ones);
+ * splits > 1 writes the [splits][m][n] split-K partial slabs to y, tail_slices > 0 takes the
+ * split-tail path. PTTS_ERR_INVALID, with a message, for a tile id that is not in this build,
+ * tail_slices > 0 on a tile without the split tail, and a k that is not a multiple of the tile's
+ * BK (ptts_gemm_tiles lists all three per tile). The tests run every shipped tile on shapes the
+ * model never runs. */
 int ptts_test_gemm(ptts_engine* e, int layout, int m, int n, int k, int splits, int tail_slices, const float* x,
                    const float* w, float* y);
+/* The GEMM tiles of this build, one line per tile: "id<TAB>tm<TAB>tn<TAB>bk<TAB>operands<TAB>tail"
+ * (tile M x N, K chunk, operands f32 | bf16 | bf16x6, tail 1 where tail_slices > 0 is served).
+ * Needs no engine and no GPU. */
+int ptts_gemm_tiles(char* buf, int buflen);
 /* Test hook of the attention path (no reference counterpart): the product launchers, unchanged, on
  * host operands, so the tests can compare RoPE, the KV append and the softmax with fp64 on operands
- * the model never produces. kind PTTS_ATTN_PREFILL: qkv_rope_append + attention(qg = 16) (FlowLM
+ * the model never produces. kind PTTS_ATTN_PREFILL: qkv_rope_append + attention (FlowLM
  * prefill, Mimi multi-frame pass); PTTS_ATTN_MIMI_STEP: attention16_qkv (RoPE and ring append fused,
  * 16 rows per slot; cap < window + 16 is refused as in the product); PTTS_ATTN_FLOW_STEP:
  * attention_step_qkv with the engine's rope_table (one row per slot, window 0).

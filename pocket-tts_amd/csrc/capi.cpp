@@ -485,6 +485,19 @@ int ptts_plan_ops(ptts_engine* e, int n_rows, char* buf, int buflen) {
   });
 }
 
+int ptts_gemm_tiles(char* buf, int buflen) {
+  return guard([&] {
+    static const char* const ops[] = {"f32", "bf16", "bf16x6"};
+    std::string s;
+    for (const ptts::TileInfo& t : ptts::TILES)
+      if (ptts::tile_info(t.id))
+        s += std::to_string(t.id) + "\t" + std::to_string(t.tm()) + "\t" + std::to_string(t.tn()) + "\t" +
+             std::to_string(t.bk) + "\t" + ops[t.ops] + "\t" + (t.split_tail() ? "1" : "0") + "\n";
+    if (!buf || buflen <= (int)s.size()) throw ptts::Error(PTTS_ERR_INVALID, "buffer too small");
+    memcpy(buf, s.c_str(), s.size() + 1);
+  });
+}
+
 const char* ptts_last_error(void) { return g_err.c_str(); }
 
 }  // extern "C"

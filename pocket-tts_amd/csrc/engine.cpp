@@ -59,10 +59,11 @@ static void tile_override(const std::string& name, int& layout, int& ksplit) {
   }
 }
 
-// layouts served by k_gemm_glds (kernels.hip gemm_launch): the only ones that split a conv's K
-static bool lds_dma_layout(int layout) {
-  return (layout >= 6 && layout <= 8) || (layout >= 11 && layout <= 16) || (layout >= 21 && layout <= 27) ||
-         (layout >= 30 && layout <= 42) || (layout >= 130 && layout <= 139) || (layout >= 230 && layout <= 239);
+// The row of a tile id in this build's table (kernels.h PTTS_TILES)
+static const TileInfo& tile_of(int layout) {
+  const TileInfo* t = tile_info(layout);
+  if (!t) throw Error(PTTS_ERR_INVALID, "gemm: tile layout " + std::to_string(layout) + " is not in this build");
+  return *t;
 }
 
 float* Engine::dalloc(size_t n) {
@@ -561,9 +562,9 @@ void Engine::derive_split() {
   PTTS_HIP(hipStreamSynchronize(stream_));
 }
 
-// A bf16x6 tile (layout >= 200) reads the split copy of its weight matrix (derive_split)
+// A bf16x6 tile reads the split copy of its weight matrix (derive_split)
 void Engine::attach_split(GemmArgs& a) const {
-  if (a.layout < 200) return;
+  if (!tile_of(a.layout).split_weights()) return;
   auto it = split_.find(a.W);
   PTTS_REQUIRE(it != split_.end(), "bf16x6 tile without a split weight copy");
   a.Whm = it->second.first;
@@ -704,24 +705,24 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
   PTTS_REQUIRE(K % 32 == 0, "GEMM K must be a multiple of 32");
   const FlowBufs& fb = fbp ? *fbp : fbm_;  // the slabs and the tail scratch the launch writes
   int S = pick_splits(M, N, K);
-  int layout = 0, tail = 0;
+  int layout = TILE_KSPLIT_4W, tail = 0;
   // wide skinny GEMMs (FlowLM qkv/ff1, flow-head adaLN): 32x128 LDS-DMA tiles, 8-way split-K
   // (tools/gemm_bench.hip on MI355X: qkv 6.7 -> 6.3 us, ff1 7.9 -> 6.5 us, ada 10.1 -> 8.7 us)
   if (M <= 64 && N >= 3072) {
-    layout = 7;  // 2-buffer LDS (40 KB) co-resides with the back part
+    layout = TILE_GLDS_32x128;  // 2-buffer LDS (40 KB) co-resides with the back part
     S = std::max(1, std::min(8, K / 64));
   } else if (M >= 256) {  // prefill passes (text admission, M = 48 rows per slot): MFMA-bound,
     // LDS-DMA tiles with the DMAs interleaved between the MFMAs and a split tail (the tiles past
     // whole rounds of the CUs' workgroup slots run as K slices; tools/mm_bench.hip at M = 1536,
     // against rocBLAS fp32 on the same box: qkv 108 / 111, out 88 / 98, ff1 112 / 125, ff2 117 /
     // 122 TF/s): 128x64, two per CU, 4 slices; linear1 128x64 one per CU, 2 slices
-    layout = N >= 4096 && K <= 1024 ? 34 : 35;
+    layout = N >= 4096 && K <= 1024 ? TILE_ILV_128x64 : TILE_ILV_128x64_2CU;
     tail = N >= 4096 && K <= 1024 ? 2 : 4;
     S = 1;
   } else if (M <= 64 && K >= 4096) {  // FlowLM ff2: 8 slabs (tools/gemm_bench.hip flow.ff2: 8.5 -> 7.3 us)
     S = 8;
   } else if (M <= 64 && N <= 512 && K == 512) {  // flow-head MLPs: 8 waves, 8 slabs (head.mlp: 3.9 -> 3.4 us)
-    layout = 9;
+    layout = TILE_KSPLIT_8W;
     S = 8;
   }
   // quantized FlowLM weights on the step path: stream int8 codes (k_gemm_w8, 32x64 tiles, the
@@ -747,7 +748,7 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
   auto f8 = f8map_.find(Wt);
   const bool wf8 = f8 != f8map_.end() && M <= 64;
   if (wf8) {  // fp8 W8A8 (k_gemm_fp8): 32x64 tiles, >= 256 workgroups, K slice <= FP8_KSLICE_MAX
-    layout = 0;
+    layout = TILE_KSPLIT_4W;
     const int tiles = ((N + 63) / 64) * ((M + 31) / 32), nch = K / 32;
     S = 1;
     while (S < 16 && tiles * S < 256 && nch / (2 * S) >= 4) S *= 2;
@@ -756,7 +757,7 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
   auto q8 = q8map_.find(Wt);
   const bool w8 = q8 != q8map_.end() && M <= 64 && (long)N * K >= (2L << 20);
   if (w8) {
-    layout = 0;
+    layout = TILE_KSPLIT_4W;
     const int tiles = ((N + 63) / 64) * ((M + 31) / 32);
     S = 1;
     while (S < 16 && tiles * S < 256 && (K / 32) / (2 * S) >= 4) S *= 2;
@@ -764,7 +765,7 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
   if (!w8 && !wf8) tile_override(name, layout, S);
   while (S > 1 && (size_t)S * M * N > fb.pcap) --S;
   PTTS_REQUIRE((size_t)S * M * N <= fb.pcap, "split-K partial buffer too small");
-  GemmArgs a{};
+  GemmArgs a = dense_gemm(layout, M, N, K, X, ldx, Wt);
   if (w8) {
     a.Wq = q8->second.first;
     a.wscale = q8->second.second;
@@ -774,15 +775,6 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
     a.Wf8 = f8->second.first;
     a.wscale = f8->second.second;
   }
-  a.mode = 0;
-  a.layout = layout;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.Nw = (N + 31) / 32 * 32;
-  a.X = X;
-  a.ldx = ldx;
-  a.W = Wt;
   a.S = S;
   a.partial = fb.partial;
   if (tail > 0 && S == 1 && !w8 && !wf8) {
@@ -793,8 +785,8 @@ void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const f
     a.tickets_cap = TICKETS;
   }
   // FlowLM / flow-head step weights are read once per step: non-temporal loads on the LDS-DMA
-  // tiles (step -1.1 %; the 32x32 register tile keeps default-policy loads)
-  a.w_nt = M <= 64 && layout != 0;
+  // tiles (step -1.1 %; the 4-wave 32x32 register tile keeps default-policy loads)
+  a.w_nt = M <= 64 && layout != TILE_KSPLIT_4W;
   a.front = 1;  // FlowLM / flow-head GEMMs (and the prefill passes, on the same stream)
   ops.push_back({name, [a, S](hipStream_t s) { gemm(a, S, s); }, 2.0 * M * N * K,
                  (w8 || wf8 ? (double)N * K + 4.0 * N : 4.0 * N * K) + 4.0 * ((double)M * K + (double)S * M * N)});
@@ -829,20 +821,10 @@ void Engine::push_rr(std::vector<Op>& ops, const std::string& name, const RowRed
 
 void Engine::dense_op(std::vector<Op>& ops, const std::string& name, const float* X, int M, const float* Wt, int N,
                       int K, const float* bias, int act, const float* rscale, const float* R, float* Y, int layout) {
-  PTTS_REQUIRE(K % 32 == 0, "GEMM K must be a multiple of 32");
   int ks = 1;
   tile_override(name, layout, ks);
-  PTTS_REQUIRE(!(layout == 8 || layout == 15 || layout == 16) || K % 64 == 0, "BK 64 tiles need K % 64 == 0");
-  GemmArgs a{};
-  a.mode = 0;
-  a.layout = layout;
-  a.M = M;
-  a.N = N;
-  a.K = K;
-  a.Nw = (N + 31) / 32 * 32;
-  a.X = X;
-  a.ldx = K;
-  a.W = Wt;
+  PTTS_REQUIRE(K % tile_of(layout).bk == 0, "GEMM K must be a multiple of the tile's BK");
+  GemmArgs a = dense_gemm(layout, M, N, K, X, K, Wt);
   a.S = 1;
   a.bias = bias;
   a.act = act;
@@ -860,12 +842,12 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
                      const float* H, int P, int stride, int elu, const float* Wt, int cout, int ktaps, int phases,
                      const float* bias, const float* R, float* Y, int T_out, int tstride, int layout, int elu_out,
                      float* Y2, int ksplit) {
-  PTTS_REQUIRE(cin % 32 == 0, "conv cin must be a multiple of 32");
   tile_override(name, layout, ksplit);
-  PTTS_REQUIRE(!(layout == 8 || layout == 15 || layout == 16) || cin % 64 == 0, "BK 64 tiles need cin % 64 == 0");
+  const TileInfo& tile = tile_of(layout);
+  PTTS_REQUIRE(cin % tile.bk == 0, "conv cin must be a multiple of the tile's BK");
   // ksplit > 1: single-phase conv on an LDS-DMA tile, K split into ksplit partial slabs in the
   // back part's slab buffer; the caller adds the row-reduce epilogue
-  PTTS_REQUIRE(ksplit == 1 || (phases == 1 && lds_dma_layout(layout)), "K-split convs need a single-phase LDS-DMA tile");
+  PTTS_REQUIRE(ksplit == 1 || (phases == 1 && tile.lds_dma()), "K-split convs need a single-phase LDS-DMA tile");
   GemmArgs a{};
   a.mode = 1;
   a.layout = layout;
@@ -909,14 +891,14 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
 
 // FlowLM transformer layers over M rows (x_ holds the residual stream, h_ = norm1_0(x_)).
 // StreamingTransformerLayer::forward (transformer.rs:66-90).
-void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag,
+void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
                          const FlowBufs* fbp) {
   // the engine's own buffers (step and admission graphs), or a voice job's: the names below shadow
   // the members on purpose, so every access in this function goes through the struct
   const FlowBufs& fb = fbp ? *fbp : fbm_;
   float *const x_ = fb.x, *const h_ = fb.h, *const q_ = fb.q, *const o_ = fb.o, *const u_ = fb.u,
                *const partial_ = fb.partial;
-  PTTS_REQUIRE(!fbp || qg != 1, "step passes run on the engine's own buffers");
+  PTTS_REQUIRE(!fbp || !step, "step passes run on the engine's own buffers");
   for (int l = 0; l < NL; ++l) {
     const Layout::TL& t = L_.fl[l];
     const std::string p = tag + ".l" + std::to_string(l);
@@ -929,7 +911,7 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
     }
     int S = 1;
     linear_split(ops, p + ".qkv_gemm", h_, D, M, W(t.in_proj), 3 * D, D, &S, fbp);
-    if (qg == 1) {  // step: slab sum + RoPE + KV append fused into the attention kernel
+    if (step) {  // step: slab sum + RoPE + KV append fused into the attention kernel
       const float* P = partial_;
       float* O = o_;
       const float* rope = rope_;
@@ -956,7 +938,7 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
         am.tab = map.ptab;
         Ma = map.mpad;
       }
-      ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, Ma, NH, am, kv, 0, qg, O, s); }});
+      ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, Ma, NH, am, kv, 0, O, s); }});
     }
     auto rr = [&](const std::string& name, int S2, int N, int act, bool resid, float* Y, const float* lnw,
                   const float* lnb, bool ln, float* Hout, float* Hfrag = nullptr) {
@@ -984,7 +966,7 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool o
     linear_split(ops, p + ".out_gemm", o_, D, M, W(t.out_proj), D, D, &S, fbp);
     // step passes with the whole-K linear1 (gemv_fk): the out reduce also stores norm2's output in
     // its A-fragment order, and linear1 applies GELU in its own epilogue (no slabs, no reduce)
-    auto fk = qg == 1 && gemv_fk_supported(M, FF, D) ? fkmap_.find(W(t.l1)) : fkmap_.end();
+    auto fk = step && gemv_fk_supported(M, FF, D) ? fkmap_.find(W(t.l1)) : fkmap_.end();
     const bool use_fk = fk != fkmap_.end() && hfrag_;
     rr(p + ".out_reduce_ln2", S, D, ACT_NONE, true, x_, W(t.n2w), W(t.n2b), true, h_, use_fk ? hfrag_ : nullptr);
     auto ffn = use_fk && ffn_hand_ ? ffnmap_.find(W(t.l2)) : ffnmap_.end();
@@ -1045,7 +1027,7 @@ void Engine::prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const F
     ops.push_back({"prefill.ln1", [=](hipStream_t s) { layernorm(x, D, h, D, T, D, w, b, 1e-5f, s); }});
   }
   RowMap map{slot, T, p0, nullptr};
-  flow_layers(ops, T, map, 16, false, "prefill", fbp);
+  flow_layers(ops, T, map, false, false, "prefill", fbp);
 }
 
 // The persistent flow-head launch needs <= 128 rows and ResBlock tensors at one uniform stride
@@ -1075,7 +1057,7 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
   // ---- FlowLM step (flow_lm.rs:98-164): input_linear -> transformer -> out_norm. The input
   // projection + norm1 of layer 0 (x_, h_) were computed by the previous step's front_commit, or
   // by refresh_xh() after anything else wrote x_, h_ or lat_in_.
-  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, 1, true, "flow");
+  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow");
   // ---- flow head (mlp.rs:215-383): cond_embed | out_eos, EOS bookkeeping, noise
   linear_split(ops, "head.cond_eos_gemm", h_, D, B, W(L_.cond_eos_w), NCOND, D, &S);
   PTTS_REQUIRE(S <= FLOW_COND_MAX_SLABS, "head.flow_cond sums at most 16 split-K slabs");
@@ -1268,12 +1250,12 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
 }
 
 // Tiles of the back part's GEMMs and convs at B >= 16 (the MFMA-bound shapes), one row per launch:
-// LDS-DMA tile layout (kernels.hip gemm_launch) and split-K slices. Chosen from tools/mm_bench.hip
+// tile id (kernels.h PTTS_TILES) and split-K slices. Chosen from tools/mm_bench.hip
 // (each launch alone on the chip, B = 32) and A/B runs of the pipelined step, where the back part
 // shares every CU with the latency-bound front part. Pipelined split-K at most 2
 // since round 5 (the front part bounds the step, and 4 slices' slab traffic slowed it: 0.549 ->
 // 0.530 ms, profiles/r05/back_splits_ab.txt). Below B = 16 every GEMM runs on the 32x32 register
-// tile (layout 0) with the split-K noted at the launch.
+// tile (TILE_KSPLIT_4W) with the split-K noted at the launch.
 struct BackTile {
   int layout, splits;
 };
@@ -1282,25 +1264,36 @@ static BackTile back_tile(const std::string& op, bool pipeline) {
     const char* op;
     BackTile seq, pipe;
   } table[] = {
-      {"mimi.qkv", {32, 1}, {32, 1}},
-      {"mimi.out", {32, 4}, {32, 2}},
-      {"mimi.ff1", {32, 1}, {32, 1}},
-      {"mimi.ff2", {32, 4}, {32, 2}},
-      {"seanet.conv0", {32, 4}, {32, 2}},
-      {"seanet.up0.convtr", {32, 4}, {32, 2}},
-      {"seanet.up1.convtr", {32, 1}, {32, 1}},
-      {"seanet.up2.convtr", {32, 1}, {32, 1}},
+      {"mimi.qkv", {TILE_ILV_64x64_2CU, 1}, {TILE_ILV_64x64_2CU, 1}},
+      {"mimi.out", {TILE_ILV_64x64_2CU, 4}, {TILE_ILV_64x64_2CU, 2}},
+      {"mimi.ff1", {TILE_ILV_64x64_2CU, 1}, {TILE_ILV_64x64_2CU, 1}},
+      {"mimi.ff2", {TILE_ILV_64x64_2CU, 4}, {TILE_ILV_64x64_2CU, 2}},
+      {"seanet.conv0", {TILE_ILV_64x64_2CU, 4}, {TILE_ILV_64x64_2CU, 2}},
+      {"seanet.up0.convtr", {TILE_ILV_64x64_2CU, 4}, {TILE_ILV_64x64_2CU, 2}},
+      {"seanet.up1.convtr", {TILE_ILV_64x64_2CU, 1}, {TILE_ILV_64x64_2CU, 1}},
+      {"seanet.up2.convtr", {TILE_ILV_64x64_2CU, 1}, {TILE_ILV_64x64_2CU, 1}},
       // the stage-0/1 residual convs when not fused (see resblock_fused)
-      {"seanet.up0.res_conv3", {18, 1}, {18, 1}},
-      {"seanet.up1.res_conv3", {20, 1}, {20, 1}},
-      {"seanet.up0.res_conv1", {6, 1}, {6, 1}},
-      {"seanet.up1.res_conv1", {6, 1}, {6, 1}},
-      {"seanet.up2.res_conv3", {14, 1}, {14, 1}},
-      {"seanet.up2.res_conv1", {6, 1}, {23, 1}},
+      {"seanet.up0.res_conv3", {TILE_RB_32x64, 1}, {TILE_RB_32x64, 1}},
+      {"seanet.up1.res_conv3", {TILE_RB_64x64, 1}, {TILE_RB_64x64, 1}},
+      {"seanet.up0.res_conv1", {TILE_GLDS_64x64, 1}, {TILE_GLDS_64x64, 1}},
+      {"seanet.up1.res_conv1", {TILE_GLDS_64x64, 1}, {TILE_GLDS_64x64, 1}},
+      {"seanet.up2.res_conv3", {TILE_GLDS_128x32, 1}, {TILE_GLDS_128x32, 1}},
+      {"seanet.up2.res_conv1", {TILE_GLDS_64x64, 1}, {TILE_GLDS_RB_128x64, 1}},
   };
   for (const auto& t : table)
     if (op == t.op) return pipeline ? t.pipe : t.seq;
   throw Error(PTTS_ERR_INVALID, "no tile for " + op);
+}
+// The back part's tile under back_mfma bf16 / bf16x6: the operand twin of the ILV tile the f32 table
+// names. Policy, not existence: bf16 keeps 128 x 64 and 128 x 128 (2 per CU), bf16x6 only 128 x 64;
+// every other tile of the f32 table (register-blocked, non-ILV) maps to the 64 x 64 twin.
+static int back_twin(int layout, int back_mfma) {
+  if (back_mfma == PTTS_BACK_BF16)
+    return TILE_TWIN_BF16 +
+           (layout == TILE_ILV_128x64_2CU || layout == TILE_ILV_128x128_2CU ? layout : TILE_ILV_64x64_2CU);
+  if (back_mfma == PTTS_BACK_F32X6)
+    return TILE_TWIN_BF16X6 + (layout == TILE_ILV_128x64_2CU ? layout : TILE_ILV_64x64_2CU);
+  return layout;
 }
 
 // BACK part of a step: Mimi decode of the frames the front part left in buffer `hb`; `qp` is the
@@ -1312,17 +1305,13 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   for (int f = 0; f < NFR_MAX; ++f) hbs[f] = (hb + std::min(f, nfr - 1)) % nhb_;
   const bool big = B >= 16;  // B * 16 >= 256 Mimi rows: the LDS-DMA tiles fill the chip
   auto tile = [&](const std::string& op, int small_splits) {
-    BackTile t = big ? back_tile(op, pipeline_) : BackTile{0, small_splits};
+    BackTile t = big ? back_tile(op, pipeline_) : BackTile{TILE_KSPLIT_4W, small_splits};
     // four-frame passes: SEANet conv0 and the stage-0 transposed conv have twice a pair pass's rows
     // (B * 64: 256 / 1,024 64 x 64 tiles at B = 32), enough to fill the chip unsplit, so neither
     // writes slabs nor needs its reduce launch (steady step 0.5179 -> 0.5137 ms,
     // profiles/r06/ab_quad_splits.txt; unsplit in pair passes: +2.7 %, profiles/r06/ab1.txt)
     if (big && nfr >= 4 && (op == "seanet.conv0" || op == "seanet.up0.convtr")) t.splits = 1;
-    // back_mfma bf16 / bf16x6: the bf16-operand / split-f32 twin of the ILV tile (kernels.hip
-    // PTTS_GLB: layout + 100, PTTS_GLX6: + 200); the register-blocked and non-ILV tiles of the f32
-    // table map to the 64 x 64 one
-    if (big && back_mfma_ == PTTS_BACK_BF16) t.layout = 100 + (t.layout == 35 || t.layout == 31 ? t.layout : 32);
-    if (big && back_mfma_ == PTTS_BACK_F32X6) t.layout = 200 + (t.layout == 35 ? t.layout : 32);
+    if (big) t.layout = back_twin(t.layout, back_mfma_);
     tile_override(op, t.layout, t.splits);  // probe builds only (tools/back_tune.py)
     return t;
   };
@@ -1350,16 +1339,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   auto split_gemm = [&](const std::string& name, const float* X, int M, const float* Wt, int N, int K, BackTile t) {
     PTTS_REQUIRE(t.splits >= 1 && t.splits <= 16, name + ": split-K 1..16");
     PTTS_REQUIRE((size_t)t.splits * M * N <= mpcap_, "back split-K slab buffer too small");
-    GemmArgs a{};
-    a.mode = 0;
-    a.layout = t.layout;
-    a.M = M;
-    a.N = N;
-    a.K = K;
-    a.Nw = (N + 31) / 32 * 32;
-    a.X = X;
-    a.ldx = K;
-    a.W = Wt;
+    GemmArgs a = dense_gemm(t.layout, M, N, K, X, K, Wt);
     a.S = t.splits;
     a.partial = mpartial_;
     attach_split(a);
@@ -1390,7 +1370,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
         float* Q = mq_;
         ops.push_back({p + ".qkv_rope", [=](hipStream_t s) { qkv_rope_append(nullptr, 0, qkv, MR, MNH, mmap, kv, Q, s); },
                        0.0, 4.0 * MR * (3.0 * MD + 3.0 * MD)});
-        ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, MR, MNH, mmap, kv, MCTX, 16, O, s); },
+        ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, MR, MNH, mmap, kv, MCTX, O, s); },
                        (double)B * nfr * 65536.0 * Wn,
                        (double)B * nfr * (4.0 * 2 * MNH * 64 * Wn + 4.0 * UP * (MD + MD))});
       }
@@ -1463,7 +1443,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     } else {
     const int s_c0 = std::max(tc.splits, 2);
     conv_op(ops, "seanet.conv0", mx_, B, 16 * nfr, 512, hist_[0], 6, 1, 0, W(L_.dc0_w), 512, 7, 1, nullptr, nullptr,
-            nullptr, 16 * nfr, 1, big ? tc.layout : 6, 0, nullptr, s_c0);
+            nullptr, 16 * nfr, 1, big ? tc.layout : TILE_GLDS_64x64, 0, nullptr, s_c0);
     RowReduceArgs r{};
     r.P = mpartial_;
     r.S = s_c0;
@@ -1548,7 +1528,8 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
       }
       ops.push_back({p + ".resblock", [rb](hipStream_t s) { resblock(rb, s); }, fl, by});
     } else {  // the two convs (few rows: 32x32 tiles, more workgroups than the fused tiles)
-      const int lr3 = big ? tile(p + ".res_conv3", 1).layout : 0, lr1 = big ? tile(p + ".res_conv1", 1).layout : 0;
+      const int lr3 = big ? tile(p + ".res_conv3", 1).layout : TILE_KSPLIT_4W,
+                lr1 = big ? tile(p + ".res_conv1", 1).layout : TILE_KSPLIT_4W;
       conv_op(ops, p + ".res_conv3", ce_[i], B, T, ch, hist_[2 + 2 * i], 2, 1, 0, W(L_.dra_w[i]), ch / 2, 3, 1,
               W(L_.dra_b[i]), nullptr, cv_[i], T, 1, lr3, 1);
       conv_op(ops, p + ".res_conv1", cv_[i], B, T, ch / 2, nullptr, 0, 1, 0, W(L_.drb_w[i]), ch, 1, 1,
@@ -2032,25 +2013,28 @@ bool Engine::fetch_ready(int calls_back) {
   return true;
 }
 
-// GEMM-core test hook: one dense GEMM (mode 0) on the given tile layout, split-K slabs (splits > 1:
-// Y receives the [splits][M][N] partial slabs) or the split tail (tail_S > 0, layouts 34 / 35),
-// from host operands; the tests compare it with an fp64 product (every shipped layout, shapes the
-// model never runs).
+// GEMM-core test hook: one dense GEMM (mode 0) on the given tile, split-K slabs (splits > 1:
+// Y receives the [splits][M][N] partial slabs) or the split tail (tail_S > 0, the tiles with
+// TileInfo::split_tail), from host operands; the tests compare it with an fp64 product (every
+// shipped tile, shapes the model never runs). A request the tile cannot serve is refused.
 void Engine::test_gemm(int layout, int M, int N, int K, int splits, int tail_S, const float* X, const float* Wt,
                        float* Y) {
   xh_dirty_ = true;
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(X && Wt && Y && M >= 1 && N >= 1 && K >= 32 && K % 32 == 0, "test_gemm: bad shape");
   PTTS_REQUIRE(splits >= 1 && splits <= 16 && (splits == 1 || tail_S == 0), "test_gemm: bad split");
+  const TileInfo& tile = tile_of(layout);
+  PTTS_REQUIRE(tail_S <= 0 || tile.split_tail(), "test_gemm: tile " + std::to_string(layout) + " has no split tail");
+  PTTS_REQUIRE(K % tile.bk == 0, "test_gemm: k must be a multiple of the tile's BK (" + std::to_string(tile.bk) + ")");
   sync();
   const int Nw = (N + 31) / 32 * 32;
   float *dx = nullptr, *dw = nullptr, *dy = nullptr;
-  unsigned* dhm = nullptr;  // bf16x6 layouts (>= 200): the split copy of W (split3)
+  unsigned* dhm = nullptr;  // bf16x6 tiles: the split copy of W (split3)
   unsigned short* dlo = nullptr;
   PTTS_HIP(hipMalloc(&dx, sizeof(float) * M * K));
   PTTS_HIP(hipMalloc(&dw, sizeof(float) * Nw * K));
   PTTS_HIP(hipMalloc(&dy, sizeof(float) * splits * M * N));
-  if (layout >= 200) {
+  if (tile.split_weights()) {
     PTTS_HIP(hipMalloc(&dhm, sizeof(unsigned) * Nw * K));
     PTTS_HIP(hipMalloc(&dlo, sizeof(unsigned short) * Nw * K));
   }
@@ -2064,16 +2048,7 @@ void Engine::test_gemm(int layout, int M, int N, int K, int splits, int tail_S, 
     PTTS_HIP(hipMemcpyAsync(dx, X, sizeof(float) * M * K, hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(dw, Wt, sizeof(float) * N * K, hipMemcpyHostToDevice, stream_));
     if (dhm) split3(dw, (long)Nw * K, dhm, dlo, stream_);
-    GemmArgs a{};
-    a.mode = 0;
-    a.layout = layout;
-    a.M = M;
-    a.N = N;
-    a.K = K;
-    a.Nw = Nw;
-    a.X = dx;
-    a.ldx = K;
-    a.W = dw;
+    GemmArgs a = dense_gemm(layout, M, N, K, dx, K, dw);
     a.Whm = dhm;
     a.Wlo = dlo;
     a.S = splits;
@@ -2104,7 +2079,7 @@ void Engine::test_gemm(int layout, int M, int N, int K, int splits, int tail_S, 
 
 // Attention-path test hook: the product launchers, unchanged, on host operands (the tests compare
 // with an fp64 softmax attention on operands the model never produces). kind 0: qkv_rope_append
-// (dense rows, S == 0, or S partial slabs) + attention(qg = 16); kind 1: attention16_qkv (the fused
+// (dense rows, S == 0, or S partial slabs) + attention; kind 1: attention16_qkv (the fused
 // Mimi step); kind 2: rope_table + attention_step_qkv. The KV store [n_slots][2][nh][cap][64] goes
 // in and comes back; pre (optional) holds each slot's shared prefix [2][nh][F][64], F =
 // pre_len[slot], back to back. Rows map to (slot, position) by the uniform RowMap {slot0, rps, p0,
@@ -2230,7 +2205,7 @@ void Engine::test_attention(int kind, int M, int nh, int cap, int window, int n_
       qkv_rope_append(S > 0 ? dqkv : nullptr, S, S > 0 ? nullptr : dqkv, M, nh, map, kv, dq, stream_);
       RowMap am = map;  // as flow_layers: the attention runs on the padded 16-row groups
       if (map.ptab) am.tab = map.ptab;
-      attention(dq, Mq, nh, am, kv, window, 16, dout, stream_);
+      attention(dq, Mq, nh, am, kv, window, dout, stream_);
     } else if (kind == 1) {
       attention16_qkv(dqkv, M, nh, map, kv, window, dout, stream_);
     } else {
@@ -2545,7 +2520,7 @@ void Engine::encoder_transformer(std::vector<Op>& ops, float* x, int T, float* h
     KvStore kv{ring + (size_t)l * 2 * MNH * T * 64, 0, T};
     dense_op(ops, "enc.qkv", h, T, W(t.in_proj), 3 * MD, MD, nullptr, ACT_NONE, nullptr, nullptr, qkv);
     ops.push_back({"enc.rope", [=](hipStream_t s) { qkv_rope_append(nullptr, 0, qkv, T, MNH, map, kv, q, s); }});
-    ops.push_back({"enc.attn", [=](hipStream_t s) { attention(q, T, MNH, map, kv, MCTX, 16, o, s); }});
+    ops.push_back({"enc.attn", [=](hipStream_t s) { attention(q, T, MNH, map, kv, MCTX, o, s); }});
     dense_op(ops, "enc.out", o, T, W(t.out_proj), MD, MD, nullptr, ACT_NONE, W(t.ls1), x, x);
     {
       const float *w = W(t.n2w), *b = W(t.n2b);
@@ -3116,7 +3091,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     map.mpad = T;
     map.qrow = qrow_dev_;
     map.orow = orow_dev_;
-    flow_layers(ops, Tc, map, 16, false, "prefill");
+    flow_layers(ops, Tc, map, false, false, "prefill");
     run_ops(ops);
   }
   // the slot state the back part owns (Mimi ring position, conv and overlap-add histories, frame

@@ -185,17 +185,17 @@ class Engine {
   void wait_unless_done(hipStream_t s, hipEvent_t e);
   void copy_out(int B, int hb, hipStream_t s);
   void push_rr(std::vector<Op>& ops, const std::string& name, const RowReduceArgs& r);
-  void flow_layers(std::vector<Op>& ops, int M, RowMap map, int qg, bool out_norm, const std::string& tag,
+  void flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
                    const FlowBufs* fb = nullptr);
   void linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M, const float* Wt,
                     int N, int K, int* S_out, const FlowBufs* fb = nullptr);
   void conv_op(std::vector<Op>& ops, const std::string& name, const float* X, int B, int T_in, int cin, const float* H,
                int P, int stride, int elu, const float* Wt, int cout, int ktaps, int phases, const float* bias,
-               const float* R, float* Y, int T_out, int tstride, int layout = 0, int elu_out = 0,
+               const float* R, float* Y, int T_out, int tstride, int layout = TILE_KSPLIT_4W, int elu_out = 0,
                float* Y2 = nullptr, int ksplit = 1);
   void dense_op(std::vector<Op>& ops, const std::string& name, const float* X, int M, const float* Wt, int N, int K,
                 const float* bias, int act, const float* rscale, const float* R, float* Y,
-                int layout = 0);
+                int layout = TILE_KSPLIT_4W);
   void encoder_transformer(std::vector<Op>& ops, float* x, int T, float* h, float* qkv, float* q, float* o, float* u,
                            float* ring);
 

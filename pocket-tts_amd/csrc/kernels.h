@@ -69,9 +69,140 @@ struct RowReduceArgs {
   // (ln, N == FK_K, M <= 32) also store the LayerNorm output in gemv_fk's A-fragment order, or nullptr
   float* Hfrag;
 };
+// ---------------------------------------------------------------------------------------------
+// The GEMM tiles, one row per tile id (GemmArgs::layout). The ids are an interface and keep their
+// values: PTTS_OVR, the tools' command lines and the records under profiles/ speak them. The
+// bf16-operand twin of an f32 tile has its id + 100, the bf16x6 twin + 200.
+//   family  the kernel: TILE_GEMM k_gemm (register operands), TILE_RB k_gemm_rb (register-blocked,
+//           the 4 waves split K), TILE_GLDS k_gemm_glds (LDS-DMA)
+//   WM WN   waves of the workgroup tile in M and N; TMW TNW 32x32 accumulators per wave; the tile
+//           is 32 WM TMW x 32 WN TNW. A k_gemm tile with more waves than WM WN deals its K chunks
+//           to them (ksplit)
+//   BK      K chunk width: K (and a conv's cin) must be a multiple of it
+//   NBUF    k_gemm_glds: LDS buffers; k_gemm: chunks in flight per wave
+//   MINB    workgroups per CU the register allocation allows; ILV: DMA issue between the MFMAs
+//   ops     operand kind (k_gemm_glds PREC); thr: threads per workgroup
+//   probe   1: compiled only into -DPTTS_PROBES builds (tools/, PTTS_OVR sweeps)
+// ---------------------------------------------------------------------------------------------
+enum TileFamily : int { TILE_GEMM, TILE_RB, TILE_GLDS };
+enum TileOps : int { OPS_F32 = 0, OPS_BF16 = 1, OPS_BF16X6 = 2 };
+//  id   family     WM WN BK NBUF TMW TNW MINB ILV ops        thr probe
+#define PTTS_TILES(X)                                                                                          \
+  X(0,   TILE_GEMM, 1, 1, 32, 1, 1, 1, 1, 0, OPS_F32,    256, 0) /*  32 x  32 ksplit, 4 waves */              \
+  X(3,   TILE_GEMM, 4, 1, 32, 1, 1, 1, 1, 0, OPS_F32,    256, 1) /* 128 x  32 */                              \
+  X(9,   TILE_GEMM, 1, 1, 32, 1, 1, 1, 1, 0, OPS_F32,    512, 0) /*  32 x  32 ksplit, 8 waves */              \
+  X(10,  TILE_GEMM, 1, 1, 32, 2, 1, 1, 1, 0, OPS_F32,    256, 1) /*  ... 4 waves, 2 chunks in flight */       \
+  X(17,  TILE_GEMM, 1, 1, 32, 2, 1, 1, 1, 0, OPS_F32,    512, 1) /*  ... 8 waves, 2 chunks in flight */       \
+  X(18,  TILE_RB,   1, 1, 32, 1, 1, 2, 1, 0, OPS_F32,    256, 0) /*  32 x  64 */                              \
+  X(19,  TILE_RB,   1, 1, 32, 1, 2, 1, 1, 0, OPS_F32,    256, 1) /*  64 x  32 */                              \
+  X(20,  TILE_RB,   1, 1, 32, 1, 2, 2, 1, 0, OPS_F32,    256, 0) /*  64 x  64 */                              \
+  X(6,   TILE_GLDS, 2, 2, 32, 2, 1, 1, 1, 0, OPS_F32,    256, 0) /*  64 x  64 */                              \
+  X(7,   TILE_GLDS, 1, 4, 32, 2, 1, 1, 1, 0, OPS_F32,    256, 0) /*  32 x 128 */                              \
+  X(8,   TILE_GLDS, 2, 2, 64, 2, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  X(11,  TILE_GLDS, 2, 2, 32, 3, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  X(12,  TILE_GLDS, 2, 2, 32, 4, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  X(13,  TILE_GLDS, 1, 4, 32, 4, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  X(14,  TILE_GLDS, 4, 1, 32, 4, 1, 1, 1, 0, OPS_F32,    256, 0) /* 128 x  32 */                              \
+  X(15,  TILE_GLDS, 2, 2, 64, 3, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  X(16,  TILE_GLDS, 1, 4, 64, 3, 1, 1, 1, 0, OPS_F32,    256, 1)                                              \
+  /* register-blocked LDS-DMA tiles (per-wave TMW x TNW accumulators) */                                      \
+  X(21,  TILE_GLDS, 2, 2, 32, 3, 2, 2, 1, 0, OPS_F32,    256, 1) /* 128 x 128 */                              \
+  X(22,  TILE_GLDS, 2, 2, 32, 3, 1, 2, 1, 0, OPS_F32,    256, 1) /*  64 x 128 */                              \
+  X(23,  TILE_GLDS, 2, 2, 32, 3, 2, 1, 1, 0, OPS_F32,    256, 0) /* 128 x  64 */                              \
+  X(24,  TILE_GLDS, 4, 1, 32, 3, 2, 1, 1, 0, OPS_F32,    256, 1) /* 256 x  32 */                              \
+  X(25,  TILE_GLDS, 4, 1, 32, 3, 1, 2, 1, 0, OPS_F32,    256, 1) /* 128 x  64 (waves stacked in M) */         \
+  X(26,  TILE_GLDS, 2, 2, 32, 4, 2, 2, 1, 0, OPS_F32,    256, 1) /* 128 x 128, 4 buffers */                   \
+  X(27,  TILE_GLDS, 1, 4, 32, 3, 2, 1, 1, 0, OPS_F32,    256, 1) /*  64 x 128 (waves side by side in N) */    \
+  /* interleaved DMA issue (ILV) */                                                                           \
+  X(30,  TILE_GLDS, 2, 2, 32, 3, 2, 2, 1, 1, OPS_F32,    256, 1) /* 128 x 128 */                              \
+  X(31,  TILE_GLDS, 2, 2, 32, 2, 2, 2, 2, 1, OPS_F32,    256, 1) /* 128 x 128, 2 per CU */                    \
+  X(32,  TILE_GLDS, 2, 2, 32, 3, 1, 1, 2, 1, OPS_F32,    256, 0) /*  64 x  64, 2 per CU (back part) */        \
+  X(33,  TILE_GLDS, 2, 2, 32, 2, 1, 1, 2, 1, OPS_F32,    256, 1) /*  64 x  64, 2 buffers, 2 per CU */         \
+  X(34,  TILE_GLDS, 2, 2, 32, 3, 2, 1, 1, 1, OPS_F32,    256, 0) /* 128 x  64 (prefill linear1) */            \
+  X(35,  TILE_GLDS, 2, 2, 32, 2, 2, 1, 2, 1, OPS_F32,    256, 0) /* 128 x  64, 2 per CU (prefill) */          \
+  X(36,  TILE_GLDS, 2, 2, 32, 3, 1, 2, 1, 1, OPS_F32,    256, 1) /*  64 x 128 */                              \
+  X(37,  TILE_GLDS, 2, 2, 32, 4, 1, 1, 1, 1, OPS_F32,    256, 1) /*  64 x  64, 4 buffers */                   \
+  X(38,  TILE_GLDS, 2, 2, 32, 4, 2, 2, 1, 1, OPS_F32,    256, 1) /* 128 x 128, 4 buffers */                   \
+  X(39,  TILE_GLDS, 2, 2, 32, 3, 1, 2, 2, 1, OPS_F32,    256, 1) /*  64 x 128, 2 per CU */                    \
+  /* bf16 operands (engine back_mfma = PTTS_BACK_BF16) */                                                     \
+  X(130, TILE_GLDS, 2, 2, 32, 3, 2, 2, 1, 1, OPS_BF16,   256, 1)                                              \
+  X(131, TILE_GLDS, 2, 2, 32, 2, 2, 2, 2, 1, OPS_BF16,   256, 0)                                              \
+  X(132, TILE_GLDS, 2, 2, 32, 3, 1, 1, 2, 1, OPS_BF16,   256, 0)                                              \
+  X(135, TILE_GLDS, 2, 2, 32, 2, 2, 1, 2, 1, OPS_BF16,   256, 0)                                              \
+  X(136, TILE_GLDS, 2, 2, 32, 3, 1, 2, 1, 1, OPS_BF16,   256, 1)                                              \
+  X(139, TILE_GLDS, 2, 2, 32, 3, 1, 2, 2, 1, OPS_BF16,   256, 1)                                              \
+  /* bf16x6 f32 (engine back_mfma = PTTS_BACK_F32X6): W pre-split (GemmArgs::Whm, Wlo) */                      \
+  X(230, TILE_GLDS, 2, 2, 32, 3, 2, 2, 1, 1, OPS_BF16X6, 256, 1)                                              \
+  X(231, TILE_GLDS, 2, 2, 32, 2, 2, 2, 2, 1, OPS_BF16X6, 256, 1)                                              \
+  X(232, TILE_GLDS, 2, 2, 32, 3, 1, 1, 2, 1, OPS_BF16X6, 256, 0)                                              \
+  X(235, TILE_GLDS, 2, 2, 32, 2, 2, 1, 2, 1, OPS_BF16X6, 256, 0)                                              \
+  X(236, TILE_GLDS, 2, 2, 32, 3, 1, 2, 1, 1, OPS_BF16X6, 256, 0)                                              \
+  X(239, TILE_GLDS, 2, 2, 32, 3, 1, 2, 2, 1, OPS_BF16X6, 256, 0)
+
+struct TileInfo {
+  int id;
+  TileFamily family;
+  int wm, wn, bk, nbuf, tmw, tnw, minb;
+  bool ilv;
+  TileOps ops;
+  int threads;
+  bool probe;
+  constexpr int tm() const { return 32 * wm * tmw; }
+  constexpr int tn() const { return 32 * wn * tnw; }
+  constexpr bool ksplit() const { return family == TILE_GEMM && threads / 64 > wm * wn; }
+  constexpr bool lds_dma() const { return family == TILE_GLDS; }  // the tiles that may split a conv's K
+  constexpr bool split_tail() const { return ilv && ops == OPS_F32; }  // GemmArgs::tail_S (dense)
+  constexpr bool split_weights() const { return ops == OPS_BF16X6; }   // reads GemmArgs::Whm / Wlo
+};
+#define PTTS_TILE_ROW(ID, FAM, WM, WN, BK, NBUF, TMW, TNW, MINB, ILV, OPS, THR, PROBE) \
+  {ID, FAM, WM, WN, BK, NBUF, TMW, TNW, MINB, ILV != 0, OPS, THR, PROBE != 0},
+inline constexpr TileInfo TILES[] = {PTTS_TILES(PTTS_TILE_ROW)};
+#undef PTTS_TILE_ROW
+constexpr int TILE_TWIN_BF16 = 100, TILE_TWIN_BF16X6 = 200;  // id offsets of the operand twins
+// the row of a tile id in the table (any build), or nullptr
+constexpr const TileInfo* tile_row(int id) {
+  for (const TileInfo& t : TILES)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+// a twin differs from its f32 tile in the operand kind alone
+constexpr bool tile_twins_match() {
+  for (const TileInfo& t : TILES) {
+    if (t.id < TILE_TWIN_BF16) continue;
+    const TileInfo* f = tile_row(t.id % 100);
+    if (!f || t.ops != (t.id >= TILE_TWIN_BF16X6 ? OPS_BF16X6 : OPS_BF16) || f->ops != OPS_F32 || f->family != t.family ||
+        f->wm != t.wm || f->wn != t.wn || f->bk != t.bk || f->nbuf != t.nbuf || f->tmw != t.tmw || f->tnw != t.tnw ||
+        f->minb != t.minb || f->ilv != t.ilv || f->threads != t.threads)
+      return false;
+  }
+  return true;
+}
+static_assert(tile_twins_match(), "PTTS_TILES: a + 100 / + 200 row must repeat its f32 tile");
+// ... in this build: nullptr for an unknown id, and for a probe-only tile in a product build
+inline const TileInfo* tile_info(int id) {
+  const TileInfo* t = tile_row(id);
+#ifndef PTTS_PROBES
+  if (t && t->probe) return nullptr;
+#endif
+  return t;
+}
+// The tiles the product selects (engine.cpp linear_split, back_tile)
+constexpr int TILE_KSPLIT_4W = 0;      // 32 x 32, K dealt to 4 waves: the skinny default, B < 16 back part
+constexpr int TILE_KSPLIT_8W = 9;      // ... to 8 waves (flow-head MLPs)
+constexpr int TILE_RB_32x64 = 18;      // register-blocked K-split (SEANet residual convs)
+constexpr int TILE_RB_64x64 = 20;
+constexpr int TILE_GLDS_64x64 = 6;     // LDS-DMA, 2 buffers
+constexpr int TILE_GLDS_32x128 = 7;    // FlowLM qkv / ff1, flow-head adaLN
+constexpr int TILE_GLDS_128x32 = 14;
+constexpr int TILE_GLDS_RB_128x64 = 23;
+constexpr int TILE_ILV_64x64_2CU = 32;  // the back part's MFMA-bound GEMMs and convs
+constexpr int TILE_ILV_128x64 = 34;     // prefill linear1
+constexpr int TILE_ILV_128x64_2CU = 35;  // prefill
+constexpr int TILE_ILV_128x128_2CU = 31;  // probe-only as f32; its bf16 twin ships
+
 struct GemmArgs {
   int mode;    // 0 dense, 1 conv
-  int layout;  // workgroup layout, see kernels.hip (0 ksplit 32x32, 1: 64x64, 2: 32x128, 3: 128x32)
+  int layout;  // tile id: a row of PTTS_TILES above
   int M, N, K;
   int Nw;  // rows present in W (N rounded up to 32)
   // A operand
@@ -82,7 +213,7 @@ struct GemmArgs {
   // B operand
   const float* W;
   long w_phase_stride;  // floats between polyphase weight blocks (mode 1)
-  // bf16x6 tiles (layout >= 200, ptts_engine_config.back_mfma = PTTS_BACK_F32X6): W split exactly
+  // bf16x6 tiles (TileInfo::split_weights, ptts_engine_config.back_mfma = PTTS_BACK_F32X6): W split exactly
   // into three bf16 pieces, W = hi + mid + lo (split3): Whm[n][k] = hi << 16 | mid (the f32 layout
   // of W, 4 B per element), Wlo[n][k] = lo (2 B per element); same indexing as W
   const unsigned* Whm;
@@ -125,7 +256,6 @@ struct GemmArgs {
   int* tickets;
   int tickets_cap;
   int tail_full, tiles_n;  // set by gemm()
-  int tiles_m, units_z;    // persistent tiles (layout 40): tile grid rows and z units, set by gemm()
   // epilogue (S == 1)
   const float* bias;
   int act;
@@ -140,6 +270,21 @@ struct GemmArgs {
   int elu_out;
   float* Y2;
 };
+// A dense GEMM (mode 0) X [M][ldx] . W [N][K]^T on tile `layout`; split-K, the split tail and the
+// epilogue are the caller's to add
+inline GemmArgs dense_gemm(int layout, int M, int N, int K, const float* X, long ldx, const float* W) {
+  GemmArgs a{};
+  a.mode = 0;
+  a.layout = layout;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.Nw = (N + 31) / 32 * 32;
+  a.X = X;
+  a.ldx = ldx;
+  a.W = W;
+  return a;
+}
 void gemm(const GemmArgs& a, int grid_z, hipStream_t s);
 // Exact three-piece bf16 split of n f32 values (the B operand of the bf16x6 tiles): x = hi + mid
 // + lo with every piece a bf16 (round to nearest even at each step; the remainders are exact in
@@ -256,11 +401,10 @@ void qkv_rope_append(const float* P, int S, const float* dense, int M, int nh, R
                      float* Q, hipStream_t s);
 
 // Causal (optionally windowed) softmax attention for rows mapped as above; rows are processed
-// in groups of qg (<= 16) consecutive rows of one slot. O[M][nh*64].
+// in groups of 16 consecutive rows of one slot. O[M][nh*64].
 // Mimi decoder step: RoPE + ring append of the dense QKV rows fused into the 16-row attention
 void attention16_qkv(const float* qkv, int M, int nh, RowMap map, KvStore kv, int window, float* O, hipStream_t s);
-void attention(const float* Q, int M, int nh, RowMap map, KvStore kv, int window, int qg, float* O,
-               hipStream_t s);
+void attention(const float* Q, int M, int nh, RowMap map, KvStore kv, int window, float* O, hipStream_t s);
 // One-query-per-row step attention fused with the QKV slab sum, RoPE and KV append (positions
 // must not wrap: FlowLM cache).
 void attention_step_qkv(const float* P, int S, int M, int nh, RowMap map, KvStore kv, const float* rope, float* O,

@@ -87,13 +87,13 @@ __device__ __forceinline__ float slab_sum(const float* p, long stride, int S) {
 // Lane (r, h) loads 16 consecutive k of its A row and of its W row (k0 + 16h ... +15);
 // MFMA #j of a chunk consumes element j of both, i.e. k-pair {k0 + j, k0 + 16 + j}.
 // =============================================================================================
-// Workgroup layouts (4 waves, each accumulating one 32x32 tile):
-//   LAYOUT 0  "ksplit": WG tile 32x32, the tile's K chunks dealt round-robin to the 4 waves,
-//             partial tiles summed through LDS (skinny M <= 32 GEMMs: more waves per tile)
-//   LAYOUT 1  2x2 waves = WG tile 64x64     LAYOUT 2  1x4 = 32x128     LAYOUT 3  4x1 = 128x32
-//   (each wave runs the whole K chain of its z-slice; neighbours share A rows / W rows in L1/L2)
-//   K-split variants of LAYOUT 0: LAYOUT 9 = 8 waves (2 per SIMD at one workgroup per CU),
-//   LAYOUT 10 = 4 waves with two chunks in flight, LAYOUT 17 = 8 waves, two chunks in flight.
+// Workgroup layouts (each wave accumulating one 32x32 tile; the TILE_GEMM rows of PTTS_TILES):
+//   tile 0   "ksplit": WG tile 32x32, the tile's K chunks dealt round-robin to the 4 waves,
+//            partial tiles summed through LDS (skinny M <= 32 GEMMs: more waves per tile)
+//   tile 3   4x1 waves = WG tile 128x32 (each wave runs the whole K chain of its z-slice;
+//            neighbours share W rows in L1/L2)
+//   K-split variants of tile 0: 9 = 8 waves (2 per SIMD at one workgroup per CU),
+//   10 = 4 waves with two chunks in flight, 17 = 8 waves, two chunks in flight.
 // Epilogue of one output element v of GEMM row `row`, column `col` (S == 1 path): bias,
 // activation, per-column scale, residual, ELU-out / dual store. Mode 1 maps row (b, q) to the
 // output time row b*T_out + q*out_tstride + phase; `ident` (wave-uniform) marks the identity map
@@ -204,27 +204,22 @@ __device__ __forceinline__ void xcd_tile(const GemmArgs& a, bool on, int& bx, in
   by = t / gx;
 }
 
-template <int LAYOUT>
-struct Lay {
-  static constexpr bool KSPLIT = LAYOUT == 0 || LAYOUT == 9 || LAYOUT == 10 || LAYOUT == 17;
-  static constexpr int NW = (LAYOUT == 9 || LAYOUT == 17) ? 8 : 4;  // waves per workgroup
-  static constexpr int PF = (LAYOUT == 10 || LAYOUT == 17) ? 2 : 1;  // chunks in flight per wave
-  static constexpr int WM = LAYOUT == 1 ? 2 : (LAYOUT == 3 ? 4 : 1);
-  static constexpr int WN = LAYOUT == 1 ? 2 : (LAYOUT == 2 ? 4 : 1);
-};
-
+// LAYOUT: the id of a TILE_GEMM row of PTTS_TILES (kernels.h), which gives the waves per workgroup,
+// WM x WN, the chunks in flight per wave (NBUF) and whether the waves split K
 template <int MODE, int LAYOUT>
-__global__ __launch_bounds__(64 * Lay<LAYOUT>::NW) void k_gemm(GemmArgs a) {
+__global__ __launch_bounds__(tile_row(LAYOUT)->threads) void k_gemm(GemmArgs a) {
   if (a.front) front_prio();
-  constexpr bool KS = Lay<LAYOUT>::KSPLIT;
-  constexpr int NW = Lay<LAYOUT>::NW;
+  constexpr TileInfo T = *tile_row(LAYOUT);
+  static_assert(T.family == TILE_GEMM, "k_gemm: not one of its tiles");
+  constexpr bool KS = T.ksplit();
+  constexpr int NW = T.threads / 64, PF = T.nbuf;
   __shared__ float red[KS ? NW * 16 * 64 : 1];
   const int lane = threadIdx.x & 63;
   // wave-uniform (SGPR) so that the chunk loop is a scalar loop: no exec-masked joins, and
   // the compiler can keep the next chunk's loads in flight across the MFMAs (counted vmcnt)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
-  constexpr int WM = Lay<LAYOUT>::WM, WN = Lay<LAYOUT>::WN;
+  constexpr int WM = T.wm, WN = T.wn;
   const int wm = KS ? 0 : wave / WN, wn = KS ? 0 : wave % WN;
   int bx, by;
   xcd_tile(a, true, bx, by);
@@ -314,7 +309,7 @@ __global__ __launch_bounds__(64 * Lay<LAYOUT>::NW) void k_gemm(GemmArgs a) {
   if (!wave_live) c = ce;
   // The prefetch is unconditional (past the end it re-reads a valid chunk, never used), so no
   // control-flow join sits between a load and the MFMAs that must not wait for it.
-  if (Lay<LAYOUT>::PF == 1) {
+  if (PF == 1) {
     // n chunks for this wave; loop body = two chunks with fixed register roles and no exits,
     // odd tail peeled (keeps the accumulator in place and the loads one chunk ahead)
     const int n = c < ce ? (ce - c + CSTEP - 1) / CSTEP : 0;
@@ -390,151 +385,6 @@ __global__ __launch_bounds__(64 * Lay<LAYOUT>::NW) void k_gemm(GemmArgs a) {
 #pragma unroll
       for (int g = 0; g < 16; ++g) store(g, acc[g]);
     }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// LDS-staged variant: operands are fetched with fully coalesced float4 loads (8 lanes cover one
-// 128-byte row segment of a 32-wide K chunk), written to LDS rows padded to 36 floats
-// (conflict-free ds_read_b128 in the MFMA fragment order), and read back per lane as the
-// 32x32x2 fragments. The next chunk's global loads are in flight while the current one is
-// multiplied.
-//   SHARED 0 (layout 4): WG tile 32x32, 4 waves split K, wave-private LDS, LDS reduce at the end.
-//   SHARED 1 (layout 5): WG tile 64x64, 2x2 waves share the A/B chunk through double-buffered
-//                        LDS (one barrier per chunk), each wave runs the full K chain.
-// ---------------------------------------------------------------------------------------------
-constexpr int LROW = 36;  // padded LDS row (floats)
-
-template <int MODE, int SHARED>
-__global__ __launch_bounds__(256) void k_gemm_lds(GemmArgs a) {
-  // SHARED 0: 4 waves x (A 32 rows + B 32 rows) x LROW ; SHARED 1: 2 buffers x (A 64 + B 64) x LROW
-  __shared__ __attribute__((aligned(16))) float lds[SHARED ? 2 * 128 * LROW : 4 * 64 * LROW];
-  __shared__ float red[SHARED ? 1 : 4 * 16 * 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int TM = SHARED ? 64 : 32, TN = SHARED ? 64 : 32;
-  const int n0 = blockIdx.x * TN, m0 = blockIdx.y * TM, z = blockIdx.z;
-  const int nchunks = a.K >> 5;
-  int cb = 0, ce = nchunks, phase = 0;
-  if (MODE == 0) {
-    cb = (int)((long)nchunks * z / a.S);
-    ce = (int)((long)nchunks * (z + 1) / a.S);
-  } else {
-    phase = z;
-  }
-  const float* W = a.W + (long)phase * a.w_phase_stride;
-  // loader mapping: row = base + lane/8 (+8 per instruction), 4 floats at col 4*(lane&7)
-  const int lrow = SHARED ? (tid >> 3) : (lane >> 3);  // 0..31 (SHARED) / 0..7 (per wave)
-  const int lcol = 4 * (tid & 7);
-  constexpr int NLD = SHARED ? 2 : 4;  // float4 loads per operand per chunk per thread
-  constexpr int RSTEP = SHARED ? 32 : 8;
-  // A and W rows this thread loads
-  const float* wp[NLD];
-  bool wv[NLD];
-  const float* ap_dense[NLD];
-  int abq[NLD], aqq[NLD];
-  bool av_ok[NLD];
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int row = lrow + RSTEP * i;
-    const int m = m0 + row;
-    av_ok[i] = m < a.M;
-    const int mm = av_ok[i] ? m : 0;
-    if (MODE == 0) {
-      ap_dense[i] = a.X + (long)mm * a.ldx + lcol;
-    } else {
-      abq[i] = mm / a.Tq;
-      aqq[i] = mm - abq[i] * a.Tq;
-    }
-    const int n = n0 + row;
-    wv[i] = n < a.Nw;
-    wp[i] = W + (long)(wv[i] ? n : 0) * a.K + lcol;
-  }
-  auto a_src = [&](int i, int k0) -> const float* {
-    if (MODE == 0) return ap_dense[i] + k0;
-    const int j = k0 / a.cin;
-    const int ci = k0 - j * a.cin + lcol;
-    const int t = aqq[i] * a.stride_in + j - a.P;
-    if (t >= 0) return a.X + ((long)abq[i] * a.T_in + t) * a.ldx + ci;
-    return a.H + ((long)abq[i] * a.P + (a.P + t)) * a.cin + ci;
-  };
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 ra[NLD], rb[NLD];
-  auto gload = [&](int c) {
-    const int k0 = c << 5;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      ra[i] = av_ok[i] ? *reinterpret_cast<const float4*>(a_src(i, k0)) : zero4;
-      rb[i] = wv[i] ? *reinterpret_cast<const float4*>(wp[i] + k0) : zero4;
-      if (MODE == 2)
-        ra[i] = make_float4(elu1(ra[i].x), elu1(ra[i].y), elu1(ra[i].z), elu1(ra[i].w));
-    }
-  };
-  // LDS regions
-  const int wm = SHARED ? wave >> 1 : 0, wn = SHARED ? wave & 1 : 0;
-  auto lds_a = [&](int buf) -> float* { return SHARED ? lds + buf * 128 * LROW : lds + wave * 64 * LROW; };
-  auto lds_b = [&](int buf) -> float* { return lds_a(buf) + (SHARED ? 64 : 32) * LROW; };
-
-  floatx16 acc;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-  const int cstep = SHARED ? 1 : 4;
-  int c = SHARED ? cb : cb + wave;
-  int buf = 0;
-  if (c < ce) gload(c);
-  for (; c < ce; c += cstep) {
-    float* la = lds_a(buf);
-    float* lb = lds_b(buf);
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      *reinterpret_cast<float4*>(la + (lrow + RSTEP * i) * LROW + lcol) = ra[i];
-      *reinterpret_cast<float4*>(lb + (lrow + RSTEP * i) * LROW + lcol) = rb[i];
-    }
-    if (SHARED) __syncthreads();
-    if (c + cstep < ce) gload(c + cstep);
-    float af[16], bf[16];
-    const float* pa = la + (32 * wm + r) * LROW + 16 * h;
-    const float* pb = lb + (32 * wn + r) * LROW + 16 * h;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 x = *reinterpret_cast<const float4*>(pa + 4 * i);
-      const float4 y = *reinterpret_cast<const float4*>(pb + 4 * i);
-      af[4 * i + 0] = x.x; af[4 * i + 1] = x.y; af[4 * i + 2] = x.z; af[4 * i + 3] = x.w;
-      bf[4 * i + 0] = y.x; bf[4 * i + 1] = y.y; bf[4 * i + 2] = y.z; bf[4 * i + 3] = y.w;
-    }
-    if (!(PTTS_PROBE(a) & 1)) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[j], bf[j], acc, 0, 0, 0);
-    }
-    if (SHARED) buf ^= 1;
-  }
-
-  const int tm0 = m0 + 32 * wm, tn0 = n0 + 32 * wn;
-  auto store = [&](int g, float v) {
-    const int row = tm0 + (g & 3) + 8 * (g >> 2) + 4 * h;
-    const int col = tn0 + r;
-    if (row >= a.M || col >= a.N) return;
-    if (a.partial) {
-      a.partial[((long)z * a.M + row) * a.N + col] = v;
-      return;
-    }
-    gemm_store(a, row, col, phase, gemm_ident(a, MODE, phase), v);
-  };
-  if (!SHARED) {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) red[(wave * 16 + g) * 64 + lane] = acc[g];
-    __syncthreads();
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      const int g = wave * 4 + gg;
-      float v = red[(0 * 16 + g) * 64 + lane] + red[(1 * 16 + g) * 64 + lane];
-      v += red[(2 * 16 + g) * 64 + lane];
-      v += red[(3 * 16 + g) * 64 + lane];
-      store(g, v);
-    }
-  } else {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) store(g, acc[g]);
   }
 }
 
@@ -1522,145 +1372,39 @@ static void launch_split_tail(K kernel, int TM, int TN, int minb, hipStream_t s,
                      cap_lds(kernel, a.max_wg_per_cu), s, b);
 }
 
+// One tile launch: the kernel instantiation, the grid and the threads all come from the tile's
+// row of PTTS_TILES (kernels.h)
+template <int MODE, int ID>
+static void launch_tile(const GemmArgs& a, int grid_z, hipStream_t s) {
+  constexpr TileInfo T = *tile_row(ID);
+  const dim3 grid((a.N + T.tn() - 1) / T.tn(), (a.M + T.tm() - 1) / T.tm(), grid_z);
+  if constexpr (T.family == TILE_GEMM) {
+    launch_tiled((k_gemm<MODE, ID>), grid, T.threads, s, a);
+  } else if constexpr (T.family == TILE_RB) {
+    launch_tiled((k_gemm_rb<MODE, T.tmw, T.tnw>), grid, T.threads, s, a);
+  } else {
+    constexpr auto kernel = k_gemm_glds<MODE, T.wm, T.wn, T.bk, T.nbuf, T.tmw, T.tnw, T.minb, T.ilv, (int)T.ops>;
+    if (T.split_weights() && (!a.Whm || !a.Wlo))
+      throw std::runtime_error("gemm: bf16x6 layout without its split weights");
+    if (MODE == 0 && T.split_tail() && a.tail_S > 0) launch_split_tail(kernel, T.tm(), T.tn(), T.minb, s, a);
+    else launch_tiled(kernel, grid, T.threads, s, a);
+  }
+}
+
+// a probe-only row expands to nothing in a product build
+#define PTTS_TILE_IF_0(...) __VA_ARGS__
+#ifdef PTTS_PROBES
+#define PTTS_TILE_IF_1(...) __VA_ARGS__
+#else
+#define PTTS_TILE_IF_1(...)
+#endif
 template <int MODE>
 static void gemm_launch(const GemmArgs& a, int grid_z, hipStream_t s) {
   switch (a.layout) {
-#define PTTS_GLDS(L, WM_, WN_, BK_, NB_)                                                               \
-  case L:                                                                                               \
-    launch_tiled((k_gemm_glds<MODE, WM_, WN_, BK_, NB_>),                                              \
-                 dim3((a.N + 32 * WN_ - 1) / (32 * WN_), (a.M + 32 * WM_ - 1) / (32 * WM_), grid_z), 256, s, a); \
-    return;
-    // the product's layouts (engine.cpp: linear_split, back_tile); the rest are compiled only into
-    // -DPTTS_PROBES builds (tools/, PTTS_OVR sweeps)
-    PTTS_GLDS(6, 2, 2, 32, 2)
-    PTTS_GLDS(7, 1, 4, 32, 2)
-    PTTS_GLDS(14, 4, 1, 32, 4)
-#ifdef PTTS_PROBES
-    PTTS_GLDS(8, 2, 2, 64, 2)
-    PTTS_GLDS(11, 2, 2, 32, 3)
-    PTTS_GLDS(12, 2, 2, 32, 4)
-    PTTS_GLDS(13, 1, 4, 32, 4)
-    PTTS_GLDS(15, 2, 2, 64, 3)
-    PTTS_GLDS(16, 1, 4, 64, 3)
-#endif
-#undef PTTS_GLDS
-#define PTTS_GLRB(L, WM_, WN_, NB_, TMW_, TNW_)                                                       \
-  case L:                                                                                             \
-    launch_tiled((k_gemm_glds<MODE, WM_, WN_, 32, NB_, TMW_, TNW_>),                                   \
-                 dim3((a.N + 32 * WN_ * TNW_ - 1) / (32 * WN_ * TNW_),                                \
-                      (a.M + 32 * WM_ * TMW_ - 1) / (32 * WM_ * TMW_), grid_z), 256, s, a);            \
-    return;
-    // register-blocked LDS-DMA tiles (per-wave TMW x TNW accumulators)
-    PTTS_GLRB(23, 2, 2, 3, 2, 1)  // 128 x  64
-#ifdef PTTS_PROBES
-    PTTS_GLRB(21, 2, 2, 3, 2, 2)  // 128 x 128
-    PTTS_GLRB(22, 2, 2, 3, 1, 2)  //  64 x 128
-    PTTS_GLRB(24, 4, 1, 3, 2, 1)  // 256 x  32
-    PTTS_GLRB(25, 4, 1, 3, 1, 2)  // 128 x  64 (waves stacked in M)
-    PTTS_GLRB(26, 2, 2, 4, 2, 2)  // 128 x 128, 4 buffers
-    PTTS_GLRB(27, 1, 4, 3, 2, 1)  //  64 x 128 (waves side by side in N)
-#endif
-#undef PTTS_GLRB
-#define PTTS_GLX(L, WM_, WN_, NB_, TMW_, TNW_, MINB_)                                                 \
-  case L:                                                                                             \
-    if (MODE == 0 && a.tail_S > 0) {                                                                  \
-      launch_split_tail((k_gemm_glds<MODE, WM_, WN_, 32, NB_, TMW_, TNW_, MINB_, true>),               \
-                        32 * WM_ * TMW_, 32 * WN_ * TNW_, MINB_, s, a);                                \
-      return;                                                                                         \
-    }                                                                                                 \
-    launch_tiled((k_gemm_glds<MODE, WM_, WN_, 32, NB_, TMW_, TNW_, MINB_, true>),                      \
-                 dim3((a.N + 32 * WN_ * TNW_ - 1) / (32 * WN_ * TNW_),                                \
-                      (a.M + 32 * WM_ * TMW_ - 1) / (32 * WM_ * TMW_), grid_z), 256, s, a);            \
-    return;
-    // interleaved DMA issue (ILV)
-    PTTS_GLX(32, 2, 2, 3, 1, 1, 2)  //  64 x  64, 2 per CU (back part)
-    PTTS_GLX(34, 2, 2, 3, 2, 1, 1)  // 128 x  64 (prefill linear1)
-    PTTS_GLX(35, 2, 2, 2, 2, 1, 2)  // 128 x  64, 2 per CU (prefill)
-#ifdef PTTS_PROBES
-    PTTS_GLX(30, 2, 2, 3, 2, 2, 1)  // 128 x 128
-    PTTS_GLX(31, 2, 2, 2, 2, 2, 2)  // 128 x 128, 2 per CU
-    PTTS_GLX(33, 2, 2, 2, 1, 1, 2)  //  64 x  64, 2 buffers, 2 per CU
-    PTTS_GLX(36, 2, 2, 3, 1, 2, 1)  //  64 x 128
-    PTTS_GLX(37, 2, 2, 4, 1, 1, 1)  //  64 x  64, 4 buffers
-    PTTS_GLX(38, 2, 2, 4, 2, 2, 1)  // 128 x 128, 4 buffers
-    PTTS_GLX(39, 2, 2, 3, 1, 2, 2)  //  64 x 128, 2 per CU
-#endif
-#undef PTTS_GLX
-    // bf16 operands (GemmArgs layout + 100; engine back_bf16): the ILV tiles of the back part
-#define PTTS_GLB(L, WM_, WN_, NB_, TMW_, TNW_, MINB_)                                                 \
-  case 100 + L:                                                                                       \
-    launch_tiled((k_gemm_glds<MODE, WM_, WN_, 32, NB_, TMW_, TNW_, MINB_, true, 1>),                   \
-                 dim3((a.N + 32 * WN_ * TNW_ - 1) / (32 * WN_ * TNW_),                                \
-                      (a.M + 32 * WM_ * TMW_ - 1) / (32 * WM_ * TMW_), grid_z), 256, s, a);            \
-    return;
-    PTTS_GLB(32, 2, 2, 3, 1, 1, 2)  //  64 x  64, 2 per CU
-    PTTS_GLB(35, 2, 2, 2, 2, 1, 2)  // 128 x  64, 2 per CU
-    PTTS_GLB(31, 2, 2, 2, 2, 2, 2)  // 128 x 128, 2 per CU
-#ifdef PTTS_PROBES
-    PTTS_GLB(30, 2, 2, 3, 2, 2, 1)  // 128 x 128
-    PTTS_GLB(36, 2, 2, 3, 1, 2, 1)  //  64 x 128
-    PTTS_GLB(39, 2, 2, 3, 1, 2, 2)  //  64 x 128, 2 per CU
-#endif
-#undef PTTS_GLB
-    // bf16x6 f32 (GemmArgs layout + 200; engine back_mfma = PTTS_BACK_F32X6): W pre-split (Whm, Wlo)
-#define PTTS_GLX6(L, WM_, WN_, NB_, TMW_, TNW_, MINB_)                                                \
-  case 200 + L:                                                                                       \
-    if (!a.Whm || !a.Wlo) throw std::runtime_error("gemm: bf16x6 layout without its split weights"); \
-    launch_tiled((k_gemm_glds<MODE, WM_, WN_, 32, NB_, TMW_, TNW_, MINB_, true, 2>),                   \
-                 dim3((a.N + 32 * WN_ * TNW_ - 1) / (32 * WN_ * TNW_),                                \
-                      (a.M + 32 * WM_ * TMW_ - 1) / (32 * WM_ * TMW_), grid_z), 256, s, a);            \
-    return;
-    PTTS_GLX6(32, 2, 2, 3, 1, 1, 2)  //  64 x  64, 2 per CU
-    PTTS_GLX6(36, 2, 2, 3, 1, 2, 1)  //  64 x 128
-    PTTS_GLX6(39, 2, 2, 3, 1, 2, 2)  //  64 x 128, 2 per CU
-    PTTS_GLX6(35, 2, 2, 2, 2, 1, 2)  // 128 x  64, 2 per CU
-    PTTS_GLX6(31, 2, 2, 2, 2, 2, 2)  // 128 x 128, 2 per CU
-    PTTS_GLX6(30, 2, 2, 3, 2, 2, 1)  // 128 x 128
-#undef PTTS_GLX6
-    default:
-      break;
-  }
-  switch (a.layout) {
-    case 0:
-      launch_tiled((k_gemm<MODE, 0>), dim3((a.N + 31) / 32, (a.M + 31) / 32, grid_z), 256, s, a);
-      return;
-    case 9:
-      launch_tiled((k_gemm<MODE, 9>), dim3((a.N + 31) / 32, (a.M + 31) / 32, grid_z), 512, s, a);
-      return;
-    case 18:
-      launch_tiled((k_gemm_rb<MODE, 1, 2>), dim3((a.N + 63) / 64, (a.M + 31) / 32, grid_z), 256, s, a);
-      return;
-    case 20:
-      launch_tiled((k_gemm_rb<MODE, 2, 2>), dim3((a.N + 63) / 64, (a.M + 63) / 64, grid_z), 256, s, a);
-      return;
-#ifdef PTTS_PROBES
-    case 4:
-      hipLaunchKernelGGL((k_gemm_lds<MODE, 0>), dim3((a.N + 31) / 32, (a.M + 31) / 32, grid_z), dim3(256), 0, s,
-                         a);
-      return;
-    case 5:
-      hipLaunchKernelGGL((k_gemm_lds<MODE, 1>), dim3((a.N + 63) / 64, (a.M + 63) / 64, grid_z), dim3(256), 0, s,
-                         a);
-      return;
-    case 1:
-      launch_tiled((k_gemm<MODE, 1>), dim3((a.N + 63) / 64, (a.M + 63) / 64, grid_z), 256, s, a);
-      return;
-    case 2:
-      launch_tiled((k_gemm<MODE, 2>), dim3((a.N + 127) / 128, (a.M + 31) / 32, grid_z), 256, s, a);
-      return;
-    case 3:
-      launch_tiled((k_gemm<MODE, 3>), dim3((a.N + 31) / 32, (a.M + 127) / 128, grid_z), 256, s, a);
-      return;
-    case 19:
-      launch_tiled((k_gemm_rb<MODE, 2, 1>), dim3((a.N + 31) / 32, (a.M + 63) / 64, grid_z), 256, s, a);
-      return;
-    case 10:
-      launch_tiled((k_gemm<MODE, 10>), dim3((a.N + 31) / 32, (a.M + 31) / 32, grid_z), 256, s, a);
-      return;
-    case 17:
-      launch_tiled((k_gemm<MODE, 17>), dim3((a.N + 31) / 32, (a.M + 31) / 32, grid_z), 512, s, a);
-      return;
-#endif
+#define PTTS_TILE_CASE(ID, FAM, WM, WN, BK, NBUF, TMW, TNW, MINB, ILV, OPS, THR, PROBE) \
+  PTTS_TILE_IF_##PROBE(case ID: return launch_tile<MODE, ID>(a, grid_z, s);)
+    PTTS_TILES(PTTS_TILE_CASE)
+#undef PTTS_TILE_CASE
     default:
       throw std::runtime_error("gemm: tile layout " + std::to_string(a.layout) + " is not in this build");
   }
@@ -2590,173 +2334,9 @@ void qkv_rope_append(const float* P, int S, const float* dense, int M, int nh, R
 }
 
 // =============================================================================================
-// Attention: one workgroup per (group of <= 16 query rows of one slot, head). Keys in tiles of
-// 64 are staged in LDS (K padded to 65 floats per row: conflict-free ds_read_b32 column reads),
-// online softmax per row; wave w owns rows w, w+4, w+8, w+12 in both the score and PV phases.
-// Mask (sdpa.rs:128-171): key kp visible to query qp iff kp <= qp and (no window or qp-kp < window).
+// Attention. Mask (sdpa.rs:128-171): key kp visible to query qp iff kp <= qp and (no window or
+// qp-kp < window).
 // =============================================================================================
-__global__ __launch_bounds__(256) void k_attention(const float* Q, int M, int nh, RowMap mp, KvStore kv, int window,
-                                                   int qg, float* O) {
-  __shared__ float sQ[16 * 64];
-  __shared__ float sK[64 * 65];
-  __shared__ float sV[64 * 64];
-  __shared__ float sP[16 * 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int head = blockIdx.y;
-  const int row0 = blockIdx.x * qg;
-  const int nrows = min(qg, M - row0);
-  int slot, qpos0, slot_l, qposl;
-  row_slot_pos(mp, row0, slot, qpos0);
-  row_slot_pos(mp, row0 + nrows - 1, slot_l, qposl);
-  const int d = nh * 64;
-  const int kmax = qposl;
-  const int kmin = window > 0 ? max(0, qpos0 - window + 1) : 0;
-  const float* kbase = kv.base + (long)slot * kv.slot_stride + (long)head * kv.cap * 64;
-  const float* vbase = kv.base + (long)slot * kv.slot_stride + (long)(nh + head) * kv.cap * 64;
-
-  for (int e = tid; e < 16 * 64; e += 256) {
-    const int i = e >> 6, dd = e & 63;
-    sQ[e] = i < nrows ? Q[(long)(row0 + i) * d + head * 64 + dd] : 0.f;
-  }
-  float m_run[4], l_run[4], o[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    m_run[r] = -INFINITY;
-    l_run[r] = 0.f;
-    o[r] = 0.f;
-  }
-  for (int kt = kmin; kt <= kmax; kt += 64) {
-    __syncthreads();
-    // stage K and V tiles: 64 keys x 16 float4 each
-#pragma unroll
-    for (int e4 = 0; e4 < 4; ++e4) {
-      const int idx = tid + 256 * e4;
-      const int j = idx >> 4, c4 = idx & 15;
-      const int kp = kt + j;
-      float4 kk = make_float4(0.f, 0.f, 0.f, 0.f), vv = kk;
-      if (kp <= kmax) {
-        const long off = (long)(kp % kv.cap) * 64 + c4 * 4;
-        kk = *reinterpret_cast<const float4*>(kbase + off);
-        vv = *reinterpret_cast<const float4*>(vbase + off);
-      }
-      sK[j * 65 + c4 * 4 + 0] = kk.x;
-      sK[j * 65 + c4 * 4 + 1] = kk.y;
-      sK[j * 65 + c4 * 4 + 2] = kk.z;
-      sK[j * 65 + c4 * 4 + 3] = kk.w;
-      *reinterpret_cast<float4*>(&sV[j * 64 + c4 * 4]) = vv;
-    }
-    __syncthreads();
-    const int kp = kt + lane;
-    float alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = wave + 4 * r;
-      alpha[r] = 1.f;
-      if (i >= nrows) continue;  // wave-uniform
-      float sc = 0.f;
-#pragma unroll 16
-      for (int dd = 0; dd < 64; ++dd) sc += sQ[i * 64 + dd] * sK[lane * 65 + dd];
-      sc *= 0.125f;  // 1/sqrt(64) (attention.rs:191,229)
-      const int qp = qpos0 + i;
-      const bool ok = kp <= qp && kp <= kmax && (window <= 0 || qp - kp < window);
-      sc = ok ? sc : -INFINITY;
-      const float mt = wave_max(sc);
-      const float mn = fmaxf(m_run[r], mt);
-      float p = 0.f;
-      if (mn != -INFINITY) {
-        alpha[r] = (m_run[r] == -INFINITY) ? 0.f : expf(m_run[r] - mn);
-        p = ok ? expf(sc - mn) : 0.f;
-      }
-      l_run[r] = l_run[r] * alpha[r] + wave_sum(p);
-      m_run[r] = mn;
-      sP[i * 64 + lane] = p;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = wave + 4 * r;
-      if (i >= nrows) continue;
-      float acc = 0.f;
-#pragma unroll 16
-      for (int j = 0; j < 64; ++j) acc += sP[i * 64 + j] * sV[j * 64 + lane];
-      o[r] = o[r] * alpha[r] + acc;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = wave + 4 * r;
-    if (i < nrows) O[(long)(row0 + i) * d + head * 64 + lane] = o[r] / l_run[r];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Decode attention, one query per (row, head) (FlowLM step, attention.rs:104-283 with the
-// single-query mask skip of sdpa.rs:3-18): one 256-thread workgroup per (row, head), the keys
-// dealt to the 4 waves 64 at a time. Lane j owns key j of its 64-key block: the whole K row
-// (16 float4) and, for P.V, lane d owns output dim d and reads V[j][d] for the block's 64 keys
-// (coalesced 256-B rows) - all loads of a block are issued before any arithmetic, so each wave
-// pays one memory round trip per block. p_j is broadcast with v_readlane. Waves combine their
-// (max, sum, o) through LDS. Positions never wrap (max_ctx covers voice + text + frames).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_attn_decode(const float* __restrict__ Q, int nh, RowMap mp, KvStore kv,
-                                                     float* __restrict__ O) {
-  __shared__ float s_m[4], s_l[4], s_o[4][64];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int row = blockIdx.x, head = blockIdx.y;
-  int slot, qp;
-  row_slot_pos(mp, row, slot, qp);
-  const int d = nh * 64;
-  const float* kbase = kv.base + (long)slot * kv.slot_stride + (long)head * kv.cap * 64;
-  const float* vbase = kv.base + (long)slot * kv.slot_stride + (long)(nh + head) * kv.cap * 64;
-  const float4* q4 = reinterpret_cast<const float4*>(Q + (long)row * d + head * 64);
-  float4 q[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) q[i] = q4[i];
-  float m = -INFINITY, l = 0.f, o = 0.f;
-  for (int base = 64 * wave; base <= qp; base += 256) {
-    const int j = base + lane;
-    const bool valid = j <= qp;
-    const float4* kr = reinterpret_cast<const float4*>(kbase + (long)(valid ? j : qp) * 64);
-    float4 k[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) k[i] = kr[i];
-    float v[64];
-#pragma unroll
-    for (int jj = 0; jj < 64; ++jj) v[jj] = vbase[(long)min(base + jj, qp) * 64 + lane];
-    float sc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sc += q[i].x * k[i].x + q[i].y * k[i].y + q[i].z * k[i].z + q[i].w * k[i].w;
-    sc = valid ? sc * 0.125f : -INFINITY;  // 1/sqrt(64) (attention.rs:191,229)
-    const float mn = fmaxf(m, wave_max(sc));  // finite: key `base` <= qp is valid
-    const float alpha = expf(m - mn);         // m = -inf -> 0
-    const float p = valid ? expf(sc - mn) : 0.f;
-    l = l * alpha + wave_sum(p);
-    o *= alpha;
-    const int pb = __builtin_bit_cast(int, p);
-#pragma unroll
-    for (int jj = 0; jj < 64; ++jj) o += __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, jj)) * v[jj];
-    m = mn;
-  }
-  if (lane == 0) {
-    s_m[wave] = m;
-    s_l[wave] = l;
-  }
-  s_o[wave][lane] = o;
-  __syncthreads();
-  if (wave == 0) {
-    const float M = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    float num = 0.f, den = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float e = s_m[w] == -INFINITY ? 0.f : expf(s_m[w] - M);
-      num += s_o[w][lane] * e;
-      den += s_l[w] * e;
-    }
-    O[(long)row * d + head * 64 + lane] = num / den;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // 16-query attention on MFMA (Mimi decoder ring window: 16 upsampled positions per row, and the
 // prefill / encoder groups): one workgroup per (16 consecutive rows of one slot, head), 16-key
@@ -2953,8 +2533,8 @@ __global__ __launch_bounds__(64 * A16_WAVES) void k_attn16(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// FlowLM step attention with the QKV split-K sum, RoPE and KV append fused in front (replaces
-// qkv_rope_append + k_attn_decode for the one-query-per-row step): the workgroup of (row, head)
+// FlowLM step attention with the QKV split-K sum, RoPE and KV append fused in front (one launch
+// instead of qkv_rope_append + a decode attention for the one-query-per-row step): the workgroup of (row, head)
 // sums its 192 q|k|v columns over the S slabs, rotates q and k (rope.rs:18-60), appends k, v at
 // the row's position and attends over the cached keys 0..pos-1 plus the new key from LDS.
 // ---------------------------------------------------------------------------------------------
@@ -3155,22 +2735,15 @@ void attention16_qkv(const float* qkv, int M, int nh, RowMap map, KvStore kv, in
                      qkv, M, nh, map, kv, window, O);
 }
 
-void attention(const float* Q, int M, int nh, RowMap map, KvStore kv, int window, int qg, float* O, hipStream_t s) {
-  if (kv.pre != nullptr && (qg != 16 || window > 0))
+void attention(const float* Q, int M, int nh, RowMap map, KvStore kv, int window, float* O, hipStream_t s) {
+  if (kv.pre != nullptr && window > 0)
     throw std::runtime_error("attention: shared voice prefixes need the 16-row causal kernel");
-  if (qg == 1 && window <= 0) {
-    hipLaunchKernelGGL(k_attn_decode, dim3(M, nh), dim3(256), cap_lds(k_attn_decode, g_wg_cap), s, Q, nh, map, kv, O);
-  } else if (qg == 16) {
-    // 16-row groups never straddle slots (rows-per-slot is 16 or the whole group)
-    const dim3 grid((M + 15) / 16, nh);
-    if ((kv.cap & (kv.cap - 1)) == 0)
-      hipLaunchKernelGGL(k_attn16<true>, grid, dim3(64 * A16_WAVES), cap_lds(k_attn16<true>, g_wg_cap), s, Q, M, nh, map, kv, window, O);
-    else
-      hipLaunchKernelGGL(k_attn16<false>, grid, dim3(64 * A16_WAVES), cap_lds(k_attn16<false>, g_wg_cap), s, Q, M, nh, map, kv, window, O);
-  } else {
-    dim3 grid((M + qg - 1) / qg, nh);
-    hipLaunchKernelGGL(k_attention, grid, dim3(256), cap_lds(k_attention, g_wg_cap), s, Q, M, nh, map, kv, window, qg, O);
-  }
+  // 16-row groups never straddle slots (rows-per-slot is 16 or the whole group)
+  const dim3 grid((M + 15) / 16, nh);
+  if ((kv.cap & (kv.cap - 1)) == 0)
+    hipLaunchKernelGGL(k_attn16<true>, grid, dim3(64 * A16_WAVES), cap_lds(k_attn16<true>, g_wg_cap), s, Q, M, nh, map, kv, window, O);
+  else
+    hipLaunchKernelGGL(k_attn16<false>, grid, dim3(64 * A16_WAVES), cap_lds(k_attn16<false>, g_wg_cap), s, Q, M, nh, map, kv, window, O);
 }
 
 // =============================================================================================

@@ -106,6 +106,7 @@ SIGNATURES = [
     ("ptts_voice_jobs_reserve", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_flush_async", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_test_gemm", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F32P, F32P, F32P]),
+    ("ptts_gemm_tiles", C.c_int, [C.c_char_p, C.c_int]),
     ("ptts_test_attention", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, F32P,
                                       F32P, F32P, I32P, C.c_int, C.c_int, C.c_int, I32P, I32P, I32P, C.c_int, F32P,
                                       F32P]),

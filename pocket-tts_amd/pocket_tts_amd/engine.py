@@ -269,6 +269,18 @@ class Engine:
         check(lib().ptts_config_check(cfg_yaml.encode()))
 
     @staticmethod
+    def gemm_tiles() -> list[dict]:
+        """The GEMM tiles of the loaded library (ptts_gemm_tiles; no GPU needed): id, tile m x n, bk,
+        operands ("f32" | "bf16" | "bf16x6") and whether test_gemm's tail_slices is served."""
+        buf = C.create_string_buffer(1 << 14)
+        check(lib().ptts_gemm_tiles(buf, len(buf)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            i, tm, tn, bk, ops, tail = line.split("\t")
+            out.append({"id": int(i), "tm": int(tm), "tn": int(tn), "bk": int(bk), "operands": ops, "tail": tail == "1"})
+        return out
+
+    @staticmethod
     def weight_blob_bytes() -> int:
         return int(lib().ptts_weight_blob_bytes())
 

@@ -15,7 +15,8 @@ def declared_symbols(header="pocket_tts.h"):
     return sorted(set(re.findall(r"\b(ptts_[a-z0-9_]+)\s*\(", text)))
 
 
-PROBE_HOOKS = {"ptts_test_gemm", "ptts_test_attention", "ptts_time_kernel", "ptts_plan_ops", "ptts_probe_overlap"}
+PROBE_HOOKS = {"ptts_test_gemm", "ptts_gemm_tiles", "ptts_test_attention", "ptts_time_kernel", "ptts_plan_ops",
+               "ptts_probe_overlap"}
 
 
 def test_boundary_header_holds_no_measurement_hooks():

@@ -4,7 +4,7 @@ weights leaves these kernels nearly untested: the weights give logits of sigma ~
 softmax is almost flat (each of 250 keys weighs ~ 1/250) and the max subtraction, the online
 rescale between key tiles, the waves' (m, l, o) merge and the mask edges hardly move the output.
 
-Kinds: A = qkv_rope_append + attention(qg = 16) (k_qkv_rope, k_attn16<RING>), B = attention16_qkv
+Kinds: A = qkv_rope_append + attention (k_qkv_rope, k_attn16<RING>), B = attention16_qkv
 (k_attn16<true, true>, RoPE and the ring append fused), C = attention_step_qkv (k_attn_decode_qkv
 with the engine's rope_table). Every case is checked in two layers, so that RoPE rounding stays out
 of the softmax gate.

@@ -88,6 +88,18 @@ def test_split_tail_matches_fp64(eng, layout, m, n):
     assert np.array_equal(y, eng.test_gemm(layout, x, w, tail_slices=4))
 
 
+def test_tail_on_a_tile_without_it_is_refused(eng):
+    """Tile 6 has no split tail (tests/test_gemm_tiles.py): the hook refuses the request instead of
+    running the plain path; so it does a tile that is not in the build, and a k off the tile's BK."""
+    import pocket_tts_amd as pt
+
+    x, w = operands(64, 64, 32, 6)
+    for layout, xs, kw in [(6, x, {"tail_slices": 4}), (1, x, {}), (32, np.zeros((64, 48), np.float32), {})]:
+        with pytest.raises(pt.PocketTTSError) as e:
+            eng.test_gemm(layout, xs, w[:, :xs.shape[1]], **kw)
+        assert e.value.code == 1, e.value  # PTTS_ERR_INVALID
+
+
 @pytest.mark.parametrize("m,n,k,scale", [(256, 512, 3584, 1.0), (512, 1536, 512, 1.0), (384, 640, 512, 1e-3),
                                          (200, 256, 2048, 30.0)])
 def test_bf16x6_tile_is_as_accurate_as_the_f32_tile(eng, m, n, k, scale):

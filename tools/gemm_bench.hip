@@ -210,11 +210,15 @@ int main(int argc, char** argv) {
       if (only_layout >= 0 && (layout != only_layout || (only_s >= 0 && S != only_s))) continue;
       GemmArgs v = a;
       v.layout = layout;
-      const int bk = (layout == 8 || layout == 15 || layout == 16) ? 64 : 32;
-      if (layout >= 6 && (a.K % bk != 0 || (a.mode == 1 && a.cin % bk != 0))) continue;
+      const TileInfo* tile = tile_info(layout);  // kernels.h PTTS_TILES
+      if (!tile) {
+        printf("   layout %d is not in this build\n", layout);
+        continue;
+      }
+      const int bk = tile->bk;
+      if (a.K % bk != 0 || (a.mode == 1 && a.cin % bk != 0)) continue;
       int gz = c.phases;
-      if (S > 1 && a.mode == 1 && (c.phases > 1 || layout < 6 || (layout >= 9 && layout <= 10) ||
-                                   (layout >= 17 && layout <= 20))) continue;
+      if (S > 1 && a.mode == 1 && (c.phases > 1 || !tile->lds_dma())) continue;
       if (S > 1) {  // dense split-K, or K-sliced single-phase conv (register-blocked LDS-DMA)
         if (a.K / bk < S) continue;
         v.S = S;

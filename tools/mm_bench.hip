@@ -159,10 +159,15 @@ int main(int argc, char** argv) {
       GemmArgs v = a;
       v.layout = layout;
       if (layout == -1 && a.mode != 0) continue;
-      const int bk = (layout == 8 || layout == 15 || layout == 16) ? 64 : 32;
-      if (layout >= 0 && (a.K % bk != 0 || (a.mode == 1 && a.cin % bk != 0))) continue;
+      const TileInfo* tile = layout >= 0 ? tile_info(layout) : nullptr;  // kernels.h PTTS_TILES
+      if (layout >= 0 && !tile) {
+        printf("   L%d is not in this build\n", layout);
+        continue;
+      }
+      const int bk = tile ? tile->bk : 32;
+      if (tile && (a.K % bk != 0 || (a.mode == 1 && a.cin % bk != 0))) continue;
       if (S < 0) {
-        if (layout < 30 || a.mode != 0) continue;
+        if (!tile || !tile->split_tail() || a.mode != 0) continue;
         v.S = 1;
         v.partial = nullptr;
         v.tail_S = -S;
