@@ -296,13 +296,41 @@ int ptts_wire_enable(ptts_engine* e, int on);
  * that of this one): the stride of the array, and fields past it read as 0, so the struct can grow
  * without an ABI bump. Zero fields are the defaults: lsd_steps as in ptts_slots_open_ex; wire_rate
  * 0 and wire_encoding 0: no wire format; one of them 0: 24000 / PTTS_WIRE_S16; speed_permille 0:
- * no speed (the field lies in what was the struct's tail padding: zero the struct before filling it). */
+ * no speed (the field lies in what was the struct's tail padding: zero the struct before filling it).
+ *
+ * Latent prefix and codec continuity (no reference counterpart: the
+ * reference starts every sentence chunk from fresh states and names teacher forcing as the better
+ * way, tts_model.py:397-400). A row may be admitted behind n_prefix >= 0 latents p[0 .. n_prefix),
+ * each [32], in FlowLM space (the values ptts_fetch returns in `latents`). It then starts in exactly
+ * the state of a row that was admitted without a prefix and ran n_prefix steps in which each
+ * sampled latent was replaced by p[j] before it became the next backbone input (what
+ * ptts_slot_set_latent after each step does), with the outputs of those steps discarded. With F
+ * voice rows and S tokens: FlowLM KV positions F+S .. F+S+n_prefix-1 hold the layers' K/V for the
+ * inputs [bos, p[0], .., p[n_prefix-2]], the next position is F+S+n_prefix, and the backbone input
+ * of the first step is p[n_prefix-1] (bos with no prefix). The generation counters count NEW frames
+ * only: max_frames, the EOS tail (frames_after_eos) and the noise stream are indexed from the first
+ * new frame; no EOS decision is taken inside the prefix, which runs no EOS head, no flow head and
+ * no Mimi decode. The capacity rule is F + S + n_prefix + max_frames <= max_ctx.
+ * keep_codec = 0: the Mimi state is fresh, as for every other admission. keep_codec = 1: the state
+ * the slot's decoder ended on (attention ring and its position, the conv histories, the overlap-add
+ * history) is NOT reset, so the first new frame is decoded as the continuation of the last frame
+ * the slot decoded; frame flags, wire state and tempo state are reset as always (a request's wire
+ * stream is its own). It needs no prefix (a seamless join without teacher forcing). It is valid
+ * only on a slot whose previous utterance has had its last frame fetched, or on a never-used slot
+ * (where it equals a fresh state): after ptts_slot_close or ptts_slots_cancel of an utterance on
+ * the slot, or with frames still unfetched, it is PTTS_ERR_STATE and admits nothing. keep_codec
+ * rows get no first-frame preview (a preview decodes from the fresh state). n_prefix < 0,
+ * n_prefix > 0 with prefix_latents NULL, keep_codec outside {0, 1} or a failing capacity rule is
+ * PTTS_ERR_INVALID and admits nothing. A caller with the older 24-byte struct gets neither. */
 typedef struct ptts_slot_opts {
   size_t size;
   int lsd_steps;
   int wire_rate;     /* 8000, 16000, 24000, 44100 or 48000 */
   int wire_encoding; /* PTTS_WIRE_* */
   int speed_permille; /* speech speed, 500 .. 2000 (ptts_tempo_enable); 0 or 1000: none */
+  const float* prefix_latents; /* host memory [n_prefix][32], read before the call returns */
+  int n_prefix;
+  int keep_codec;
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an

@@ -313,7 +313,8 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     const size_t size = opts[0].size ? opts[0].size : sizeof(ptts_slot_opts);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n), speed(n);
+    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n);
+    std::vector<const float*> pre(n);
     for (int i = 0; i < n; ++i) {
       ptts_slot_opts o{};
       std::memcpy(&o, (const char*)opts + (size_t)i * size, std::min(size, sizeof o));
@@ -322,8 +323,12 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
       rate[i] = o.wire_rate;
       enc[i] = o.wire_encoding;
       speed[i] = o.speed_permille;
+      pre[i] = o.prefix_latents;
+      npre[i] = o.n_prefix;
+      keep[i] = o.keep_codec;
     }
-    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data());
+    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data(),
+                      pre.data(), npre.data(), keep.data());
   });
 }
 

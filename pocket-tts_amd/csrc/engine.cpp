@@ -190,10 +190,14 @@ Engine::Engine(const ptts_engine_config& cfg) {
   admit_slots_ = (int*)dalloc(B);
   admit_st_ = (SlotState*)dalloc((sizeof(SlotState) * B + 3) / 4);
   admit_fpos_ = (int*)dalloc(B);
+  plat_dev_ = dalloc((size_t)PREFILL * LDIM);
+  admit_lat_ = dalloc((size_t)B * LDIM);
+  admit_opt_ = (int*)dalloc(B);
   vpre_ = (const float**)dalloc((sizeof(float*) * B + 3) / 4);  // zero: no slot has a prefix
   vlen_ = (int*)dalloc(B);
   slot_voice_.assign(B, nullptr);
   drained_.assign(B, 1);
+  codec_ok_.assign(B, 1);
   admit_call_.assign(B, -1);
   slot_lsd_.assign(B, 0);
   cancelled_.assign(B, 0);
@@ -269,6 +273,9 @@ Engine::Engine(const ptts_engine_config& cfg) {
   PTTS_HIP(hipHostMalloc((void**)&h_fp_, sizeof(int) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_ids_, sizeof(int) * PREFILL, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_tab_, sizeof(int) * 4 * PREFILL, hipHostMallocDefault));  // ptab | ctab | qrow | orow
+  PTTS_HIP(hipHostMalloc((void**)&h_plat_, sizeof(float) * PREFILL * LDIM, hipHostMallocDefault));
+  PTTS_HIP(hipHostMalloc((void**)&h_alat_, sizeof(float) * B * LDIM, hipHostMallocDefault));
+  PTTS_HIP(hipHostMalloc((void**)&h_aopt_, sizeof(int) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_vpre_, sizeof(float*) * B, hipHostMallocDefault));
   PTTS_HIP(hipHostMalloc((void**)&h_vlen_, sizeof(int) * B, hipHostMallocDefault));
   memset(h_vpre_, 0, sizeof(float*) * B);
@@ -361,7 +368,7 @@ Engine::~Engine() {
     if (hp) (void)hipHostFree(hp);
   if (h_err_) (void)hipHostFree(h_err_);
   for (void* hp : {(void*)h_slots_, (void*)h_st_, (void*)h_fp_, (void*)h_ids_, (void*)h_tab_, (void*)h_vpre_,
-                   (void*)h_vlen_})
+                   (void*)h_vlen_, (void*)h_plat_, (void*)h_alat_, (void*)h_aopt_})
     if (hp) (void)hipHostFree(hp);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -1949,7 +1956,7 @@ void Engine::fetch(int B, float* pcm, uint8_t* valid, uint8_t* last, float* eos,
     // after that frame's call (a driver that admits the next utterance before fetching the last
     // frame of the previous one, as bench.py does): then the frame is the previous utterance's and
     // the new one's back passes are still to come
-    if (ok && hf[b].last && fk >= admit_call_[b]) drained_[b] = 1;  // (lsd_run_for: the row counts no more)
+    if (ok && hf[b].last && fk >= admit_call_[b]) drained_[b] = codec_ok_[b] = 1;  // (lsd_run_for: the row counts no more)
     if (valid) valid[b] = ok;
     if (last) last[b] = ok && hf[b].last;
     if (pcm) {
@@ -2948,13 +2955,17 @@ int Engine::lsd_run_for(int B) const {
 // through a row table.
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                         const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
-                        const int* wire_enc, const int* speed) {
+                        const int* wire_enc, const int* speed, const float* const* prefix, const int* n_prefix,
+                        const int* keep_codec) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
   std::vector<char> seen(max_slots_, 0);
   std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
   std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
+  std::vector<int> npre(n, 0);  // the rows' latent prefixes (frames) and RESET_* bits (section 20)
+  std::vector<int> ropt(n, 0);
+  bool any_prefix = false, any_opt = false;
   long total_ids = 0;
   for (int i = 0; i < n; ++i) {
     const int wr = wire_rate ? wire_rate[i] : 0, we = wire_enc ? wire_enc[i] : 0;
@@ -2984,11 +2995,25 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     PTTS_REQUIRE(!lsd_steps || lsd_steps[i] == 0 || (lsd_steps[i] >= 1 && lsd_steps[i] <= lsd_),
                  "lsd_steps must be 0 (the default) or in [1, " + std::to_string(lsd_) + "] (the engine's lsd_decode_steps)");
     PTTS_REQUIRE(p.frames_after_eos >= 0, "frames_after_eos must be >= 0");
-    PTTS_REQUIRE((long)v->F + n_ids[i] + p.max_frames <= max_ctx_, "voice + text + max_frames exceeds max_ctx");
+    npre[i] = n_prefix ? n_prefix[i] : 0;
+    const int keep = keep_codec ? keep_codec[i] : 0;
+    PTTS_REQUIRE(npre[i] >= 0, "n_prefix must be >= 0");
+    PTTS_REQUIRE(npre[i] == 0 || (prefix && prefix[i]), "n_prefix > 0 with no prefix_latents");
+    PTTS_REQUIRE(keep == 0 || keep == 1, "keep_codec must be 0 or 1");
+    PTTS_REQUIRE((long)v->F + n_ids[i] + npre[i] + p.max_frames <= max_ctx_,
+                 npre[i] ? "voice + text + prefix + max_frames exceeds max_ctx" : "voice + text + max_frames exceeds max_ctx");
+    ropt[i] = (keep ? RESET_KEEP_CODEC : 0) | (npre[i] ? RESET_LAT_SRC : 0);
+    any_prefix = any_prefix || npre[i] > 0;
+    any_opt = any_opt || ropt[i] != 0;
     for (int j = 0; j < n_ids[i]; ++j)
       PTTS_REQUIRE(ids[total_ids + j] >= 0 && ids[total_ids + j] < VOCAB, "token id out of range");
     total_ids += n_ids[i];
   }
+  // keep_codec: the slot's codec state must be that of a whole utterance, with nothing in flight
+  for (int i = 0; i < n; ++i)
+    if ((ropt[i] & RESET_KEEP_CODEC) && !(drained_[slots[i]] && codec_ok_[slots[i]]))
+      throw Error(PTTS_ERR_STATE, "keep_codec: the slot's previous utterance was closed or cancelled, or its last "
+                                  "frame is not fetched yet");
   // Stream-ordered admission (no drain of the pipeline: a full sync() here stalled the front part
   // at every admission, a large share of the serving path's time): the host waits only until the
   // previous admission has consumed the pinned staging buffers (its event), and stream_ waits on
@@ -3032,12 +3057,21 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     }
   }
   // text prefill (tts_model.rs:947-964) of every admitted utterance in shared passes
+  // a row's latent prefix follows its text, at positions F + S + j: inputs bos, p[0] .. p[n_prefix - 2]
+  // (rid: PREFILL_SRC_BOS, then PREFILL_SRC_LAT0 - j; rlat: where latent j lies in the caller's memory)
   std::vector<int> tab, rid;
+  std::vector<const float*> rlat;
   long off = 0;
   for (int i = 0; i < n; ++i) {
     for (int j = 0; j < n_ids[i]; ++j) {
       tab.push_back(slots[i] << 16 | (voices[i]->F + j));
       rid.push_back(ids[off + j]);
+    }
+    for (int j = 0; j < npre[i]; ++j) {
+      tab.push_back(slots[i] << 16 | (voices[i]->F + n_ids[i] + j));
+      rid.push_back(j == 0 ? PREFILL_SRC_BOS : PREFILL_SRC_LAT0);
+      rlat.resize(tab.size(), nullptr);
+      if (j > 0) rlat.back() = prefix[i] + (size_t)(j - 1) * LDIM;
     }
     while (tab.size() % 16) {
       tab.push_back(-1);
@@ -3054,7 +3088,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     int* h_ctab = h_tab_ + PREFILL;
     int* h_qrow = h_tab_ + 2 * PREFILL;
     int* h_orow = h_tab_ + 3 * PREFILL;
-    int Tc = 0;
+    int Tc = 0, nlat = 0;
     for (int r = 0; r < T; ++r) {
       const int v = tab[c0 + r];
       h_ptab[r] = v;
@@ -3063,10 +3097,16 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
         h_ctab[Tc] = v;
         h_qrow[Tc] = r;
         h_ids_[Tc] = rid[c0 + r];
+        if (c0 + r < rlat.size() && rlat[c0 + r]) {  // staged for this pass (at most T <= PREFILL latents)
+          memcpy(h_plat_ + (size_t)nlat * LDIM, rlat[c0 + r], sizeof(float) * LDIM);
+          h_ids_[Tc] = PREFILL_SRC_LAT0 - nlat++;
+        }
         ++Tc;
       }
     }
     if (Tc == 0) continue;
+    if (nlat)
+      PTTS_HIP(hipMemcpyAsync(plat_dev_, h_plat_, sizeof(float) * nlat * LDIM, hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(ids_dev_, h_ids_, sizeof(int) * Tc, hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(rowtab_dev_, h_ptab, sizeof(int) * T, hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(ctab_dev_, h_ctab, sizeof(int) * Tc, hipMemcpyHostToDevice, stream_));
@@ -3077,7 +3117,12 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       const int* idp = ids_dev_;
       const float* tb = W(L_.embed);
       float* x = x_;
-      ops.push_back({"prefill.embed", [=](hipStream_t s) { embed_gather(idp, Tc, tb, D, x, s); }});
+      if (any_prefix) {  // token and latent rows in one launch
+        const float *pl = plat_dev_, *bos = W(L_.bos), *wt = inw_t_;
+        ops.push_back({"prefill.input", [=](hipStream_t s) { prefill_input(idp, Tc, tb, pl, bos, wt, D, x, s); }});
+      } else {
+        ops.push_back({"prefill.embed", [=](hipStream_t s) { embed_gather(idp, Tc, tb, D, x, s); }});
+      }
     }
     {
       float* x = x_;
@@ -3110,6 +3155,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   }
   for (int i = 0; i < n; ++i) {
     drained_[slots[i]] = 0;
+    codec_ok_[slots[i]] = 0;
     cancelled_[slots[i]] = 0;
     admit_call_[slots[i]] = k_;
     slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
@@ -3136,7 +3182,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     s.noise_clamp = p.noise_clamp;
     s.seed = p.seed;
     s.lsd = slot_lsd_[slots[i]];
-    fp[i] = voices[i]->F + n_ids[i];
+    fp[i] = voices[i]->F + n_ids[i] + npre[i];
   }
   // staged through pinned buffers so the copies are truly asynchronous: admission returns with
   // the prefill still running and the caller's first step queued right behind it (no host
@@ -3154,8 +3200,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   // first-frame previews: each admitted row's first front part runs at call k_ + admit_delay_ (a
   // re-admitted slot's unfetched preview belonged to its previous utterance)
   for (int i = 0; i < n; ++i) pv_forget(slots[i]);
+  // (a preview decodes from the fresh codec state: not the frame a keep_codec row produces)
   if (pv_max_ > 0)
-    for (int i = 0; i < n; ++i) pv_pending_.push_back({slots[i], k_ + admit_delay_});
+    for (int i = 0; i < n; ++i)
+      if (!(ropt[i] & RESET_KEEP_CODEC)) pv_pending_.push_back({slots[i], k_ + admit_delay_});
   memcpy(h_slots_, slots, sizeof(int) * n);
   memcpy(h_st_, st.data(), sizeof(SlotState) * n);
   memcpy(h_fp_, fp.data(), sizeof(int) * n);
@@ -3166,6 +3214,14 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   PTTS_HIP(hipMemcpyAsync(admit_slots_, h_slots_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_st_, h_st_, sizeof(SlotState) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_fpos_, h_fp_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  if (any_opt) {  // the rows' first backbone input (the prefix's last latent) and RESET_* bits
+    memcpy(h_aopt_, ropt.data(), sizeof(int) * n);
+    for (int i = 0; i < n; ++i)
+      if (npre[i]) memcpy(h_alat_ + (size_t)i * LDIM, prefix[i] + (size_t)(npre[i] - 1) * LDIM, sizeof(float) * LDIM);
+    PTTS_HIP(hipMemcpyAsync(admit_opt_, h_aopt_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+    if (any_prefix)
+      PTTS_HIP(hipMemcpyAsync(admit_lat_, h_alat_, sizeof(float) * n * LDIM, hipMemcpyHostToDevice, stream_));
+  }
   {
     ResetArgs r{};
     for (int i = 0; i < 8; ++i) {
@@ -3194,6 +3250,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       r.tempo_src = admit_tempo_;
       r.tempo_sp = tempo_sp_;
       r.tempo_state = tempo_state_;
+    }
+    if (any_opt) {
+      r.opt_src = admit_opt_;
+      r.lat_src = admit_lat_;
     }
     slot_reset(r, stream_);
     PTTS_HIP(hipGetLastError());
@@ -3468,6 +3528,7 @@ void Engine::decode_latents(int slot, const float* lat, int n, float* pcm, float
   }
   mark_admission();
   drained_[slot] = 1;
+  codec_ok_[slot] = 0;  // not an utterance's state
   pv_forget(slot);
 }
 
@@ -3490,6 +3551,7 @@ void Engine::slot_close(int slot) {
   mark_admission();
   PTTS_HIP(hipStreamSynchronize(stream_));
   drained_[slot] = 1;
+  codec_ok_[slot] = 0;
   cancelled_[slot] = 0;
   pv_forget(slot);
   voice_release(slot, true);
@@ -3519,6 +3581,7 @@ void Engine::slots_cancel(int n, const int* slots) {
     // admitted inside a multi-frame pass and not started yet: it never starts
     act_slots_.erase(std::remove(act_slots_.begin(), act_slots_.end(), slot), act_slots_.end());
     cancelled_[slot] = 1;
+    codec_ok_[slot] = 0;
     slot_lsd_[slot] = 0;  // lsd_run_for: the row counts no more
     if (k_ > admit_call_[slot]) cancel_wins_.push_back({slot, admit_call_[slot], k_});
     pv_forget(slot);

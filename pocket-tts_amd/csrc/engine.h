@@ -82,9 +82,13 @@ class Engine {
                  int lsd_steps = 0);
   // wire_rate / wire_enc (wire-enabled engines): the row's output format, per row; 0 in both (or null
   // arrays) = none, 0 in one = its default (24000 Hz, PTTS_WIRE_S16)
+  // prefix / n_prefix / keep_codec (null arrays: none): row i starts behind
+  // n_prefix[i] teacher-forced latents prefix[i] [n_prefix[i]][32] (host memory, read before the
+  // call returns), and with keep_codec[i] = 1 on the codec state its slot's last utterance ended on
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
                   const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
-                  const int* wire_enc = nullptr, const int* speed = nullptr);
+                  const int* wire_enc = nullptr, const int* speed = nullptr, const float* const* prefix = nullptr,
+                  const int* n_prefix = nullptr, const int* keep_codec = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -281,6 +285,10 @@ class Engine {
   int* admit_slots_ = nullptr;  // [max_slots] staged admission list
   SlotState* admit_st_ = nullptr;
   int* admit_fpos_ = nullptr;
+  // latent prefixes (section 20): one pass's prefix latents [PREFILL][32], the admitted rows' first
+  // backbone inputs [max_slots][32] and RESET_* bits [max_slots], each with its pinned staging
+  float *plat_dev_ = nullptr, *h_plat_ = nullptr, *admit_lat_ = nullptr, *h_alat_ = nullptr;
+  int *admit_opt_ = nullptr, *h_aopt_ = nullptr;
   float *ysilu_ = nullptr, *mods_ = nullptr, *xf_ = nullptr, *hf_ = nullptr, *uf_ = nullptr;
   // persistent flow-head chain (k_flow_head): hand-off rows, counters, timeout word
   bool head_uniform_stride() const;  // ResBlock tensors at one stride (k_flow_head, its packing)
@@ -401,6 +409,9 @@ class Engine {
   // slots whose utterance has no frame left in flight (never admitted, closed, or its last frame
   // fetched): their admission need not wait for the back parts already queued (ev_be_tail_)
   std::vector<char> drained_;
+  // slots whose codec state is that of a whole utterance (never used, or its last frame fetched, and
+  // neither closed nor cancelled since): the ones keep_codec may be admitted on
+  std::vector<char> codec_ok_;
 
   // ---- first-frame previews (preview_enable)
   static constexpr int PV_MAX = 8;  // rows per preview pass (the small-tile back path: < 16 rows)

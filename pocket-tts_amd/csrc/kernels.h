@@ -587,7 +587,10 @@ void step_commit(const CommitArgs& a, hipStream_t s);
 
 // Admission reset of n slots (tts_model.rs:941 init_states per segment): zero the per-slot
 // regions of up to 10 state buffers, backbone input = bos, SlotState / FlowLM / Mimi positions
-// from the staged per-admission arrays (index i -> slots[i]).
+// from the staged per-admission arrays (index i -> slots[i]). Rows admitted behind a latent prefix
+// or onto their slot's codec state say so in opt_src[i].
+constexpr int RESET_KEEP_CODEC = 1;  // leave buf[] and mpos of the row as they are
+constexpr int RESET_LAT_SRC = 2;     // backbone input = lat_src[i] (the prefix's last latent), not bos
 struct ResetArgs {
   float* buf[10];
   long per_slot[10];
@@ -612,6 +615,9 @@ struct ResetArgs {
   const int* tempo_src = nullptr;
   int* tempo_sp = nullptr;
   int* tempo_state = nullptr;  // [max_slots][TEMPO_STATE]
+  // per-row RESET_* bits and staged backbone inputs [n][32] (null: no row of the admission has any)
+  const int* opt_src = nullptr;
+  const float* lat_src = nullptr;
 };
 void slot_reset(const ResetArgs& a, hipStream_t s);
 // The first-frame preview pass's inputs, one launch: row i < n gets the latent and frame flags of
@@ -634,6 +640,12 @@ void time_embeddings(const TimeEmbedWeights& w, int n, float* tmp, float* out, h
 
 // Token embedding gather: out[i] = table[ids[i]].
 void embed_gather(const int* ids, int n, const float* table, int dim, float* out, hipStream_t s);
+// The same for a prefill pass with latent-prefix rows (dim = 1024): src[i] >= 0 is a token id;
+// PREFILL_SRC_BOS: out[i] = input_linear(bos); PREFILL_SRC_LAT0 - k: out[i] = input_linear(lat[k]),
+// lat [*][32] staged latents, Wt the transposed input_linear weight [32][1024] (input_ln).
+constexpr int PREFILL_SRC_BOS = -1, PREFILL_SRC_LAT0 = -2;
+void prefill_input(const int* src, int n, const float* table, const float* lat, const float* bos, const float* Wt,
+                   int dim, float* out, hipStream_t s);
 
 // Strided copy: dst[r][c] = src[r][c] for rows x cols (used for small packing jobs).
 void copy2d(const float* src, long lds, float* dst, long ldd, int rows, int cols, hipStream_t s);

@@ -2988,9 +2988,8 @@ __global__ __launch_bounds__(256) void k_commit(CommitArgs a) {
 // over the 256 threads of the workgroup (one row): flow_lm.rs:117 input_linear +
 // transformer.rs:66-90 norm1 of layer 0. The weight arrives transposed, Wt [32][1024], so the 64
 // lanes of a wave read one contiguous 1-KB run of Wt[k] per load. lat: the row's 32 inputs.
-__device__ __forceinline__ void input_ln_row(const float* lat, const float* __restrict__ Wt,
-                                             const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                             float* __restrict__ xr, float* __restrict__ hr, float* sh) {
+// input_linear4 is the projection alone (the prefill's latent-prefix rows, k_prefill_input).
+__device__ __forceinline__ float4 input_linear4(const float* lat, const float* __restrict__ Wt) {
   const int n = 4 * threadIdx.x;  // N = 1024
   float4 lv[8];
 #pragma unroll
@@ -3010,7 +3009,14 @@ __device__ __forceinline__ void input_ln_row(const float* lat, const float* __re
     }
     acc[q] = t;
   }
-  const float4 v = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  return make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+__device__ __forceinline__ void input_ln_row(const float* lat, const float* __restrict__ Wt,
+                                             const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                             float* __restrict__ xr, float* __restrict__ hr, float* sh) {
+  const int n = 4 * threadIdx.x;  // N = 1024
+  const float4 v = input_linear4(lat, Wt);
   *reinterpret_cast<float4*>(xr + n) = v;
   const float mean = block_sum((v.x + v.y) + (v.z + v.w), sh) / 1024.f;
   const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
@@ -3075,16 +3081,19 @@ void step_commit(const CommitArgs& a, hipStream_t s) {
 __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
   const int i = blockIdx.x, b = blockIdx.y;
   const int slot = a.slots[i];
+  const int opt = a.opt_src ? a.opt_src[i] : 0;
   if (b < a.nb) {
+    if (opt & RESET_KEEP_CODEC) return;  // the row decodes on from the state its slot ended on
     float* p = a.buf[b] + (long)slot * a.per_slot[b];
     for (long e = threadIdx.x; e < a.per_slot[b]; e += 256) p[e] = 0.f;
     return;
   }
-  if (threadIdx.x < 32) a.lat_in[slot * 32 + threadIdx.x] = a.bos[threadIdx.x];
+  if (threadIdx.x < 32)
+    a.lat_in[slot * 32 + threadIdx.x] = (opt & RESET_LAT_SRC) ? a.lat_src[i * 32 + threadIdx.x] : a.bos[threadIdx.x];
   if (threadIdx.x == 0) {
     a.st[slot] = a.st_src[i];
     a.fpos[slot] = a.fpos_src[i];
-    a.mpos[slot] = 0;
+    if (!(opt & RESET_KEEP_CODEC)) a.mpos[slot] = 0;
     for (int q = 0; q < NHB_MAX; ++q)
       if (a.flags[q]) a.flags[q][slot] = FrameFlags{0, 0};
     if (a.wire_fmt) {
@@ -3182,6 +3191,32 @@ __global__ void k_embed(const int* ids, int n, const float* table, int dim, floa
 }
 void embed_gather(const int* ids, int n, const float* table, int dim, float* out, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_embed, dim3(n), dim3(256), 0, s, ids, n, table, dim, out);
+}
+
+// Input rows of a prefill pass that holds latent-prefix rows (one 256-thread block per compact row):
+// src[i] >= 0: the embedding row of that token, as k_embed; PREFILL_SRC_BOS: input_linear(bos);
+// below it: input_linear of staged latent PREFILL_SRC_LAT0 - src[i] (the projection of
+// input_ln_row, in its summation order: what a step computes from the same backbone input).
+__global__ __launch_bounds__(256) void k_prefill_input(const int* __restrict__ src, const float* __restrict__ table,
+                                                       const float* __restrict__ lat, const float* __restrict__ bos,
+                                                       const float* __restrict__ Wt, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float s_lat[32];
+  const int i = blockIdx.x, n = 4 * threadIdx.x;
+  const int v = src[i];  // uniform over the block
+  float4* dst = reinterpret_cast<float4*>(out + (long)i * 1024 + n);
+  if (v >= 0) {
+    *dst = *reinterpret_cast<const float4*>(table + (long)v * 1024 + n);
+    return;
+  }
+  if (threadIdx.x < 32)
+    s_lat[threadIdx.x] = v == PREFILL_SRC_BOS ? bos[threadIdx.x] : lat[(long)(PREFILL_SRC_LAT0 - v) * 32 + threadIdx.x];
+  __syncthreads();
+  *dst = input_linear4(s_lat, Wt);
+}
+void prefill_input(const int* src, int n, const float* table, const float* lat, const float* bos, const float* Wt,
+                   int dim, float* out, hipStream_t s) {
+  if (dim != 1024) throw std::runtime_error("prefill_input: dim must be 1024");
+  if (n > 0) hipLaunchKernelGGL(k_prefill_input, dim3(n), dim3(256), 0, s, src, table, lat, bos, Wt, out);
 }
 
 __global__ void k_copy2d(const float* src, long lds, float* dst, long ldd, int rows, int cols) {

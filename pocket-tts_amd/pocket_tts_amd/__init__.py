@@ -6,9 +6,9 @@ from .engine import Engine, GenerationParams, StepResult, Voice
 from .quantize import QuantizeConfig, QuantizedTensor, calculate_snr, quantize_weights
 from .text import (Tokenizer, estimate_frames_after_eos, load_tokenizer, max_gen_len, prepare_text_prompt,
                    split_into_best_sentences)
-from .tts_model import TTSModel
+from .tts_model import Continuation, TTSModel
 
-__all__ = ["Engine", "GenerationParams", "StepResult", "Voice", "TTSModel", "PocketTTSError", "FRAME",
+__all__ = ["Engine", "GenerationParams", "StepResult", "Voice", "TTSModel", "Continuation", "PocketTTSError", "FRAME",
            "SAMPLE_RATE", "LIB_PATH", "lib", "build_id", "source_build_id", "check_build_id", "prepare_text_prompt", "estimate_frames_after_eos", "max_gen_len",
            "Tokenizer", "load_tokenizer", "split_into_best_sentences", "QuantizeConfig", "QuantizedTensor",
            "quantize_weights", "calculate_snr", "QUANT_NONE", "QUANT_FLOW_LM", "QUANT_ALL", "BACK_F32", "BACK_BF16",

@@ -71,6 +71,16 @@ class SlotOpts(C.Structure):
     ]
 
 
+class SlotOpts2(C.Structure):
+    """ptts_slot_opts with the latent prefix and keep_codec (40 bytes; SlotOpts is the 24-byte struct
+    the wire formats introduced, which the library keeps reading as it always did)."""
+    _fields_ = SlotOpts._fields_ + [
+        ("prefix_latents", C.c_void_p),
+        ("n_prefix", C.c_int),
+        ("keep_codec", C.c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol include/pocket_tts.h (the boundary) and
 # include/pocket_tts_probe.h (measurement / test hooks) declare
 SIGNATURES = [

@@ -9,7 +9,7 @@ import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SlotOpts, check, fptr, lib, u8ptr)
+                   SlotOpts, SlotOpts2, check, fptr, lib, u8ptr)
 from .audio import speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
@@ -49,6 +49,20 @@ class GenerationParams:
     # speech speed of the row's wire bytes (tempo-enabled engines), 0.5 .. 2.0; None or 1.0: unchanged.
     # A speed with no wire format implies 24000 / 16-bit. The f32 PCM of fetch() never depends on it.
     speed: float | None = None
+    # latent prefix and codec continuity (ptts_slot_opts.prefix_latents / .keep_codec; DESIGN.md
+    # section 20): the row starts as if it had been teacher-forced through these [n, 32] FlowLM
+    # latents (values fetch() returned), and with keep_codec on the codec state its slot ended on.
+    prefix_latents: np.ndarray | None = None
+    keep_codec: bool = False
+
+    def prefix(self) -> np.ndarray | None:
+        """The prefix as a contiguous [n, 32] float32 array; None: no prefix."""
+        if self.prefix_latents is None:
+            return None
+        a = np.ascontiguousarray(self.prefix_latents, np.float32)
+        if a.ndim != 2 or a.shape[1] != LDIM:
+            raise ValueError(f"prefix_latents must be [n, {LDIM}], got {a.shape}")
+        return a if a.shape[0] else None
 
     def wire(self) -> tuple[int, int]:
         """(wire_rate, wire_encoding) of ptts_slot_opts; (0, 0): none."""
@@ -400,7 +414,7 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
-        if params.opts() != (0, 0, 0):
+        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec:
             return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
@@ -418,6 +432,15 @@ class Engine:
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
+        pre = [p.prefix() for p in params_list]  # (kept alive until the call returns)
+        if any(a is not None for a in pre) or any(p.keep_codec for p in params_list):
+            opts = (SlotOpts2 * n)(*[SlotOpts2(C.sizeof(SlotOpts2), int(lsd[i]), *p.opts(),
+                                               pre[i].ctypes.data if pre[i] is not None else None,
+                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec))
+                                     for i, p in enumerate(params_list)])
+            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
+            return
         if any(p.opts() != (0, 0, 0) for p in params_list):  # a wire format or a speed: ptts_slots_open_opts
             opts = (SlotOpts * n)(*[SlotOpts(C.sizeof(SlotOpts), int(lsd[i]), *p.opts())
                                     for i, p in enumerate(params_list)])

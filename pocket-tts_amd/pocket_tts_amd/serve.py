@@ -94,12 +94,12 @@ import struct
 import threading
 import time
 from collections import OrderedDict, deque
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
-from ._lib import FRAME, SAMPLE_RATE, WIRE_RATES
+from ._lib import FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
 from .audio import (ENCODINGS, pcm_i16_le_bytes, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes)
 from .engine import GenerationParams, Voice
@@ -320,6 +320,13 @@ class Request(_Consumer):
     sched: object = None   # the scheduler that holds the request (cancel())
     group: object = None   # the RequestGroup this request is a text segment of
     ended: bool = False    # the end marker was put
+    # continuity: a segment of a continuity group keeps the latents of its
+    # frames (lat; None: not kept), and one that follows another text segment with no pause in
+    # between names it (pred): it is admitted on pred's slot behind pred's ids and latents (own: the
+    # segment's own ids, which `ids` then follows pred's in)
+    lat: list | None = None
+    pred: object = None
+    own: np.ndarray | None = None
 
     def __post_init__(self):
         rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
@@ -353,8 +360,9 @@ class RequestGroup(_Consumer):
     active at once, the next one joining the tail of the scheduler's queue when one finishes.
     deliver() runs on the scheduler thread only."""
 
-    def __init__(self, sched, items, rows: int, wire):
+    def __init__(self, sched, items, rows: int, wire, continuity: bool = False):
         self.sched, self.items, self.rows, self.wire = sched, items, max(1, int(rows)), wire
+        self.continuity = bool(continuity)  # one segment at a time, each continuing the one before it
         self.out = FrameChannel()
         self.waker: Callable[[], None] | None = None
         self.times: dict = {"submit": time.time()}
@@ -443,6 +451,9 @@ class BatchScheduler:
         self.waiting: deque[Request] = deque()
         self.active: dict[int, Request] = {}
         self.cancels: deque = deque()  # requests / groups to stop at the next pass (cancel())
+        # continuity successors that were handed their predecessor's slot (already in `active`): they
+        # join the next batched admission
+        self.handoff: list[Request] = []
         # calls by which a fetched frame trails the step that computed it
         self.lag = int(bool(getattr(engine, "pipeline", False)))  # (an engine without frame_lag: one call if pipelined)
         if hasattr(engine, "frame_lag"):
@@ -485,20 +496,29 @@ class BatchScheduler:
         return req
 
     def submit_group(self, segments, voice: Voice | VoiceClip, wire: tuple[int, str] | None = None,
-                     segment_rows: int | None = None) -> RequestGroup:
+                     segment_rows: int | None = None, continuity: bool = False) -> RequestGroup:
         """A long-form request: segments in text order, ("text", ids, params) | ("pause", ms). Every
         text segment is an utterance of its own (the max_ctx rule of submit() applies to each); a
-        pause becomes silence, in the group's wire format (`wire`: (rate, encoding)) if it has one."""
+        pause becomes silence, in the group's wire format (`wire`: (rate, encoding)) if it has one.
+        continuity: the group runs one text segment at a time, and a segment
+        that follows another with no pause in between takes over its slot when its last frame is
+        delivered, admitted with the two segments' ids, the predecessor's delivered latents as a
+        teacher-forced prefix and keep_codec (where that exceeds max_ctx: as a plain segment). A
+        pause starts a new chain."""
         items = []
         for seg in segments:
             if seg[0] == "text":
                 items.append(self._new_request(seg[1], voice, seg[2]))
+                if continuity:
+                    items[-1].lat, items[-1].own = [], items[-1].ids
+                    if len(items) > 1 and isinstance(items[-2], Request):
+                        items[-1].pred = items[-2]
             elif wire is not None:
                 items.append(wire_bytes(np.zeros(silence_samples(seg[1], wire[0]), np.float32), wire[1]))
             else:
                 items.append(np.zeros(silence_samples(seg[1], SAMPLE_RATE), np.float32))
         rows = self.segment_rows if segment_rows is None else max(1, min(int(segment_rows), self.max_rows))
-        g = RequestGroup(self, items, rows, wire)
+        g = RequestGroup(self, items, 1 if continuity else rows, wire, continuity)
         with self.cv:
             if not self.running:
                 raise RuntimeError("scheduler stopped")
@@ -530,6 +550,7 @@ class BatchScheduler:
             mine = {id(r) for r in (t.segments if isinstance(t, RequestGroup) else [t])}
             if any(id(r) in mine for r in self.waiting):
                 self.waiting = deque(r for r in self.waiting if id(r) not in mine)
+            self.handoff = [r for r in self.handoff if id(r) not in mine]
             for slot, r in list(self.active.items()):
                 if id(r) in mine:
                     del self.active[slot]
@@ -586,10 +607,26 @@ class BatchScheduler:
         self.retired = []
 
     # -- driver thread
+    def _continue(self, req: Request, nxt: Request, slot: int) -> bool:
+        """(under self.cv) make `nxt` the continuation of `req`, whose last frame was just delivered
+        from `slot`: the two segments' ids, req's delivered latents (its EOS tail included) as the
+        prefix, keep_codec, on the same slot, in the next batched admission. False (nxt untouched: a
+        plain segment) where the engine's capacity rule would refuse it."""
+        pre = np.array(req.lat, np.float32).reshape(-1, LDIM)
+        voice = nxt.voice if nxt.voice is not None else nxt.clip
+        if voice.n_frames + req.own.size + nxt.own.size + pre.shape[0] + nxt.params.max_frames > self.engine.max_ctx:
+            return False
+        nxt.ids = np.concatenate([req.own, nxt.own])
+        nxt.params = replace(nxt.params, prefix_latents=pre, keep_codec=True)
+        nxt.slot = slot
+        self.active[slot] = nxt
+        self.handoff.append(nxt)
+        return True
+
     def _take(self) -> list[Request]:
         """(under self.cv) waiting requests that fit the free slots, slots assigned and reserved"""
         free = [s for s in range(self.max_rows) if s not in self.active]
-        batch = []
+        batch, self.handoff = self.handoff, []
         while self.waiting and free:
             req = self.waiting.popleft()
             req.slot = free.pop(0)
@@ -674,6 +711,8 @@ class BatchScheduler:
                     if fstep < req.start_step:  # still the cancelled row's frame
                         continue
                     self.stale.discard(slot)
+                if req.lat is not None:  # a continuity segment: what its successor is forced through
+                    req.lat.append(np.array(res.latents[slot], np.float32))
                 if req.preview == 1:  # frame 0, already delivered from the preview
                     req.preview = 2
                 else:
@@ -771,10 +810,14 @@ class BatchScheduler:
                     if done:
                         with self.cv:
                             for slot in done:
-                                g = self.active.pop(slot).group
+                                req = self.active.pop(slot)
+                                g = req.group
                                 # a long-form request's next segment joins the tail of the queue
                                 if g is not None and g.pending and not g.ended:
-                                    self.waiting.append(g.pending.popleft())
+                                    nxt = g.pending.popleft()
+                                    if nxt.pred is req and self._continue(req, nxt, slot):
+                                        continue  # the slot went straight to the successor
+                                    self.waiting.append(nxt)
                             if self.on_load is not None:
                                 self.on_load(len(self.active) + len(self.waiting))
         except BaseException as e:  # deliver the failure to every waiting client
@@ -812,9 +855,13 @@ class MultiGpuScheduler:
         i = min(range(len(self.schedulers)), key=lambda k: self.schedulers[k].load())
         return self.schedulers[i].submit(ids, voices if isinstance(voices, VoiceClip) else voices[i], params)
 
-    def submit_group(self, segments, voices: Sequence[Voice] | VoiceClip, wire=None) -> RequestGroup:
+    def submit_group(self, segments, voices: Sequence[Voice] | VoiceClip, wire=None,
+                     continuity: bool = False) -> RequestGroup:
         i = min(range(len(self.schedulers)), key=lambda k: self.schedulers[k].load())
-        return self.schedulers[i].submit_group(segments, voices if isinstance(voices, VoiceClip) else voices[i], wire)
+        v = voices if isinstance(voices, VoiceClip) else voices[i]
+        if continuity:
+            return self.schedulers[i].submit_group(segments, v, wire, continuity=True)
+        return self.schedulers[i].submit_group(segments, v, wire)
 
     def close(self):
         for s in self.schedulers:
@@ -973,8 +1020,11 @@ class TTSService:
                  tokenizer: Callable[[str], Sequence[int]] | None = None, temp: float = 0.7,
                  eos_threshold: float = -4.0, noise_clamp: float | None = None, lsd_decode_steps: int = 1,
                  max_lsd_steps: int | None = None, max_voice_seconds: float = 30.0, voice_chunk_frames: int = 0,
-                 voice_resampler: str = "poly", max_ctx: int | None = None, long_form: bool = False):
-        """long_form: whether a text request that does not say is split into segments on parallel
+                 voice_resampler: str = "poly", max_ctx: int | None = None, long_form: bool = False,
+                 continuity: bool = False):
+        """continuity: whether a text request that does not say runs its sentence chunks as a
+        continuity chain (request(continuity=...); it implies the long-form cut).
+        long_form: whether a text request that does not say is split into segments on parallel
         rows (request(long_form=...)).
         lsd_decode_steps: the Euler step count of a request that names none (the engine's own
         default). max_lsd_steps: the largest `lsd_steps` a request may ask for, the engine's cap
@@ -996,6 +1046,7 @@ class TTSService:
         self.lsd_decode_steps = lsd_decode_steps
         self.max_lsd_steps = lsd_decode_steps if max_lsd_steps is None else max_lsd_steps
         self.long_form = bool(long_form)
+        self.continuity = bool(continuity)
         self._seed = 0
         self._lock = threading.Lock()
 
@@ -1007,8 +1058,13 @@ class TTSService:
                 temperature: float | None = None, eos_threshold: float | None = None,
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None, sample_rate: int | None = None,
-                encoding: str | None = None, long_form: bool | None = None, speed: float | None = None) -> Request:
-        """speed: 0.5 .. 2.0, the row's wire bytes time-scaled on the GPU (None or 1.0: unchanged).
+                encoding: str | None = None, long_form: bool | None = None, speed: float | None = None,
+                continuity: bool | None = None) -> Request:
+        """continuity (None: the server's default, --continuity): the long-form
+        cut, with the sentence chunks of a text piece generated one after another on one slot, each
+        teacher-forced through the one before it and decoded on from its codec state, so prosody
+        and the codec run across the joins. token_ids are never split, so they cannot ask for it.
+        speed: 0.5 .. 2.0, the row's wire bytes time-scaled on the GPU (None or 1.0: unchanged).
         long_form (None: the server's default, --long-form): the text is split as the reference's
         routes split it (generate_stream_long: pause markers and natural pauses become silence,
         each text piece is cut into sentence chunks of at most 50 tokens) and the chunks run as
@@ -1016,6 +1072,9 @@ class TTSService:
         token_ids are never split."""
         if long_form and token_ids is not None:
             raise ValueError("long_form needs `text`: token_ids are never split")
+        if continuity and token_ids is not None:
+            raise ValueError("continuity needs `text`: token_ids are never split")
+        chain = token_ids is None and (self.continuity if continuity is None else bool(continuity))
         if sample_rate is not None or encoding is not None:
             if sample_rate is not None and sample_rate not in WIRE_RATES:
                 raise ValueError(f"sample_rate must be one of {list(WIRE_RATES)}")
@@ -1042,7 +1101,7 @@ class TTSService:
         elif text is not None:
             if self.tokenizer is None:
                 raise ValueError("no tokenizer configured: send token_ids")
-            if self.long_form if long_form is None else long_form:
+            if chain or (self.long_form if long_form is None else long_form):
                 segments = []  # ("text", ids, max_frames, frames_after_eos) | ("pause", ms), in text order
                 for kind, val in long_form_segments(text, self._count_tokens, pauses=True):
                     if kind == "text":
@@ -1071,6 +1130,8 @@ class TTSService:
                 wire = None  # (pauses: silence of their stated duration, whatever the speed)
                 if sample_rate is not None or encoding is not None or speed is not None:
                     wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
+                if chain:
+                    return self.scheduler.submit_group(segs, target, wire, continuity=True)
                 return self.scheduler.submit_group(segs, target, wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
                                        sample_rate, encoding, speed)
@@ -1186,6 +1247,8 @@ class GenerateRequest(BaseModel):
     speed: float | None = None
     # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
     long_form: bool | None = None
+    # the long-form cut with each sentence chunk continuing the one before it (None: --continuity)
+    continuity: bool | None = None
 
 
 class OpenAIRequest(BaseModel):
@@ -1201,6 +1264,7 @@ class OpenAIRequest(BaseModel):
     encoding: str | None = None
     speed: float | None = None  # 0.5 .. 2.0, as in the API this route imitates (0.25 .. 4.0 there)
     long_form: bool | None = None
+    continuity: bool | None = None
 
 
 # /stream: at most one chunk per stream per 20 ms after the first (32 streams x 50 wakes/s keep the
@@ -1354,7 +1418,7 @@ def create_app(service: TTSService):
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
-                   encoding=enc, long_form=req.long_form, speed=req.speed)
+                   encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity)
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
@@ -1385,6 +1449,7 @@ class StandInEngine:
         self.max_slots, self.max_ctx, self.pipeline = max_slots, max_ctx, True
         self.step_s = step_s
         self.rows, self.pending = {}, None
+        self.admit_log = []  # every admitted row: (slot, ids, prefix latents or None, keep_codec)
 
     @staticmethod
     def weight_blob_bytes():
@@ -1427,8 +1492,12 @@ class StandInEngine:
         self.voice_frames_reserved = int(max_frames)
 
     def open_many(self, slots, voices, ids_list, params_list):
+        """Records every admitted row in `admit_log`; the latents of admission a's frame k hold a * 1000 + k."""
         for s, ids, p in zip(slots, ids_list, params_list):
-            self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames]
+            pre = getattr(p, "prefix_latents", None)
+            self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames, len(self.admit_log)]
+            self.admit_log.append((int(s), [int(i) for i in ids], None if pre is None else np.array(pre, np.float32),
+                                  bool(getattr(p, "keep_codec", False))))
             if self.pending is not None and s < self.pending[1].size:  # drop the slot's undrained frame
                 self.pending[1][s] = False
 
@@ -1445,16 +1514,19 @@ class StandInEngine:
         if self.step_s:
             time.sleep(self.step_s)
         pcm, valid, last = np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool)
+        lat = np.zeros((n, LDIM), np.float32)
         for s, st in list(self.rows.items()):
             if s < n:
                 pcm[s], valid[s] = stand_in_sample(st[0], st[1]), True
+                lat[s] = st[3] * 1000 + st[1]
                 st[1] += 1
                 last[s] = st[1] == st[2]
                 if last[s]:
                     del self.rows[s]
-        prev, self.pending = self.pending, (pcm, valid, last)
+        prev, self.pending = self.pending, (pcm, valid, last, lat)
         self.prev_out = getattr(self, "out", None)
-        self.out = (np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool))
+        self.out = (np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool),
+                    np.zeros((n, LDIM), np.float32))
         if prev is not None:  # the previous call's frame, over this call's rows
             m = min(n, prev[1].size)
             for a, b in zip(self.out, prev):
@@ -1467,7 +1539,7 @@ class StandInEngine:
         from types import SimpleNamespace
 
         out = self.out if calls_back == 0 else self.prev_out
-        return SimpleNamespace(pcm=out[0], valid=out[1], last=out[2])
+        return SimpleNamespace(pcm=out[0], valid=out[1], last=out[2], latents=out[3])
 
     def close(self):
         pass
@@ -1572,6 +1644,9 @@ def main(argv=None):
     ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
                     help="default of requests that do not say `long_form`: split the text into pause and sentence "
                          "segments (the reference's generate_stream_long) and run them on parallel rows")
+    ap.add_argument("--continuity", action=argparse.BooleanOptionalAction, default=False,
+                    help="default of requests that do not say `continuity`: the long-form cut, each sentence chunk "
+                         "teacher-forced through the one before it and decoded on from its codec state")
     ap.add_argument("--segment-rows", type=int, default=4,
                     help="text segments of one long-form request that may be waiting or active at once "
                          "(clamped to --slots)")
@@ -1633,7 +1708,8 @@ def main(argv=None):
     service = TTSService(scheduler, voices, default_voice=next(iter(voices)),
                          tokenizer=load_tokenizer(args.tokenizer) if args.tokenizer else None,
                          lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
-                         max_voice_seconds=args.max_voice_seconds, long_form=args.long_form)
+                         max_voice_seconds=args.max_voice_seconds, long_form=args.long_form,
+                         continuity=args.continuity)
     service.worker = {"rank": rank, "world": world, "pid": os.getpid(), "weights_checksum": checksum}
     socks = [_listen_socket(args.host, args.port)]
     board = None

@@ -23,6 +23,7 @@ is accepted too (one segment, no splitting).
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Callable, Iterator, Sequence
 
 import numpy as np
@@ -35,7 +36,19 @@ from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments
 
 DEFAULT_VARIANT = "b6369a24"
 
-__all__ = ["TTSModel", "prepare_text_prompt", "estimate_frames_after_eos", "max_gen_len", "DEFAULT_VARIANT"]
+__all__ = ["TTSModel", "Continuation", "prepare_text_prompt", "estimate_frames_after_eos", "max_gen_len",
+           "DEFAULT_VARIANT"]
+
+
+@dataclass
+class Continuation:
+    """What the next link of a continuity chain needs of the one before it (generate_continued;
+    DESIGN.md section 20): the segment's own token ids, the latents of every frame it delivered
+    (its EOS tail included) and the engine slot whose codec state it ended on."""
+
+    ids: np.ndarray
+    latents: np.ndarray
+    slot: int = 0
 
 
 def _mono(audio: np.ndarray) -> np.ndarray:
@@ -181,15 +194,24 @@ class TTSModel:
                              "(max_lsd_decode_steps at load)")
 
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
-                 sample_rate: int | None = None, encoding=None, speed: float | None = None) -> Iterator[np.ndarray]:
+                 sample_rate: int | None = None, encoding=None, speed: float | None = None,
+                 previous: Continuation | None = None, latents: list | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
         (sample_rate / encoding; a wire-enabled engine) or a speed (a tempo-enabled one; 24 kHz
         16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
-        GPU (Engine.fetch_wire), instead of f32 frames."""
+        GPU (Engine.fetch_wire), instead of f32 frames.
+        previous: the segment continues that one (section 20): admitted behind its ids and, as a
+        teacher-forced prefix, its latents, on the codec state it left (only the new frames are
+        yielded); where that exceeds the engine's max_ctx, as a plain segment. latents: a list that
+        receives the latent of every frame yielded."""
         self._check_lsd()
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
         params.sample_rate, params.encoding, params.speed = sample_rate, encoding, speed
+        if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
+                                     + max_frames <= self.engine.max_ctx):
+            ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
+            params.prefix_latents, params.keep_codec = np.asarray(previous.latents, np.float32), True
         wire = params.opts() != (0, 0, 0)
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
@@ -202,6 +224,8 @@ class TTSModel:
                     continue
                 return
             lead = 0
+            if latents is not None:
+                latents.append(np.array(r.latents[0], np.float32))
             yield self.engine.fetch_wire(1)[0] if wire else r.pcm[0].reshape(1, 1, FRAME).copy()
             if r.last[0]:
                 return
@@ -249,17 +273,59 @@ class TTSModel:
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
 
-    def generate_stream_long(self, text: str, voice_state: Voice) -> Iterator[np.ndarray]:
-        """tts_model.rs:1074-1131: text segments between pause markers, silence for each pause."""
+    def generate_stream_long(self, text: str, voice_state: Voice, continuity: bool = False) -> Iterator[np.ndarray]:
+        """tts_model.rs:1074-1131: text segments between pause markers, silence for each pause.
+        continuity (what tts_model.py:397-400 of the reference names and leaves
+        out): the sentence chunks of one text piece run one after another on one slot, chunk k+1
+        admitted with ids = ids(chunk k) ++ ids(chunk k+1), every delivered latent of chunk k as a
+        teacher-forced prefix and keep_codec, so neither the prosody nor the codec restarts at the
+        join; only the new frames are yielded. A pause starts a new chain."""
         for kind, val in long_text_segments(text):
-            if kind == "text":
+            if kind != "text":
+                yield np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)
+            elif not continuity:
                 yield from self.generate_stream(val, voice_state)
             else:
-                yield np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)
+                prev = None
+                for chunk in self.split_into_best_sentences(val):
+                    link = self._link(chunk, voice_state, prev)
+                    yield from link
+                    prev = link.continuation
 
-    def generate_with_pauses(self, text: str, voice_state: Voice) -> np.ndarray:
+    def _link(self, chunk: str, voice_state: Voice, previous: Continuation | None):
+        """One sentence chunk as a link of a continuity chain: an iterator over its frames whose
+        `continuation` is complete once it is exhausted."""
+        prepared = prepare_text_prompt(chunk)
+        ids = np.asarray(self._tok()(prepared), np.int32)
+        lat: list = []
+        frames = self._segment(ids, voice_state, max_gen_len(prepared), estimate_frames_after_eos(chunk),
+                               previous=previous, latents=lat)
+
+        class Link:
+            continuation = None
+
+            def __iter__(link):
+                yield from frames
+                link.continuation = Continuation(ids, np.array(lat, np.float32).reshape(-1, 32), 0)
+
+        return Link()
+
+    def generate_continued(self, text: str, voice_state: Voice,
+                           previous: Continuation | None = None) -> tuple[np.ndarray, Continuation]:
+        """One link of a continuity chain (section 20): `text` as ONE segment (no sentence split),
+        continuing `previous` (the Continuation an earlier call returned; None: a plain segment).
+        Returns the new audio [1, N*1920] and the Continuation to hand to the next call. The chain
+        lives on engine row 0: nothing else may be generated on this model between two links that
+        are to join seamlessly."""
+        link = self._link(text, voice_state, previous)
+        frames = list(link)
+        if not frames:
+            raise RuntimeError("No audio generated")
+        return np.concatenate(frames, axis=2)[0], link.continuation
+
+    def generate_with_pauses(self, text: str, voice_state: Voice, continuity: bool = False) -> np.ndarray:
         """tts_model.rs:856-883."""
-        chunks = list(self.generate_stream_long(text, voice_state))
+        chunks = list(self.generate_stream_long(text, voice_state, continuity))
         if not chunks:
             raise RuntimeError("No audio generated")
         return np.concatenate(chunks, axis=2)[0]
