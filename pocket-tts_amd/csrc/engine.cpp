@@ -78,6 +78,50 @@ float* Engine::dalloc(size_t n) {
   return (float*)p;
 }
 
+// dalloc's pinned-host counterpart (not zeroed): freed by the destructor's one loop
+void* Engine::halloc(size_t bytes) {
+  void* p = nullptr;
+  PTTS_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+  hallocs_.push_back(p);
+  return p;
+}
+
+// The back part's workspace and codec state for `rows` rows and passes of up to nfr frames, all zero:
+// the fresh state every utterance starts from
+Engine::BackBufs Engine::back_alloc(int rows, int nfr) {
+  const size_t P = (size_t)rows, BF = P * nfr;  // utterance frames of one pass
+  BackBufs b;
+  b.ring = dalloc((size_t)ring_slot_ * P);
+  b.mpos = (int*)dalloc(P);
+  // overlap-add history [row][512] (the last committed frame's quantizer output) and the
+  // pass's quantizer outputs [row][NFR_MAX][512], copied into it by the commit (quant_upsample)
+  b.qprev = dalloc((size_t)(1 + NFR_MAX) * P * MD);
+  b.qcur = b.qprev + P * MD;
+  b.mx = dalloc(BF * UP * MD);
+  b.mh = dalloc(BF * UP * MD);
+  b.mq = dalloc(BF * UP * MD);
+  b.mo = dalloc(BF * UP * MD);
+  b.mqkv = dalloc(BF * UP * 3 * MD);
+  b.mu = dalloc(BF * UP * MFF);
+  b.a0 = dalloc(BF * 16 * 512);
+  int T = 16, ch = 512;
+  for (int i = 0; i < 3; ++i) {
+    T *= RATIOS[i];
+    ch /= 2;
+    b.cb[i] = dalloc(BF * T * ch);
+    b.ce[i] = dalloc(BF * T * ch);
+    b.cv[i] = dalloc(BF * T * (ch / 2));
+    b.ca[i] = dalloc(BF * T * ch);
+  }
+  // split-K slabs: up to 8 slices of the Mimi / conv0 rows (rows * 16 x 512), 4 of the stage-0
+  // transposed conv (rows * 16 x 6 * 256), per frame of a pass
+  b.mpcap = (size_t)nfr * std::max({(size_t)8 * P * UP * MD, (size_t)4 * P * UP * RATIOS[0] * (MD / 2)});
+  b.mpartial = dalloc(b.mpcap);
+  for (int i = 0; i < 8; ++i) b.hist[i] = dalloc(P * hist_P_[i] * hist_C_[i]);
+  b.fin_side = dalloc(P * (nfr * FRAME / RESBLOCK_FIN_TT) * 2);
+  return b;
+}
+
 Engine::Engine(const ptts_engine_config& cfg) {
   check_model_config(cfg.cfg_yaml);  // before any device work
   PTTS_REQUIRE(cfg.max_slots >= 1 && cfg.max_slots <= 256, "max_slots must be in [1, 256]");
@@ -113,21 +157,20 @@ Engine::Engine(const ptts_engine_config& cfg) {
   }
 
   const int B = max_slots_;
-  kv_layer_ = (long)2 * NH * max_ctx_ * 64;
-  kv_slot_ = kv_layer_ * NL;
-  kv_ = dalloc((size_t)kv_slot_ * B);
+  fbm_.kv_layer = (long)2 * NH * max_ctx_ * 64;
+  fbm_.kv = KvStore{dalloc((size_t)fbm_.kv_layer * NL * B), fbm_.kv_layer * NL, max_ctx_};
   ring_layer_ = (long)2 * MNH * RING * 64;
   ring_slot_ = ring_layer_ * MNL;
-  ring_ = dalloc((size_t)ring_slot_ * B);
+  // streaming conv histories (SEANetDecoder, seanet.rs:307-402): source T, channels, rows kept
+  const int hT[8] = {16, 16, 96, 96, 480, 480, 1920, 1920};
+  const int hC[8] = {512, 512, 256, 256, 128, 128, 64, 64};
+  const int hP[8] = {6, 1, 2, 1, 2, 1, 2, 2};
+  for (int i = 0; i < 8; ++i) hist_T_[i] = hT[i], hist_C_[i] = hC[i], hist_P_[i] = hP[i];
+  bbm_ = back_alloc(B, nfr_);
   fpos_ = (int*)dalloc(B);
-  mpos_ = (int*)dalloc(B);
   st_ = (SlotState*)dalloc((sizeof(SlotState) * B + 3) / 4);
   lat_in_ = dalloc((size_t)B * LDIM);
   cur_ = dalloc((size_t)B * LDIM);
-  // overlap-add history [slot][512] (the last committed frame's quantizer output) and the
-  // pass's quantizer outputs [slot][NFR_MAX][512], copied into it by the commit (quant_upsample)
-  qprev_ = dalloc((size_t)(1 + NFR_MAX) * B * MD);
-  qcur_ = qprev_ + (size_t)B * MD;
   eos_ = dalloc(B);
   static_assert(sizeof(FrameFlags) == 2 * sizeof(float), "FrameFlags packs into two floats");
   meta_floats_ = (size_t)B * (LDIM + 1 + 2);
@@ -139,7 +182,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
     for (int p = 0; p < nhb_ / nfr_; ++p) {
       const size_t n = (size_t)B * nfr_ * FRAME + nfr_ * mstride;
       pcmp_[p] = dalloc(n);
-      PTTS_HIP(hipHostMalloc((void**)&h_pcmp_[p], sizeof(float) * n, hipHostMallocDefault));
+      h_pcmp_[p] = (float*)halloc(sizeof(float) * n);
     }
   for (int q = 0; q < NHB; ++q) {  // front -> back hand-off buffers
     meta_[q] = nfr_ > 1 && q < nhb_ ? pcmp_[q / nfr_] + (size_t)B * nfr_ * FRAME + (q % nfr_) * mstride
@@ -149,39 +192,20 @@ Engine::Engine(const ptts_engine_config& cfg) {
     eos_out_[q] = meta_[q] + (size_t)B * (LDIM + 2);
     pcm_[q] = dalloc((size_t)B * FRAME);
   }
-  fin_side_ = dalloc((size_t)B * (nfr_ * FRAME / RESBLOCK_FIN_TT) * 2);  // fused final conv's boundary shares
-  PTTS_HIP(hipHostMalloc((void**)&h_act_, sizeof(SlotState) * B, hipHostMallocDefault));
-  // back part's own split-K slabs: up to 8 slices of the Mimi / conv0 rows (B * 16 x 512), 4 of the
-  // stage-0 transposed conv (B * 16 x 6 * 256), per frame of a pass
-  mpcap_ = (size_t)nfr_ * std::max({(size_t)8 * B * UP * MD, (size_t)4 * B * UP * RATIOS[0] * (MD / 2)});
-  mpartial_ = dalloc(mpcap_);
-
-  // streaming conv histories (SEANetDecoder, seanet.rs:307-402): source T, channels, rows kept
-  const int hT[8] = {16, 16, 96, 96, 480, 480, 1920, 1920};
-  const int hC[8] = {512, 512, 256, 256, 128, 128, 64, 64};
-  const int hP[8] = {6, 1, 2, 1, 2, 1, 2, 2};
-  for (int i = 0; i < 8; ++i) {
-    hist_T_[i] = hT[i];
-    hist_C_[i] = hC[i];
-    hist_P_[i] = hP[i];
-    hist_[i] = dalloc((size_t)B * hP[i] * hC[i]);
-  }
+  h_act_ = (SlotState*)halloc(sizeof(SlotState) * B);
 
   const int R = std::max(B, PREFILL);
-  x_ = dalloc((size_t)R * D);
-  h_ = dalloc((size_t)R * D);
-  q_ = dalloc((size_t)R * D);
-  o_ = dalloc((size_t)R * D);
-  u_ = dalloc((size_t)R * FF);
+  fbm_.x = dalloc((size_t)R * D);
+  fbm_.h = dalloc((size_t)R * D);
+  fbm_.q = dalloc((size_t)R * D);
+  fbm_.o = dalloc((size_t)R * D);
+  fbm_.u = dalloc((size_t)R * FF);
   // split-K slabs: skinny FlowLM/head GEMMs, and the 2-way split Mimi QKV (B*16 rows x 1536)
-  pcap_ = std::max({(size_t)4 << 20, (size_t)2 * B * UP * 3 * MD, (size_t)PREFILL * FF});
-  partial_ = dalloc(pcap_);
-  tslab_ = dalloc(TAIL_CAP);
-  tickets_ = (int*)dalloc(TICKETS);  // zero; every split-tail launch leaves them zero
-  fbm_.x = x_, fbm_.h = h_, fbm_.q = q_, fbm_.o = o_, fbm_.u = u_, fbm_.partial = partial_;
-  fbm_.pcap = pcap_, fbm_.tslab = tslab_, fbm_.tail_cap = (long)TAIL_CAP, fbm_.tickets = tickets_;
-  fbm_.kv = KvStore{kv_, kv_slot_, max_ctx_};
-  fbm_.kv_layer = kv_layer_;
+  fbm_.pcap = std::max({(size_t)4 << 20, (size_t)2 * B * UP * 3 * MD, (size_t)PREFILL * FF});
+  fbm_.partial = dalloc(fbm_.pcap);
+  fbm_.tslab = dalloc(TAIL_CAP);
+  fbm_.tail_cap = (long)TAIL_CAP;
+  fbm_.tickets = (int*)dalloc(TICKETS);  // zero; every split-tail launch leaves them zero
   ids_dev_ = (int*)dalloc(PREFILL);
   rowtab_dev_ = (int*)dalloc(PREFILL);
   ctab_dev_ = (int*)dalloc(PREFILL);
@@ -202,6 +226,10 @@ Engine::Engine(const ptts_engine_config& cfg) {
   slot_lsd_.assign(B, 0);
   cancelled_.assign(B, 0);
   share_voice_ = probe_env("PTTS_NO_SHARED_VOICE") == nullptr;
+  if (share_voice_) {  // positions below a slot's voice length read the voice's own cache
+    fbm_.kv.pre = vpre_;
+    fbm_.kv.pre_len = vlen_;
+  }
 #ifdef PTTS_PROBES
   if (probe_env("PTTS_STAMPS")) {
     stamp_ring_ = (unsigned long long*)dalloc((size_t)STAMP_CAP * 4);
@@ -233,51 +261,33 @@ Engine::Engine(const ptts_engine_config& cfg) {
   PTTS_HIP(hipDeviceSynchronize());                    // null-stream memset: see dalloc
   hctr_ = (int*)dalloc(4 * ((B + 15) / 16) + 4);
   herr_ = (int*)dalloc(4);
-  const size_t BF = (size_t)B * nfr_;  // utterance frames of one back-part pass
-  mx_ = dalloc(BF * UP * MD);
-  mh_ = dalloc(BF * UP * MD);
-  mq_ = dalloc(BF * UP * MD);
-  mo_ = dalloc(BF * UP * MD);
-  mqkv_ = dalloc(BF * UP * 3 * MD);
-  mu_ = dalloc(BF * UP * MFF);
-  a0_ = dalloc(BF * 16 * 512);
-  int T = 16, ch = 512;
-  for (int i = 0; i < 3; ++i) {
-    T *= RATIOS[i];
-    ch /= 2;
-    cb_[i] = dalloc(BF * T * ch);
-    ce_[i] = dalloc(BF * T * ch);
-    cv_[i] = dalloc(BF * T * (ch / 2));
-    ca_[i] = dalloc(BF * T * ch);
-    trb_[i] = dalloc((size_t)RATIOS[i] * ch);
-  }
-  temb_ = dalloc((size_t)temb_row0(lsd_ + 1) * FD);  // every count 1 .. lsd_, triangular (finalize)
+  for (int i = 0, ch = MD / 2; i < 3; ++i, ch /= 2) trb_[i] = dalloc((size_t)RATIOS[i] * ch);
+  temb_ =dalloc((size_t)temb_row0(lsd_ + 1) * FD);  // every count 1 .. lsd_, triangular (finalize)
   rope_ = dalloc((size_t)max_ctx_ * 64);
   temb_tmp_ = dalloc((size_t)2 * lsd_ * FD);
 
   for (int q = 0; q < NHB; ++q) {
-    PTTS_HIP(hipHostMalloc((void**)&h_pcm_[q], sizeof(float) * B * FRAME, hipHostMallocDefault));
-    if (nfr_ > 1 && q < nhb_)  // inside the pass's pinned block (above)
-      h_meta_[q] = h_pcmp_[q / nfr_] + (size_t)B * nfr_ * FRAME + (q % nfr_) * ((meta_floats_ + 31) / 32 * 32);
-    else
-      PTTS_HIP(hipHostMalloc((void**)&h_meta_[q], sizeof(float) * meta_floats_, hipHostMallocDefault));
+    h_pcm_[q] = (float*)halloc(sizeof(float) * B * FRAME);
+    // inside the pass's pinned block (above), or a block of its own
+    h_meta_[q] = nfr_ > 1 && q < nhb_ ? h_pcmp_[q / nfr_] + (size_t)B * nfr_ * FRAME + (q % nfr_) * mstride
+                                      : (float*)halloc(sizeof(float) * meta_floats_);
     memset(h_meta_[q], 0, sizeof(float) * meta_floats_);
   }
-  PTTS_HIP(hipHostMalloc((void**)&h_err_, sizeof(int), hipHostMallocDefault));
+  h_err_ = (int*)halloc(sizeof(int));
   *h_err_ = 0;
-  PTTS_HIP(hipHostMalloc((void**)&h_slots_, sizeof(int) * B, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_st_, sizeof(SlotState) * B, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_idle_, sizeof(SlotState), hipHostMallocDefault));
+  h_slots_ = (int*)halloc(sizeof(int) * B);
+  h_st_ = (SlotState*)halloc(sizeof(SlotState) * B);
+  h_idle_ = (SlotState*)halloc(sizeof(SlotState));
   *h_idle_ = SlotState{};
   h_idle_->eos_step = -1;
-  PTTS_HIP(hipHostMalloc((void**)&h_fp_, sizeof(int) * B, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_ids_, sizeof(int) * PREFILL, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_tab_, sizeof(int) * 4 * PREFILL, hipHostMallocDefault));  // ptab | ctab | qrow | orow
-  PTTS_HIP(hipHostMalloc((void**)&h_plat_, sizeof(float) * PREFILL * LDIM, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_alat_, sizeof(float) * B * LDIM, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_aopt_, sizeof(int) * B, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_vpre_, sizeof(float*) * B, hipHostMallocDefault));
-  PTTS_HIP(hipHostMalloc((void**)&h_vlen_, sizeof(int) * B, hipHostMallocDefault));
+  h_fp_ = (int*)halloc(sizeof(int) * B);
+  h_ids_ = (int*)halloc(sizeof(int) * PREFILL);
+  h_tab_ = (int*)halloc(sizeof(int) * 4 * PREFILL);  // ptab | ctab | qrow | orow
+  h_plat_ = (float*)halloc(sizeof(float) * PREFILL * LDIM);
+  h_alat_ = (float*)halloc(sizeof(float) * B * LDIM);
+  h_aopt_ = (int*)halloc(sizeof(int) * B);
+  h_vpre_ = (const float**)halloc(sizeof(const float*) * B);
+  h_vlen_ = (int*)halloc(sizeof(int) * B);
   memset(h_vpre_, 0, sizeof(float*) * B);
   memset(h_vlen_, 0, sizeof(int) * B);
   PTTS_HIP(hipStreamCreateWithFlags(&stream_be_, hipStreamNonBlocking));
@@ -331,10 +341,8 @@ Engine::~Engine() {
   for (auto& kv : graph_defs_) (void)hipGraphDestroy(kv.second);
   for (auto& kv : pv_graphs_) (void)hipGraphExecDestroy(kv.second);
   for (auto& kv : pv_graph_defs_) (void)hipGraphDestroy(kv.second);
-  for (PvEntry& q : pv_q_) {
+  for (PvEntry& q : pv_q_)
     if (q.ev) (void)hipEventDestroy(q.ev);
-    if (q.h_pcm) (void)hipHostFree(q.h_pcm);
-  }
   for (int q = 0; q < NHB; ++q)
     if (ev_pv_read_[q]) (void)hipEventDestroy(ev_pv_read_[q]);
   if (ev_pv_front_) (void)hipEventDestroy(ev_pv_front_);
@@ -354,22 +362,7 @@ Engine::~Engine() {
     if (e) (void)hipEventDestroy(e);
   if (stream_vc_) (void)hipStreamDestroy(stream_vc_);
   for (void* p : allocs_) (void)hipFree(p);
-  for (int q = 0; q < NHB; ++q) {
-    if (h_pcm_[q]) (void)hipHostFree(h_pcm_[q]);
-    if (h_meta_[q] && !(nfr_ > 1 && q < nhb_)) (void)hipHostFree(h_meta_[q]);
-  }
-  for (int p = 0; p < NHB / 2; ++p)
-    if (h_pcmp_[p]) (void)hipHostFree(h_pcmp_[p]);
-  if (h_act_) (void)hipHostFree(h_act_);
-  if (h_idle_) (void)hipHostFree(h_idle_);
-  if (h_wire_) (void)hipHostFree(h_wire_);
-  if (h_tempo_) (void)hipHostFree(h_tempo_);
-  for (unsigned char* hp : h_wireb_)
-    if (hp) (void)hipHostFree(hp);
-  if (h_err_) (void)hipHostFree(h_err_);
-  for (void* hp : {(void*)h_slots_, (void*)h_st_, (void*)h_fp_, (void*)h_ids_, (void*)h_tab_, (void*)h_vpre_,
-                   (void*)h_vlen_, (void*)h_plat_, (void*)h_alat_, (void*)h_aopt_})
-    if (hp) (void)hipHostFree(hp);
+  for (void* p : hallocs_) (void)hipHostFree(p);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -627,7 +620,7 @@ void Engine::finalize() {
 }
 
 void Engine::run_ops(const std::vector<Op>& ops) {
-  xh_dirty_ = true;  // the admission's text prefill uses x_ / h_ as scratch
+  xh_dirty_ = true;  // the admission's text prefill uses fbm_.x / fbm_.h as scratch
   run_ops_on(ops, stream_);
 }
 
@@ -708,9 +701,8 @@ void Engine::derive_fp8() {
 
 // ------------------------------------------------------------------ op builders
 void Engine::linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M,
-                          const float* Wt, int N, int K, int* S_out, const FlowBufs* fbp) {
+                          const float* Wt, int N, int K, int* S_out, const FlowBufs& fb) {
   PTTS_REQUIRE(K % 32 == 0, "GEMM K must be a multiple of 32");
-  const FlowBufs& fb = fbp ? *fbp : fbm_;  // the slabs and the tail scratch the launch writes
   int S = pick_splits(M, N, K);
   int layout = TILE_KSPLIT_4W, tail = 0;
   // wide skinny GEMMs (FlowLM qkv/ff1, flow-head adaLN): 32x128 LDS-DMA tiles, 8-way split-K
@@ -848,12 +840,12 @@ void Engine::dense_op(std::vector<Op>& ops, const std::string& name, const float
 void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float* X, int B, int T_in, int cin,
                      const float* H, int P, int stride, int elu, const float* Wt, int cout, int ktaps, int phases,
                      const float* bias, const float* R, float* Y, int T_out, int tstride, int layout, int elu_out,
-                     float* Y2, int ksplit) {
+                     float* Y2, int ksplit, float* slabs, size_t slab_cap) {
   tile_override(name, layout, ksplit);
   const TileInfo& tile = tile_of(layout);
   PTTS_REQUIRE(cin % tile.bk == 0, "conv cin must be a multiple of the tile's BK");
   // ksplit > 1: single-phase conv on an LDS-DMA tile, K split into ksplit partial slabs in the
-  // back part's slab buffer; the caller adds the row-reduce epilogue
+  // caller's slab buffer; the caller adds the row-reduce epilogue
   PTTS_REQUIRE(ksplit == 1 || (phases == 1 && tile.lds_dma()), "K-split convs need a single-phase LDS-DMA tile");
   GemmArgs a{};
   a.mode = 1;
@@ -886,9 +878,9 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
   const int nph = phases;
   attach_split(a);
   if (ksplit > 1) {
-    PTTS_REQUIRE((size_t)ksplit * a.M * a.N <= mpcap_, "back split-K slab buffer too small");
+    PTTS_REQUIRE((size_t)ksplit * a.M * a.N <= slab_cap, "back split-K slab buffer too small");
     a.S = ksplit;
-    a.partial = mpartial_;
+    a.partial = slabs;
     phases = ksplit;  // grid z
   }
   ops.push_back({name, [a, phases](hipStream_t s) { gemm(a, phases, s); }, 2.0 * a.M * a.N * a.K * nph,
@@ -896,31 +888,23 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
                         (double)B * T_out * cout * ((R ? 2 : 1) + (Y2 ? 1 : 0)))});
 }
 
-// FlowLM transformer layers over M rows (x_ holds the residual stream, h_ = norm1_0(x_)).
-// StreamingTransformerLayer::forward (transformer.rs:66-90).
+// FlowLM transformer layers over M rows of the workspace fb (fb.x holds the residual stream, fb.h =
+// norm1_0(fb.x)). StreamingTransformerLayer::forward (transformer.rs:66-90).
 void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
-                         const FlowBufs* fbp) {
-  // the engine's own buffers (step and admission graphs), or a voice job's: the names below shadow
-  // the members on purpose, so every access in this function goes through the struct
-  const FlowBufs& fb = fbp ? *fbp : fbm_;
-  float *const x_ = fb.x, *const h_ = fb.h, *const q_ = fb.q, *const o_ = fb.o, *const u_ = fb.u,
-               *const partial_ = fb.partial;
-  PTTS_REQUIRE(!fbp || !step, "step passes run on the engine's own buffers");
+                         const FlowBufs& fb) {
+  // (the step's fused launches hand over through hfrag_ / ffn_hand_, of which there is one set)
+  PTTS_REQUIRE(!step || &fb == &fbm_, "step passes run on the engine's own buffers");
   for (int l = 0; l < NL; ++l) {
     const Layout::TL& t = L_.fl[l];
     const std::string p = tag + ".l" + std::to_string(l);
     KvStore kv = fb.kv;
     kv.base += (long)l * fb.kv_layer;
-    if (!fbp && share_voice_) {  // positions below a slot's voice length read the voice's own cache
-      kv.pre = vpre_;
-      kv.pre_len = vlen_;
-      kv.layer = l;
-    }
+    if (kv.pre) kv.layer = l;  // shared voice prefixes (fbm_)
     int S = 1;
-    linear_split(ops, p + ".qkv_gemm", h_, D, M, W(t.in_proj), 3 * D, D, &S, fbp);
+    linear_split(ops, p + ".qkv_gemm", fb.h, D, M, W(t.in_proj), 3 * D, D, &S, fb);
     if (step) {  // step: slab sum + RoPE + KV append fused into the attention kernel
-      const float* P = partial_;
-      float* O = o_;
+      const float* P = fb.partial;
+      float* O = fb.o;
       const float* rope = rope_;
       // K and V of every head over the cached positions the launch reads (8,192 B per position):
       // each row's own positions, plus ONE copy of every distinct shared voice prefix (the rows of
@@ -933,12 +917,12 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
                      8192.0 * kvu + (double)M * (4.0 * (S * 3.0 * D + 2.0 * D + D) + 64.0 * 4 * 2)});
     } else {
       {
-        const float* P = partial_;
-        float* Q = q_;
+        const float* P = fb.partial;
+        float* Q = fb.q;
         ops.push_back({p + ".qkv_rope", [=](hipStream_t s) { qkv_rope_append(P, S, nullptr, M, NH, map, kv, Q, s); }});
       }
-      const float* Q = q_;
-      float* O = o_;
+      const float* Q = fb.q;
+      float* O = fb.o;
       RowMap am = map;  // compact admission: the attention runs on the padded 16-row groups
       int Ma = M;
       if (map.ptab) {
@@ -951,13 +935,13 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
                   const float* lnb, bool ln, float* Hout, float* Hfrag = nullptr) {
       RowReduceArgs a{};
       a.Hfrag = Hfrag;
-      a.P = partial_;
+      a.P = fb.partial;
       a.S = S2;
       a.M = M;
       a.N = N;
       a.act = act;
       if (resid) {
-        a.R = x_;
+        a.R = fb.x;
         a.ldr = D;
       }
       a.Y = Y;
@@ -970,12 +954,12 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
       a.ldh = N;
       push_rr(ops, name, a);
     };
-    linear_split(ops, p + ".out_gemm", o_, D, M, W(t.out_proj), D, D, &S, fbp);
+    linear_split(ops, p + ".out_gemm", fb.o, D, M, W(t.out_proj), D, D, &S, fb);
     // step passes with the whole-K linear1 (gemv_fk): the out reduce also stores norm2's output in
     // its A-fragment order, and linear1 applies GELU in its own epilogue (no slabs, no reduce)
     auto fk = step && gemv_fk_supported(M, FF, D) ? fkmap_.find(W(t.l1)) : fkmap_.end();
     const bool use_fk = fk != fkmap_.end() && hfrag_;
-    rr(p + ".out_reduce_ln2", S, D, ACT_NONE, true, x_, W(t.n2w), W(t.n2b), true, h_, use_fk ? hfrag_ : nullptr);
+    rr(p + ".out_reduce_ln2", S, D, ACT_NONE, true, fb.x, W(t.n2w), W(t.n2b), true, fb.h, use_fk ? hfrag_ : nullptr);
     auto ffn = use_fk && ffn_hand_ ? ffnmap_.find(W(t.l2)) : ffnmap_.end();
     if (ffn != ffnmap_.end()) {
       // linear1 + GELU + linear2 in one launch (16 K slices of linear2 into the slabs): layer l uses
@@ -983,7 +967,7 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
       // set 0 for the next step's first, NL even)
       static_assert(NL % 2 == 0, "the fused FFN's hand-off sets alternate by layer");
       const float *A = hfrag_, *P1 = fk->second, *P2 = ffn->second;
-      float *hand = ffn_hand_, *Pp = partial_;
+      float *hand = ffn_hand_, *Pp = fb.partial;
       int* err = herr_;
       const int set = l & 1;
       const int groups = ffn_groups_;
@@ -1008,33 +992,32 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
       if (use_fk) {
         const float* Pk = fk->second;
         const float* A = hfrag_;
-        float* U = u_;
+        float* U = fb.u;
         ops.push_back({p + ".ff1_gemm", [=](hipStream_t s) { gemv_fk(A, M, FF, Pk, nullptr, ACT_GELU, U, FF, s); },
                        2.0 * M * FF * D, 4.0 * ((double)FF * D + (double)M * D + (double)M * FF)});
       } else {
-        linear_split(ops, p + ".ff1_gemm", h_, D, M, W(t.l1), FF, D, &S, fbp);
-        rr(p + ".ff1_reduce_gelu", S, FF, ACT_GELU, false, u_, nullptr, nullptr, false, nullptr);
+        linear_split(ops, p + ".ff1_gemm", fb.h, D, M, W(t.l1), FF, D, &S, fb);
+        rr(p + ".ff1_reduce_gelu", S, FF, ACT_GELU, false, fb.u, nullptr, nullptr, false, nullptr);
       }
-      linear_split(ops, p + ".ff2_gemm", u_, FF, M, W(t.l2), D, FF, &S, fbp);
+      linear_split(ops, p + ".ff2_gemm", fb.u, FF, M, W(t.l2), D, FF, &S, fb);
     }
     if (l + 1 < NL)
-      rr(p + ".ff2_reduce_ln1", S, D, ACT_NONE, true, x_, W(L_.fl[l + 1].n1w), W(L_.fl[l + 1].n1b), true, h_);
+      rr(p + ".ff2_reduce_ln1", S, D, ACT_NONE, true, fb.x, W(L_.fl[l + 1].n1w), W(L_.fl[l + 1].n1b), true, fb.h);
     else
-      rr(p + ".ff2_reduce_outnorm", S, D, ACT_NONE, true, x_, W(L_.out_norm_w), W(L_.out_norm_b), out_norm, h_);
+      rr(p + ".ff2_reduce_outnorm", S, D, ACT_NONE, true, fb.x, W(L_.out_norm_w), W(L_.out_norm_b), out_norm, fb.h);
   }
 }
 
-// Prefill T rows already in x_ into slot `slot` at positions p0.. (tts_model.rs:580-599, 958-964).
-void Engine::prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs* fbp) {
+// Prefill T rows already in fb.x into slot `slot` at positions p0.. (tts_model.rs:580-599, 958-964).
+void Engine::prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs& fb) {
   {
-    float* x = fbp ? fbp->x : x_;
-    float* h = fbp ? fbp->h : h_;
+    float *x = fb.x, *h = fb.h;
     const float* w = W(L_.fl[0].n1w);
     const float* b = W(L_.fl[0].n1b);
     ops.push_back({"prefill.ln1", [=](hipStream_t s) { layernorm(x, D, h, D, T, D, w, b, 1e-5f, s); }});
   }
   RowMap map{slot, T, p0, nullptr};
-  flow_layers(ops, T, map, false, false, "prefill", fbp);
+  flow_layers(ops, T, map, false, false, "prefill", fb);
 }
 
 // The persistent flow-head launch needs <= 128 rows and ResBlock tensors at one uniform stride
@@ -1062,14 +1045,15 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
   PTTS_REQUIRE(lsd_run >= 1 && lsd_run <= lsd_, "lsd_run outside [1, cap]");
   int S = 1;
   // ---- FlowLM step (flow_lm.rs:98-164): input_linear -> transformer -> out_norm. The input
-  // projection + norm1 of layer 0 (x_, h_) were computed by the previous step's front_commit, or
-  // by refresh_xh() after anything else wrote x_, h_ or lat_in_.
-  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow");
+  // projection + norm1 of layer 0 (fbm_.x, fbm_.h) were computed by the previous step's front_commit,
+  // or by refresh_xh() after anything else wrote them or lat_in_.
+  const FlowBufs& fb = fbm_;
+  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow", fb);
   // ---- flow head (mlp.rs:215-383): cond_embed | out_eos, EOS bookkeeping, noise
-  linear_split(ops, "head.cond_eos_gemm", h_, D, B, W(L_.cond_eos_w), NCOND, D, &S);
+  linear_split(ops, "head.cond_eos_gemm", fb.h, D, B, W(L_.cond_eos_w), NCOND, D, &S, fb);
   PTTS_REQUIRE(S <= FLOW_COND_MAX_SLABS, "head.flow_cond sums at most 16 split-K slabs");
   {
-    const float* P = partial_;
+    const float* P = fb.partial;
     const float* bias = W(L_.cond_eos_b);
     const float* temb = temb_;
     const int lsd = lsd_run, cap = lsd_;
@@ -1080,10 +1064,10 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
                    4.0 * ((double)S * B * NCOND + NCOND + lsd * FD + lsd * (double)B * FD + B * (LDIM + 1.0))});
   }
   // all adaLN modulations of all lsd steps in one GEMM (mlp.rs:322-368)
-  linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_run * B, W(L_.ada_w), NADA, FD, &S);
+  linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_run * B, W(L_.ada_w), NADA, FD, &S, fb);
   {
     RowReduceArgs a{};
-    a.P = partial_;
+    a.P = fb.partial;
     a.S = S;
     a.M = lsd_run * B;
     a.N = NADA;
@@ -1149,10 +1133,10 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
   for (int st = 0; st < lsd_run && !use_head_chain(B); ++st) {
     const float* mods = mods_ + (size_t)st * B * NADA;
     const std::string p = "head.s" + std::to_string(st);
-    linear_split(ops, p + ".inproj_gemm", cur_, LDIM, B, W(L_.inproj_w), FD, LDIM, &S);
+    linear_split(ops, p + ".inproj_gemm", cur_, LDIM, B, W(L_.inproj_w), FD, LDIM, &S, fb);
     {
       RowReduceArgs a{};
-      a.P = partial_;
+      a.P = fb.partial;
       a.S = S;
       a.M = B;
       a.N = FD;
@@ -1173,9 +1157,9 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
     for (int i = 0; i < FDEPTH; ++i) {
       const std::string pb = p + ".rb" + std::to_string(i);
       {
-        linear_split(ops, pb + ".mlp0_gemm", hf_, FD, B, W(L_.rb_w0[i]), FD, FD, &S);
+        linear_split(ops, pb + ".mlp0_gemm", hf_, FD, B, W(L_.rb_w0[i]), FD, FD, &S, fb);
         RowReduceArgs a{};
-        a.P = partial_;
+        a.P = fb.partial;
         a.S = S;
         a.M = B;
         a.N = FD;
@@ -1185,10 +1169,10 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
         a.ldy = FD;
         push_rr(ops, pb + ".mlp0_reduce", a);
       }
-      linear_split(ops, pb + ".mlp2_gemm", uf_, FD, B, W(L_.rb_w2[i]), FD, FD, &S);
+      linear_split(ops, pb + ".mlp2_gemm", uf_, FD, B, W(L_.rb_w2[i]), FD, FD, &S, fb);
       {
         RowReduceArgs a{};
-        a.P = partial_;
+        a.P = fb.partial;
         a.S = S;
         a.M = B;
         a.N = FD;
@@ -1216,10 +1200,10 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
         push_rr(ops, pb + ".mlp2_reduce", a);
       }
     }
-    linear_split(ops, p + ".final_gemm", hf_, FD, B, W(L_.fin_w), LDIM, FD, &S);
+    linear_split(ops, p + ".final_gemm", hf_, FD, B, W(L_.fin_w), LDIM, FD, &S, fb);
     {
       RowReduceArgs a{};
-      a.P = partial_;
+      a.P = fb.partial;
       a.S = S;
       a.M = B;
       a.N = LDIM;
@@ -1245,8 +1229,8 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
     c.Wt = inw_t_;
     c.lnw = W(L_.fl[0].n1w);
     c.lnb = W(L_.fl[0].n1b);
-    c.x = x_;
-    c.h = h_;
+    c.x = fb.x;
+    c.h = fb.h;
     c.err_dev = herr_;
     c.err_host = h_err_;
     c.n_zero = nfr_ > 1 ? max_slots_ - B : 0;
@@ -1303,13 +1287,33 @@ static int back_twin(int layout, int back_mfma) {
   return layout;
 }
 
-// BACK part of a step: Mimi decode of the frames the front part left in buffer `hb`; `qp` is the
-// frame's parity for the quantizer history (the previous frame's quantizer output is in qp ^ 1).
-void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, int pcm_frames) {
+// The engine's own pass over the frames the front parts left in buffers hb .. hb + nfr - 1
+Engine::BackPass Engine::step_pass(int hb, int nfr) const {
+  BackPass p;
+  p.nfr = nfr;
+  for (int f = 0; f < nfr; ++f) {
+    p.lat[f] = lat_out_[(hb + f) % nhb_];
+    p.flags[f] = flags_[(hb + f) % nhb_];
+  }
+  p.pcm = nfr_ == 1 ? pcm_[hb] : pcmp_[hb / nfr_];
+  p.pcm_ld = (long)nfr_ * FRAME;
+  p.wire = wire_ ? wireb_[nfr_ > 1 ? hb / nfr_ : hb] : nullptr;
+  return p;
+}
+
+// BACK part of a step: Mimi decode of the rows [0, B) of the pass's frames, over the workspace and
+// codec state bb.
+void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const BackPass& pass) {
+  const int nfr = pass.nfr, pcm_frames = (int)(pass.pcm_ld / FRAME);
   PTTS_REQUIRE(nfr >= 1 && nfr <= nfr_, "frames per back pass out of range");
   PTTS_REQUIRE(pcm_frames >= nfr, "pass block smaller than the pass");
-  int hbs[NFR_MAX];  // frame f's hand-off buffer (f < nfr)
-  for (int f = 0; f < NFR_MAX; ++f) hbs[f] = (hb + std::min(f, nfr - 1)) % nhb_;
+  // (the launch arguments hold NFR_MAX frames: those past the pass repeat its last)
+  std::array<const float*, NFR_MAX> lat;
+  std::array<const FrameFlags*, NFR_MAX> fl;
+  for (int f = 0; f < NFR_MAX; ++f) {
+    lat[f] = pass.lat[std::min(f, nfr - 1)];
+    fl[f] = pass.flags[std::min(f, nfr - 1)];
+  }
   const bool big = B >= 16;  // B * 16 >= 256 Mimi rows: the LDS-DMA tiles fill the chip
   auto tile = [&](const std::string& op, int small_splits) {
     BackTile t = big ? back_tile(op, pipeline_) : BackTile{TILE_KSPLIT_4W, small_splits};
@@ -1326,29 +1330,23 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   {
     const float *sd = W(L_.emb_std), *mn = W(L_.emb_mean), *wq = W(L_.quant_w), *wu = W(L_.up_w);
     const float *lw = W(L_.mdec[0].n1w), *lb = W(L_.mdec[0].n1b);
-    const float* qin = qprev_;
-    float* qout = qcur_;
-    float *x = mx_, *h = mh_;
-    std::array<const float*, NFR_MAX> lat;
-    std::array<const FrameFlags*, NFR_MAX> fl;
-    for (int f = 0; f < NFR_MAX; ++f) {
-      lat[f] = lat_out_[hbs[f]];
-      fl[f] = flags_[hbs[f]];
-    }
+    const float* qin = bb.qprev;
+    float* qout = bb.qcur;
+    float *x = bb.mx, *h = bb.mh;
     ops.push_back({"mimi.quant_upsample",
                    [=](hipStream_t s) { quant_upsample(lat.data(), fl.data(), nfr, B, sd, mn, wq, wu, qin, qout, x, h, lw, lb, s); },
                    (double)B * nfr * (2.0 * MD * LDIM + 2.0 * MD * 2 * UP + 8.0 * UP * MD),
                    4.0 * ((double)B * nfr * (LDIM + 2 * MD + 2.0 * UP * MD) + 2.0 * MD * LDIM + MD * 2.0 * UP + 2.0 * MD)});
   }
   const int MR = B * UP * nfr;  // Mimi rows of the pass: 16 per frame per utterance
-  RowMap mmap{0, UP * nfr, 0, mpos_};
+  RowMap mmap{0, UP * nfr, 0, bb.mpos};
   // a split-K GEMM into the back part's own slab buffer, its epilogue in a row reduce
   auto split_gemm = [&](const std::string& name, const float* X, int M, const float* Wt, int N, int K, BackTile t) {
     PTTS_REQUIRE(t.splits >= 1 && t.splits <= 16, name + ": split-K 1..16");
-    PTTS_REQUIRE((size_t)t.splits * M * N <= mpcap_, "back split-K slab buffer too small");
+    PTTS_REQUIRE((size_t)t.splits * M * N <= bb.mpcap, "back split-K slab buffer too small");
     GemmArgs a = dense_gemm(t.layout, M, N, K, X, K, Wt);
     a.S = t.splits;
-    a.partial = mpartial_;
+    a.partial = bb.mpartial;
     attach_split(a);
     const int S = t.splits;
     ops.push_back({name, [a, S](hipStream_t s) { gemm(a, S, s); }, 2.0 * M * N * K,
@@ -1357,13 +1355,13 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   for (int l = 0; l < MNL; ++l) {
     const Layout::TL& t = L_.mdec[l];
     const std::string p = "mimi.l" + std::to_string(l);
-    KvStore kv{ring_ + (long)l * ring_layer_, ring_slot_, RING};
+    KvStore kv{bb.ring + (long)l * ring_layer_, ring_slot_, RING};
     {  // QKV in one pass; RoPE + ring append inside the attention launch
       const BackTile tq = tile("mimi.qkv", 1);
-      dense_op(ops, p + ".qkv_gemm", mh_, MR, W(t.in_proj), 3 * MD, MD, nullptr, ACT_NONE, nullptr, nullptr, mqkv_,
+      dense_op(ops, p + ".qkv_gemm", bb.mh, MR, W(t.in_proj), 3 * MD, MD, nullptr, ACT_NONE, nullptr, nullptr, bb.mqkv,
                tq.layout);
-      const float* qkv = mqkv_;
-      float* O = mo_;
+      const float* qkv = bb.mqkv;
+      float* O = bb.mo;
       // per utterance: the K and V of its window (W keys x 8 heads x 64 x 2, read once for its 16
       // queries), its 16 QKV rows in, the 16 output rows, the appended K/V; 16 queries x W keys x
       // 8 heads x 64 x 4 flops = 65,536 W
@@ -1374,7 +1372,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
                        (double)B * (4.0 * 2 * MNH * 64 * Wn + 4.0 * UP * (3.0 * MD + MD + 2.0 * MD))});
       } else {  // two frames: the second frame's queries see the first frame's keys, appended by
         // other workgroups, so the append (with RoPE) is its own launch ahead of the attention
-        float* Q = mq_;
+        float* Q = bb.mq;
         ops.push_back({p + ".qkv_rope", [=](hipStream_t s) { qkv_rope_append(nullptr, 0, qkv, MR, MNH, mmap, kv, Q, s); },
                        0.0, 4.0 * MR * (3.0 * MD + 3.0 * MD)});
         ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, MR, MNH, mmap, kv, MCTX, O, s); },
@@ -1384,51 +1382,51 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     }
     {  // out projection, split-K; LayerScale + residual and this layer's norm2 in the reduce
       const BackTile to = tile("mimi.out", 4);
-      split_gemm(p + ".out_gemm", mo_, MR, W(t.out_proj), MD, MD, to);
+      split_gemm(p + ".out_gemm", bb.mo, MR, W(t.out_proj), MD, MD, to);
       RowReduceArgs r{};
-      r.P = mpartial_;
+      r.P = bb.mpartial;
       r.S = to.splits;
       r.M = MR;
       r.N = MD;
       r.gate = W(t.ls1);  // per-column LayerScale: gate row stride 0
       r.ldg = 0;
-      r.R = mx_;
+      r.R = bb.mx;
       r.ldr = MD;
-      r.Y = mx_;
+      r.Y = bb.mx;
       r.ldy = MD;
       r.ln = 1;
       r.ln_w = W(t.n2w);
       r.ln_b = W(t.n2b);
       r.eps = 1e-5f;
-      r.Hout = mh_;
+      r.Hout = bb.mh;
       r.ldh = MD;
       ops.push_back(rr_op(p + ".out_reduce_ln2", r));
     }
     {  // linear1 + GELU in the tile epilogue
       const BackTile tf = tile("mimi.ff1", 1);
-      dense_op(ops, p + ".ff1_gemm", mh_, MR, W(t.l1), MFF, MD, nullptr, ACT_GELU, nullptr, nullptr, mu_, tf.layout);
+      dense_op(ops, p + ".ff1_gemm", bb.mh, MR, W(t.l1), MFF, MD, nullptr, ACT_GELU, nullptr, nullptr, bb.mu, tf.layout);
     }
     {  // linear2 (K = 2048), split-K; LayerScale + residual (+ the next layer's norm1) in the reduce.
        // Few rows (B < 16, the first-chunk path): 32x32 tiles, 8 slices (16 -> 128 workgroups)
       const BackTile tf = tile("mimi.ff2", 8);
-      split_gemm(p + ".ff2_gemm", mu_, MR, W(t.l2), MD, MFF, tf);
+      split_gemm(p + ".ff2_gemm", bb.mu, MR, W(t.l2), MD, MFF, tf);
       RowReduceArgs r{};
-      r.P = mpartial_;
+      r.P = bb.mpartial;
       r.S = tf.splits;
       r.M = MR;
       r.N = MD;
       r.gate = W(t.ls2);
       r.ldg = 0;
-      r.R = mx_;
+      r.R = bb.mx;
       r.ldr = MD;
-      r.Y = mx_;
+      r.Y = bb.mx;
       r.ldy = MD;
       if (l + 1 < MNL) {  // the next layer's norm1 on the reduced rows (no separate LayerNorm launch)
         r.ln = 1;
         r.ln_w = W(L_.mdec[l + 1].n1w);
         r.ln_b = W(L_.mdec[l + 1].n1b);
         r.eps = 1e-5f;
-        r.Hout = mh_;
+        r.Hout = bb.mh;
         r.ldh = MD;
       }
       ops.push_back(rr_op(p + ".ff2_reduce", r));
@@ -1445,29 +1443,29 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
      // at B = 1 the unsplit launch had 16 workgroups, 27.4 us)
     const BackTile tc = tile("seanet.conv0", 8);
     if (big && tc.splits == 1) {  // unsplit: bias + ELU in the tile epilogue, no reduce launch
-      conv_op(ops, "seanet.conv0", mx_, B, 16 * nfr, 512, hist_[0], 6, 1, 0, W(L_.dc0_w), 512, 7, 1, W(L_.dc0_b),
-              nullptr, a0_, 16 * nfr, 1, tc.layout, 1, nullptr, 1);
+      conv_op(ops, "seanet.conv0", bb.mx, B, 16 * nfr, 512, bb.hist[0], 6, 1, 0, W(L_.dc0_w), 512, 7, 1, W(L_.dc0_b),
+              nullptr, bb.a0, 16 * nfr, 1, tc.layout, 1, nullptr, 1);
     } else {
     const int s_c0 = std::max(tc.splits, 2);
-    conv_op(ops, "seanet.conv0", mx_, B, 16 * nfr, 512, hist_[0], 6, 1, 0, W(L_.dc0_w), 512, 7, 1, nullptr, nullptr,
-            nullptr, 16 * nfr, 1, big ? tc.layout : TILE_GLDS_64x64, 0, nullptr, s_c0);
+    conv_op(ops, "seanet.conv0", bb.mx, B, 16 * nfr, 512, bb.hist[0], 6, 1, 0, W(L_.dc0_w), 512, 7, 1, nullptr, nullptr,
+            nullptr, 16 * nfr, 1, big ? tc.layout : TILE_GLDS_64x64, 0, nullptr, s_c0, bb.mpartial, bb.mpcap);
     RowReduceArgs r{};
-    r.P = mpartial_;
+    r.P = bb.mpartial;
     r.S = s_c0;
     r.M = B * 16 * nfr;
     r.N = 512;
     r.bias = W(L_.dc0_b);
     r.act = ACT_ELU;
-    r.Y = a0_;
+    r.Y = bb.a0;
     r.ldy = 512;
     ops.push_back(rr_op("seanet.conv0_reduce", r));
     }
   }
-  const float* cin_buf = a0_;
+  const float* cin_buf = bb.a0;
   int T = 16 * nfr, ch = 512;
   // a pass's PCM is [B][pcm_frames][1920] in its pass block (frames past nfr untouched)
-  float* pcm_out = pcm_frames == 1 ? pcm_[hb] : pcmp_[hb / pcm_frames];
-  const long pcm_ld = (long)pcm_frames * FRAME;
+  float* pcm_out = pass.pcm;
+  const long pcm_ld = pass.pcm_ld;
   bool fin_fused = false;  // the final conv ran in the stage-2 residual block's epilogue
   // fused residual blocks (k3 conv + ELU + k1 conv + skip + ELU, the hidden rows in LDS) where they
   // beat the two conv launches: stage 2 (480 workgroups; 22.5 us against 16.8 + 11.0). Stages
@@ -1492,43 +1490,43 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     raw_only[i] = fuse_res(i) && !(big && tt.splits > 1);
     if (big && tt.splits > 1) {  // stage 0 (M = 16 B rows): split-K; bias + dual raw / ELU store in the reduce
       PTTS_REQUIRE(i == 0, "split-K transposed conv: stage 0 only");
-      conv_op(ops, p + ".convtr", cin_buf, B, T, ch, hist_[1], 1, 1, 0, W(L_.dtr_w[0]), r * (ch / 2), 2, 1, nullptr,
-              nullptr, nullptr, T, 1, tt.layout, 0, nullptr, tt.splits);
+      conv_op(ops, p + ".convtr", cin_buf, B, T, ch, bb.hist[1], 1, 1, 0, W(L_.dtr_w[0]), r * (ch / 2), 2, 1, nullptr,
+              nullptr, nullptr, T, 1, tt.layout, 0, nullptr, tt.splits, bb.mpartial, bb.mpcap);
       RowReduceArgs rr{};
-      rr.P = mpartial_;
+      rr.P = bb.mpartial;
       rr.S = tt.splits;
       rr.M = B * T;
       rr.N = r * (ch / 2);
       rr.bias = trb_[0];
-      rr.Y = cb_[0];
-      rr.Y2 = ce_[0];
+      rr.Y = bb.cb[0];
+      rr.Y2 = bb.ce[0];
       rr.ldy = r * (ch / 2);
       ops.push_back(rr_op(p + ".convtr_reduce", rr));
     } else {
       // stage 2 fused below: no ELU'd copy (the residual block ELUs the raw rows as it loads them)
-      conv_op(ops, p + ".convtr", cin_buf, B, T, ch, hist_[1 + 2 * i], 1, 1, 0, W(L_.dtr_w[i]), r * (ch / 2), 2, 1,
-              trb_[i], nullptr, cb_[i], T, 1, tt.layout, 0, fuse_res(i) ? nullptr : ce_[i]);
+      conv_op(ops, p + ".convtr", cin_buf, B, T, ch, bb.hist[1 + 2 * i], 1, 1, 0, W(L_.dtr_w[i]), r * (ch / 2), 2, 1,
+              trb_[i], nullptr, bb.cb[i], T, 1, tt.layout, 0, fuse_res(i) ? nullptr : bb.ce[i]);
     }
     T *= r;
     ch /= 2;
     if (fuse_res(i)) {
-      ResBlockArgs rb{ce_[i], hist_[2 + 2 * i], cb_[i], W(L_.dra_w[i]), W(L_.dra_b[i]), W(L_.drb_w[i]),
-                      W(L_.drb_b[i]), ca_[i], B, T, ch};
+      ResBlockArgs rb{bb.ce[i], bb.hist[2 + 2 * i], bb.cb[i], W(L_.dra_w[i]), W(L_.dra_b[i]), W(L_.drb_w[i]),
+                      W(L_.drb_b[i]), bb.ca[i], B, T, ch};
       const double hd = ch / 2;
       double fl = 2.0 * B * T * (hd * 3 * ch + ch * hd);
       double by = 4.0 * ((double)B * T * ch * 3 + B * 2.0 * ch + hd * 3 * ch + ch * hd + hd + ch);
       if (raw_only[i]) {  // E = elu(R) as the rows enter LDS (a split-K reduce stores both)
-        rb.E = cb_[i];
+        rb.E = bb.cb[i];
         rb.e_raw = 1;
         by -= 4.0 * B * T * ch;  // E and R are the same rows: read once
       }
       if (i == 2 && T % RESBLOCK_FIN_TT == 0) {  // + the final conv (64 -> 1, k = 3) of the tile's rows
         rb.fw = W(L_.dfin_w);
         rb.fb = W(L_.dfin_b);
-        rb.fH = hist_[7];
+        rb.fH = bb.hist[7];
         rb.fout = pcm_out;
         rb.fld = pcm_ld;
-        rb.fside = fin_side_;
+        rb.fside = bb.fin_side;
         fin_fused = true;
         fl += 2.0 * B * T * 3 * 64;
         by += 4.0 * ((double)B * T + B * 2.0 * 64 + 3 * 64 + 1);
@@ -1537,37 +1535,39 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     } else {  // the two convs (few rows: 32x32 tiles, more workgroups than the fused tiles)
       const int lr3 = big ? tile(p + ".res_conv3", 1).layout : TILE_KSPLIT_4W,
                 lr1 = big ? tile(p + ".res_conv1", 1).layout : TILE_KSPLIT_4W;
-      conv_op(ops, p + ".res_conv3", ce_[i], B, T, ch, hist_[2 + 2 * i], 2, 1, 0, W(L_.dra_w[i]), ch / 2, 3, 1,
-              W(L_.dra_b[i]), nullptr, cv_[i], T, 1, lr3, 1);
-      conv_op(ops, p + ".res_conv1", cv_[i], B, T, ch / 2, nullptr, 0, 1, 0, W(L_.drb_w[i]), ch, 1, 1,
-              W(L_.drb_b[i]), cb_[i], ca_[i], T, 1, lr1, 1);
+      conv_op(ops, p + ".res_conv3", bb.ce[i], B, T, ch, bb.hist[2 + 2 * i], 2, 1, 0, W(L_.dra_w[i]), ch / 2, 3, 1,
+              W(L_.dra_b[i]), nullptr, bb.cv[i], T, 1, lr3, 1);
+      conv_op(ops, p + ".res_conv1", bb.cv[i], B, T, ch / 2, nullptr, 0, 1, 0, W(L_.drb_w[i]), ch, 1, 1,
+              W(L_.drb_b[i]), bb.cb[i], bb.ca[i], T, 1, lr1, 1);
     }
-    cin_buf = ca_[i];
+    cin_buf = bb.ca[i];
   }
   if (!fin_fused) {
-    const float *X = ca_[2], *H = hist_[7], *w = W(L_.dfin_w), *b = W(L_.dfin_b);
+    const float *X = bb.ca[2], *H = bb.hist[7], *w = W(L_.dfin_w), *b = W(L_.dfin_b);
     float* Y = pcm_out;
     const int TF = FRAME * nfr;
     ops.push_back({"seanet.conv_final", [=](hipStream_t s) { conv_cout1(X, H, B, TF, 64, 3, w, b, Y, 0, s, pcm_ld); },
                    2.0 * B * TF * 3 * 64, 4.0 * ((double)B * TF * 64 + B * 2.0 * 64 + B * TF + 3 * 64 + 1)});
   }
-  // ---- commit of the back part: conv histories and Mimi positions of rows with a frame
-  {
+  // ---- commit of the back part: conv histories and Mimi positions of rows with a frame (it also
+  // adds the fused final conv's tile-boundary shares into the PCM)
+  PTTS_REQUIRE(pass.commit || !fin_fused, "a pass without the commit: the small-row path only");
+  if (pass.commit) {
     CommitArgs c{};
-    const float* srcs[8] = {mx_, a0_, ce_[0], ca_[0], ce_[1], ca_[1], ce_[2], ca_[2]};
-    for (int i = 0; i < 8; ++i) c.h[i] = HistDesc{srcs[i], hist_[i], hist_T_[i] * nfr, hist_C_[i], hist_P_[i]};
+    const float* srcs[8] = {bb.mx, bb.a0, bb.ce[0], bb.ca[0], bb.ce[1], bb.ca[1], bb.ce[2], bb.ca[2]};
+    for (int i = 0; i < 8; ++i) c.h[i] = HistDesc{srcs[i], bb.hist[i], hist_T_[i] * nfr, hist_C_[i], hist_P_[i]};
     for (int i = 0; i < 3; ++i)  // a raw-only fused stage's k3-conv history: elu(raw rows)
-      if (raw_only[i]) c.h[2 + 2 * i] = HistDesc{cb_[i], hist_[2 + 2 * i], hist_T_[2 + 2 * i] * nfr, hist_C_[2 + 2 * i], hist_P_[2 + 2 * i], 1};
+      if (raw_only[i]) c.h[2 + 2 * i] = HistDesc{bb.cb[i], bb.hist[2 + 2 * i], hist_T_[2 + 2 * i] * nfr, hist_C_[2 + 2 * i], hist_P_[2 + 2 * i], 1};
     c.nh = 8;
     c.B = B;
-    for (int f = 0; f < NFR_MAX; ++f) c.flags[f] = flags_[hbs[f]];
+    for (int f = 0; f < NFR_MAX; ++f) c.flags[f] = fl[f];
     c.nfr = nfr;
-    c.mpos = mpos_;
-    c.qcur = qcur_;
-    c.qprev = qprev_;
+    c.mpos = bb.mpos;
+    c.qcur = bb.qcur;
+    c.qprev = bb.qprev;
     if (fin_fused) {
       c.fin_pcm = pcm_out;
-      c.fin_side = fin_side_;
+      c.fin_side = bb.fin_side;
       c.fin_T = FRAME * nfr;
       c.fin_ld = pcm_ld;
     }
@@ -1577,7 +1577,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
   }
   // ---- wire stage (wire-enabled engines): after the commit, which still adds the fused final
   // conv's tile-boundary shares into the PCM
-  if (wire_ && !wire_skip_) {
+  if (pass.wire) {
     if (tempo_) {  // the speed rows' chunks first: the wire stage reads them in place of the PCM
       TempoArgs ta{};
       ta.B = B;
@@ -1585,7 +1585,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
       ta.pcm_frames = pcm_frames;
       ta.out_frames = nfr_;
       ta.pcm = pcm_out;
-      for (int f = 0; f < NFR_MAX; ++f) ta.flags[f] = flags_[hbs[f]];
+      for (int f = 0; f < NFR_MAX; ++f) ta.flags[f] = fl[f];
       ta.sp = tempo_sp_;
       ta.state = tempo_state_;
       ta.hist = tempo_hist_;
@@ -1601,15 +1601,14 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
     w.pcm_frames = pcm_frames;
     w.out_frames = nfr_;
     w.pcm = pcm_out;
-    for (int f = 0; f < NFR_MAX; ++f) w.flags[f] = flags_[hbs[f]];
+    for (int f = 0; f < NFR_MAX; ++f) w.flags[f] = fl[f];
     w.fmt = wire_fmt_;
     w.frames = wire_frames_;
     w.tail = wire_tail_;
     w.taps = wire_taps_;
     for (int r = 0; r < WIRE_RATES; ++r) w.plan[r] = wire_plan_[r];
-    unsigned char* blk = wireb_[nfr_ > 1 ? hb / nfr_ : hb];
-    w.counts = (int*)blk;
-    w.out = blk + wire_head_bytes();
+    w.counts = (int*)pass.wire;
+    w.out = pass.wire + wire_head_bytes();
     w.chunk = wire_chunk_max();
     if (tempo_) {
       w.tempo_sp = tempo_sp_;
@@ -1625,7 +1624,7 @@ void Engine::build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, in
 std::vector<Op> Engine::build_step(int B) {
   std::vector<Op> ops;
   build_front(ops, B, 0, lsd_run_for(B));
-  build_back(ops, B, 0, nfr_, 0, nfr_);
+  build_back(ops, B, bbm_, step_pass(0, nfr_));
   return ops;
 }
 
@@ -1636,7 +1635,7 @@ std::vector<std::string> Engine::plan_names(int B) {
   sync();
   std::vector<int> fp(B), mp(B);
   PTTS_HIP(hipMemcpy(fp.data(), fpos_, sizeof(int) * B, hipMemcpyDeviceToHost));
-  PTTS_HIP(hipMemcpy(mp.data(), mpos_, sizeof(int) * B, hipMemcpyDeviceToHost));
+  PTTS_HIP(hipMemcpy(mp.data(), bbm_.mpos, sizeof(int) * B, hipMemcpyDeviceToHost));
   double L = 0, Wn = 0, kvu = 0;
   std::vector<const float*> seen;  // distinct shared voice prefixes: read once per launch
   for (int b = 0; b < B; ++b) {
@@ -1700,7 +1699,7 @@ hipGraphExec_t Engine::part_graph(int part, int B, int hb, int qp, int nfr, int 
   if (it != graphs_.end()) return it->second;
   std::vector<Op> ops;
   if (part == 0) build_front(ops, B, hb, lsd_run);
-  else build_back(ops, B, hb, nfr, qp, nfr_);
+  else build_back(ops, B, bbm_, step_pass(hb, nfr));
   hipGraph_t g = nullptr;
   // captured on the stream it is launched on (the back part of a pipelined step: stream_be_)
   hipStream_t cs = part == 1 && pipeline_ ? stream_be_ : stream_;
@@ -2067,9 +2066,9 @@ void Engine::test_gemm(int layout, int M, int N, int K, int splits, int tail_S, 
     }
     if (tail_S > 0) {
       a.tail_S = tail_S;
-      a.tail_slab = tslab_;
-      a.tail_cap = (long)TAIL_CAP;
-      a.tickets = tickets_;
+      a.tail_slab = fbm_.tslab;
+      a.tail_cap = fbm_.tail_cap;
+      a.tickets = fbm_.tickets;
       a.tickets_cap = TICKETS;
     }
     gemm(a, splits, stream_);
@@ -2234,7 +2233,7 @@ void Engine::test_attention(int kind, int M, int nh, int cap, int window, int n_
 }
 
 double Engine::time_op(int B, const std::string& name, int reps) {
-  xh_dirty_ = true;  // replays write x_ / h_
+  xh_dirty_ = true;  // replays write fbm_.x / fbm_.h
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
   PTTS_REQUIRE(reps >= 1, "reps must be >= 1");
@@ -2292,7 +2291,7 @@ double Engine::time_op(int B, const std::string& name, int reps) {
 // times each alone and both launched together on two streams (no dependency, data races are
 // irrelevant for timing). us[0] = front alone, us[1] = back alone, us[2] = both concurrently.
 void Engine::overlap_probe(int B, int reps, double* us) {
-  xh_dirty_ = true;  // replays write x_ / h_
+  xh_dirty_ = true;  // replays write fbm_.x / fbm_.h
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(B >= 1 && B <= max_slots_ && reps >= 1, "bad probe arguments");
   PTTS_HIP(hipSetDevice(dev_));
@@ -2473,7 +2472,7 @@ void Engine::overlap_probe(int B, int reps, double* us) {
         if (sf)
           for (size_t i = 0; i < cut; ++i) ops[i].fn(sf);
         if (sb && kind == 'e') {
-          for (int i = 0; i < N; ++i) copy2d(x_, 1, q_, 1, 1, 1, sb);
+          for (int i = 0; i < N; ++i) copy2d(fbm_.x, 1, fbm_.q, 1, 1, 1, sb);
         } else if (sb && kind == 'm') {
           const long half = ((long)N << 20) / 8;  // floats copied: N/2 MB read + N/2 MB written
           copy2d(big, 1024, big + half, 1024, (int)(half / 1024), 1024, sb);
@@ -2820,7 +2819,7 @@ void Engine::voice_clone(const VoicePlan* p, const VoiceWs& w, hipStream_t st, p
     b.kv = KvStore{v->kv, 0, F};  // the voice's own compact cache [NL][2][NH][F][64]
     b.kv_layer = (long)2 * NH * F * 64;
     std::vector<Op> ops;
-    prefill_rows(ops, 0, T, c0, &b);
+    prefill_rows(ops, 0, T, c0, b);
     run_ops_on(ops, st);
   }
   if (v->ev) PTTS_HIP(hipEventRecord(v->ev, st));
@@ -3051,7 +3050,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     // copy-on-admit of the immutable voice prefixes
     for (int i = 0; i < n; ++i) {
       const ptts_voice* v = voices[i];
-      PTTS_HIP(hipMemcpy2DAsync(kv_ + (size_t)slots[i] * kv_slot_, sizeof(float) * max_ctx_ * 64, v->kv,
+      PTTS_HIP(hipMemcpy2DAsync(fbm_.kv.base + (size_t)slots[i] * fbm_.kv.slot_stride, sizeof(float) * max_ctx_ * 64, v->kv,
                                 sizeof(float) * v->F * 64, sizeof(float) * v->F * 64, NL * 2 * NH,
                                 hipMemcpyDeviceToDevice, stream_));
     }
@@ -3116,7 +3115,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     {
       const int* idp = ids_dev_;
       const float* tb = W(L_.embed);
-      float* x = x_;
+      float* x = fbm_.x;
       if (any_prefix) {  // token and latent rows in one launch
         const float *pl = plat_dev_, *bos = W(L_.bos), *wt = inw_t_;
         ops.push_back({"prefill.input", [=](hipStream_t s) { prefill_input(idp, Tc, tb, pl, bos, wt, D, x, s); }});
@@ -3125,8 +3124,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       }
     }
     {
-      float* x = x_;
-      float* h = h_;
+      float *x = fbm_.x, *h = fbm_.h;
       const float* w = W(L_.fl[0].n1w);
       const float* b = W(L_.fl[0].n1b);
       ops.push_back({"prefill.ln1", [=](hipStream_t s) { layernorm(x, D, h, D, Tc, D, w, b, 1e-5f, s); }});
@@ -3136,7 +3134,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     map.mpad = T;
     map.qrow = qrow_dev_;
     map.orow = orow_dev_;
-    flow_layers(ops, Tc, map, false, false, "prefill");
+    flow_layers(ops, Tc, map, false, false, "prefill", fbm_);
     run_ops(ops);
   }
   // the slot state the back part owns (Mimi ring position, conv and overlap-add histories, frame
@@ -3223,24 +3221,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       PTTS_HIP(hipMemcpyAsync(admit_lat_, h_alat_, sizeof(float) * n * LDIM, hipMemcpyHostToDevice, stream_));
   }
   {
-    ResetArgs r{};
-    for (int i = 0; i < 8; ++i) {
-      r.buf[i] = hist_[i];
-      r.per_slot[i] = (long)hist_P_[i] * hist_C_[i];
-    }
-    r.buf[8] = qprev_;  // the overlap-add history
-    r.per_slot[8] = MD;
-    r.nb = 9;
-    r.slots = admit_slots_;
-    r.n = n;
-    r.lat_in = lat_in_;
-    r.bos = W(L_.bos);
-    r.st_src = admit_st_;
-    r.fpos_src = admit_fpos_;
-    r.st = st_;
-    r.fpos = fpos_;
-    r.mpos = mpos_;
-    for (int q = 0; q < NHB; ++q) r.flags[q] = flags_[q];
+    ResetArgs r = reset_args(n);
     if (wire_) {  // the wire state is back-owned too: same reset, same ordering
       r.wire_src = admit_wire_;
       r.wire_fmt = wire_fmt_;
@@ -3284,7 +3265,7 @@ void Engine::wire_enable(bool on) {
     wire_frames_ = (int*)dalloc(B);
     admit_wire_ = (int*)dalloc(B);
     wire_tail_ = dalloc(B * WIRE_TAIL);
-    PTTS_HIP(hipHostMalloc((void**)&h_wire_, sizeof(int) * B, hipHostMallocDefault));
+    h_wire_ = (int*)halloc(sizeof(int) * B);
     std::vector<float> taps;
     for (int r = 0; r < WIRE_RATES; ++r) {
       const ResamplePlan rp = resample_plan(PTTS_SAMPLE_RATE, WIRE_RATE_HZ[r]);
@@ -3299,7 +3280,7 @@ void Engine::wire_enable(bool on) {
     const size_t bytes = wire_block_bytes(max_slots_);
     for (int p = 0; p < WIRE_BLOCKS; ++p) {
       wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
-      PTTS_HIP(hipHostMalloc((void**)&h_wireb_[p], bytes, hipHostMallocDefault));
+      h_wireb_[p] = (unsigned char*)halloc(bytes);
       memset(h_wireb_[p], 0, wire_head_bytes());
     }
   }
@@ -3388,19 +3369,17 @@ void Engine::tempo_enable(bool on) {
     tempo_out_ = dalloc(B * nfr_ * TEMPO_OUT_MAX);
     tempo_cnt_ = (int*)dalloc(B * nfr_);
     admit_tempo_ = (int*)dalloc(B);
-    PTTS_HIP(hipHostMalloc((void**)&h_tempo_, sizeof(int) * B, hipHostMallocDefault));
+    h_tempo_ = (int*)halloc(sizeof(int) * B);
     const std::vector<float> w = tempo_window();
     tempo_win_ = dalloc(w.size());
     PTTS_HIP(hipMemcpy(tempo_win_, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
   }
-  if (on != tempo_) {  // the chunk slots change size: new pass blocks
+  if (on != tempo_) {  // the chunk slots change size: new pass blocks (the old ones stay until destruction)
     tempo_ = on;
     const size_t bytes = wire_block_bytes(max_slots_);
     for (int p = 0; p < WIRE_BLOCKS; ++p) {
-      (void)hipHostFree(h_wireb_[p]);
-      h_wireb_[p] = nullptr;
       wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
-      PTTS_HIP(hipHostMalloc((void**)&h_wireb_[p], bytes, hipHostMallocDefault));
+      h_wireb_[p] = (unsigned char*)halloc(bytes);
       memset(h_wireb_[p], 0, wire_head_bytes());
     }
   }
@@ -3435,14 +3414,38 @@ void Engine::tempo_host(const float* pcm, int n, int sp, float* out) {
 void Engine::mark_admission() {
   PTTS_HIP(hipEventRecord(ev_admit_, stream_));
   admit_pending_ = true;
-  xh_dirty_ = true;  // lat_in_ (and, with a prefill, x_ / h_) rewritten
+  xh_dirty_ = true;  // lat_in_ (and, with a prefill, fbm_.x / fbm_.h) rewritten
 }
 
-// x_, h_ rows of every slot from lat_in_ (the step's input projection + layer-0 norm1), on stream_
-// ahead of the next front part: after an admission, a voice prefill or anything else that used
-// x_ / h_ as scratch or wrote lat_in_ (the step graphs keep them current themselves)
+// The reset of n staged slots (admit_slots_ / admit_st_ / admit_fpos_): the front-owned state and the
+// codec state of bbm_ (conv histories, the overlap-add history, Mimi position), pending frame flags
+ResetArgs Engine::reset_args(int n) const {
+  ResetArgs r{};
+  for (int i = 0; i < 8; ++i) {
+    r.buf[i] = bbm_.hist[i];
+    r.per_slot[i] = (long)hist_P_[i] * hist_C_[i];
+  }
+  r.buf[8] = bbm_.qprev;  // the overlap-add history
+  r.per_slot[8] = MD;
+  r.nb = 9;
+  r.slots = admit_slots_;
+  r.n = n;
+  r.lat_in = lat_in_;
+  r.bos = W(L_.bos);
+  r.st_src = admit_st_;
+  r.fpos_src = admit_fpos_;
+  r.st = st_;
+  r.fpos = fpos_;
+  r.mpos = bbm_.mpos;
+  for (int q = 0; q < NHB; ++q) r.flags[q] = flags_[q];
+  return r;
+}
+
+// fbm_.x, fbm_.h rows of every slot from lat_in_ (the step's input projection + layer-0 norm1), on
+// stream_ ahead of the next front part: after an admission, a voice prefill or anything else that
+// used them as scratch or wrote lat_in_ (the step graphs keep them current themselves)
 void Engine::refresh_xh() {
-  input_ln(lat_in_, inw_t_, W(L_.fl[0].n1w), W(L_.fl[0].n1b), x_, h_, max_slots_, stream_);
+  input_ln(lat_in_, inw_t_, W(L_.fl[0].n1w), W(L_.fl[0].n1b), fbm_.x, fbm_.h, max_slots_, stream_);
   PTTS_HIP(hipGetLastError());
   xh_dirty_ = false;
 }
@@ -3469,25 +3472,7 @@ void Engine::decode_latents(int slot, const float* lat, int n, float* pcm, float
     PTTS_HIP(hipMemcpyAsync(admit_slots_, h_slots_, sizeof(int), hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(admit_st_, h_st_, sizeof(SlotState), hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(admit_fpos_, h_fp_, sizeof(int), hipMemcpyHostToDevice, stream_));
-    ResetArgs r{};
-    for (int i = 0; i < 8; ++i) {
-      r.buf[i] = hist_[i];
-      r.per_slot[i] = (long)hist_P_[i] * hist_C_[i];
-    }
-    r.buf[8] = qprev_;
-    r.per_slot[8] = MD;
-    r.nb = 9;
-    r.slots = admit_slots_;
-    r.n = 1;
-    r.lat_in = lat_in_;
-    r.bos = W(L_.bos);
-    r.st_src = admit_st_;
-    r.fpos_src = admit_fpos_;
-    r.st = st_;
-    r.fpos = fpos_;
-    r.mpos = mpos_;
-    for (int q = 0; q < NHB; ++q) r.flags[q] = flags_[q];
-    slot_reset(r, stream_);
+    slot_reset(reset_args(1), stream_);
     PTTS_HIP(hipGetLastError());
   }
   const FrameFlags on{1, 0}, off{0, 0};
@@ -3496,32 +3481,29 @@ void Engine::decode_latents(int slot, const float* lat, int n, float* pcm, float
                             stream_));
   };
   for (int i = 0; i < n; ++i) {
-    const int par = i & 1;  // quant_upsample reads the previous frame's quantizer output from par ^ 1
+    const int par = i & 1;  // the frame's hand-off buffer
     PTTS_HIP(hipMemcpyAsync(lat_out_[par] + (size_t)slot * LDIM, lat + (size_t)i * LDIM, sizeof(float) * LDIM,
                             hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipMemcpyAsync(flags_[par] + slot, &on, sizeof on, hipMemcpyHostToDevice, stream_));
+    BackPass pass;  // one frame from buffer par into pcm_[par]; the seam decodes to f32 only: no wire block
+    pass.lat[0] = lat_out_[par];
+    pass.flags[0] = flags_[par];
+    pass.pcm = pcm_[par];
     std::vector<Op> ops;
-    wire_skip_ = true;  // the seam decodes to f32 only
-    try {
-      build_back(ops, slot + 1, par, 1, par, 1);
-    } catch (...) {
-      wire_skip_ = false;
-      throw;
-    }
-    wire_skip_ = false;
+    build_back(ops, slot + 1, bbm_, pass);
     size_t j = 0;
     for (; j < ops.size(); ++j) {
-      if (ops[j].name == "seanet.conv0" && tr) rows16(tr + (size_t)i * UP * MD, mx_);
+      if (ops[j].name == "seanet.conv0" && tr) rows16(tr + (size_t)i * UP * MD, bbm_.mx);
       ops[j].fn(stream_);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) throw Error(PTTS_ERR_HIP, "launch of " + ops[j].name + " failed: " + hipGetErrorString(e));
-      if (j == 0 && up) rows16(up + (size_t)i * UP * MD, mx_);
+      if (j == 0 && up) rows16(up + (size_t)i * UP * MD, bbm_.mx);
     }
     if (pcm)
-      PTTS_HIP(hipMemcpyAsync(pcm + (size_t)i * FRAME, pcm_[par] + (size_t)slot * FRAME, sizeof(float) * FRAME,
+      PTTS_HIP(hipMemcpyAsync(pcm + (size_t)i * FRAME, pass.pcm + (size_t)slot * FRAME, sizeof(float) * FRAME,
                               hipMemcpyDeviceToHost, stream_));
     if (quant)
-      PTTS_HIP(hipMemcpyAsync(quant + (size_t)i * MD, qcur_ + (size_t)slot * NFR_MAX * MD,
+      PTTS_HIP(hipMemcpyAsync(quant + (size_t)i * MD, bbm_.qcur + (size_t)slot * NFR_MAX * MD,
                               sizeof(float) * MD, hipMemcpyDeviceToHost, stream_));
     PTTS_HIP(hipMemcpyAsync(flags_[par] + slot, &off, sizeof off, hipMemcpyHostToDevice, stream_));
     PTTS_HIP(hipStreamSynchronize(stream_));
@@ -3634,33 +3616,6 @@ void Engine::set_latent(int slot, const float* lat) {
 // frame 0 from, so the preview is that frame up to float rounding of the other tile shapes; the
 // regular pass still decodes it (it advances the row's own state), and the caller delivers the
 // first of the two to arrive (serve.py BatchScheduler).
-void Engine::swap_back(BackBufs& b) {
-  std::swap(ring_, b.ring);
-  std::swap(qprev_, b.qprev);
-  std::swap(qcur_, b.qcur);
-  std::swap(mx_, b.mx);
-  std::swap(mh_, b.mh);
-  std::swap(mq_, b.mq);
-  std::swap(mo_, b.mo);
-  std::swap(mqkv_, b.mqkv);
-  std::swap(mu_, b.mu);
-  std::swap(a0_, b.a0);
-  std::swap(mpartial_, b.mpartial);
-  std::swap(mpcap_, b.mpcap);
-  std::swap(fin_side_, b.fin_side);
-  for (int i = 0; i < 3; ++i) {
-    std::swap(cb_[i], b.cb[i]);
-    std::swap(cv_[i], b.cv[i]);
-    std::swap(ca_[i], b.ca[i]);
-    std::swap(ce_[i], b.ce[i]);
-  }
-  for (int i = 0; i < 8; ++i) std::swap(hist_[i], b.hist[i]);
-  std::swap(lat_out_[0], b.lat);
-  std::swap(flags_[0], b.flags);
-  std::swap(pcm_[0], b.pcm);
-  std::swap(mpos_, b.mpos);
-}
-
 void Engine::preview_enable(int max_rows) {
   static_assert(PV_MAX <= GATHER_MAX, "preview rows travel in the gather's arguments");
   PTTS_REQUIRE(max_rows >= 0 && max_rows <= PV_MAX, "preview rows must be in [0, 8]");
@@ -3668,37 +3623,13 @@ void Engine::preview_enable(int max_rows) {
   PTTS_HIP(hipSetDevice(dev_));
   if (max_rows > 0 && !stream_pv_) {
     const size_t P = PV_MAX;
-    BackBufs& b = pv_;
-    b.ring = dalloc((size_t)ring_slot_ * P);
-    b.mpos = (int*)dalloc(P);
-    b.qprev = dalloc((size_t)(1 + NFR_MAX) * P * MD);
-    b.qcur = b.qprev + P * MD;
-    b.mx = dalloc(P * UP * MD);
-    b.mh = dalloc(P * UP * MD);
-    b.mq = dalloc(P * UP * MD);
-    b.mo = dalloc(P * UP * MD);
-    b.mqkv = dalloc(P * UP * 3 * MD);
-    b.mu = dalloc(P * UP * MFF);
-    b.a0 = dalloc(P * 16 * 512);
-    int T = 16, ch = 512;
-    for (int i = 0; i < 3; ++i) {
-      T *= RATIOS[i];
-      ch /= 2;
-      b.cb[i] = dalloc(P * T * ch);
-      b.ce[i] = dalloc(P * T * ch);
-      b.cv[i] = dalloc(P * T * (ch / 2));
-      b.ca[i] = dalloc(P * T * ch);
-    }
-    b.mpcap = std::max({(size_t)8 * P * UP * MD, (size_t)4 * P * UP * RATIOS[0] * (MD / 2)});
-    b.mpartial = dalloc(b.mpcap);
-    for (int i = 0; i < 8; ++i) b.hist[i] = dalloc(P * hist_P_[i] * hist_C_[i]);
-    b.fin_side = dalloc(P * (FRAME / RESBLOCK_FIN_TT) * 2);
-    b.lat = dalloc(P * LDIM);
-    b.flags = (FrameFlags*)dalloc(P * 2);
-    b.pcm = dalloc(P * FRAME);
+    pv_ = back_alloc(PV_MAX, 1);
+    pv_lat_ = dalloc(P * LDIM);
+    pv_flags_ = (FrameFlags*)dalloc(P * 2);
+    pv_pcm_ = dalloc(P * FRAME);
     for (PvEntry& q : pv_q_) {
       PTTS_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-      PTTS_HIP(hipHostMalloc((void**)&q.h_pcm, sizeof(float) * P * FRAME, hipHostMallocDefault));
+      q.h_pcm = (float*)halloc(sizeof(float) * P * FRAME);
     }
     for (int q = 0; q < NHB; ++q) PTTS_HIP(hipEventCreateWithFlags(&ev_pv_read_[q], hipEventDisableTiming));
     PTTS_HIP(hipEventCreateWithFlags(&ev_pv_front_, hipEventDisableTiming));
@@ -3726,25 +3657,20 @@ void Engine::pv_forget(int slot) {
 hipGraphExec_t Engine::pv_graph(int P) {
   auto it = pv_graphs_.find(P);
   if (it != pv_graphs_.end()) return it->second;
-  std::vector<Op> ops;
-  swap_back(pv_);  // build_back over the preview buffers (its lambdas capture the pointers)
-  wire_skip_ = true;  // previews stay f32 at 24 kHz
-  try {
-    build_back(ops, P, 0, 1, 0, 1);
-  } catch (...) {
-    wire_skip_ = false;
-    swap_back(pv_);
-    throw;
-  }
-  wire_skip_ = false;
-  swap_back(pv_);
-  // The preview state must stay the fresh one (zero conv and overlap-add histories, Mimi position
-  // 0): the pass's closing commit, the only op that writes it, is left out, so the buffers keep
-  // the zeros dalloc gave them and no reset runs per preview. (The attention ring is rewritten at
-  // positions 0..15 by each preview before it reads them. The small-row path has no fused final
+  // One frame of the gathered batch over the previews' own workspace, f32 at 24 kHz only (no wire
+  // block). The preview state must stay the fresh one (zero conv and overlap-add histories, Mimi
+  // position 0): the pass's closing commit, the only op that writes it, is left out, so the buffers
+  // keep the zeros dalloc gave them and no reset runs per preview. (The attention ring is rewritten
+  // at positions 0..15 by each preview before it reads them. The small-row path has no fused final
   // conv, whose tile-boundary shares the commit would otherwise add.)
-  PTTS_REQUIRE(P < 16 && !ops.empty() && ops.back().name == "commit", "preview pass: unexpected plan");
-  ops.pop_back();
+  PTTS_REQUIRE(P < 16, "preview pass: the small-row path only");
+  BackPass pass;
+  pass.lat[0] = pv_lat_;
+  pass.flags[0] = pv_flags_;
+  pass.pcm = pv_pcm_;
+  pass.commit = false;
+  std::vector<Op> ops;
+  build_back(ops, P, pv_, pass);
   hipGraph_t g = nullptr;
   PTTS_HIP(hipStreamBeginCapture(stream_pv_, hipStreamCaptureModeThreadLocal));
   try {
@@ -3785,12 +3711,12 @@ void Engine::launch_previews(int B, int hb) {
   for (int i = 0; i < n; ++i) e.slots[i] = rows[i];
   PTTS_HIP(hipEventRecord(ev_pv_front_, stream_));
   PTTS_HIP(hipStreamWaitEvent(stream_pv_, ev_pv_front_, 0));
-  gather_preview(lat_out_[hb], flags_[hb], rows.data(), n, P, pv_.lat, pv_.flags, stream_pv_);
+  gather_preview(lat_out_[hb], flags_[hb], rows.data(), n, P, pv_lat_, pv_flags_, stream_pv_);
   PTTS_HIP(hipGetLastError());
   PTTS_HIP(hipEventRecord(ev_pv_read_[hb], stream_pv_));  // front(k + nhb_) rewrites buffer hb
   pv_read_pending_[hb] = true;
   PTTS_HIP(hipGraphLaunch(graph, stream_pv_));
-  PTTS_HIP(hipMemcpyAsync(e.h_pcm, pv_.pcm, sizeof(float) * n * FRAME, hipMemcpyDeviceToHost, stream_pv_));
+  PTTS_HIP(hipMemcpyAsync(e.h_pcm, pv_pcm_, sizeof(float) * n * FRAME, hipMemcpyDeviceToHost, stream_pv_));
   PTTS_HIP(hipEventRecord(e.ev, stream_pv_));
   ++pv_count_;
 }

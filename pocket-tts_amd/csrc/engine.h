@@ -154,34 +154,55 @@ class Engine {
   int fp8_matrices() const { return (int)f8map_.size(); }
 
  private:
-  float* dalloc(size_t n);
+  float* dalloc(size_t n);      // device memory (zeroed) and pinned host memory whose lifetime is the
+  void* halloc(size_t bytes);   // engine's: tracked in allocs_ / hallocs_, freed by the destructor
   const float* W(size_t off) const { return blob_ + off; }
   void upload_weights(TensorSource* src);
   void derive_int8();
   void derive_fp8();
-  // The buffers flow_layers / linear_split write: the engine's own (fbm_, the step and admission
-  // graphs) or a voice clone's (VoiceWs). kv is layer 0's store; layer l's base is kv.base + l * kv_layer.
+  // Every pass is built over an explicit workspace. FlowLM side, what flow_layers / linear_split
+  // write: the engine's own (fbm_: step and admission graphs) or a voice clone's (VoiceWs). kv is layer
+  // 0's store (fbm_'s carries the shared voice prefixes); layer l's base is kv.base + l * kv_layer.
   struct FlowBufs {
     float *x = nullptr, *h = nullptr, *q = nullptr, *o = nullptr, *u = nullptr, *partial = nullptr;
     size_t pcap = 0;
     float* tslab = nullptr;
     long tail_cap = 0;
     int* tickets = nullptr;
-    KvStore kv{};
+    KvStore kv{};  // [max_slots][NL][2][NH][max_ctx][64]
     long kv_layer = 0;
   };
   FlowBufs fbm_{};
-  void prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs* fb = nullptr);
+  // Mimi / SEANet side: the workspace and per-row codec state build_back reads and writes, the
+  // engine's own (bbm_: max_slots rows, back_frames frames per pass) or the previews' (pv_)
+  struct BackBufs {
+    float *ring = nullptr, *qprev = nullptr, *qcur = nullptr, *mx = nullptr, *mh = nullptr, *mq = nullptr,
+          *mo = nullptr, *mqkv = nullptr, *mu = nullptr, *a0 = nullptr, *mpartial = nullptr, *fin_side = nullptr;
+    float *cb[3] = {}, *cv[3] = {}, *ca[3] = {}, *ce[3] = {}, *hist[8] = {};
+    int* mpos = nullptr;
+    size_t mpcap = 0;  // floats of mpartial, the back part's own split-K slabs
+  };
+  BackBufs bbm_{};
+  BackBufs back_alloc(int rows, int nfr);
+  // The frames one back pass decodes and where its output goes
+  struct BackPass {
+    int nfr = 1;
+    const float* lat[NFR_MAX] = {};  // per frame f < nfr: latents [B][32] and frame flags [B]
+    const FrameFlags* flags[NFR_MAX] = {};
+    float* pcm = nullptr;  // frame f of row b at pcm + b * pcm_ld + f * FRAME
+    long pcm_ld = FRAME;
+    unsigned char* wire = nullptr;  // the pass's wire block; null: no wire / tempo ops
+    bool commit = true;             // the pass ends in the commit of the rows' codec state
+  };
+  BackPass step_pass(int hb, int nfr) const;  // the engine's own pass over hand-off buffers hb .. hb + nfr - 1
+  ResetArgs reset_args(int n) const;  // the slot_reset of n staged admissions
+  void prefill_rows(std::vector<Op>& ops, int slot, int T, int p0, const FlowBufs& fb);
   void run_ops(const std::vector<Op>& ops);
   void run_ops_on(const std::vector<Op>& ops, hipStream_t s);
   std::vector<Op> build_step(int B);
-  // hb: front -> back hand-off buffer (frame index mod NHB); qp: parity of the back part's
-  // quantizer history (frame index mod 2; the back part reads the previous frame's half)
+  // hb: front -> back hand-off buffer (frame index mod NHB); qp: the back part's frame index mod 2
   void build_front(std::vector<Op>& ops, int B, int hb, int lsd_run);
-  // back part over nfr consecutive frames from hand-off buffers hb, hb + 1, .. hb + nfr - 1; the
-  // PCM goes to the pass block of hb (pcm_frames frames per row, pcmp_) or, with pcm_frames 1, to
-  // pcm_[hb]
-  void build_back(std::vector<Op>& ops, int B, int hb, int nfr, int qp, int pcm_frames);
+  void build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const BackPass& pass);
   // multi-frame passes: a pass whose later calls were all flushes decodes only the frames its
   // calls started (nfr in part_graph's key)
   // (front parts: lsd_run, the Euler steps the graph runs, is part of the key too)
@@ -190,13 +211,13 @@ class Engine {
   void copy_out(int B, int hb, hipStream_t s);
   void push_rr(std::vector<Op>& ops, const std::string& name, const RowReduceArgs& r);
   void flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
-                   const FlowBufs* fb = nullptr);
+                   const FlowBufs& fb);
   void linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M, const float* Wt,
-                    int N, int K, int* S_out, const FlowBufs* fb = nullptr);
+                    int N, int K, int* S_out, const FlowBufs& fb);
   void conv_op(std::vector<Op>& ops, const std::string& name, const float* X, int B, int T_in, int cin, const float* H,
                int P, int stride, int elu, const float* Wt, int cout, int ktaps, int phases, const float* bias,
                const float* R, float* Y, int T_out, int tstride, int layout = TILE_KSPLIT_4W, int elu_out = 0,
-               float* Y2 = nullptr, int ksplit = 1);
+               float* Y2 = nullptr, int ksplit = 1, float* slabs = nullptr, size_t slab_cap = 0);
   void dense_op(std::vector<Op>& ops, const std::string& name, const float* X, int M, const float* Wt, int N, int K,
                 const float* bias, int act, const float* rscale, const float* R, float* Y,
                 int layout = TILE_KSPLIT_4W);
@@ -244,15 +265,11 @@ class Engine {
   hipStream_t stream_ = nullptr;
   Layout L_{};
   float* blob_ = nullptr;
-  std::vector<void*> allocs_;
+  std::vector<void*> allocs_, hallocs_;
 
-  // per-slot streaming state
-  float* kv_ = nullptr;  // [max_slots][NL][2][NH][max_ctx][64]
-  long kv_slot_ = 0, kv_layer_ = 0;
-  float* ring_ = nullptr;  // [max_slots][MNL][2][MNH][RING][64]
+  // per-slot streaming state (the FlowLM KV in fbm_, the codec's in bbm_)
   long ring_slot_ = 0, ring_layer_ = 0;
   int* fpos_ = nullptr;
-  int* mpos_ = nullptr;
   // shared voice prefixes (KvStore::pre): per slot, the voice cache its positions < F read from
   // and F (0: the slot's own rows); pinned host mirrors; the
   // voice each slot references. PTTS_NO_SHARED_VOICE (probe builds) copies the prefix in instead.
@@ -266,19 +283,14 @@ class Engine {
   // work may still read it, else stream_ is synchronized first)
   void voice_release(int slot, bool drained);
   SlotState* st_ = nullptr;
-  float *lat_in_ = nullptr, *cur_ = nullptr, *qprev_ = nullptr, *qcur_ = nullptr, *eos_ = nullptr;
-  float* hist_[8] = {};
+  float *lat_in_ = nullptr, *cur_ = nullptr, *eos_ = nullptr;
   int hist_T_[8] = {}, hist_C_[8] = {}, hist_P_[8] = {};
 
   // activations
   static constexpr int PREFILL = 2048;  // rows per prefill pass (batched admission: all slots' text)
-  size_t pcap_ = 0;
-  float *x_ = nullptr, *h_ = nullptr, *q_ = nullptr, *o_ = nullptr, *u_ = nullptr, *partial_ = nullptr;
   // split-tail scratch of the prefill GEMMs (GemmArgs::tail_S; one stream at a time uses it)
   static constexpr size_t TAIL_CAP = (size_t)16 << 20;
   static constexpr int TICKETS = 1024;
-  float* tslab_ = nullptr;
-  int* tickets_ = nullptr;
   int* ids_dev_ = nullptr;
   int* rowtab_dev_ = nullptr;   // [PREFILL] slot << 16 | pos, -1 = padding row (16-row groups)
   int *ctab_dev_ = nullptr, *qrow_dev_ = nullptr, *orow_dev_ = nullptr;  // compact admission rows (RowMap)
@@ -301,9 +313,6 @@ class Engine {
   size_t hx_floats(int B, int lsd) const { return (size_t)lsd * 13 * ((B + 15) / 16 * 16) * FD; }
   float* inw_t_ = nullptr;  // input_linear weight transposed, [32][1024] (k_input_ln)
   int *hctr_ = nullptr, *herr_ = nullptr;
-  float *mx_ = nullptr, *mh_ = nullptr, *mq_ = nullptr, *mo_ = nullptr, *mqkv_ = nullptr, *mu_ = nullptr;
-  float* a0_ = nullptr;
-  float *cb_[3] = {}, *cv_[3] = {}, *ca_[3] = {}, *ce_[3] = {};
   float* trb_[3] = {};  // transposed-conv biases replicated over the r output phases [r][Cout]
   // front -> back hand-off per step parity, and the back part's own split-K slabs
   // Up to three hand-off buffers: front(k) writes buffer k % nhb_ and waits only for back(k - nhb_)
@@ -324,7 +333,6 @@ class Engine {
   // buffers, per pass (buffers q with q / nfr = p), and its pinned host copy
   float* pcmp_[NHB / 2] = {};
   float* h_pcmp_[NHB / 2] = {};
-  float* fin_side_ = nullptr;  // [slot][nfr * FRAME / 128][2]: the fused final conv's tile-boundary shares
   // rows admitted inside a pass's calls (not at a call k with k % nfr == 0) start at the next pass
   // boundary: their SlotState (active) is written right before that front part (pinned staging)
   SlotState* h_act_ = nullptr;
@@ -340,9 +348,6 @@ class Engine {
   float* pcm_[NHB] = {};
   float* meta_[NHB] = {};  // per parity, one allocation: lat_out [B][32] | flags [B] | eos_out [B]
   size_t meta_floats_ = 0;
-  float* mpartial_ = nullptr;
-  size_t mpcap_ = 0;
-  // in-launch split-K combine (front part only; the back part never uses it)
   int back_cap_ = 1;  // max workgroups per CU of the pipelined back part's kernels (PTTS_BACK_WG_CAP: probe builds)
   // pipelined stepping (cfg.pipeline): back part on its own stream, parity events
   bool pipeline_ = false;
@@ -380,7 +385,7 @@ class Engine {
   SlotState* h_idle_ = nullptr;  // pinned, constant: the idle state (active 0, eos_step -1) slots_cancel copies in
   int front_rows_ = 0;       // rows of the last front part (0: the call was a flush)
   bool admitted_since_call_ = false;  // an admission since the last step / flush call
-  // x_ / h_ / lat_in_ written outside the step graphs since the last front part (refresh_xh)
+  // fbm_.x / fbm_.h / lat_in_ written outside the step graphs since the last front part (refresh_xh)
   bool xh_dirty_ = true;
   void refresh_xh();
   void call_async(int B, bool front);
@@ -416,17 +421,6 @@ class Engine {
   // ---- first-frame previews (preview_enable)
   static constexpr int PV_MAX = 8;  // rows per preview pass (the small-tile back path: < 16 rows)
   static constexpr int PV_Q = 8;    // previews in flight / not yet fetched
-  // the buffers build_back reads and writes, swapped in while the preview graphs are built
-  struct BackBufs {
-    float *ring = nullptr, *qprev = nullptr, *qcur = nullptr, *mx = nullptr, *mh = nullptr, *mq = nullptr,
-          *mo = nullptr, *mqkv = nullptr, *mu = nullptr, *a0 = nullptr, *mpartial = nullptr, *fin_side = nullptr;
-    float *cb[3] = {}, *cv[3] = {}, *ca[3] = {}, *ce[3] = {}, *hist[8] = {};
-    float *lat = nullptr, *pcm = nullptr;
-    FrameFlags* flags = nullptr;
-    int* mpos = nullptr;
-    size_t mpcap = 0;
-  };
-  void swap_back(BackBufs& b);
   struct PvEntry {
     int n = 0;
     int slots[PV_MAX] = {};
@@ -435,7 +429,10 @@ class Engine {
   };
   int pv_max_ = 0;
   hipStream_t stream_pv_ = nullptr;
+  // the preview passes' own workspace (its codec state stays the fresh one) and their compact batch
   BackBufs pv_{};
+  float *pv_lat_ = nullptr, *pv_pcm_ = nullptr;
+  FrameFlags* pv_flags_ = nullptr;
   PvEntry pv_q_[PV_Q];
   int pv_head_ = 0, pv_count_ = 0;  // FIFO of launched, unfetched previews
   std::vector<std::pair<int, long long>> pv_pending_;  // (slot, call of its first front part)
@@ -454,7 +451,6 @@ class Engine {
 
   // ---- wire stage (wire_enable)
   bool wire_ = false;
-  bool wire_skip_ = false;  // build_back for a preview pass: no wire op
   int* wire_fmt_ = nullptr;     // [max_slots] encoding | rate index << 8 (0: none)
   std::vector<int> slot_wire_;  // its host mirror (copy_out: no chunk copy while no row has a format)
   int* wire_frames_ = nullptr;  // [max_slots] frames received
