@@ -361,6 +361,32 @@ int ptts_tempo_enable(ptts_engine* e, int on);
  * ptts_tempo_len samples. */
 long ptts_tempo_len(long n, int speed_permille);
 int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, float* out);
+/* FLAC (no reference counterpart; RFC 9639, restated in DESIGN.md section 21). A row admitted with
+ * wire_encoding = PTTS_WIRE_FLAC gets, per frame, the FLAC frames of the 16-bit samples its
+ * PTTS_WIRE_S16 chunk at the same rate (and speed) would hold: mono, 16 bit, blocks of at most 4,608
+ * samples (one frame per chunk; up to three on a tempo-enabled engine), fixed predictors of order
+ * 0..4 with partitioned Rice codes chosen by the deterministic rule of section 21, CONSTANT or
+ * VERBATIM subframes where they are cheaper. The frames carry the index of their first sample within
+ * the row's utterance (variable-blocksize strategy), counted from 0 at the admission, so a row's
+ * chunks behind a STREAMINFO header (42 bytes, built by the caller: min / max blocksize 16 / 4608,
+ * the row's rate, 1 channel, 16 bits) are a complete stream that decodes to exactly those samples.
+ * The encoder runs on the GPU behind the wire stage and writes over the chunk slot; a chunk of n
+ * samples is at most ptts_flac_bound(n) = 2 n + 17 ceil(n / 4608) bytes, which fits the chunk slots
+ * of ptts_fetch_wire. Only the row's wire bytes change: its f32 PCM, latents and flags, and every
+ * other row, are what they are without it. PTTS_WIRE_FLAC asked of an engine without
+ * ptts_flac_enable is PTTS_ERR_INVALID and admits nothing; ptts_wire_len returns 0 for it and
+ * ptts_wire_encode rejects it (the size is not a function of n).
+ * ptts_flac_enable: valid on a wire-enabled idle engine before its first step (PTTS_ERR_INVALID
+ * otherwise); on = 0, or never called: the passes, graphs and copies the engine has without it. */
+#define PTTS_WIRE_FLAC 4
+int ptts_flac_enable(ptts_engine* e, int on);
+/* The FLAC seam alone: the bound above (0 for n < 1; host only), and the stage's chunk encoder on
+ * n <= 11,058 arbitrary 16-bit samples at sample_rate (one of the wire rates), the first of which
+ * has index first_sample (0 <= first_sample, first_sample + n <= 2^36) in its stream; out holds
+ * ptts_flac_bound(n) bytes, *n_bytes receives the frames' byte total. */
+long ptts_flac_bound(long n);
+int ptts_flac_encode(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
+                     uint8_t* out, int* n_bytes);
 
 /* *cap: cfg.lsd_decode_steps. *last_run: the Euler steps the most recent step call ran (0 before
  * the first): the largest count among that call's rows still open (admitted, not closed, last

@@ -358,6 +358,15 @@ int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, floa
   return guard([&] { eng(e).tempo_host(pcm, n, speed_permille, out); });
 }
 
+int ptts_flac_enable(ptts_engine* e, int on) { return guard([&] { eng(e).flac_enable(on != 0); }); }
+
+long ptts_flac_bound(long n) { return ptts::Engine::flac_bound(n); }
+
+int ptts_flac_encode(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
+                     uint8_t* out, int* n_bytes) {
+  return guard([&] { eng(e).flac_encode_host(samples, n, sample_rate, first_sample, out, n_bytes); });
+}
+
 int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run) {
   return guard([&] {
     if (!e || !e->impl) throw ptts::Error(PTTS_ERR_INVALID, "null engine");

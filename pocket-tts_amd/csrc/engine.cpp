@@ -1615,8 +1615,23 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       w.tin = tempo_out_;
       w.tcnt = tempo_cnt_;
     }
+    if (flac_) w.first = flac_first_;
     ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
                    (double)B * nfr * (4.0 * FRAME + wire_chunk_max())});
+    if (flac_) {  // the FLAC rows' 16-bit chunks become frames, in place (section 21)
+      FlacArgs fa{};
+      fa.B = B;
+      fa.out_frames = nfr_;
+      fa.fmt = wire_fmt_;
+      fa.first = flac_first_;
+      fa.out = w.out;
+      fa.counts = w.counts;
+      fa.chunk = w.chunk;
+      Op op{"flac", [fa](hipStream_t s) { flac_stage(fa, s); }, 0.0, (double)B * nfr * 2.0 * wire_chunk_max()};
+      // an isolated replay (time_op) encodes fresh 16-bit chunks: the stage overwrites its input
+      op.prep = [w](hipStream_t s) { wire_stage(w, s); };
+      ops.push_back(op);
+    }
   }
 }
 
@@ -2978,7 +2993,8 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
-      PTTS_REQUIRE(we >= 0 && we <= WIRE_ALAW, "wire_encoding must be 0 (s16) or PTTS_WIRE_S16 / _ULAW / _ALAW");
+      PTTS_REQUIRE(we != WIRE_FLAC || flac_, "PTTS_WIRE_FLAC needs a FLAC-enabled engine (ptts_flac_enable before the first step)");
+      PTTS_REQUIRE(we >= 0 && we <= WIRE_FLAC, "wire_encoding must be 0 (s16) or PTTS_WIRE_S16 / _ULAW / _ALAW / _FLAC");
       wfmt[i] = (we ? we : WIRE_S16) | ri << 8;
     }
     const int slot = slots[i];
@@ -3409,6 +3425,47 @@ void Engine::tempo_host(const float* pcm, int n, int sp, float* out) {
     throw;
   }
   (void)hipFree(dx), (void)hipFree(dw), (void)hipFree(dy);
+}
+
+// ------------------------------------------------------------------ FLAC stage
+void Engine::flac_enable(bool on) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the FLAC stage is chosen on an idle engine before its first step");
+  PTTS_REQUIRE(!on || wire_, "the FLAC stage needs a wire-enabled engine (ptts_wire_enable first)");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !flac_first_) flac_first_ = (int*)dalloc((size_t)max_slots_ * nfr_);
+  flac_ = on;
+}
+
+long Engine::flac_bound(long n) { return n < 1 ? 0 : ptts::flac_bound(n); }
+
+void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes) {
+  PTTS_REQUIRE(x && out && n_bytes, "null argument");
+  PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11077]");
+  const int ri = wire_rate_index(rate);
+  PTTS_REQUIRE(ri >= 0, "sample_rate must be one of 8000, 16000, 24000, 44100, 48000");
+  PTTS_REQUIRE(first >= 0 && first + n <= (1LL << 36), "first_sample outside the 36-bit sample number");
+  const size_t cap = ((size_t)flac_bound(n) + 3) / 4 * 4;
+  sync();
+  void *dx = nullptr, *dy = nullptr, *dn = nullptr;
+  int got = 0;
+  try {
+    PTTS_HIP(hipMalloc(&dx, sizeof(int16_t) * n));
+    PTTS_HIP(hipMalloc(&dy, cap));
+    PTTS_HIP(hipMalloc(&dn, sizeof(int)));
+    PTTS_HIP(hipMemcpyAsync(dx, x, sizeof(int16_t) * n, hipMemcpyHostToDevice, stream_));
+    ptts::flac_encode((const short*)dx, n, ri, first, (unsigned char*)dy, (int*)dn, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(&got, dn, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+    if (got < 1 || (size_t)got > cap) throw Error(PTTS_ERR_STATE, "flac_encode: corrupt byte count");
+    PTTS_HIP(hipMemcpy(out, dy, (size_t)got, hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(dy), (void)hipFree(dn);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(dy), (void)hipFree(dn);
+  *n_bytes = got;
 }
 
 void Engine::mark_admission() {

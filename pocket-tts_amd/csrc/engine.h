@@ -140,6 +140,13 @@ class Engine {
   int wire_chunk_max() const { return tempo_ ? WIRE_CHUNK_MAX_TEMPO : WIRE_CHUNK_MAX; }
   // the seam alone: whole-signal f32 at 24 kHz -> tempo_len(n, sp) samples
   void tempo_host(const float* pcm, int n, int sp, float* out);
+  // FLAC stage (ptts_flac_enable): rows admitted with PTTS_WIRE_FLAC have their
+  // 16-bit chunks encoded as FLAC frames (kernels.h flac_stage) behind the wire stage
+  void flac_enable(bool on);
+  bool flac() const { return flac_; }
+  static long flac_bound(long n);  // bytes of an n-sample chunk's frames, at most (0: n < 1)
+  // the seam alone: the stage's chunk encoder on n 16-bit samples at `rate`
+  void flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes);
 
   double time_op(int B, const std::string& name, int reps);
   // GEMM-core test hook (ptts_test_gemm): Y = X W^T on tile `layout` (host buffers)
@@ -469,6 +476,9 @@ class Engine {
   int* tempo_cnt_ = nullptr;     // [max_slots][nfr]
   int* admit_tempo_ = nullptr;   // staged speeds of an admission (device), h_tempo_ (pinned)
   int* h_tempo_ = nullptr;
+  // ---- FLAC stage (flac_enable)
+  bool flac_ = false;
+  int* flac_first_ = nullptr;    // [max_slots][nfr] a FLAC chunk's first sample index (k_wire -> k_flac)
   // per pass (index: hand-off buffer / frames per pass): counts [max_slots][nfr] | chunks
   // [max_slots][nfr][WIRE_CHUNK_MAX], and its pinned host copy
   static constexpr int WIRE_BLOCKS = 3;

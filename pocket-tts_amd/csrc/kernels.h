@@ -719,6 +719,8 @@ void voice_ingest(const void* x, int fmt_s16, int n_in, const float* taps, const
 // frames received and the last WIRE_TAIL input samples; the admission reset (k_slot_reset) zeroes
 // the count and writes the format.
 constexpr int WIRE_NONE = 0, WIRE_S16 = 1, WIRE_ULAW = 2, WIRE_ALAW = 3;
+// FLAC (below): k_wire treats the row as WIRE_S16 and records each chunk's first sample index
+constexpr int WIRE_FLAC = 4;
 constexpr int WIRE_RATES = 5;
 constexpr int WIRE_RATE_HZ[WIRE_RATES] = {8000, 16000, 24000, 44100, 48000};
 constexpr int WIRE_CHUNK_MAX = 8192;  // bytes per (row, frame) slot: 3860 16-bit samples at most
@@ -748,6 +750,7 @@ struct WireArgs {
   const int* tempo_sp = nullptr;  // [B] (null: no tempo stage)
   const float* tin = nullptr;
   const int* tcnt = nullptr;
+  int* first = nullptr;     // [B][out_frames] (null: no FLAC stage) a WIRE_FLAC chunk's first output index
 };
 void wire_stage(const WireArgs& a, hipStream_t s);
 // n samples already at the wire rate -> n (G.711) or 2 n (16-bit) bytes; `out` holds the byte count
@@ -791,6 +794,37 @@ struct TempoArgs {
 void tempo_stage(const TempoArgs& a, hipStream_t s);
 // whole signal: x [n] -> y [tempo_len(n, sp)], one workgroup, the hop functions of the stage
 void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_t s);
+
+// FLAC stage: behind the wire stage, the 16-bit chunk of every WIRE_FLAC row
+// becomes ceil(n / FLAC_BLOCK) FLAC frames (mono, 16 bit, fixed predictors of order 0..4, partitioned
+// Rice codes, the exhaustive choice rule of section 21), written back to back over the chunk slot,
+// and the chunk's count becomes their byte total. One workgroup per (row, frame slot); it holds the
+// whole chunk in LDS before its first store, so encoding in place is safe. Integer arithmetic only.
+constexpr int FLAC_BLOCK = 4608;                 // the subset limit at <= 48 kHz
+constexpr int FLAC_FRAME_OVERHEAD = 17;          // 14 header, 1 subframe header, 2 CRC-16
+constexpr int FLAC_CHUNK_SAMPLES = 2 * TEMPO_OUT_MAX + 21;  // the slot bound above; the longest chunk is 11,058
+constexpr int flac_rate_code(int ri) { return ri == 0 ? 4 : ri == 1 ? 5 : ri == 2 ? 7 : ri == 3 ? 9 : 10; }  // by WIRE_RATE_HZ
+constexpr long flac_bound(long n) {              // bytes of the frames of an n-sample chunk, at most
+  return 2 * n + FLAC_FRAME_OVERHEAD * ((n + FLAC_BLOCK - 1) / FLAC_BLOCK);
+}
+static_assert(flac_bound(3860) <= WIRE_CHUNK_MAX, "a FLAC chunk fits the chunk slot");
+static_assert(flac_bound(FLAC_CHUNK_SAMPLES) <= WIRE_CHUNK_MAX_TEMPO && FLAC_CHUNK_SAMPLES <= 3 * FLAC_BLOCK &&
+                  2 * FLAC_CHUNK_SAMPLES <= WIRE_CHUNK_MAX_TEMPO,
+              "a FLAC chunk of a tempo row is at most three frames and fits the chunk slot");
+static_assert(TEMPO_HS * WIRE_RATE_HZ[0] / 24000 >= 16, "the shortest non-last chunk (one tempo hop at 8 kHz) is a legal block");
+struct FlacArgs {
+  int B, out_frames;
+  const int* fmt;           // [B] the wire formats
+  const int* first;         // [B][out_frames] from k_wire
+  unsigned char* out;       // the wire stage's chunk slots, encoded in place
+  int* counts;              // [B][out_frames] in: bytes of the s16 chunk; out: bytes of its frames
+  int chunk;
+};
+void flac_stage(const FlacArgs& a, hipStream_t s);
+// the stage's chunk encoder on n <= FLAC_CHUNK_SAMPLES samples (device pointers): frames into `out`
+// (flac_bound(n) bytes rounded up to a multiple of 4), their byte total into *n_bytes
+void flac_encode(const short* x, int n, int rate_index, long long first_sample, unsigned char* out, int* n_bytes,
+                 hipStream_t s);
 
 // dst [nch][rows][cols]: row r of chunk c = src[c * chunk_stride .. + cols) (each encoder chunk's
 // first row replicated: the history of the chunked ConvDownsample1d), one launch over all chunks

@@ -3673,7 +3673,8 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
   __shared__ __attribute__((aligned(16))) float s_y[WIRE_OUT_MAX];
   const int b = blockIdx.x, t = threadIdx.x;
   const int fmt = a.fmt[b];
-  const int enc = fmt & 0xFF, ri = fmt >> 8;
+  const bool flac = (fmt & 0xFF) == WIRE_FLAC;  // uniform: 16-bit chunks, which k_flac encodes in place
+  const int enc = flac ? WIRE_S16 : fmt & 0xFF, ri = fmt >> 8;
   int* cnt = a.counts + (long)b * a.out_frames;
   if (enc == WIRE_NONE || ri < 0 || ri >= WIRE_RATES) {  // uniform
     if (t < a.out_frames) cnt[t] = 0;
@@ -3715,6 +3716,7 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
         m1 = fl.last && fin ? (N1 * p.up + p.down - 1) / p.down
                             : (N1 == 0 ? 0 : (N1 * p.up - 1 - p.half) / p.down + 1);
       }
+      if (flac && a.first && done == 0 && t == 0) a.first[(long)b * a.out_frames + f] = (int)m0;
       // (never more: the chunk sizes of kernels.h)
       const long count = max(min(min(m1 - m0, (long)WIRE_OUT_MAX - rem), cap - 4 * gbase - rem), 0L);
       const long tot = rem + count;
@@ -3765,6 +3767,331 @@ void wire_stage(const WireArgs& a, hipStream_t s) {
     if (a.plan[r].L > WIRE_TAPS_MAX || a.plan[r].L < 1 || 2 * a.plan[r].half > WIRE_TAIL * a.plan[r].up)
       throw std::runtime_error("wire_stage: plan outside the kernel's LDS window");
   hipLaunchKernelGGL(k_wire, dim3(a.B), dim3(WIRE_THREADS), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------------------------
+// FLAC stage (see kernels.h; the format and the choice rule are DESIGN.md section 21). Per block of
+// at most FLAC_BLOCK samples, all in LDS: (1) sum the folded residuals' Rice costs per order, finest
+// partition and parameter; (2) choose (order, partition order, parameters); (3) scan the code
+// lengths over the workgroup and OR the codes into a zeroed bit buffer, whose words hold the
+// stream's bytes big-endian; (4) CRC-16 as the XOR of per-lane run CRCs shifted by x^(8 bytes after);
+// (5) byte-swapped dword stores. A frame starts at any byte, so the buffer starts at the dword that
+// holds the frame's first byte and word 0 carries the bytes of the previous frame (`carry`).
+constexpr int FLAC_THREADS = 1024, FLAC_PARTS = 64, FLAC_KS = 15, FLAC_ORDERS = 5;
+constexpr int FLAC_SUMS = FLAC_ORDERS * FLAC_PARTS * FLAC_KS;
+constexpr int FLAC_BITS_WORDS = (3 + FLAC_FRAME_OVERHEAD + 2 * FLAC_BLOCK + 3) / 4 + 2;
+constexpr unsigned FLAC_COST_SAT = 1u << 24;  // > the verbatim cost of any block: 64 of them fit 32 bits
+static_assert(FLAC_BITS_WORDS * 4 <= FLAC_SUMS * 8, "the bit buffer lives in the cost sums' LDS");
+static_assert(8 + 16 * FLAC_BLOCK < FLAC_COST_SAT, "saturated partition costs change no decision");
+
+// nbits <= 16 of val at bit `pos` of the stream held in buf (bit 31 of a word first)
+__device__ __forceinline__ void flac_put(unsigned* buf, unsigned pos, int nbits, unsigned val) {
+  const unsigned long long v = (unsigned long long)val << (64 - nbits - (int)(pos & 31));
+  const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
+  if ((pos >> 5) + 1 >= (unsigned)FLAC_BITS_WORDS) return;  // (never: a frame is at most 17 + 2 n bytes)
+  if (hi) atomicOr(&buf[pos >> 5], hi);
+  if (lo) atomicOr(&buf[(pos >> 5) + 1], lo);
+}
+__device__ __forceinline__ unsigned flac_byte(const unsigned* buf, int y) {
+  return (buf[y >> 2] >> (24 - 8 * (y & 3))) & 0xFFu;
+}
+// a b mod x^16 + x^15 + x^2 + 1
+__device__ __forceinline__ unsigned flac_mulmod(unsigned a, unsigned b) {
+  unsigned r = 0;
+  for (int i = 15; i >= 0; --i) {
+    r <<= 1;
+    if (r & 0x10000u) r ^= 0x18005u;
+    if ((b >> i) & 1u) r ^= a;
+  }
+  return r;
+}
+// the residual of the fixed predictor of order o at sample i >= o
+__device__ __forceinline__ int flac_residual(const short* s, int i, int o) {
+  const int s0 = s[i];
+  if (o == 0) return s0;
+  const int s1 = s[i - 1];
+  if (o == 1) return s0 - s1;
+  const int s2 = s[i - 2];
+  if (o == 2) return s0 - 2 * s1 + s2;
+  const int s3 = s[i - 3];
+  if (o == 3) return s0 - 3 * s1 + 3 * s2 - s3;
+  return s0 - 4 * s1 + 6 * s2 - 4 * s3 + s[i - 4];
+}
+// the sum of v over each row of 16 lanes, in every lane of the row: four DPP rotations, no LDS
+// round trip (a __shfl_xor tree costs one per step: 90 of them per order and segment were 75 % of
+// the launch)
+__device__ __forceinline__ unsigned flac_row_sum(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xF, 0xF, false);  // row_ror:2
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xF, 0xF, false);  // row_ror:1
+  return v;
+}
+__device__ __forceinline__ unsigned flac_fold(int e) { return ((unsigned)e << 1) ^ (unsigned)(e >> 31); }
+__device__ __forceinline__ int flac_number_bytes(long long v) {
+  return v < (1LL << 7) ? 1 : v < (1LL << 11) ? 2 : v < (1LL << 16) ? 3 : v < (1LL << 21) ? 4
+       : v < (1LL << 26) ? 5 : v < (1LL << 31) ? 6 : 7;
+}
+
+// The chunk s_x [n_total] (LDS) -> its frames at dst (dwords; may be the chunk's own global slot,
+// which is not read here); returns their byte total. Called by every lane of a FLAC_THREADS workgroup.
+__device__ int flac_chunk(const short* s_x, int n_total, int rc, long long first, unsigned* dst) {
+  __shared__ unsigned long long s_sum[FLAC_SUMS];  // [order][finest partition][k], then prefix sums over partitions
+  __shared__ unsigned s_pcost[FLAC_ORDERS][128];   // [order][(1 << p) - 1 + partition]: best cost, saturated
+  __shared__ unsigned char s_pk[FLAC_ORDERS][128]; // and its parameter
+  __shared__ unsigned s_cost[FLAC_ORDERS][7];
+  __shared__ unsigned s_wsum[FLAC_THREADS / 64];
+  __shared__ unsigned s_crc;
+  unsigned* s_bits = reinterpret_cast<unsigned*>(s_sum);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  unsigned carry = 0;
+  int boff = 0, total_bytes = 0;
+  long wbase = 0;
+  for (int off = 0; off < n_total; off += FLAC_BLOCK) {
+    const short* s = s_x + off;
+    const int n = min(FLAC_BLOCK, n_total - off);
+    const int c = (n + FLAC_THREADS - 1) / FLAC_THREADS;  // consecutive samples per lane
+    const int i0 = min(t * c, n), i1 = min(i0 + c, n);
+    int diff = 0;
+    for (int i = i0; i < i1; ++i) diff |= s[i] != s[0];
+    __syncthreads();  // the previous block's stores have read the bit buffer
+    for (int i = t; i < FLAC_SUMS; i += FLAC_THREADS) s_sum[i] = 0;
+    if (t == 0) s_crc = 0;
+    const bool varied = __syncthreads_or(diff) != 0;
+    int pmax = -1;  // no candidate below 16 samples
+    if (n >= 16) {
+      pmax = min(__ffs(n) - 1, 6);
+      while ((n >> pmax) < 16) --pmax;
+    }
+    int kind = 0, bo = 0, bp = 0;  // 0 CONSTANT, 1 VERBATIM, 2 FIXED
+    if (varied) kind = 1;
+    if (varied && pmax >= 0) {  // uniform
+      // ---- (1) cost sums at the finest partitions. A segment is a run of samples inside one finest
+      // partition (a whole one, or a 1 / S of it when there are fewer partitions than waves): at most
+      // 288 samples, so a row's sum fits 32 bits. A wave strides over its segment, each row of 16
+      // lanes reduces by DPP, and the rows' first lanes add into the partition's sums.
+      const int P = 1 << pmax, psz = n >> pmax;
+      const int S = P >= FLAC_THREADS / 64 ? 1 : FLAC_THREADS / 64 / P;
+      for (int g = wv; g < P * S; g += FLAC_THREADS / 64) {  // uniform per wave
+        const int j = g / S, r = g - j * S;
+        const int a0 = j * psz + r * psz / S, a1 = j * psz + (r + 1) * psz / S;
+#pragma unroll 1
+        for (int o = 0; o < FLAC_ORDERS; ++o) {  // one order at a time: 15 sums in registers
+          unsigned acc[FLAC_KS];
+#pragma unroll
+          for (int k = 0; k < FLAC_KS; ++k) acc[k] = 0;
+          for (int i = max(a0, o) + lane; i < a1; i += 64) {  // the first o samples are warm-up
+            const unsigned u = flac_fold(flac_residual(s, i, o));
+#pragma unroll
+            for (int k = 0; k < FLAC_KS; ++k) acc[k] += u >> k;
+          }
+#pragma unroll
+          for (int k = 0; k < FLAC_KS; ++k) {
+            const unsigned v = flac_row_sum(acc[k]);  // every lane holds the sum of its row of 16
+            if ((lane & 15) == 0 && v) atomicAdd(&s_sum[(o * FLAC_PARTS + j) * FLAC_KS + k], (unsigned long long)v);
+          }
+        }
+      }
+      __syncthreads();
+      if (t < FLAC_ORDERS * FLAC_KS) {  // inclusive prefix sums along the partitions: any partition is two reads
+        const int o = t / FLAC_KS, k = t - o * FLAC_KS;
+        unsigned long long run = 0;
+        for (int j = 0; j < P; ++j) {
+          run += s_sum[(o * FLAC_PARTS + j) * FLAC_KS + k];
+          s_sum[(o * FLAC_PARTS + j) * FLAC_KS + k] = run;
+        }
+      }
+      __syncthreads();
+      // ---- (2) the best parameter of every partition of every (o, p), then the cost of every (o, p)
+      if (t < FLAC_ORDERS * 128) {
+        const int o = t >> 7, idx = t & 127;
+        const int p = 31 - __clz(idx + 1), q = idx + 1 - (1 << p);
+        if (idx < 127 && p <= pmax) {
+          const int span = 1 << (pmax - p);
+          const unsigned long long cnt = (unsigned)((n >> p) - (q == 0 ? o : 0));
+          unsigned long long best = ~0ull;
+          int bk = 0;
+          for (int k = 0; k < FLAC_KS; ++k) {
+            const unsigned long long sum = s_sum[(o * FLAC_PARTS + (q + 1) * span - 1) * FLAC_KS + k] -
+                                           (q ? s_sum[(o * FLAC_PARTS + q * span - 1) * FLAC_KS + k] : 0ull);
+            const unsigned long long cost = sum + cnt * (unsigned)(k + 1);
+            if (cost < best) best = cost, bk = k;
+          }
+          best += 4;
+          s_pcost[o][idx] = best < FLAC_COST_SAT ? (unsigned)best : FLAC_COST_SAT;
+          s_pk[o][idx] = (unsigned char)bk;
+        }
+      }
+      __syncthreads();
+      if (t < FLAC_ORDERS * 7) {
+        const int o = t / 7, p = t % 7;
+        if (p <= pmax) {
+          unsigned cost = 8 + 16 * o + 6;
+          for (int q = 0; q < (1 << p); ++q) cost += s_pcost[o][(1 << p) - 1 + q];
+          s_cost[o][p] = cost;
+        }
+      }
+      __syncthreads();
+      unsigned best = 8u + 16u * (unsigned)n;  // VERBATIM unless something is strictly cheaper
+      for (int o = 0; o < FLAC_ORDERS; ++o)
+        for (int p = 0; p <= pmax; ++p)
+          if (s_cost[o][p] < best) best = s_cost[o][p], kind = 2, bo = o, bp = p;
+    }
+    __syncthreads();  // the sums are dead: their LDS becomes the bit buffer
+    for (int i = t; i < FLAC_BITS_WORDS; i += FLAC_THREADS) s_bits[i] = i == 0 ? carry : 0u;
+    __syncthreads();
+    // ---- (3) header (lane 0), then the subframe's codes
+    const long long v = first + off;
+    const int nb = flac_number_bytes(v);
+    const unsigned base = 8u * (unsigned)(boff + 4 + nb + (n <= 256 ? 1 : 2) + 1) + 8u;  // after the subframe header
+    if (t == 0) {
+      unsigned pos = 8u * (unsigned)boff, crc = 0;
+      auto emit = [&](unsigned byte) {
+        flac_put(s_bits, pos, 8, byte);
+        pos += 8;
+        crc ^= byte;
+        for (int i = 0; i < 8; ++i) crc = (crc & 0x80u ? (crc << 1) ^ 0x07u : crc << 1) & 0xFFu;
+      };
+      emit(0xFFu);
+      emit(0xF9u);
+      emit(((n <= 256 ? 6u : 7u) << 4) | (unsigned)rc);
+      emit(0x08u);
+      if (nb == 1) {
+        emit((unsigned)v);
+      } else {
+        emit(((0xFFu << (8 - nb)) & 0xFFu) | (unsigned)(nb == 7 ? 0 : v >> (6 * (nb - 1))));
+        for (int i = nb - 2; i >= 0; --i) emit(0x80u | (unsigned)((v >> (6 * i)) & 0x3F));
+      }
+      if (n > 256) emit((unsigned)(n - 1) >> 8);
+      emit((unsigned)(n - 1) & 0xFFu);
+      const unsigned c8 = crc;
+      emit(c8);
+      flac_put(s_bits, pos, 8, kind == 0 ? 0u : kind == 1 ? 2u : (8u | (unsigned)bo) << 1);
+      if (kind == 0) flac_put(s_bits, base, 16, (unsigned)s[0] & 0xFFFFu);
+    }
+    unsigned bits_end = base + 16;
+    if (kind == 1) {
+      for (int i = i0; i < i1; ++i) flac_put(s_bits, base + 16u * i, 16, (unsigned)s[i] & 0xFFFFu);
+      bits_end = base + 16u * n;
+    } else if (kind == 2) {
+      const int pn = n >> bp;  // samples per partition
+      const unsigned char* ks = &s_pk[bo][(1 << bp) - 1];
+      unsigned mine = 0;
+      for (int i = i0; i < i1; ++i) {
+        if (i < bo) {
+          mine += 16;
+          continue;
+        }
+        const int k = ks[i / pn];
+        mine += (flac_fold(flac_residual(s, i, bo)) >> k) + 1 + k + (i == bo ? 10 : i % pn == 0 ? 4 : 0);
+      }
+      unsigned incl = mine;  // exclusive scan of the lanes' bit counts over the workgroup
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned y = __shfl_up(incl, d);
+        if (lane >= d) incl += y;
+      }
+      if (lane == 63) s_wsum[wv] = incl;
+      __syncthreads();
+      unsigned before = 0, all = 0;
+      for (int w = 0; w < FLAC_THREADS / 64; ++w) {
+        if (w < wv) before += s_wsum[w];
+        all += s_wsum[w];
+      }
+      unsigned pos = base + before + incl - mine;
+      for (int i = i0; i < i1; ++i) {
+        if (i < bo) {
+          flac_put(s_bits, pos, 16, (unsigned)s[i] & 0xFFFFu);
+          pos += 16;
+          continue;
+        }
+        const int k = ks[i / pn];
+        if (i == bo) {  // 00 (Rice, 4-bit parameters) | partition order | the first parameter
+          flac_put(s_bits, pos, 10, (unsigned)bp << 4 | (unsigned)k);
+          pos += 10;
+        } else if (i % pn == 0) {
+          flac_put(s_bits, pos, 4, (unsigned)k);
+          pos += 4;
+        }
+        const unsigned u = flac_fold(flac_residual(s, i, bo));
+        pos += u >> k;  // the unary zeros are already there
+        flac_put(s_bits, pos, k + 1, 1u << k | (u & ((1u << k) - 1)));
+        pos += k + 1;
+      }
+      bits_end = base + all;
+    }
+    __syncthreads();
+    // ---- (4) CRC-16 over bytes [boff, eb) of the buffer
+    const int eb = min((int)((bits_end + 7) >> 3), boff + FLAC_FRAME_OVERHEAD - 2 + 2 * n);  // (never the bound)
+    {
+      const int len = eb - boff, run = (len + FLAC_THREADS - 1) / FLAC_THREADS;
+      const int y0 = min(boff + t * run, eb), y1 = min(y0 + run, eb);
+      unsigned crc = 0;
+      for (int y = y0; y < y1; ++y) {
+        crc ^= flac_byte(s_bits, y) << 8;
+        for (int i = 0; i < 8; ++i) crc = (crc & 0x8000u ? (crc << 1) ^ 0x8005u : crc << 1) & 0xFFFFu;
+      }
+      unsigned pw = 0x100u;  // x^8, squared per bit of the byte count after the run
+      for (int m = eb - y1; m > 0 && crc; m >>= 1) {
+        if (m & 1) crc = flac_mulmod(crc, pw);
+        pw = flac_mulmod(pw, pw);
+      }
+      for (int d = 32; d >= 1; d >>= 1) crc ^= __shfl_xor(crc, d);
+      if (lane == 0 && crc) atomicXor(&s_crc, crc);
+    }
+    __syncthreads();
+    if (t == 0) flac_put(s_bits, 8u * (unsigned)eb, 16, s_crc);
+    __syncthreads();
+    // ---- (5) the whole dwords leave; the rest is carried into the next frame's first word
+    const int tb = eb + 2, nfull = tb >> 2;
+    for (int w = t; w < nfull; w += FLAC_THREADS) dst[wbase + w] = __builtin_bswap32(s_bits[w]);
+    carry = tb & 3 ? s_bits[nfull] : 0u;
+    wbase += nfull;
+    total_bytes += tb - boff;
+    boff = tb & 3;
+  }
+  if (boff && t == 0) dst[wbase] = __builtin_bswap32(carry);  // zeros pad the last dword (inside the slot)
+  return total_bytes;
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void k_flac(FlacArgs a) {
+  __shared__ __attribute__((aligned(16))) short s_x[(FLAC_CHUNK_SAMPLES + 7) / 8 * 8];
+  const int b = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+  const int fmt = a.fmt[b], ri = fmt >> 8;
+  if ((fmt & 0xFF) != WIRE_FLAC || ri < 0 || ri >= WIRE_RATES) return;  // uniform
+  const long idx = (long)b * a.out_frames + f;
+  // k_wire's 16-bit chunk (never more than the frames of which fit the slot: the chunk sizes of kernels.h)
+  const int n = min(min(a.counts[idx] / 2, (a.chunk - 3 * FLAC_FRAME_OVERHEAD) / 2), FLAC_CHUNK_SAMPLES);
+  if (n <= 0) return;
+  unsigned* slot = reinterpret_cast<unsigned*>(a.out + idx * a.chunk);
+  for (int i = t; i < (n + 1) / 2; i += FLAC_THREADS) reinterpret_cast<unsigned*>(s_x)[i] = slot[i];
+  __syncthreads();
+  const int bytes = flac_chunk(s_x, n, flac_rate_code(ri), a.first[idx], slot);
+  if (t == 0) a.counts[idx] = bytes;
+}
+
+void flac_stage(const FlacArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.out_frames < 1 || a.out_frames > NFR_MAX || !a.fmt || !a.first || !a.out || !a.counts)
+    throw std::runtime_error("flac_stage: bad pass shape");
+  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || a.chunk > WIRE_CHUNK_MAX_TEMPO)
+    throw std::runtime_error("flac_stage: bad chunk slot");
+  hipLaunchKernelGGL(k_flac, dim3(a.B, a.out_frames), dim3(FLAC_THREADS), 0, s, a);
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void k_flac_encode(const short* __restrict__ x, int n, int rc,
+                                                              long long first, unsigned* out, int* n_bytes) {
+  __shared__ __attribute__((aligned(16))) short s_x[(FLAC_CHUNK_SAMPLES + 7) / 8 * 8];
+  for (int i = threadIdx.x; i < n; i += FLAC_THREADS) s_x[i] = x[i];
+  __syncthreads();
+  const int bytes = flac_chunk(s_x, n, rc, first, out);
+  if (threadIdx.x == 0) *n_bytes = bytes;
+}
+void flac_encode(const short* x, int n, int rate_index, long long first_sample, unsigned char* out, int* n_bytes,
+                 hipStream_t s) {
+  if (n < 1 || n > FLAC_CHUNK_SAMPLES || rate_index < 0 || rate_index >= WIRE_RATES || first_sample < 0 ||
+      first_sample + n > (1LL << 36))
+    throw std::runtime_error("flac_encode: bad chunk");
+  hipLaunchKernelGGL(k_flac_encode, dim3(1), dim3(FLAC_THREADS), 0, s, x, n, flac_rate_code(rate_index), first_sample,
+                     reinterpret_cast<unsigned*>(out), n_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ SAMPLE_RATE = 24000
 QUANT_NONE, QUANT_FLOW_LM, QUANT_ALL = 0, 1, 2
 BACK_F32, BACK_BF16, BACK_F32X6 = 0, 1, 2  # ptts_engine_config.back_mfma (PTTS_BACK_*)
 SAMPLES_F32, SAMPLES_S16 = 0, 1  # sample_format of ptts_voice_job_start (PTTS_SAMPLES_*)
-WIRE_NONE, WIRE_S16, WIRE_ULAW, WIRE_ALAW = 0, 1, 2, 3  # PTTS_WIRE_*
+WIRE_NONE, WIRE_S16, WIRE_ULAW, WIRE_ALAW, WIRE_FLAC = 0, 1, 2, 3, 4  # PTTS_WIRE_*
 WIRE_CHUNK_MAX = 8192  # PTTS_WIRE_CHUNK_MAX
 WIRE_CHUNK_MAX_TEMPO = 22528  # PTTS_WIRE_CHUNK_MAX_TEMPO
 WIRE_RATES = (8000, 16000, 24000, 44100, 48000)
@@ -138,6 +138,10 @@ SIGNATURES = [
     ("ptts_tempo_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_tempo_len", C.c_long, [C.c_long, C.c_int]),
     ("ptts_tempo", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, F32P]),
+    ("ptts_flac_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_flac_bound", C.c_long, [C.c_long]),
+    ("ptts_flac_encode", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,
+                                   C.POINTER(C.c_int)]),
     ("ptts_lsd_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ptts_probe_overlap", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("ptts_slot_close", C.c_int, [C.c_void_p, C.c_int]),

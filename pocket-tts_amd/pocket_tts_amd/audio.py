@@ -12,6 +12,8 @@ Mirrors crates/pocket-tts/src/audio.rs:
   * `lin2ulaw` / `lin2alaw` / `wire_bytes`: the host restatement of the engine's wire stage
     encodings (include/pocket_tts.h, PTTS_WIRE_*): what the GPU writes, for tests and for rows
     that did not go through it.
+  * `flac_stream_header` / `flac_frames`: the host restatement of the engine's FLAC stage
+    (DESIGN.md section 21): the same blocks and the same choice rule, byte for byte.
   * `normalize_peak` (audio.rs:187-194).
 Resampling to 24 kHz is not here: it runs on the GPU inside `ptts_voice_from_audio`
 (the polyphase resampler of pocket-tts_amd/csrc/kernels.hip).
@@ -30,7 +32,7 @@ WAVE_FORMAT_IEEE_FLOAT = 0x0003
 WAVE_FORMAT_ALAW = 0x0006
 WAVE_FORMAT_MULAW = 0x0007
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
-ENCODINGS = ("pcm_s16le", "ulaw", "alaw")
+ENCODINGS = ("pcm_s16le", "ulaw", "alaw", "flac")  # by PTTS_WIRE_* - 1
 
 
 class WavError(ValueError):
@@ -133,6 +135,8 @@ def wire_bytes(audio: np.ndarray, encoding: str = "pcm_s16le") -> bytes:
     """Mono float32 samples (already at the wire rate) -> the bytes of `encoding`."""
     if encoding not in ENCODINGS:
         raise ValueError(f"encoding must be one of {list(ENCODINGS)}, got {encoding!r}")
+    if encoding == "flac":
+        raise ValueError("flac is a stream of frames, not a per-sample encoding: flac_stream_header + flac_frames")
     s = pcm_i16(np.asarray(audio, np.float32).reshape(-1))
     if encoding == "pcm_s16le":
         return s.astype("<i2").tobytes()
@@ -145,6 +149,8 @@ def wav_header(n_data: int, sample_rate: int = 24000, encoding: str = "pcm_s16le
     and a fact chunk holding the sample count per channel, as non-PCM formats require."""
     if encoding not in ENCODINGS:
         raise ValueError(f"encoding must be one of {list(ENCODINGS)}, got {encoding!r}")
+    if encoding == "flac":
+        raise ValueError("a WAV file cannot carry flac: send the FLAC stream itself (flac_stream_header + frames)")
     ch = channels
     if encoding == "pcm_s16le":
         fmt = b"fmt " + struct.pack("<IHHIIHH", 16, WAVE_FORMAT_PCM, ch, sample_rate, sample_rate * 2 * ch, 2 * ch, 16)
@@ -177,6 +183,155 @@ def wav_bytes(audio, sample_rate: int = 24000, encoding: str = "pcm_s16le") -> b
 
 def write_wav(path, audio: np.ndarray, sample_rate: int = 24000) -> None:
     Path(path).write_bytes(wav_bytes(audio, sample_rate))
+
+
+# ---- FLAC: the host restatement of DESIGN.md section 21 (the GPU FLAC stage's format and rule)
+FLAC_BLOCK = 4608  # samples per frame at most (the subset limit at <= 48 kHz)
+FLAC_RATE_CODES = {8000: 4, 16000: 5, 24000: 7, 44100: 9, 48000: 10}
+
+
+def wire_samples(n: int, rate: int, sp: int = 0) -> int:
+    """Samples at `rate` of an utterance of n samples at 24 kHz (time-scaled first at a speed of sp
+    permille, 0: none): what its wire chunks add up to (ceil(n' rate / 24000))."""
+    n = tempo_len(n, sp) if sp else int(n)
+    return -(-n * int(rate) // 24000)
+
+
+def flac_stream_header(rate: int, total_samples: int = 0) -> bytes:
+    """`fLaC` and one STREAMINFO block (42 bytes): block sizes 16 .. 4608, frame sizes unknown, mono,
+    16 bit, total_samples (0: unknown, for streams), no MD5."""
+    if rate not in FLAC_RATE_CODES:
+        raise ValueError(f"sample rate must be one of {sorted(FLAC_RATE_CODES)}")
+    if not 0 <= total_samples < 1 << 36:
+        raise ValueError("total_samples must fit 36 bits")
+    word = (int(rate) << 44) | (0 << 41) | (15 << 36) | int(total_samples)
+    info = struct.pack(">HH", 16, FLAC_BLOCK) + bytes(6) + word.to_bytes(8, "big") + bytes(16)
+    return b"fLaC" + bytes([0x80, 0, 0, 0x22]) + info
+
+
+def _crc_table(poly: int, bits: int) -> list[int]:
+    top, mask, out = 1 << (bits - 1), (1 << bits) - 1, []
+    for b in range(256):
+        c = b << (bits - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly if c & top else c << 1) & mask
+        out.append(c)
+    return out
+
+
+_CRC8, _CRC16 = _crc_table(0x07, 8), _crc_table(0x8005, 16)
+
+
+def flac_crc8(data: bytes) -> int:
+    c = 0
+    for b in data:
+        c = _CRC8[c ^ b]
+    return c
+
+
+def flac_crc16(data: bytes) -> int:
+    c = 0
+    for b in data:
+        c = ((c << 8) & 0xFFFF) ^ _CRC16[(c >> 8) ^ b]
+    return c
+
+
+def flac_number(v: int) -> bytes:
+    """The UTF-8-like code of a frame's first sample index, extended to 36 bits."""
+    if v < 0x80:
+        return bytes([v])
+    nb = next(i for i, lim in enumerate((11, 16, 21, 26, 31, 36), 2) if v < 1 << lim)
+    first = ((0xFF << (8 - nb)) & 0xFF) | (0 if nb == 7 else v >> (6 * (nb - 1)))
+    return bytes([first] + [0x80 | ((v >> (6 * i)) & 0x3F) for i in range(nb - 2, -1, -1)])
+
+
+def flac_choose(s: np.ndarray):
+    """The choice rule on one block (int64 samples): ("constant",), ("verbatim",) or
+    ("fixed", order, partition order, parameters [2^p])."""
+    n = s.size
+    if np.all(s == s[0]):
+        return ("constant",)
+    best, pick = 8 + 16 * n, ("verbatim",)
+    if n < 16:
+        return pick
+    pmax = min((n & -n).bit_length() - 1, 6)
+    while (n >> pmax) < 16:
+        pmax -= 1
+    ks = np.arange(15, dtype=np.int64)[:, None]
+    for o in range(5):
+        e = np.diff(s, o) if o else s
+        u = np.concatenate([np.zeros(o, np.int64), np.where(e >= 0, 2 * e, -2 * e - 1)])
+        fine = (u[None, :] >> ks).reshape(15, 1 << pmax, -1).sum(axis=2)  # [k][finest partition]
+        for p in range(pmax + 1):
+            cnt = np.full(1 << p, n >> p, np.int64)
+            cnt[0] -= o
+            cost = fine.reshape(15, 1 << p, -1).sum(axis=2) + cnt[None, :] * (ks + 1)
+            k = cost.argmin(axis=0)  # the first minimum: the lower k
+            total = 8 + 16 * o + 6 + int((cost.min(axis=0) + 4).sum())
+            if total < best:
+                best, pick = total, ("fixed", o, p, k)
+    return pick
+
+
+def _flac_pack(fields_val, fields_nb, fields_skip) -> np.ndarray:
+    """Bit fields (value, width <= 16, zero bits before it), in order -> the bits (uint8 0/1)."""
+    val = np.asarray(fields_val, np.int64)
+    nb = np.asarray(fields_nb, np.int64)
+    skip = np.asarray(fields_skip, np.int64)
+    end = np.cumsum(nb + skip)
+    pos = end - nb  # where each field's value starts
+    bits = np.zeros(int(end[-1]) if end.size else 0, np.uint8)
+    for b in range(int(nb.max()) if nb.size else 0):
+        m = nb > b
+        bits[pos[m] + b] = (val[m] >> (nb[m] - 1 - b)) & 1
+    return bits
+
+
+def flac_frame(s: np.ndarray, first_sample: int, rate: int) -> bytes:
+    """One FLAC frame of the block s (1 .. 4608 int16 samples) whose first sample has that index."""
+    s = np.asarray(s, np.int16).astype(np.int64).reshape(-1)
+    n = s.size
+    if not 1 <= n <= FLAC_BLOCK:
+        raise ValueError("a block holds 1 .. 4608 samples")
+    head = bytes([0xFF, 0xF9, ((6 if n <= 256 else 7) << 4) | FLAC_RATE_CODES[rate], 0x08]) + flac_number(first_sample)
+    head += bytes([n - 1]) if n <= 256 else struct.pack(">H", n - 1)
+    head += bytes([flac_crc8(head)])
+    pick = flac_choose(s)
+    if pick[0] == "constant":
+        body = bytes([0x00]) + struct.pack(">h", int(s[0]))
+    elif pick[0] == "verbatim":
+        body = bytes([0x02]) + s.astype(">i2").tobytes()
+    else:
+        _, o, p, k = pick
+        e = np.diff(s, o) if o else s
+        u = np.where(e >= 0, 2 * e, -2 * e - 1)
+        i = np.arange(o, n)
+        kk = k[i // (n >> p)]
+        # per residual: an optional prefix (the method, partition order and first parameter, or a
+        # partition's parameter), then u >> k zeros and the one bit with the k low bits
+        pre_nb = np.where(i == o, 10, np.where(i % (n >> p) == 0, 4, 0))
+        pre_val = np.where(i == o, (p << 4) | kk, kk)
+        val = np.stack([pre_val, (1 << kk) | (u & ((1 << kk) - 1))], axis=1).reshape(-1)
+        nb = np.stack([pre_nb, kk + 1], axis=1).reshape(-1)
+        skip = np.stack([np.zeros_like(u), u >> kk], axis=1).reshape(-1)
+        warm = s[:o] & 0xFFFF
+        bits = _flac_pack(np.concatenate([[(8 | o) << 1], warm, val]), np.concatenate([[8], np.full(o, 16), nb]),
+                          np.concatenate([np.zeros(1 + o, np.int64), skip]))
+        body = np.packbits(bits).tobytes()  # zero bits to the byte boundary
+    frame = head + body
+    return frame + struct.pack(">H", flac_crc16(frame))
+
+
+def flac_frames(samples_i16, first_sample: int, rate: int) -> bytes:
+    """The FLAC frames of a chunk of 16-bit samples (blocks of 4,608, the last one shorter), the
+    first of which has index first_sample in its stream: what the engine's FLAC stage writes for
+    that chunk, byte for byte."""
+    s = np.asarray(samples_i16, np.int16).reshape(-1)
+    if rate not in FLAC_RATE_CODES:
+        raise ValueError(f"sample rate must be one of {sorted(FLAC_RATE_CODES)}")
+    if first_sample < 0 or first_sample + s.size > 1 << 36:
+        raise ValueError("sample indices must fit 36 bits")
+    return b"".join(flac_frame(s[a:a + FLAC_BLOCK], first_sample + a, rate) for a in range(0, s.size, FLAC_BLOCK))
 
 
 def normalize_peak(audio: np.ndarray) -> np.ndarray:

@@ -8,12 +8,12 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
-                   WIRE_ALAW, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
+                   WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
                    SlotOpts, SlotOpts2, check, fptr, lib, u8ptr)
 from .audio import speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
-WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW}
+WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW, "flac": WIRE_FLAC}
 
 
 def wire_encoding_code(encoding) -> int:
@@ -42,7 +42,7 @@ class GenerationParams:
     # admission passes it beside the struct (ptts_slot_open_ex).
     lsd_steps: int | None = None
     # wire format of the row (wire-enabled engines; Engine.fetch_wire returns its bytes): sample_rate
-    # one of WIRE_RATES, encoding "pcm_s16le" / "ulaw" / "alaw" (or a PTTS_WIRE_* code). None in both:
+    # one of WIRE_RATES, encoding "pcm_s16le" / "ulaw" / "alaw" / "flac" (or a PTTS_WIRE_* code). None in both:
     # no wire output; None in one: 24000 / 16-bit. Passed beside the struct too (ptts_slots_open_opts).
     sample_rate: int | None = None
     encoding: str | int | None = None
@@ -140,7 +140,7 @@ class Engine:
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
                  back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
-                 tempo: bool = False):
+                 tempo: bool = False, flac: bool = False):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -159,7 +159,9 @@ class Engine:
         wire=True (ptts_wire_enable): rows admitted with GenerationParams.sample_rate / encoding also
         get their wire bytes, converted on the GPU (fetch_wire).
         tempo=True (ptts_tempo_enable; needs wire): rows admitted with GenerationParams.speed have
-        their wire bytes time-scaled on the GPU."""
+        their wire bytes time-scaled on the GPU.
+        flac=True (ptts_flac_enable; needs wire): rows admitted with encoding "flac" get FLAC frames
+        of their 16-bit chunks, encoded on the GPU."""
         if back_mfma is None:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
@@ -195,6 +197,13 @@ class Engine:
         if tempo:
             try:
                 check(lib().ptts_tempo_enable(self.handle, 1))
+            except Exception:
+                self.close()
+                raise
+        self.flac_enabled = bool(flac)
+        if flac:
+            try:
+                check(lib().ptts_flac_enable(self.handle, 1))
             except Exception:
                 self.close()
                 raise
@@ -527,6 +536,16 @@ class Engine:
         out = np.zeros(max(n, 1), np.uint8)
         check(lib().ptts_wire_encode(self.handle, fptr(x), x.size, int(sample_rate), enc, out.ctypes.data_as(U8P)))
         return out[:n].tobytes()
+
+    def flac_encode(self, samples_i16: np.ndarray, sample_rate: int = 24000, first_sample: int = 0) -> bytes:
+        """The FLAC stage's chunk encoder on up to 11,058 arbitrary 16-bit samples (ptts_flac_encode):
+        the frames audio.flac_frames restates on the host, byte for byte."""
+        x = np.ascontiguousarray(np.asarray(samples_i16, np.int16).reshape(-1))
+        out = np.zeros(max(int(lib().ptts_flac_bound(x.size)), 1), np.uint8)
+        n = C.c_int(0)
+        check(lib().ptts_flac_encode(self.handle, x.ctypes.data_as(C.POINTER(C.c_int16)), x.size, int(sample_rate),
+                                     int(first_sample), out.ctypes.data_as(U8P), C.byref(n)))
+        return out[: n.value].tobytes()
 
     @staticmethod
     def tempo_len(n: int, speed) -> int:

@@ -26,7 +26,7 @@ HTTP (`create_app`, FastAPI; routes of pocket-tts-cli/src/server/routes.rs:20-30
   POST /stream             same body -> chunked 16-bit PCM LE (handlers.rs:215-310): the first
                            frame as soon as it exists, later frames coalesced to at most one
                            chunk per 20 ms per stream
-  POST /v1/audio/speech    OpenAI body {model, input, voice?, response_format?} -> wav / pcm
+  POST /v1/audio/speech    OpenAI body {model, input, voice?, response_format?} -> wav / pcm / flac
                            (handlers.rs:380-398)
   POST /voices/{name}      body: a mono RIFF/WAVE clip, or a safetensors file holding `audio_prompt`
                            [F x 1024]: registers (or replaces) a named voice at run time
@@ -44,6 +44,17 @@ untouched; requests with different formats, and with none, share a batch. /gener
 WAV file of that encoding (G.711: format tag 7 / 6, 8 bits, a `fact` chunk), /stream with the raw
 bytes. A request that names neither field gets today's bytes by today's code path. Unknown values,
 or either field on a `--no-wire` server, get 400.
+
+FLAC (`--flac`, on with `--wire`): `encoding: "flac"` on the three audio
+routes, or `response_format: "flac"` on /v1/audio/speech, answers `audio/flac`: the row's 16-bit
+samples at its `sample_rate` (and `speed`) as lossless FLAC frames, encoded on the GPU behind the
+wire stage. /stream sends the 42-byte stream header and then the row's chunks untouched; /generate
+and /v1/audio/speech send a complete file whose header holds the sample count. A row numbers its
+samples from 0, so FLAC with `long_form` or `continuity` (several rows behind one response) gets
+400, as does FLAC on a server without the stage (`--no-flac`, `--no-wire`).
+
+    curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
+         -d '{"input": "Hello there.", "voice": "alba", "response_format": "flac"}' -o hello.flac
 
 Per-request speech speed (`--tempo`, on with `--wire`; the `speed` of the API /v1/audio/speech
 imitates): the three audio routes also take `speed`, a factor in [0.5, 2.0]. The model has no
@@ -100,8 +111,8 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, pcm_i16_le_bytes, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
-                    wire_bytes)
+from .audio import (ENCODINGS, flac_stream_header, pcm_i16_le_bytes, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
+                    wire_bytes, wire_samples)
 from .engine import GenerationParams, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
                    silence_samples)
@@ -690,7 +701,8 @@ class BatchScheduler:
                 # a resampled row's first chunk is shorter than its preview's frame (the filter's
                 # delay): it waits for its regular first chunk; a 24 kHz row's preview is encoded here
                 # a speed row's first chunk is not its first frame either
-                if fmt[0] != SAMPLE_RATE or req.speed:
+                # a FLAC row's frames are written by the engine alone
+                if fmt[0] != SAMPLE_RATE or req.speed or fmt[1] == "flac":
                     continue
                 pcm = wire_bytes(pcm, fmt[1])
             req.preview = 1
@@ -1038,6 +1050,7 @@ class TTSService:
         self.max_ctx = max_ctx if max_ctx is not None else getattr(eng, "max_ctx", None)
         self.wire = bool(getattr(eng, "wire", False))  # the engines convert to wire formats (--wire)
         self.tempo = self.wire and bool(getattr(eng, "tempo_enabled", False))  # and time-scale (--tempo)
+        self.flac = self.wire and bool(getattr(eng, "flac_enabled", False))  # and encode FLAC (--flac)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -1083,6 +1096,13 @@ class TTSService:
             if not self.wire:
                 raise ValueError("this server runs without wire output (--no-wire): sample_rate / encoding "
                                  "are not available")
+        if encoding == "flac":
+            if not self.flac:
+                raise ValueError("this server runs without the FLAC stage (--no-flac or --no-wire): encoding flac is "
+                                 "not available")
+            if chain or (token_ids is None and (self.long_form if long_form is None else long_form)):
+                raise ValueError("flac with long_form or continuity is not available: the segments of one response "
+                                 "are separate rows, each numbering its samples from 0")
         if speed_permille(speed) == 0:  # (ValueError outside [0.5, 2.0]); 1.0: the request without it
             speed = None
         elif not self.tempo:
@@ -1257,7 +1277,7 @@ class OpenAIRequest(BaseModel):
     model: str = "pocket-tts"
     input: str | None = None
     voice: str | None = None
-    response_format: str | None = None  # wav (default), pcm, ulaw, alaw (raw G.711, 8 kHz unless sample_rate)
+    response_format: str | None = None  # wav (default), pcm, flac, ulaw, alaw (raw G.711, 8 kHz unless sample_rate)
     token_ids: list[int] | None = None
     words: int | None = None
     sample_rate: int | None = None
@@ -1332,6 +1352,21 @@ async def pcm_chunks(r: Request):
             r.cancel()
 
 
+async def flac_chunks(r: Request):
+    """/stream body of a FLAC request: the stream header (sample count unknown), then pcm_chunks."""
+    yield flac_stream_header(r.wire[0])
+    async for chunk in pcm_chunks(r):
+        yield chunk
+
+
+def flac_file(r) -> bytes:
+    """A FLAC request's whole output as a file: the header with the true sample count (one item per
+    frame of the row, whatever its size), then the chunks untouched."""
+    chunks = list(r.stream())
+    total = wire_samples(len(chunks) * FRAME, r.wire[0], getattr(r, "speed", 0))
+    return flac_stream_header(r.wire[0], total) + b"".join(chunks)
+
+
 def create_app(service: TTSService):
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
@@ -1388,6 +1423,8 @@ def create_app(service: TTSService):
         if redirect is not None:
             return redirect
         r = submit(**req.model_dump())
+        if r.wire is not None and r.wire[1] == "flac":
+            return Response(flac_file(r), media_type="audio/flac", headers=hdr)
         if r.wire is not None:
             return Response(wav_bytes(r.wire_audio(), *r.wire), media_type="audio/wav", headers=hdr)
         return Response(wav_bytes(r.audio()), media_type="audio/wav", headers=hdr)
@@ -1400,6 +1437,9 @@ def create_app(service: TTSService):
             return redirect
         r = submit(**req.model_dump())
         r.times["route"] = t_route
+        if r.wire is not None and r.wire[1] == "flac":
+            return StreamingResponse(flac_chunks(r), media_type="audio/flac",
+                                     headers={**hdr, "X-PTTS-Route-Time": f"{t_route:.6f}"})
         media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1] if r.wire else "", "audio/pcm")
         return StreamingResponse(pcm_chunks(r), media_type=media,
                                  headers={**hdr, "X-PTTS-Route-Time": f"{t_route:.6f}"})
@@ -1415,10 +1455,16 @@ def create_app(service: TTSService):
             if enc not in (None, fmt):
                 raise HTTPException(status_code=400, detail=f"response_format {fmt} contradicts encoding {enc}")
             rate, enc = rate or 8000, fmt
+        elif fmt == "flac":
+            if enc not in (None, fmt):
+                raise HTTPException(status_code=400, detail=f"response_format {fmt} contradicts encoding {enc}")
+            enc = fmt
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
                    encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity)
+        if r.wire is not None and r.wire[1] == "flac":
+            return Response(flac_file(r), media_type="audio/flac", headers=hdr)
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
@@ -1573,7 +1619,7 @@ def _worker_engine(args, Engine):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     kw = dict(max_slots=args.slots, max_ctx=args.max_ctx, weights_path=args.weights, pipeline=True,
               back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
-              wire=args.wire, tempo=args.wire and args.tempo)
+              wire=args.wire, tempo=args.wire and args.tempo, flac=args.wire and args.flac)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1638,6 +1684,9 @@ def main(argv=None):
     ap.add_argument("--wire", action=argparse.BooleanOptionalAction, default=True,
                     help="wire formats converted on the GPU (requests' sample_rate / encoding); --no-wire: the "
                          "engine as before, such requests get 400")
+    ap.add_argument("--flac", action=argparse.BooleanOptionalAction, default=True,
+                    help="FLAC output (requests' encoding / response_format flac) encoded on the GPU; needs --wire (off "
+                         "with --no-wire); --no-flac: the wire-enabled engine as before, such requests get 400")
     ap.add_argument("--tempo", action=argparse.BooleanOptionalAction, default=True,
                     help="per-request speech speed (requests' speed) time-scaled on the GPU; needs --wire (off "
                          "with --no-wire); --no-tempo: the wire-enabled engine as before, such requests get 400")

@@ -28,8 +28,8 @@ from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
-from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
-from .audio import read_wav, read_wav_from_bytes, speed_permille, wire_bytes
+from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE, WIRE_FLAC
+from .audio import flac_stream_header, read_wav, read_wav_from_bytes, speed_permille, wire_bytes, wire_samples
 from .engine import Engine, GenerationParams, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
@@ -87,7 +87,7 @@ class TTSModel:
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
-                         back_frames: int = 1, tempo: bool = False) -> "TTSModel":
+                         back_frames: int = 1, tempo: bool = False, flac: bool = False) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
@@ -95,7 +95,8 @@ class TTSModel:
         weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
         from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json.
         wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=); tempo (with wire):
-        its tempo stage too, for generate(.., speed=)."""
+        its tempo stage too, for generate(.., speed=); flac (with wire): its FLAC stage, for
+        generate(.., encoding="flac")."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
@@ -103,7 +104,7 @@ class TTSModel:
         eng = Engine(device=device, max_slots=int(max_slots), max_ctx=max_ctx, pipeline=pipeline,
                      back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
-                     wire=wire, tempo=tempo)
+                     wire=wire, tempo=tempo, flac=flac)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -243,9 +244,15 @@ class TTSModel:
         resampled on its own: its chunks are the whole-signal resample of the segment).
         speed (0.5 .. 2.0; a tempo-enabled engine): the segments' audio is time-scaled on the GPU
         ahead of that conversion, pitch kept; the items are wire bytes then
-        too, 24 kHz 16-bit unless a format is given. None or 1.0 changes nothing."""
+        too, 24 kHz 16-bit unless a format is given. None or 1.0 changes nothing.
+        encoding "flac" (a FLAC-enabled engine): the items are the FLAC frames of each chunk (DESIGN.md
+        section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0, so
+        the text must be one segment: ValueError where it splits into several."""
         if speed_permille(speed) == 0:
             speed = None
+        if encoding in ("flac", WIRE_FLAC) and isinstance(text_or_ids, str) and \
+                len(self.split_into_best_sentences(text_or_ids)) > 1:
+            raise ValueError("flac: the text splits into several segments, each a stream of its own (section 21, Limits)")
         if not isinstance(text_or_ids, str):
             ids = np.asarray(text_or_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
@@ -265,10 +272,14 @@ class TTSModel:
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
                  speed: float | None = None):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
-        speed, the wire bytes of generate_stream concatenated."""
+        speed, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
+        the stream header with the true sample count and then the frames."""
         frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed))
         if not frames:
             raise RuntimeError("No audio generated")
+        if encoding in ("flac", WIRE_FLAC):
+            rate = int(sample_rate or SAMPLE_RATE)
+            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, speed_permille(speed))) + b"".join(frames)
         if sample_rate is not None or encoding is not None or speed_permille(speed):
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
@@ -347,6 +358,8 @@ class TTSModel:
         carries it (generate_stream); pauses keep their stated duration. Closing the generator early
         cancels the rows it still holds (Engine.cancel_slots)."""
         self._check_lsd()
+        if encoding in ("flac", WIRE_FLAC):
+            raise ValueError("flac: parallel rows are separate streams, each numbered from 0 (section 21, Limits)")
         tok = self._tok()
         eng = self.engine
         speed = speed if speed_permille(speed) else None
