@@ -259,6 +259,7 @@ Engine::Engine(const ptts_engine_config& cfg) {
   fhm_ = dalloc((size_t)lsd_ * ((B + 15) / 16) * (FDEPTH + 1) * 2 * 16 * FD);
   PTTS_HIP(hipMemset(hx_, 0xFF, hx_floats(B) * 4));  // empty (the launch ahead re-arms the used part)
   PTTS_HIP(hipDeviceSynchronize());                    // null-stream memset: see dalloc
+  hp_hand_ = dalloc((size_t)lsd_ * 2 * HP_REGION_FLOATS);
   hctr_ = (int*)dalloc(4 * ((B + 15) / 16) + 4);
   herr_ = (int*)dalloc(4);
   for (int i = 0, ch = MD / 2; i < 3; ++i, ch /= 2) trb_[i] = dalloc((size_t)RATIOS[i] * ch);
@@ -598,6 +599,19 @@ void Engine::finalize() {
     fhw_ = (float*)p;
   }
   if (fhw_) pack_flow_head(W(L_.rb_w0[0]), W(L_.rb_w2[0]), (long)(L_.rb_w0[1] - L_.rb_w0[0]), W(L_.fin_w), fhw_, stream_);
+  // flow-head prelude (f32 engines; the quantized engines' heads stream codes through their own
+  // launches): cond | EOS on the whole-K GEMM, the adaLN matrix in the prelude's fragment order
+  static_assert(HP_NCOND == NCOND_PAD && HP_NADA == NADA, "head_prelude's shapes are the flow head's");
+  if (wq_ == QUANT_NONE && !fp8_ && hfrag_ && gemv_fk_supported(1, NCOND_PAD, D)) {
+    if (!hp_w_) {  // every element is written by the packing below
+      void* p = nullptr;
+      PTTS_HIP(hipMalloc(&p, sizeof(float) * ((size_t)NCOND_PAD * D + (size_t)NADA * FD)));
+      allocs_.push_back(p);
+      hp_w_ = (float*)p;
+    }
+    pack_gemv_fk(W(L_.cond_eos_w), NCOND_PAD, D, hp_w_, stream_);
+    pack_head_ada(W(L_.ada_w), hp_w_ + (size_t)NCOND_PAD * D, stream_);
+  }
   TimeEmbedWeights tw;
   for (int i = 0; i < 2; ++i) {
     tw.l1w[i] = W(L_.te_l1w[i]);
@@ -932,9 +946,12 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
       ops.push_back({p + ".attention", [=](hipStream_t s) { attention(Q, Ma, NH, am, kv, 0, O, s); }});
     }
     auto rr = [&](const std::string& name, int S2, int N, int act, bool resid, float* Y, const float* lnw,
-                  const float* lnb, bool ln, float* Hout, float* Hfrag = nullptr) {
+                  const float* lnb, bool ln, float* Hout, float* Hfrag = nullptr, float* fill = nullptr,
+                  long fill_n4 = 0) {
       RowReduceArgs a{};
       a.Hfrag = Hfrag;
+      a.fill = fill;
+      a.fill_n4 = fill_n4;
       a.P = fb.partial;
       a.S = S2;
       a.M = M;
@@ -1003,8 +1020,14 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
     }
     if (l + 1 < NL)
       rr(p + ".ff2_reduce_ln1", S, D, ACT_NONE, true, fb.x, W(L_.fl[l + 1].n1w), W(L_.fl[l + 1].n1b), true, fb.h);
-    else
-      rr(p + ".ff2_reduce_outnorm", S, D, ACT_NONE, true, fb.x, W(L_.out_norm_w), W(L_.out_norm_b), out_norm, fb.h);
+    else {
+      // ahead of the head prelude: out_norm's rows also in its A-fragment order, and its hand-off
+      // regions emptied (those of the cap: the run length is the front's, not this pass's)
+      const bool pre = step && out_norm && use_head_prelude(M);
+      const long n4 = (long)lsd_ * ((M + 15) / 16) * HP_REGION_FLOATS / 4;
+      rr(p + ".ff2_reduce_outnorm", S, D, ACT_NONE, true, fb.x, W(L_.out_norm_w), W(L_.out_norm_b), out_norm, fb.h,
+         pre ? hfrag_ : nullptr, pre ? hp_hand_ : nullptr, pre ? n4 : 0);
+    }
   }
 }
 
@@ -1029,6 +1052,12 @@ bool Engine::use_head_chain(int B) const {
   return head_uniform_stride();
 }
 
+// One launch for the head's prelude (head_prelude): f32 engines (hp_w_), at most 32 rows, ahead
+// of the persistent chain (whose x0 and region side jobs it carries).
+bool Engine::use_head_prelude(int B) const {
+  return hp_w_ && head_prelude_supported(B, 1) && gemv_fk_supported(B, NCOND_PAD, D) && use_head_chain(B);
+}
+
 bool Engine::head_uniform_stride() const {
   const long s = (long)(L_.rb_w0[1] - L_.rb_w0[0]);
   for (int i = 1; i < FDEPTH; ++i)
@@ -1049,44 +1078,86 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
   // or by refresh_xh() after anything else wrote them or lat_in_.
   const FlowBufs& fb = fbm_;
   flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow", fb);
-  // ---- flow head (mlp.rs:215-383): cond_embed | out_eos, EOS bookkeeping, noise
-  linear_split(ops, "head.cond_eos_gemm", fb.h, D, B, W(L_.cond_eos_w), NCOND, D, &S, fb);
-  PTTS_REQUIRE(S <= FLOW_COND_MAX_SLABS, "head.flow_cond sums at most 16 split-K slabs");
-  {
-    const float* P = fb.partial;
-    const float* bias = W(L_.cond_eos_b);
-    const float* temb = temb_;
-    const int lsd = lsd_run, cap = lsd_;
-    SlotState* st = st_;
-    float *ys = ysilu_, *cur = cur_, *eos = eos_;
-    ops.push_back({"head.flow_cond", [=](hipStream_t s) { flow_cond(P, S, B, bias, temb, lsd, cap, st, ys, cur, eos, s); },
-                   (double)B * NCOND * (S + 1) + 4.0 * lsd * B * FD,
-                   4.0 * ((double)S * B * NCOND + NCOND + lsd * FD + lsd * (double)B * FD + B * (LDIM + 1.0))});
-  }
-  // all adaLN modulations of all lsd steps in one GEMM (mlp.rs:322-368)
-  linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_run * B, W(L_.ada_w), NADA, FD, &S, fb);
-  {
-    RowReduceArgs a{};
-    a.P = fb.partial;
-    a.S = S;
-    a.M = lsd_run * B;
-    a.N = NADA;
-    a.bias = W(L_.ada_b);
-    a.Y = mods_;
-    a.ldy = NADA;
-    if (use_head_chain(B)) {  // side jobs: x0 into hand-off region 0, empty the other regions
-      const size_t r0 = (size_t)((B + 15) / 16 * 16) * FD;  // floats per hand-off region
-      a.fill = hx_ + r0;
-      a.fill_n4 = (long)((hx_floats(B, lsd_run) - r0) / 4);  // the regions of this run, not of the cap
-      a.x0_cur = cur_;
-      a.x0_w = fh_inw_t_;
-      a.x0_b = W(L_.inproj_b);
-      a.x0_hx = hx_;
-      a.x0_B = B;
-      a.fhm = fhm_;
-      a.fhm_B = B;
+  // ---- flow head (mlp.rs:215-383): cond_embed | out_eos, EOS bookkeeping, noise, adaLN
+  // modulations of all lsd steps: one launch (head_prelude) ahead of the chain, or four
+  if (use_head_prelude(B)) {
+    const int RG = (B + 15) / 16;
+    const size_t r0 = (size_t)(RG * 16) * FD;  // floats per hand-off region of the chain
+    HeadPreludeArgs a{};
+    a.B = B;
+    a.lsd = lsd_run;
+    a.lsd_cap = lsd_;
+    a.A = hfrag_;
+    a.Pc = hp_w_;
+    a.cbias = W(L_.cond_eos_b);
+    a.temb = temb_;
+    a.st = st_;
+    a.eos_out = eos_;
+    a.cur = cur_;
+    a.hand = hp_hand_;
+    a.Pa = hp_w_ + (size_t)NCOND_PAD * D;
+    a.abias = W(L_.ada_b);
+    a.mods = mods_;
+    a.fhm = fhm_;
+    a.x0_w = fh_inw_t_;
+    a.x0_b = W(L_.inproj_b);
+    a.x0_hx = hx_;
+    a.fill = hx_ + r0;
+    a.fill_n4 = (long)((hx_floats(B, lsd_run) - r0) / 4);  // the regions of this run, not of the cap
+    a.err = herr_;
+    const double mn = (double)lsd_run * B * NADA, hand = (double)lsd_run * RG * HP_REGION_FLOATS;
+    // weights, biases and the A fragment in; EOS, cur, mods and the shift / scale copy out; the
+    // hand-off written and read; x0 and the emptied regions (as the adaLN reduce counted them)
+    Op op{"head.prelude", [a](hipStream_t s) { head_prelude(a, s); },
+          2.0 * B * NCOND_PAD * D + 2.0 * lsd_run * B * NADA * FD + 2.0 * B * LDIM * FD + 4.0 * lsd_run * B * FD,
+          4.0 * ((double)NCOND_PAD * D + NCOND_PAD + (double)FK_A_FLOATS + (double)NADA * FD + NADA + lsd_run * FD +
+                 B * (LDIM + 1.0) + 2.0 * hand + mn + mn * 2.0 / 3.0 + (double)B * (LDIM + FD) + (double)LDIM * FD +
+                 4.0 * a.fill_n4)};
+    // an isolated replay (time_op, overlap_probe) finds its regions empty again
+    float* hh = hp_hand_;
+    const size_t nh = (size_t)lsd_run * RG * HP_REGION_FLOATS;
+    op.prep = [hh, nh](hipStream_t s) { PTTS_HIP(hipMemsetD32Async(hh, 0xFFFFFFFFu, nh, s)); };
+    ops.push_back(op);
+  } else {
+    linear_split(ops, "head.cond_eos_gemm", fb.h, D, B, W(L_.cond_eos_w), NCOND, D, &S, fb);
+    PTTS_REQUIRE(S <= FLOW_COND_MAX_SLABS, "head.flow_cond sums at most 16 split-K slabs");
+    {
+      const float* P = fb.partial;
+      const float* bias = W(L_.cond_eos_b);
+      const float* temb = temb_;
+      const int lsd = lsd_run, cap = lsd_;
+      SlotState* st = st_;
+      float *ys = ysilu_, *cur = cur_, *eos = eos_;
+      ops.push_back(
+          {"head.flow_cond", [=](hipStream_t s) { flow_cond(P, S, B, bias, temb, lsd, cap, st, ys, cur, eos, s); },
+           (double)B * NCOND * (S + 1) + 4.0 * lsd * B * FD,
+           4.0 * ((double)S * B * NCOND + NCOND + lsd * FD + lsd * (double)B * FD + B * (LDIM + 1.0))});
     }
-    push_rr(ops, "head.ada_reduce", a);
+    // all adaLN modulations of all lsd steps in one GEMM (mlp.rs:322-368)
+    linear_split(ops, "head.ada_gemm", ysilu_, FD, lsd_run * B, W(L_.ada_w), NADA, FD, &S, fb);
+    {
+      RowReduceArgs a{};
+      a.P = fb.partial;
+      a.S = S;
+      a.M = lsd_run * B;
+      a.N = NADA;
+      a.bias = W(L_.ada_b);
+      a.Y = mods_;
+      a.ldy = NADA;
+      if (use_head_chain(B)) {  // side jobs: x0 into hand-off region 0, empty the other regions
+        const size_t r0 = (size_t)((B + 15) / 16 * 16) * FD;  // floats per hand-off region
+        a.fill = hx_ + r0;
+        a.fill_n4 = (long)((hx_floats(B, lsd_run) - r0) / 4);  // the regions of this run, not of the cap
+        a.x0_cur = cur_;
+        a.x0_w = fh_inw_t_;
+        a.x0_b = W(L_.inproj_b);
+        a.x0_hx = hx_;
+        a.x0_B = B;
+        a.fhm = fhm_;
+        a.fhm_B = B;
+      }
+      push_rr(ops, "head.ada_reduce", a);
+    }
   }
   // lsd_decode Euler steps (flow_lm.rs:7-22) over ResBlocks (mlp.rs:146-213): one persistent
   // launch (k_flow_head) for the whole chain, or 28 GEMM + row-reduce launches per step

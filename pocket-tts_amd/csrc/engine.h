@@ -318,6 +318,11 @@ class Engine {
   float* fh_inw_t_ = nullptr;  // flow-head input projection transposed [32][512] (x0 side job)
   size_t hx_floats(int B) const { return hx_floats(B, lsd_); }
   size_t hx_floats(int B, int lsd) const { return (size_t)lsd * 13 * ((B + 15) / 16 * 16) * FD; }
+  // flow-head prelude (head_prelude: f32 engines, B <= 32 on the chain): the cond | EOS matrix in
+  // gemv_fk's order followed by the adaLN matrix in pack_head_ada's (finalize), and its hand-off
+  // regions [cap][2][HP_REGION_FLOATS], emptied by the out_norm reduce ahead of it
+  bool use_head_prelude(int B) const;
+  float *hp_w_ = nullptr, *hp_hand_ = nullptr;
   float* inw_t_ = nullptr;  // input_linear weight transposed, [32][1024] (k_input_ln)
   int *hctr_ = nullptr, *herr_ = nullptr;
   float* trb_[3] = {};  // transposed-conv biases replicated over the r output phases [r][Cout]

@@ -482,6 +482,39 @@ struct FlowHeadArgs {
   int* err;
   unsigned long long* dbg;  // probe only: s_memrealtime stamps of workgroups 0-3, or nullptr
 };
+// ---------------------------------------------------------------------------------------------
+// Flow-head prelude in one persistent launch (B <= 32 rows, f32 weights, ahead of flow_head): what
+// the cond | EOS GEMM, flow_cond, the adaLN GEMM and the adaLN reduce compute, without slabs.
+// HP_PRODUCERS workgroups run cond | EOS = A Wc^T + bc over the whole K as gemv_fk does (A: the
+// out_norm rows in gemv_fk's fragment order, Pc: pack_gemv_fk of the NCOND_PAD x 1024 matrix),
+// write the EOS logits and hand y_s = silu(temb_n[min(s, n - 1)] + c) (flow_cond's rule) of each
+// of the lsd Euler steps to the HP_CONSUMERS workgroups through `hand` (data-as-flag, lsd x
+// ceil(B / 16) regions of HP_REGION_FLOATS, all 0xFFFFFFFF at launch: emptied by the launch ahead).
+// Each consumer holds 64 columns of the adaLN matrix over the whole K = 512 in registers
+// (Pa: pack_head_ada) and writes mods [lsd][B][HP_NADA] = y W_ada^T + b_ada and the shift / scale
+// columns' copy fhm (FlowHeadArgs::fhm). While they wait the consumers draw the rows' noise into
+// cur, compute x0 = cur W_in^T + b_in into the chain's hand-off region 0 (x0_w: W_in transposed)
+// and empty fill[0 .. 4 * fill_n4) (the chain's other regions). A hand-off wait that times out
+// sets *err.
+constexpr int HP_NCOND = 544, HP_NADA = (FH_DEPTH * 3 + 2) * FH_D;
+constexpr int HP_PRODUCERS = HP_NCOND / 16, HP_CONSUMERS = HP_NADA / 64;
+constexpr long HP_REGION_FLOATS = 16L * FH_D;
+struct HeadPreludeArgs {
+  int B, lsd, lsd_cap;
+  const float *A, *Pc, *cbias, *temb;
+  const SlotState* st;
+  float *eos_out, *cur, *hand;
+  const float *Pa, *abias;
+  float *mods, *fhm;
+  const float *x0_w, *x0_b;
+  float* x0_hx;
+  float* fill;
+  long fill_n4;
+  int* err;
+};
+bool head_prelude_supported(int B, int lsd_run);
+void pack_head_ada(const float* W, float* packed, hipStream_t s);  // [HP_NADA][512] -> fragment order
+void head_prelude(const HeadPreludeArgs& a, hipStream_t s);
 // Launches issued while a cap > 0 is set reserve dynamic LDS so that at most `cap` workgroups of
 // each kernel share a CU (0 = no cap). Per host thread; the engine sets it around graph capture.
 void set_wg_cap(int cap);

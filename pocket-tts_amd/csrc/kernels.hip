@@ -2086,17 +2086,23 @@ __device__ __forceinline__ float4 rr_value(const RowReduceArgs& a, int m, int n)
   if (a.R) v = f4add(v, rr);
   return v;
 }
+// FlowHeadArgs::fhm float4 index of adaLN columns n .. n + 3 (n % 4 == 0) of row b of a batch of B
+// rows at Euler step st, or -1 for a gate column: the columns are [shift | scale | gate] x 6
+// ResBlocks, then [shift | scale] (final)
+__device__ __forceinline__ long fhm_index(int st, int b, int B, int n) {
+  const int RG = (B + 15) / 16;
+  const int i = min(n / (3 * FH_D), FH_DEPTH), rem = n - i * 3 * FH_D;
+  const int t = rem / FH_D, k = rem - t * FH_D;
+  if (t >= 2) return -1;
+  return (((((long)(st * RG + b / 16) * (FH_DEPTH + 1) + i) * 2 + t) * 8 + (k >> 6)) * 4 + ((k >> 4) & 3)) * 64 +
+         (b & 15) + 16 * ((k >> 2) & 3);
+}
 __device__ __forceinline__ void rr_store(const RowReduceArgs& a, int m, int n, float4 v) {
   if (a.Y) *reinterpret_cast<float4*>(a.Y + (long)m * a.ldy + n) = v;
-  if (a.fhm) {  // adaLN columns [shift | scale | gate] x 6 ResBlocks, then [shift | scale] (final)
-    const int st = m / a.fhm_B, b = m - st * a.fhm_B, RG = (a.fhm_B + 15) / 16;
-    const int i = min(n / (3 * FH_D), FH_DEPTH), rem = n - i * 3 * FH_D;
-    const int t = rem / FH_D, k = rem - t * FH_D;
-    if (t < 2) {
-      const long idx = (((((long)(st * RG + b / 16) * (FH_DEPTH + 1) + i) * 2 + t) * 8 + (k >> 6)) * 4 + ((k >> 4) & 3)) * 64 +
-                       (b & 15) + 16 * ((k >> 2) & 3);
-      reinterpret_cast<float4*>(a.fhm)[idx] = v;
-    }
+  if (a.fhm) {
+    const int st = m / a.fhm_B;
+    const long idx = fhm_index(st, m - st * a.fhm_B, a.fhm_B, n);
+    if (idx >= 0) reinterpret_cast<float4*>(a.fhm)[idx] = v;
   }
   if (a.Y2) *reinterpret_cast<float4*>(a.Y2 + (long)m * a.ldy + n) = make_float4(elu1(v.x), elu1(v.y), elu1(v.z), elu1(v.w));
   if (a.euler) {
@@ -2142,19 +2148,24 @@ __device__ __forceinline__ float4 fh_inproj4(const float4 (&cv)[8], const float*
 // x0 of Euler step 0 into hand-off region 0 ([RG][32][16][16] tiles; plain stores, read by the
 // next launch), one output per thread i0, i0 + nthr, ...; the weight is read transposed (w_t
 // [32][512], made at finalize) so each load instruction of a wave is one contiguous 256-B run
+// column n of row b, whose 32 latent values are at c
+__device__ __forceinline__ void fh_x0_one(const float* c, const float* w_t, const float* bias, float* hx, int b,
+                                          int n) {
+  float t = bias[n];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float4 cj = *reinterpret_cast<const float4*>(c + 4 * j);
+    const float* w = w_t + (long)(4 * j) * FH_D + n;
+    t += fh_dot4(cj, make_float4(w[0], w[FH_D], w[2 * FH_D], w[3 * FH_D]));
+  }
+  if (t != t) t = __uint_as_float(0x7FC00000u);  // never the hand-off's empty pattern
+  hx[((long)((b >> 4) * 32 + (n >> 4))) * 256 + (b & 15) * 16 + (n & 15)] = t;
+}
 __device__ __forceinline__ void fh_x0_job(const float* cur, const float* w_t, const float* bias, float* hx, int B,
                                           long i0, long nthr) {
   for (long i = i0; i < (long)B * FH_D; i += nthr) {
     const int b = (int)(i / FH_D), n = (int)(i % FH_D);
-    float t = bias[n];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 c = *reinterpret_cast<const float4*>(cur + (long)b * FH_L + 4 * j);
-      const float* w = w_t + (long)(4 * j) * FH_D + n;
-      t += fh_dot4(c, make_float4(w[0], w[FH_D], w[2 * FH_D], w[3 * FH_D]));
-    }
-    if (t != t) t = __uint_as_float(0x7FC00000u);  // never the hand-off's empty pattern
-    hx[((long)((b >> 4) * 32 + (n >> 4))) * 256 + (b & 15) * 16 + (n & 15)] = t;
+    fh_x0_one(cur + (long)b * FH_L, w_t, bias, hx, b, n);
   }
 }
 __global__ void k_fh_x0(const float* cur, const float* w, const float* bias, float* hx, int B) {
@@ -2764,6 +2775,22 @@ __device__ float normal_at(unsigned long long seed, int step, int k, int attempt
   return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
+// element k of a row's x0 noise: N(0, sqrt(temp)), optionally truncated to |x| <= clamp
+// (flow_lm.rs:39-65); 0 at temp 0
+__device__ __forceinline__ float flow_noise(float temp, float clamp, unsigned long long seed, int step, int k) {
+  float x0 = 0.f;
+  if (temp > 0.f) {
+    const float sd = sqrtf(temp);
+    x0 = sd * normal_at(seed, step, k, 0);
+    if (clamp > 0.f) {
+      int att = 1;
+      while (fabsf(x0) > clamp && att < 64) x0 = sd * normal_at(seed, step, k, att++);
+      x0 = fminf(fmaxf(x0, -clamp), clamp);
+    }
+  }
+  return x0;
+}
+
 __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B, const float* bias, const float* temb,
                                                    int lsd, int lsd_cap, const SlotState* st, float* ysilu,
                                                    float* cur, float* eos_out) {
@@ -2805,19 +2832,7 @@ __global__ __launch_bounds__(256) void k_flow_cond(const float* P, int S, int B,
     ysilu[((long)s * B + b) * 512 + tid + 256] = silu(tn[ts * 512 + tid + 256] + c1);
   }
   if (tid == 0) eos_out[b] = e + be;  // out_eos logit (flow_lm.rs:139-145); the EOS rule runs in front_commit
-  if (tid < 32) {
-    float x0 = 0.f;
-    if (temp > 0.f) {  // flow_lm.rs:39-65: N(0, sqrt(temp)), optionally truncated to |x| <= clamp
-      const float sd = sqrtf(temp);
-      x0 = sd * normal_at(seed, step, tid, 0);
-      if (clamp > 0.f) {
-        int att = 1;
-        while (fabsf(x0) > clamp && att < 64) x0 = sd * normal_at(seed, step, tid, att++);
-        x0 = fminf(fmaxf(x0, -clamp), clamp);
-      }
-    }
-    cur[b * 32 + tid] = x0;
-  }
+  if (tid < 32) cur[b * 32 + tid] = flow_noise(temp, clamp, seed, step, tid);
 }
 
 void flow_cond(const float* P, int S, int B, const float* bias, const float* temb, int lsd_run, int lsd_cap,
@@ -2826,6 +2841,205 @@ void flow_cond(const float* P, int S, int B, const float* bias, const float* tem
   if (lsd_run < 1 || lsd_run > lsd_cap) throw std::runtime_error("flow_cond: lsd_run outside [1, cap]");
   hipLaunchKernelGGL(k_flow_cond, dim3(B), dim3(256), 0, s, P, S, B, bias, temb, lsd_run, lsd_cap, st, ysilu, cur,
                      eos_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flow-head prelude in ONE launch (kernels.h head_prelude): cond | EOS GEMM, silu(c + temb), the
+// adaLN GEMM, and the side jobs of k_flow_cond / the adaLN reduce (noise, x0, emptying the chain's
+// regions). Workgroups 0 .. HP_PRODUCERS - 1 are producers, the HP_CONSUMERS after them consumers.
+//
+// Progress: a producer waits for nothing. A consumer waits only for producers, and workgroups are
+// dispatched in index order, so whenever a consumer is resident every producer is resident or has
+// finished: the launch completes however few workgroups fit on the device at once.
+//
+// Producer ct: columns 16 ct .. + 15 of cond | EOS over the whole K = 1024 exactly as k_gemv_fk
+// (A in gemv_fk's fragment order, the weight packed by pack_gemv_fk); its epilogue adds the bias,
+// writes the EOS logit (column 512) and, for every Euler step s of the launch, publishes
+// y_s = silu(temb_row(s) + c) into hand-off region (s, row tile t) in the consumers' A-fragment
+// order: float4 (kq * 8 + j) * 64 + 16 g + r = y_s[row 16 t + r][128 kq + 32 g + 4 j .. + 3]
+// (data-as-flag, sc1 stores, a NaN stored canonical; rows past B as 0).
+// Consumer cw: adaLN columns 64 cw .. + 63 over the whole K = 512. Wave w takes the 128-k range
+// kq = w & 3 of the column tiles 2 (w >> 2) and 2 (w >> 2) + 1; its two weight fragments
+// (pack_head_ada: float4 ((((cw * 8 + w) * 2 + c2) * 8 + j) * 64 + l = W[64 cw + 32 (w >> 2) +
+// 16 c2 + (l & 15)][128 kq + 32 (l >> 4) + 4 j .. + 3]) are requested at the start and stay in
+// registers for every Euler step and row tile. v_mfma_f32_16x16x4f32 sums k = 128 kq + 32 g + s
+// over the lane groups g at step s for A and B alike; the 4 k ranges of a column tile are summed
+// in LDS in kq order (a fixed order: a row's result depends on neither B nor its row index).
+// ---------------------------------------------------------------------------------------------
+__global__ void k_pack_head_ada(const float* __restrict__ W, float* __restrict__ P) {
+  const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i4 >= (long)HP_NADA * FH_D / 4) return;
+  const int l = (int)(i4 & 63), j = (int)((i4 >> 6) & 7), c2 = (int)((i4 >> 9) & 1), w = (int)((i4 >> 10) & 7);
+  const int cw = (int)(i4 >> 13);
+  const int n = 64 * cw + 32 * (w >> 2) + 16 * c2 + (l & 15), k = 128 * (w & 3) + 32 * (l >> 4) + 4 * j;
+  reinterpret_cast<float4*>(P)[i4] = *reinterpret_cast<const float4*>(W + (long)n * FH_D + k);
+}
+void pack_head_ada(const float* W, float* packed, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_head_ada, dim3(HP_NADA * FH_D / 4 / 256), dim3(256), 0, s, W, packed);
+}
+
+__global__ __launch_bounds__(512) void k_head_prelude(HeadPreludeArgs a) {
+  front_prio();
+  __shared__ __attribute__((aligned(16))) float red[8 * 2 * 4 * 64];
+  __shared__ __attribute__((aligned(16))) float sC[32 * 16];  // producer: c tile; consumer: the row's noise
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int RG = (a.B + 15) >> 4;
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const auto hr = sc1_rsrc(a.hand);
+  if (blockIdx.x < HP_PRODUCERS) {
+    const int ct = blockIdx.x;
+    const f4v* wp = reinterpret_cast<const f4v*>(a.Pc) + ((long)(ct * 8 + w) * 8) * 64 + lane;
+    const f4v* ap = reinterpret_cast<const f4v*>(a.A) + ((long)(w * 2) * 8) * 64 + lane;
+    f4v b[8], a0[8], a1[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      b[j] = (front_skip() & 1) ? f4v{0.f, 0.f, 0.f, 0.f} : __builtin_nontemporal_load(wp + j * 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      a0[j] = ap[j * 64];
+      a1[j] = ap[(8 + j) * 64];
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first MFMA (k_gemv_fk)
+    floatx4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (front_skip() & 2) break;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[j][e], b[j][e], c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[j][e], b[j][e], c1, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      red[((w * 2 + 0) * 4 + i) * 64 + lane] = c0[i];
+      red[((w * 2 + 1) * 4 + i) * 64 + lane] = c1[i];
+    }
+    __syncthreads();
+    {  // thread tid: row tile t, register i, lane ll (C map: column ll & 15, row (ll >> 4) * 4 + i)
+      const int t = tid >> 8, i = (tid >> 6) & 3, ll = tid & 63;
+      float v = red[((0 * 2 + t) * 4 + i) * 64 + ll];
+#pragma unroll
+      for (int ww = 1; ww < 8; ++ww) v += red[((ww * 2 + t) * 4 + i) * 64 + ll];
+      const int row = 16 * t + (ll >> 4) * 4 + i, col = ct * 16 + (ll & 15);
+      v += a.cbias[col];
+      if (col == FH_D && row < a.B) a.eos_out[row] = v;  // out_eos logit; the EOS rule runs in front_commit
+      sC[row * 16 + (ll & 15)] = v;
+    }
+    __syncthreads();
+    if (ct < FH_D / 16 && tid < 128) {  // row m, columns k .. k + 3 of cond_embed
+      const int m = tid & 31, c4 = tid >> 5, k = 16 * ct + 4 * c4;
+      if ((m >> 4) < RG) {
+        const bool live = m < a.B;
+        const float4 c = *reinterpret_cast<const float4*>(&sC[m * 16 + 4 * c4]);
+        // the row's own Euler step count: its time embeddings are rows temb_row0(n) .. + n - 1
+        const int nrow = live ? min(max(a.st[m].lsd, 1), a.lsd_cap) : 1;
+        const float* tn = a.temb + (long)temb_row0(nrow) * FH_D + k;
+        const int off = (((k >> 7) * 8 + ((k >> 2) & 7)) * 64 + ((k >> 5) & 3) * 16 + (m & 15)) * 16;
+        for (int s = 0; s < a.lsd; ++s) {  // steps past the row's count repeat its last (finite, unused)
+          const float4 te = *reinterpret_cast<const float4*>(tn + (long)min(s, nrow - 1) * FH_D);
+          float4 y = make_float4(silu(te.x + c.x), silu(te.y + c.y), silu(te.z + c.z), silu(te.w + c.w));
+          if (!live) y = make_float4(0.f, 0.f, 0.f, 0.f);
+          fh_put(hr, (s * RG + (m >> 4)) * (int)(HP_REGION_FLOATS * 4) + off, y);
+        }
+      }
+    }
+    return;
+  }
+  // ---- consumer
+  const int cw = blockIdx.x - HP_PRODUCERS;
+  const int kq = w & 3;
+  const f4v* wp = reinterpret_cast<const f4v*>(a.Pa) + ((long)((cw * 8 + w) * 2) * 8) * 64 + lane;
+  f4v b0[8], b1[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    b0[j] = (front_skip() & 1) ? f4v{0.f, 0.f, 0.f, 0.f} : __builtin_nontemporal_load(wp + j * 64);
+    b1[j] = (front_skip() & 1) ? f4v{0.f, 0.f, 0.f, 0.f} : __builtin_nontemporal_load(wp + (8 + j) * 64);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // side jobs behind the weight request, through the wait for the producers: they depend on nothing
+  // in this launch. Consumer 4 b + q: row b's noise, then columns 128 q .. + 127 of its x0 into the
+  // chain's region 0; every consumer: its share of the chain's other regions, emptied
+  if (cw < 4 * a.B) {
+    const int b = cw >> 2, q = cw & 3;
+    if (tid < FH_L) {
+      const SlotState& ss = a.st[b];
+      const float x0 = flow_noise(ss.temp, ss.noise_clamp, ss.seed, ss.step, tid);
+      sC[tid] = x0;
+      if (q == 0) a.cur[b * FH_L + tid] = x0;
+    }
+    __syncthreads();
+    if (tid < 128) fh_x0_one(sC, a.x0_w, a.x0_b, a.x0_hx, b, 128 * q + tid);
+  }
+  for (long i = (long)cw * 512 + tid; i < a.fill_n4; i += (long)HP_CONSUMERS * 512)
+    reinterpret_cast<uint4*>(a.fill)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  bool dead = false;
+  for (int s = 0; s < a.lsd; ++s)
+    for (int t = 0; t < RG; ++t) {
+      // this wave's A fragment of region (s, t), swept until none of it is empty (fh_sweep); a
+      // timeout sets *err and stops waiting for the rest of the launch
+      const int aoff = (s * RG + t) * (int)(HP_REGION_FLOATS * 4) + (kq * 8 * 64 + lane) * 16;
+      float4 av[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) av[j] = fh_ld(hr, aoff + j * 64 * 16);
+      unsigned spins = 0;
+      while (!dead) {
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ok &= !fh_empty(av[j]);
+        if (__all(ok)) break;
+        __builtin_amdgcn_s_sleep(1);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (fh_empty(av[j])) av[j] = fh_ld(hr, aoff + j * 64 * 16);
+        if (++spins > (1u << 20)) {
+          if (lane == 0) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          dead = true;
+        }
+      }
+      floatx4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (front_skip() & 2) break;
+        const float ae[4] = {av[j].x, av[j].y, av[j].z, av[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[e], b0[j][e], c0, 0, 0, 0);
+          c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[e], b1[j][e], c1, 0, 0, 0);
+        }
+      }
+      __syncthreads();  // the tile before this one is read out of red (and the side job out of sC)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        red[((w * 2 + 0) * 4 + i) * 64 + lane] = c0[i];
+        red[((w * 2 + 1) * 4 + i) * 64 + lane] = c1[i];
+      }
+      __syncthreads();
+      if (tid < 256) {  // column tile ctl of the workgroup's 4, row r, columns 4 q4 .. + 3 of the tile
+        const int ctl = tid >> 6, r = (tid >> 2) & 15, q4 = tid & 3;
+        // C map: register r & 3 of lanes (r >> 2) * 16 + 4 q4 .. + 3: one aligned float4 of red
+        const float* rp = red + (((ctl >> 1) * 4 * 2 + (ctl & 1)) * 4 + (r & 3)) * 64 + (r >> 2) * 16 + 4 * q4;
+        float4 v = *reinterpret_cast<const float4*>(rp);
+#pragma unroll
+        for (int kk = 1; kk < 4; ++kk) v = f4add(v, *reinterpret_cast<const float4*>(rp + kk * 2 * 4 * 64));
+        const int brow = 16 * t + r, n = 64 * cw + 16 * ctl + 4 * q4;
+        if (brow < a.B) {
+          v = f4add(v, *reinterpret_cast<const float4*>(a.abias + n));
+          *reinterpret_cast<float4*>(a.mods + ((long)s * a.B + brow) * HP_NADA + n) = v;
+          const long idx = fhm_index(s, brow, a.B, n);
+          if (idx >= 0) reinterpret_cast<float4*>(a.fhm)[idx] = v;
+        }
+      }
+    }
+}
+
+bool head_prelude_supported(int B, int lsd_run) { return B >= 1 && B <= 32 && lsd_run >= 1; }
+
+void head_prelude(const HeadPreludeArgs& a, hipStream_t s) {
+  if (!head_prelude_supported(a.B, a.lsd) || a.lsd > a.lsd_cap) throw std::runtime_error("head_prelude: bad shape");
+  hipLaunchKernelGGL(k_head_prelude, dim3(HP_PRODUCERS + HP_CONSUMERS), dim3(512), cap_lds(k_head_prelude, g_wg_cap), s,
+                     a);
 }
 
 // =============================================================================================

@@ -38,9 +38,9 @@ def run(cap):
         el = time.perf_counter() - t0
         capq, last = eng.lsd_steps()
         chain = eng.time_kernel(B, "head.chain", reps=300)
-        cond = eng.time_kernel(B, "head.flow_cond", reps=300)
+        prelude = eng.time_kernel(B, "head.prelude", reps=300)
         return {"cap": capq, "last_run": last, "steady_ms_per_step": round(1000 * el / STEPS, 4),
-                "head_chain_us": round(chain, 3), "flow_cond_us": round(cond, 3)}
+                "head_chain_us": round(chain, 3), "head_prelude_us": round(prelude, 3)}
     finally:
         eng.close()
 
