@@ -293,7 +293,8 @@ int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice
  * before its first step, as ptts_preview_enable is; PTTS_ERR_INVALID later. */
 int ptts_wire_enable(ptts_engine* e, int on);
 /* Per-row admission options. size = sizeof(ptts_slot_opts) of the caller's header (0 is read as
- * that of this one): the stride of the array, and fields past it read as 0, so the struct can grow
+ * 40, the struct that ended at keep_codec, as it was for callers built before pitch_cents: a caller
+ * that sets pitch_cents states its size): the stride of the array, and fields past it read as 0, so the struct can grow
  * without an ABI bump. Zero fields are the defaults: lsd_steps as in ptts_slots_open_ex; wire_rate
  * 0 and wire_encoding 0: no wire format; one of them 0: 24000 / PTTS_WIRE_S16; speed_permille 0:
  * no speed (the field lies in what was the struct's tail padding: zero the struct before filling it).
@@ -331,6 +332,7 @@ typedef struct ptts_slot_opts {
   const float* prefix_latents; /* host memory [n_prefix][32], read before the call returns */
   int n_prefix;
   int keep_codec;
+  int pitch_cents; /* pitch shift, -1200 .. 1200 cents (ptts_pitch_enable); 0: none. Size 40 -> 48 */
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
@@ -361,6 +363,33 @@ int ptts_tempo_enable(ptts_engine* e, int on);
  * ptts_tempo_len samples. */
 long ptts_tempo_len(long n, int speed_permille);
 int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, float* out);
+/* Pitch (no reference counterpart; the model has no pitch input). A row admitted with
+ * ptts_slot_opts.pitch_cents = c (-1200 .. 1200; 0: none, today's bytes) has its wire bytes shifted
+ * in pitch by 2^(c / 1200) at the duration its speed asks for, by the rule of DESIGN.md section 23:
+ * the WSOLA stage runs at wsola_permille = round(speed * 2^20 / step) and a streaming windowed-sinc
+ * resampler then reads step_q20 / 2^20 input samples per output sample, step_q20 =
+ * round(2^(c / 1200) * 2^20). It is a resampling shift: formants move with the fundamental. The
+ * chunks of a row concatenate to the whole-signal rule (ptts_tempo, then ptts_pitch_resample) over
+ * its PCM, bit for bit; only the wire bytes change (the PCM of ptts_fetch, the latents, the EOS
+ * logits and the stop frames do not depend on pitch). A pitch with no wire format implies 24000 /
+ * PTTS_WIRE_S16. A pitch outside the range, one whose wsola_permille leaves [500, 2000], or one asked
+ * of an engine without ptts_pitch_enable, is PTTS_ERR_INVALID and admits nothing. A caller with a
+ * struct shorter than 48 bytes gets none.
+ * ptts_pitch_enable: valid on a tempo-enabled idle engine before its first step (PTTS_ERR_INVALID
+ * otherwise); on = 0, or never called: the passes, graphs and copies the engine has without it. The
+ * chunk slots stay PTTS_WIRE_CHUNK_MAX_TEMPO (a last frame at 48 kHz holds 11,196 16-bit samples at
+ * most). */
+int ptts_pitch_enable(ptts_engine* e, int on);
+/* The pitch seam alone. ptts_pitch_plan (host only): the plan of (cents, speed_permille; 0: 1000),
+ * PTTS_ERR_INVALID for an invalid request; either pointer may be NULL. ptts_pitch_len (host only):
+ * floor(n 2^20 / step_q20) (0 if the arguments are invalid). ptts_pitch_table (host only): the
+ * prototype table T and its differences D, n = 16385 entries each. ptts_pitch_resample: the
+ * whole-signal rule on the GPU (the tap loop of the streaming stage), step_q20 in [2^19, 2^21]; y
+ * receives ptts_pitch_len samples. */
+int ptts_pitch_plan(int cents, int speed_permille, int* wsola_permille, uint32_t* step_q20);
+long ptts_pitch_len(long n, uint32_t step_q20);
+int ptts_pitch_table(float* t, float* d, int n);
+int ptts_pitch_resample(ptts_engine* e, const float* x, int n, uint32_t step_q20, float* y);
 /* FLAC (no reference counterpart; RFC 9639, restated in DESIGN.md section 21). A row admitted with
  * wire_encoding = PTTS_WIRE_FLAC gets, per frame, the FLAC frames of the 16-bit samples its
  * PTTS_WIRE_S16 chunk at the same rate (and speed) would hold: mono, 16 bit, blocks of at most 4,608
@@ -381,7 +410,7 @@ int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, floa
 #define PTTS_WIRE_FLAC 4
 int ptts_flac_enable(ptts_engine* e, int on);
 /* The FLAC seam alone: the bound above (0 for n < 1; host only), and the stage's chunk encoder on
- * n <= 11,058 arbitrary 16-bit samples at sample_rate (one of the wire rates), the first of which
+ * n <= 11,221 arbitrary 16-bit samples at sample_rate (one of the wire rates), the first of which
  * has index first_sample (0 <= first_sample, first_sample + n <= 2^36) in its stream; out holds
  * ptts_flac_bound(n) bytes, *n_bytes receives the frames' byte total. */
 long ptts_flac_bound(long n);

@@ -310,10 +310,11 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     if (n < 1) throw ptts::Error(PTTS_ERR_INVALID, "number of admissions out of range");
     // entries are `size` bytes apart (the caller's struct); fields past it read as 0 (checked ahead
     // of everything else: a caller with another header learns so whatever the engine's state)
-    const size_t size = opts[0].size ? opts[0].size : sizeof(ptts_slot_opts);
+    // (0: the 40-byte struct that ended at keep_codec, what 0 meant to callers built before pitch_cents)
+    const size_t size = opts[0].size ? opts[0].size : offsetof(ptts_slot_opts, pitch_cents);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n);
+    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n);
     std::vector<const float*> pre(n);
     for (int i = 0; i < n; ++i) {
       ptts_slot_opts o{};
@@ -326,9 +327,10 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
       pre[i] = o.prefix_latents;
       npre[i] = o.n_prefix;
       keep[i] = o.keep_codec;
+      pitch[i] = o.pitch_cents;
     }
     eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data(),
-                      pre.data(), npre.data(), keep.data());
+                      pre.data(), npre.data(), keep.data(), pitch.data());
   });
 }
 
@@ -356,6 +358,33 @@ long ptts_tempo_len(long n, int speed_permille) {
 
 int ptts_tempo(ptts_engine* e, const float* pcm, int n, int speed_permille, float* out) {
   return guard([&] { eng(e).tempo_host(pcm, n, speed_permille, out); });
+}
+
+int ptts_pitch_enable(ptts_engine* e, int on) { return guard([&] { eng(e).pitch_enable(on != 0); }); }
+
+int ptts_pitch_plan(int cents, int speed_permille, int* wsola_permille, uint32_t* step_q20) {
+  int sp_w = 0;
+  unsigned step = 0;
+  if (!ptts::pitch_plan(cents, speed_permille, &sp_w, &step)) return PTTS_ERR_INVALID;
+  if (wsola_permille) *wsola_permille = sp_w;
+  if (step_q20) *step_q20 = step;
+  return PTTS_OK;
+}
+
+long ptts_pitch_len(long n, uint32_t step_q20) {
+  if (n < 0 || n >= (1L << 40) || step_q20 < ptts::PITCH_STEP_MIN || step_q20 > ptts::PITCH_STEP_MAX) return 0;
+  return ptts::pitch_len(n, step_q20);
+}
+
+int ptts_pitch_table(float* t, float* d, int n) {
+  if (!t || !d || n != ptts::PITCH_TAB) return PTTS_ERR_INVALID;
+  const std::vector<float> tab = ptts::pitch_table();
+  for (int i = 0; i < n; ++i) t[i] = tab[2 * i], d[i] = tab[2 * i + 1];
+  return PTTS_OK;
+}
+
+int ptts_pitch_resample(ptts_engine* e, const float* x, int n, uint32_t step_q20, float* y) {
+  return guard([&] { eng(e).pitch_host(x, n, step_q20, y); });
 }
 
 int ptts_flac_enable(ptts_engine* e, int on) { return guard([&] { eng(e).flac_enable(on != 0); }); }

@@ -1666,6 +1666,26 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       ops.push_back({"tempo", [ta](hipStream_t s) { tempo_stage(ta, s); }, 0.0,
                      (double)B * nfr * 4.0 * (FRAME + TEMPO_OUT_MAX)});
     }
+    if (pitch_) {  // then the pitch rows' chunks, from the PCM or the tempo chunks (section 23)
+      PitchArgs pa{};
+      pa.B = B;
+      pa.nfr = nfr;
+      pa.pcm_frames = pcm_frames;
+      pa.out_frames = nfr_;
+      pa.pcm = pcm_out;
+      for (int f = 0; f < NFR_MAX; ++f) pa.flags[f] = fl[f];
+      pa.step = pitch_step_;
+      pa.tempo_sp = tempo_sp_;
+      pa.tin = tempo_out_;
+      pa.tcnt = tempo_cnt_;
+      pa.state = pitch_state_;
+      pa.hist = pitch_hist_;
+      pa.tab = pitch_tab_;
+      pa.out = pitch_out_;
+      pa.counts = pitch_cnt_;
+      ops.push_back({"pitch", [pa](hipStream_t s) { pitch_stage(pa, s); }, 0.0,
+                     (double)B * nfr * 4.0 * (TEMPO_OUT_MAX + PITCH_OUT_MAX)});
+    }
     WireArgs w{};
     w.B = B;
     w.nfr = nfr;
@@ -1685,6 +1705,11 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       w.tempo_sp = tempo_sp_;
       w.tin = tempo_out_;
       w.tcnt = tempo_cnt_;
+    }
+    if (pitch_) {
+      w.pitch_step = pitch_step_;
+      w.pin = pitch_out_;
+      w.pcnt = pitch_cnt_;
     }
     if (flac_) w.first = flac_first_;
     ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
@@ -3041,13 +3066,14 @@ int Engine::lsd_run_for(int B) const {
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                         const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
                         const int* wire_enc, const int* speed, const float* const* prefix, const int* n_prefix,
-                        const int* keep_codec) {
+                        const int* keep_codec, const int* pitch) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
   std::vector<char> seen(max_slots_, 0);
   std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
   std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
+  std::vector<unsigned> wpt(n, 0u);  // the rows' pitch steps (Q20; 0: none)
   std::vector<int> npre(n, 0);  // the rows' latent prefixes (frames) and RESET_* bits (section 20)
   std::vector<int> ropt(n, 0);
   bool any_prefix = false, any_opt = false;
@@ -3060,7 +3086,16 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       PTTS_REQUIRE(tempo_, "a speed needs a tempo-enabled engine (ptts_tempo_enable before the first step)");
       wsp[i] = sp;
     }
-    if (wr || we || wsp[i]) {  // a speed with no format: 24000 / 16 bit
+    const int cents = pitch ? pitch[i] : 0;
+    if (cents != 0) {  // the WSOLA stage runs at sp_w, the resampler at step (section 23)
+      PTTS_REQUIRE(cents >= -PITCH_CENTS_MAX && cents <= PITCH_CENTS_MAX, "pitch_cents must be in [-1200, 1200]");
+      PTTS_REQUIRE(pitch_, "a pitch needs a pitch-enabled engine (ptts_pitch_enable before the first step)");
+      int sp_w = 0;
+      PTTS_REQUIRE(pitch_plan(cents, sp, &sp_w, &wpt[i]),
+                   "pitch_cents with this speed leaves the time-scaling range (speed / 2^(cents / 1200) in [0.5, 2.0])");
+      wsp[i] = sp_w == 1000 ? 0 : sp_w;
+    }
+    if (wr || we || wsp[i] || wpt[i]) {  // a speed or a pitch with no format: 24000 / 16 bit
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
@@ -3250,6 +3285,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     memcpy(h_tempo_, wsp.data(), sizeof(int) * n);
     PTTS_HIP(hipMemcpyAsync(admit_tempo_, h_tempo_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   }
+  if (pitch_) {
+    memcpy(h_pitch_, wpt.data(), sizeof(unsigned) * n);
+    PTTS_HIP(hipMemcpyAsync(admit_pitch_, h_pitch_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
+  }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
   std::vector<int> fp(n);
@@ -3318,6 +3357,11 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       r.tempo_src = admit_tempo_;
       r.tempo_sp = tempo_sp_;
       r.tempo_state = tempo_state_;
+    }
+    if (pitch_) {
+      r.pitch_src = admit_pitch_;
+      r.pitch_step = pitch_step_;
+      r.pitch_state = pitch_state_;
     }
     if (any_opt) {
       r.opt_src = admit_opt_;
@@ -3439,6 +3483,7 @@ void Engine::wire_encode_host(const float* pcm, int n, int rate, int enc, unsign
 void Engine::tempo_enable(bool on) {
   PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the tempo stage is chosen on an idle engine before its first step");
   PTTS_REQUIRE(!on || wire_, "the tempo stage needs a wire-enabled engine (ptts_wire_enable first)");
+  PTTS_REQUIRE(on || !pitch_, "the pitch stage needs the tempo stage (ptts_pitch_enable(0) first)");
   // section 19: a pending hop reads nothing older than TEMPO_HIST samples, a chunk fits its slots
   static_assert(TEMPO_R == TEMPO_D + TEMPO_HS + TEMPO_W && 2 * TEMPO_HS == TEMPO_W, "tempo constants");
   const int step_max = (TEMPO_HS * TEMPO_SP_MAX + 999) / 1000, step_min = TEMPO_HS * TEMPO_SP_MIN / 1000;
@@ -3498,6 +3543,74 @@ void Engine::tempo_host(const float* pcm, int n, int sp, float* out) {
   (void)hipFree(dx), (void)hipFree(dw), (void)hipFree(dy);
 }
 
+// ------------------------------------------------------------------ pitch stage
+void Engine::pitch_enable(bool on) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the pitch stage is chosen on an idle engine before its first step");
+  PTTS_REQUIRE(!on || tempo_, "the pitch stage needs a tempo-enabled engine (ptts_tempo_enable first)");
+  // section 23: the history covers 2 H inputs, and the largest chunk (a last frame: the tempo stage's
+  // last chunk and the H flushed inputs, over step / 2^20) fits PITCH_OUT_MAX, the chunk slot through
+  // the 48 kHz resampler, and the FLAC stage's chunk. sp_w grows with the speed: the smallest valid
+  // speed of each pitch bounds it.
+  long out_max = 0;
+  int h_max = 0;
+  for (int cents = -PITCH_CENTS_MAX; cents <= PITCH_CENTS_MAX; ++cents) {
+    int sp_w = 0;
+    unsigned step = 0;
+    int sp = TEMPO_SP_MIN;
+    while (sp <= TEMPO_SP_MAX && !pitch_plan(cents, sp, &sp_w, &step)) ++sp;
+    PTTS_REQUIRE(sp <= TEMPO_SP_MAX, "a pitch with no valid speed");
+    const int H = pitch_support(step);
+    const long in_max = (long)(FRAME + TEMPO_R - 1) * 1000 / sp_w + 1;  // (a PCM frame at sp_w 1000 is shorter)
+    h_max = std::max(h_max, H);
+    out_max = std::max(out_max, (((in_max + H) << 20) + step - 1) / step);
+  }
+  PTTS_REQUIRE(2 * h_max <= PITCH_HIST && out_max <= PITCH_OUT_MAX && 2L * PITCH_OUT_MAX + 21 <= FLAC_CHUNK_SAMPLES &&
+                   (2L * PITCH_OUT_MAX + 21) * 2 <= WIRE_CHUNK_MAX_TEMPO,
+               "pitch constants violate the history or chunk bounds of DESIGN.md section 23");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !pitch_step_) {
+    const size_t B = max_slots_;
+    pitch_step_ = (unsigned*)dalloc(B);
+    pitch_state_ = (int*)dalloc(B * PITCH_STATE);
+    pitch_hist_ = dalloc(B * PITCH_HIST);
+    pitch_out_ = dalloc(B * nfr_ * PITCH_OUT_MAX);
+    pitch_cnt_ = (int*)dalloc(B * nfr_);
+    admit_pitch_ = (unsigned*)dalloc(B);
+    h_pitch_ = (unsigned*)halloc(sizeof(unsigned) * B);
+    const std::vector<float> tab = pitch_table();
+    pitch_tab_ = dalloc(tab.size());
+    PTTS_HIP(hipMemcpy(pitch_tab_, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+  }
+  pitch_ = on;
+}
+
+void Engine::pitch_host(const float* x, int n, unsigned step, float* y) {
+  PTTS_REQUIRE(x && y && n >= 1, "empty input");
+  PTTS_REQUIRE(step >= PITCH_STEP_MIN && step <= PITCH_STEP_MAX, "step_q20 must be in [2^19, 2^21]");
+  PTTS_REQUIRE(n < (1 << 29), "input too long");
+  const long n_out = pitch_len(n, step);
+  if (n_out < 1) return;
+  sync();
+  void *dx = nullptr, *dt = nullptr, *dy = nullptr;
+  try {
+    const std::vector<float> tab = pitch_table();
+    PTTS_HIP(hipMalloc(&dx, sizeof(float) * n));
+    PTTS_HIP(hipMalloc(&dt, sizeof(float) * tab.size()));
+    PTTS_HIP(hipMalloc(&dy, sizeof(float) * n_out));
+    PTTS_HIP(hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    PTTS_HIP(hipMemcpy(dt, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    ptts::pitch_resample((const float*)dx, n, step, (const float*)dt, (float*)dy, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(y, dy, sizeof(float) * n_out, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(dt), (void)hipFree(dy);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(dt), (void)hipFree(dy);
+}
+
 // ------------------------------------------------------------------ FLAC stage
 void Engine::flac_enable(bool on) {
   PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the FLAC stage is chosen on an idle engine before its first step");
@@ -3511,7 +3624,7 @@ long Engine::flac_bound(long n) { return n < 1 ? 0 : ptts::flac_bound(n); }
 
 void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes) {
   PTTS_REQUIRE(x && out && n_bytes, "null argument");
-  PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11077]");
+  PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11221]");
   const int ri = wire_rate_index(rate);
   PTTS_REQUIRE(ri >= 0, "sample_rate must be one of 8000, 16000, 24000, 44100, 48000");
   PTTS_REQUIRE(first >= 0 && first + n <= (1LL << 36), "first_sample outside the 36-bit sample number");

@@ -88,7 +88,7 @@ class Engine {
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
                   const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
                   const int* wire_enc = nullptr, const int* speed = nullptr, const float* const* prefix = nullptr,
-                  const int* n_prefix = nullptr, const int* keep_codec = nullptr);
+                  const int* n_prefix = nullptr, const int* keep_codec = nullptr, const int* pitch = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -140,6 +140,13 @@ class Engine {
   int wire_chunk_max() const { return tempo_ ? WIRE_CHUNK_MAX_TEMPO : WIRE_CHUNK_MAX; }
   // the seam alone: whole-signal f32 at 24 kHz -> tempo_len(n, sp) samples
   void tempo_host(const float* pcm, int n, int sp, float* out);
+  // Pitch stage (ptts_pitch_enable): rows admitted with pitch_cents have their
+  // (time-scaled) PCM resampled by a fractional ratio (kernels.h pitch_stage) between the tempo and
+  // the wire stage; needs the tempo stage, keeps its chunk slots
+  void pitch_enable(bool on);
+  bool pitch() const { return pitch_; }
+  // the seam alone: whole-signal f32 -> pitch_len(n, step) samples
+  void pitch_host(const float* x, int n, unsigned step, float* y);
   // FLAC stage (ptts_flac_enable): rows admitted with PTTS_WIRE_FLAC have their
   // 16-bit chunks encoded as FLAC frames (kernels.h flac_stage) behind the wire stage
   void flac_enable(bool on);
@@ -481,6 +488,16 @@ class Engine {
   int* tempo_cnt_ = nullptr;     // [max_slots][nfr]
   int* admit_tempo_ = nullptr;   // staged speeds of an admission (device), h_tempo_ (pinned)
   int* h_tempo_ = nullptr;
+  // ---- pitch stage (pitch_enable): per-row step and state, back-owned like the tempo state
+  bool pitch_ = false;
+  unsigned* pitch_step_ = nullptr;  // [max_slots] Q20 input samples per output sample (0: none)
+  int* pitch_state_ = nullptr;      // [max_slots][PITCH_STATE]
+  float* pitch_hist_ = nullptr;     // [max_slots][PITCH_HIST]
+  float* pitch_tab_ = nullptr;      // [PITCH_TAB][2]
+  float* pitch_out_ = nullptr;      // [max_slots][nfr][PITCH_OUT_MAX]: one pass's chunks (k_pitch -> k_wire)
+  int* pitch_cnt_ = nullptr;        // [max_slots][nfr]
+  unsigned* admit_pitch_ = nullptr; // staged steps of an admission (device), h_pitch_ (pinned)
+  unsigned* h_pitch_ = nullptr;
   // ---- FLAC stage (flac_enable)
   bool flac_ = false;
   int* flac_first_ = nullptr;    // [max_slots][nfr] a FLAC chunk's first sample index (k_wire -> k_flac)

@@ -648,6 +648,10 @@ struct ResetArgs {
   const int* tempo_src = nullptr;
   int* tempo_sp = nullptr;
   int* tempo_state = nullptr;  // [max_slots][TEMPO_STATE]
+  // pitch stage (null without it): the row's step from the staged array, no input, no output yet
+  const unsigned* pitch_src = nullptr;
+  unsigned* pitch_step = nullptr;
+  int* pitch_state = nullptr;  // [max_slots][PITCH_STATE]
   // per-row RESET_* bits and staged backbone inputs [n][32] (null: no row of the admission has any)
   const int* opt_src = nullptr;
   const float* lat_src = nullptr;
@@ -784,6 +788,11 @@ struct WireArgs {
   const float* tin = nullptr;
   const int* tcnt = nullptr;
   int* first = nullptr;     // [B][out_frames] (null: no FLAC stage) a WIRE_FLAC chunk's first output index
+  // pitch stage (null without it): a row whose pitch_step is not 0 reads its pitch chunk instead,
+  // `pin` [B][out_frames][PITCH_OUT_MAX] and its sample counts `pcnt`
+  const unsigned* pitch_step = nullptr;  // [B]
+  const float* pin = nullptr;
+  const int* pcnt = nullptr;
 };
 void wire_stage(const WireArgs& a, hipStream_t s);
 // n samples already at the wire rate -> n (G.711) or 2 n (16-bit) bytes; `out` holds the byte count
@@ -828,6 +837,56 @@ void tempo_stage(const TempoArgs& a, hipStream_t s);
 // whole signal: x [n] -> y [tempo_len(n, sp)], one workgroup, the hop functions of the stage
 void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_t s);
 
+// Pitch stage: a streaming fractional resampler between the tempo stage and
+// the wire stage. A row with pitch `cents` has its PCM time-scaled by WSOLA at sp_w (pitch_plan) and
+// then read at `step` / 2^20 input samples per output sample through a Kaiser-windowed sinc
+// (PITCH_Z zero crossings a side, PITCH_P table entries per crossing, linear interpolation between
+// entries, cutoff lowered to 1 / step when step > 2^20). Output m reads inputs i0 - H .. i0 + H,
+// i0 = m step >> 20. Streaming: after N inputs every m with i0 + H <= N - 1 has been emitted, the
+// frame flagged `last` emits the rest up to pitch_len(N, step), so a row's chunks concatenate to the
+// whole-signal rule (pitch_resample()) bit for bit. Per-row state: step (0: none), inputs received,
+// outputs emitted, the last PITCH_HIST inputs.
+constexpr int PITCH_CENTS_MAX = 1200;
+constexpr int PITCH_Z = 32, PITCH_P = 512;
+constexpr double PITCH_BETA = 12.0;
+constexpr int PITCH_TAB = PITCH_Z * PITCH_P + 1;          // (T[i], D[i]) pairs, 0 <= i <= Z P
+constexpr unsigned PITCH_STEP_MIN = 1u << 19, PITCH_STEP_MAX = 1u << 21;
+constexpr long pitch_cq(unsigned step) {                  // cutoff scale, Q20
+  return (1L << 40) / step < (1L << 20) ? (1L << 40) / step : (1L << 20);
+}
+constexpr int pitch_support(unsigned step) {              // H: one-sided support in input samples
+  return (int)((((long)PITCH_Z << 20) + pitch_cq(step) - 1) / pitch_cq(step)) + 1;
+}
+constexpr int PITCH_H_MAX = pitch_support(PITCH_STEP_MAX);  // 65
+constexpr int PITCH_HIST = 2 * PITCH_H_MAX + 2;             // 132: the first pending output reads from N - 2 H on
+// samples of one chunk: a last frame emits at most (tempo's last chunk + H) 2^20 / step, 5,588 over
+// all valid (cents, speed) (section 23; pitch_enable recomputes it)
+constexpr int PITCH_OUT_MAX = 5600;
+constexpr int PITCH_STATE = 2;  // ints per row: inputs received, outputs emitted
+static_assert(PITCH_HIST % 4 == 0 && PITCH_OUT_MAX % 4 == 0 && (2L * PITCH_OUT_MAX + 21) * 2 <= WIRE_CHUNK_MAX_TEMPO,
+              "a pitch chunk at 48 kHz, 16 bit, fits the tempo-enabled chunk slot");
+// host only: the WSOLA speed and the Q20 step of (cents, speed permille; 0: 1000); false: invalid
+bool pitch_plan(int cents, int sp, int* sp_w, unsigned* step);
+long pitch_len(long n, unsigned step);                    // floor(n 2^20 / step)
+std::vector<float> pitch_table();                         // [PITCH_TAB][2]: T[i], D[i] = T[i+1] - T[i]
+struct PitchArgs {
+  int B, nfr, pcm_frames, out_frames;      // as WireArgs
+  const float* pcm;
+  const FrameFlags* flags[NFR_MAX];
+  const unsigned* step;                    // [B] (0: none)
+  const int* tempo_sp;                     // [B] the row's input is its tempo chunk (tin, tcnt) if not 0
+  const float* tin;
+  const int* tcnt;
+  int* state;                              // [B][PITCH_STATE]
+  float* hist;                             // [B][PITCH_HIST]
+  const float* tab;                        // pitch_table()
+  float* out;                              // [B][out_frames][PITCH_OUT_MAX]
+  int* counts;                             // [B][out_frames] samples of each chunk
+};
+void pitch_stage(const PitchArgs& a, hipStream_t s);
+// whole signal: x [n] -> y [pitch_len(n, step)], the tap loop of the stage
+void pitch_resample(const float* x, int n, unsigned step, const float* tab, float* y, hipStream_t s);
+
 // FLAC stage: behind the wire stage, the 16-bit chunk of every WIRE_FLAC row
 // becomes ceil(n / FLAC_BLOCK) FLAC frames (mono, 16 bit, fixed predictors of order 0..4, partitioned
 // Rice codes, the exhaustive choice rule of section 21), written back to back over the chunk slot,
@@ -835,7 +894,8 @@ void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_
 // whole chunk in LDS before its first store, so encoding in place is safe. Integer arithmetic only.
 constexpr int FLAC_BLOCK = 4608;                 // the subset limit at <= 48 kHz
 constexpr int FLAC_FRAME_OVERHEAD = 17;          // 14 header, 1 subframe header, 2 CRC-16
-constexpr int FLAC_CHUNK_SAMPLES = 2 * TEMPO_OUT_MAX + 21;  // the slot bound above; the longest chunk is 11,058
+// the slot bound above; the longest chunk is 11,058 of a tempo row, 11,196 of a pitch row (section 23)
+constexpr int FLAC_CHUNK_SAMPLES = 2 * PITCH_OUT_MAX + 21;
 constexpr int flac_rate_code(int ri) { return ri == 0 ? 4 : ri == 1 ? 5 : ri == 2 ? 7 : ri == 3 ? 9 : 10; }  // by WIRE_RATE_HZ
 constexpr long flac_bound(long n) {              // bytes of the frames of an n-sample chunk, at most
   return 2 * n + FLAC_FRAME_OVERHEAD * ((n + FLAC_BLOCK - 1) / FLAC_BLOCK);

@@ -3318,6 +3318,10 @@ __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
       a.tempo_sp[slot] = a.tempo_src[i];
       for (int q = 0; q < TEMPO_STATE; ++q) a.tempo_state[slot * TEMPO_STATE + q] = 0;
     }
+    if (a.pitch_step) {
+      a.pitch_step[slot] = a.pitch_src[i];
+      for (int q = 0; q < PITCH_STATE; ++q) a.pitch_state[slot * PITCH_STATE + q] = 0;
+    }
   }
 }
 
@@ -3899,6 +3903,7 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
   if (!identity)
     for (int i = t; i < p.L; i += WIRE_THREADS) s_taps[i] = a.taps[p.tap_off + i];
   const int sp = a.tempo_sp ? a.tempo_sp[b] : 0;  // uniform: the row's input is its tempo chunk
+  const unsigned pt = a.pitch_step ? a.pitch_step[b] : 0u;  // uniform: or its pitch chunk (behind the tempo stage)
   const long cap = a.chunk / (enc == WIRE_S16 ? 2 : 1);  // samples a chunk slot holds
   long n = a.frames[b];  // input samples of the row received so far
   if (t < WIRE_TAIL) s_x[t] = n > 0 ? a.tail[(long)b * WIRE_TAIL + t] : 0.f;
@@ -3910,9 +3915,12 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
       continue;
     }
     any = true;
-    const float* in = sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
-                         : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
-    const int n_in = sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX) : 1920;
+    const float* in = pt   ? a.pin + ((long)b * a.out_frames + f) * PITCH_OUT_MAX
+                      : sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
+                           : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
+    const int n_in = pt   ? min(max(a.pcnt[(long)b * a.out_frames + f], 0), PITCH_OUT_MAX)
+                     : sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX)
+                          : 1920;
     unsigned char* dst = a.out + ((long)b * a.out_frames + f) * a.chunk;
     long gbase = 0, total = 0;  // groups of four stored, samples of the chunk
     int rem = 0, done = 0;      // outputs carried in s_y[0, rem), inputs walked
@@ -3975,7 +3983,8 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
 void wire_stage(const WireArgs& a, hipStream_t s) {
   if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
     throw std::runtime_error("wire_stage: bad pass shape");
-  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || (a.tempo_sp && (!a.tin || !a.tcnt || a.chunk < WIRE_CHUNK_MAX_TEMPO)))
+  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || (a.tempo_sp && (!a.tin || !a.tcnt || a.chunk < WIRE_CHUNK_MAX_TEMPO)) ||
+      (a.pitch_step && (!a.tempo_sp || !a.pin || !a.pcnt)))
     throw std::runtime_error("wire_stage: bad chunk slot");
   for (int r = 0; r < WIRE_RATES; ++r)
     if (a.plan[r].L > WIRE_TAPS_MAX || a.plan[r].L < 1 || 2 * a.plan[r].half > WIRE_TAIL * a.plan[r].up)
@@ -4539,6 +4548,164 @@ std::vector<float> tempo_window() {
 void tempo(const float* x, int n, int sp, const float* win, float* y, hipStream_t s) {
   if (n < 1 || sp < TEMPO_SP_MIN || sp > TEMPO_SP_MAX) throw std::runtime_error("tempo: bad arguments");
   hipLaunchKernelGGL(k_tempo_whole, dim3(1), dim3(TEMPO_THREADS), 0, s, x, (long)n, sp, win, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pitch stage (see kernels.h; the rule is DESIGN.md section 23). The tap loop is a template on how a
+// sample is read (the LDS window of the stream, or the whole signal), so the streaming stage and the
+// seam are equal by construction. The prototype table (128 KB, shared by all rows, read-only) is
+// read through the cache.
+struct PitchWindow {  // sample j of the row is s[j - base], base <= j < n (0 outside [0, n))
+  const float* s;
+  long base, n;
+  __device__ __forceinline__ float operator()(long j) const { return j >= base && j >= 0 && j < n ? s[j - base] : 0.f; }
+};
+struct PitchSignal {
+  const float* __restrict__ x;
+  long n;
+  __device__ __forceinline__ float operator()(long j) const { return j >= 0 && j < n ? x[j] : 0.f; }
+};
+
+// Output m: one ascending f64 chain over j = i0 - H .. i0 + H. Taps outside the signal or past the
+// table's support contribute u * 0 or 0 * h, which leaves the f64 sum as it is, so they are skipped.
+// Every product (f32 x 20 bits, f32 x f32) is exact in f64: contraction cannot change a bit.
+template <class X>
+__device__ __forceinline__ float pitch_out(const X& x, const float2* __restrict__ tab, long m, unsigned step, long cq,
+                                           int H) {
+  const long pos = m * (long)step, i0 = pos >> 20;
+  const long jlo = max(i0 - H, 0L), jhi = min(i0 + H, x.n - 1);
+  double acc = 0.0;
+#pragma unroll 4
+  for (long j = jlo; j <= jhi; ++j) {
+    const long dd = pos - j * (1L << 20);
+    const long q = ((dd < 0 ? -dd : dd) * cq) >> 20;
+    const long qp = q * PITCH_P, ti = qp >> 20;
+    if (ti >= PITCH_Z * PITCH_P) continue;
+    const float2 td = tab[ti];
+    const double fr = (double)(qp & ((1L << 20) - 1)) * (1.0 / 1048576.0);
+    const float h = (float)((double)td.x + (double)td.y * fr);
+    acc += (double)x(j) * (double)h;
+  }
+  return (float)(acc * ((double)cq * (1.0 / 1048576.0)));
+}
+
+// One workgroup per row walks the pass's frames in order, so the row's state is touched by this
+// workgroup alone. LDS: the last PITCH_HIST inputs | the frame's input (a PCM frame or a tempo
+// chunk). Lanes take whole outputs: a chunk is up to PITCH_OUT_MAX independent chains of at most
+// 2 H + 1 products, five or six per lane, whose table loads do not depend on the running sum.
+constexpr int PITCH_THREADS = 1024;
+__global__ __launch_bounds__(PITCH_THREADS) void k_pitch(PitchArgs a) {
+  __shared__ __attribute__((aligned(16))) float s_x[PITCH_HIST + TEMPO_OUT_MAX];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned step = a.step[b];
+  int* cnt = a.counts + (long)b * a.out_frames;
+  if (step < PITCH_STEP_MIN || step > PITCH_STEP_MAX) {  // uniform: a row without pitch
+    if (t < a.out_frames) cnt[t] = 0;
+    return;
+  }
+  const long cq = pitch_cq(step);
+  const int H = pitch_support(step);
+  const int sp = a.tempo_sp[b];  // uniform: the row's input is its tempo chunk
+  int* st = a.state + (long)b * PITCH_STATE;
+  long n = st[0], e = st[1];  // inputs received, outputs emitted
+  if (t < PITCH_HIST) s_x[t] = n > 0 ? a.hist[(long)b * PITCH_HIST + t] : 0.f;
+  bool any = false;
+  for (int f = 0; f < a.out_frames; ++f) {
+    const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
+    if (!fl.valid) {  // uniform
+      if (t == 0) cnt[f] = 0;
+      continue;
+    }
+    any = true;
+    const float* in = sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
+                         : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
+    const int n_in = sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX) : 1920;
+    __syncthreads();  // the history is in place
+    for (int i = t; 4 * i < n_in; i += PITCH_THREADS)
+      reinterpret_cast<float4*>(s_x + PITCH_HIST)[i] = reinterpret_cast<const float4*>(in)[i];
+    __syncthreads();
+    const long N1 = n + n_in;
+    // emitted(N) = ceil((N - H) 2^20 / step): every m with (m step >> 20) + H <= N - 1
+    long e1 = fl.last ? (N1 << 20) / step : (N1 > H ? (((N1 - H) << 20) + step - 1) / step : 0);
+    e1 = min(max(e1, e), e + PITCH_OUT_MAX);  // (never more: the chunk bound of kernels.h)
+    const int count = (int)(e1 - e);
+    const PitchWindow x{s_x, n - PITCH_HIST, N1};
+    float* out = a.out + ((long)b * a.out_frames + f) * PITCH_OUT_MAX;
+    for (int i = t; i < count; i += PITCH_THREADS)
+      out[i] = pitch_out(x, reinterpret_cast<const float2*>(a.tab), e + i, step, cq, H);
+    if (t == 0) cnt[f] = count;
+    const float hv = t < PITCH_HIST ? s_x[n_in + t] : 0.f;  // the last PITCH_HIST samples of history | input
+    __syncthreads();  // every lane has read the window
+    if (t < PITCH_HIST) s_x[t] = hv;
+    n = N1;
+    e = e1;
+  }
+  if (!any) return;  // uniform
+  if (t < PITCH_HIST) a.hist[(long)b * PITCH_HIST + t] = s_x[t];  // each lane wrote its own entry
+  if (t == 0) {
+    st[0] = (int)n;
+    st[1] = (int)e;
+  }
+}
+
+void pitch_stage(const PitchArgs& a, hipStream_t s) {
+  static_assert(TEMPO_OUT_MAX % 4 == 0 && TEMPO_OUT_MAX >= 1920 && PITCH_HIST >= 2 * PITCH_H_MAX, "k_pitch's window");
+  if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
+    throw std::runtime_error("pitch_stage: bad pass shape");
+  if (!a.step || !a.tempo_sp || !a.tin || !a.tcnt || !a.state || !a.hist || !a.tab || !a.out || !a.counts)
+    throw std::runtime_error("pitch_stage: null argument");
+  hipLaunchKernelGGL(k_pitch, dim3(a.B), dim3(PITCH_THREADS), 0, s, a);
+}
+
+__global__ __launch_bounds__(256) void k_pitch_whole(const float* __restrict__ xs, long n, unsigned step,
+                                                     const float2* __restrict__ tab, long L, float* __restrict__ y) {
+  const long m = (long)blockIdx.x * 256 + threadIdx.x;
+  if (m >= L) return;
+  const PitchSignal x{xs, n};
+  y[m] = pitch_out(x, tab, m, step, pitch_cq(step), pitch_support(step));
+}
+
+bool pitch_plan(int cents, int sp, int* sp_w, unsigned* step) {
+  if (sp == 0) sp = 1000;
+  if (cents < -PITCH_CENTS_MAX || cents > PITCH_CENTS_MAX || sp < TEMPO_SP_MIN || sp > TEMPO_SP_MAX) return false;
+  const long st = std::llround(std::exp2((double)cents / 1200.0) * 1048576.0);
+  const long w = (((long)sp << 20) + st / 2) / st;
+  if (w < TEMPO_SP_MIN || w > TEMPO_SP_MAX) return false;
+  if (sp_w) *sp_w = (int)w;
+  if (step) *step = (unsigned)st;
+  return true;
+}
+
+long pitch_len(long n, unsigned step) { return (n << 20) / step; }
+
+// T[i] = f32(sinc(i / P) kaiser(i / (P Z))) in f64, exactly 0 at the sinc's zeros and past Z P;
+// D[i] = f32(T[i + 1] - T[i]); interleaved (T[i], D[i]) so a tap is one 8-byte load
+std::vector<float> pitch_table() {
+  std::vector<float> T(PITCH_TAB + 1, 0.f);
+  const double i0b = bessel_i0(PITCH_BETA);
+  for (int i = 0; i < PITCH_Z * PITCH_P; ++i) {
+    if (i == 0) {
+      T[i] = 1.f;
+      continue;
+    }
+    if (i % PITCH_P == 0) continue;
+    const double v = (double)i / PITCH_P, r = (double)i / ((double)PITCH_P * PITCH_Z);
+    T[i] = (float)(std::sin(M_PI * v) / (M_PI * v) * (bessel_i0(PITCH_BETA * std::sqrt(1.0 - r * r)) / i0b));
+  }
+  std::vector<float> tab(2 * (size_t)PITCH_TAB);
+  for (int i = 0; i < PITCH_TAB; ++i) {
+    tab[2 * i] = T[i];
+    tab[2 * i + 1] = (float)((double)T[i + 1] - (double)T[i]);
+  }
+  return tab;
+}
+
+void pitch_resample(const float* x, int n, unsigned step, const float* tab, float* y, hipStream_t s) {
+  if (n < 1 || step < PITCH_STEP_MIN || step > PITCH_STEP_MAX) throw std::runtime_error("pitch_resample: bad arguments");
+  const long L = pitch_len(n, step);
+  if (L < 1) return;
+  hipLaunchKernelGGL(k_pitch_whole, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, x, (long)n, step,
+                     reinterpret_cast<const float2*>(tab), L, y);
 }
 
 // whole-signal encode of n samples (already at the wire rate), four per lane

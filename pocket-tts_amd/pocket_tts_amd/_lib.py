@@ -81,6 +81,13 @@ class SlotOpts2(C.Structure):
     ]
 
 
+class SlotOpts3(C.Structure):
+    """ptts_slot_opts with pitch_cents (48 bytes): the struct of a row admitted with a pitch."""
+    _fields_ = SlotOpts2._fields_ + [
+        ("pitch_cents", C.c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol include/pocket_tts.h (the boundary) and
 # include/pocket_tts_probe.h (measurement / test hooks) declare
 SIGNATURES = [
@@ -138,6 +145,11 @@ SIGNATURES = [
     ("ptts_tempo_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_tempo_len", C.c_long, [C.c_long, C.c_int]),
     ("ptts_tempo", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, F32P]),
+    ("ptts_pitch_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_pitch_plan", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    ("ptts_pitch_len", C.c_long, [C.c_long, C.c_uint32]),
+    ("ptts_pitch_table", C.c_int, [F32P, F32P, C.c_int]),
+    ("ptts_pitch_resample", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_uint32, F32P]),
     ("ptts_flac_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_flac_bound", C.c_long, [C.c_long]),
     ("ptts_flac_encode", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,

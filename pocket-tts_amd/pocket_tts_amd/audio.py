@@ -190,10 +190,15 @@ FLAC_BLOCK = 4608  # samples per frame at most (the subset limit at <= 48 kHz)
 FLAC_RATE_CODES = {8000: 4, 16000: 5, 24000: 7, 44100: 9, 48000: 10}
 
 
-def wire_samples(n: int, rate: int, sp: int = 0) -> int:
+def wire_samples(n: int, rate: int, sp: int = 0, cents: int = 0) -> int:
     """Samples at `rate` of an utterance of n samples at 24 kHz (time-scaled first at a speed of sp
-    permille, 0: none): what its wire chunks add up to (ceil(n' rate / 24000))."""
-    n = tempo_len(n, sp) if sp else int(n)
+    permille, 0: none, and shifted by `cents`, 0: none): what its wire chunks add up to
+    (ceil(n' rate / 24000))."""
+    if cents:
+        sp_w, step = pitch_plan(cents, sp)
+        n = pitch_len(tempo_len(n, sp_w) if sp_w != 1000 else int(n), step)
+    else:
+        n = tempo_len(n, sp) if sp else int(n)
     return -(-n * int(rate) // 24000)
 
 
@@ -434,3 +439,147 @@ def tempo_wsola(x: np.ndarray, sp: int, frame_len: int | None = None):
         done = end
     return chunks
 
+
+
+# ---- pitch: the host restatement of DESIGN.md section 23 (the GPU pitch stage's rule)
+PITCH_CENTS_MAX = 1200
+PITCH_Z, PITCH_P, PITCH_BETA = 32, 512, 12.0  # zero crossings a side, table entries per crossing, Kaiser beta
+PITCH_ONE = 1 << 20  # a step is Q20: input samples per output sample
+_PITCH_TABLE = None
+
+
+def pitch_cents(pitch) -> int:
+    """A pitch shift in semitones as the integer cents the engine takes; 0 for None or 0.
+    ValueError outside [-12, 12]."""
+    if pitch is None:
+        return 0
+    f = float(pitch)
+    c = round(100.0 * f) if math.isfinite(f) else PITCH_CENTS_MAX + 1
+    if not -PITCH_CENTS_MAX <= c <= PITCH_CENTS_MAX:
+        raise ValueError(f"pitch must be in [-12, 12] semitones, got {pitch!r}")
+    return c
+
+
+def pitch_plan(cents: int, sp: int = 0) -> tuple[int, int]:
+    """(sp_w, step) of a pitch of `cents` at speed sp permille (0: 1000): the speed the WSOLA stage
+    runs at and the resampler's Q20 step, from the library's ptts_pitch_plan (the single source of the
+    rule). ValueError for an invalid request (cents outside [-1200, 1200], sp_w outside [500, 2000])."""
+    import ctypes as C
+
+    from ._lib import lib
+    w, st = C.c_int(0), C.c_uint32(0)
+    if lib().ptts_pitch_plan(int(cents), int(sp), C.byref(w), C.byref(st)) != 0:
+        raise ValueError(f"pitch of {cents} cents at speed {sp or 1000} permille is outside the valid range "
+                         "(cents in [-1200, 1200], speed / 2^(cents / 1200) in [0.5, 2.0])")
+    return w.value, st.value
+
+
+def pitch_cq(step: int) -> int:
+    """The cutoff scale in Q20: min(2^20, floor(2^40 / step))."""
+    return min(PITCH_ONE, (1 << 40) // int(step))
+
+
+def pitch_support(step: int) -> int:
+    """H: the one-sided support in input samples, ceil(Z 2^20 / cq) + 1."""
+    cq = pitch_cq(step)
+    return -(-(PITCH_Z << 20) // cq) + 1
+
+
+def pitch_len(n: int, step: int) -> int:
+    """Outputs of n inputs: floor(n 2^20 / step)."""
+    return (int(n) << 20) // int(step)
+
+
+def pitch_emitted(n: int, step: int) -> int:
+    """Outputs a stream has emitted after n inputs (not its last frame): the m with
+    (m step >> 20) + H <= n - 1, ceil((n - H) 2^20 / step)."""
+    h = pitch_support(step)
+    return -(-((int(n) - h) << 20) // int(step)) if n > h else 0
+
+
+def pitch_chunk_samples(n_before: int, n_after: int, step: int, last: bool) -> int:
+    """Samples the pitch stage emits in the frame that takes a row from n_before to n_after inputs: a
+    pure function of the plan and the input counts. The last frame emits the rest up to pitch_len."""
+    return (pitch_len(n_after, step) if last else pitch_emitted(n_after, step)) - pitch_emitted(n_before, step)
+
+
+def _bessel_i0(x: np.ndarray) -> np.ndarray:
+    """The power series of the library's bessel_i0, term by term in its order (terms past its stopping
+    point do not change the f64 sum)."""
+    x = np.asarray(x, np.float64)
+    s, t, q = np.ones_like(x), np.ones_like(x), 0.25 * x * x
+    for k in range(1, 500):
+        t = t * (q / (float(k) * k))
+        s = s + t
+    return s
+
+
+def pitch_table() -> tuple[np.ndarray, np.ndarray]:
+    """(T, D): T[i] = f32(sinc(i / P) kaiser_beta(i / (P Z))) for 0 <= i <= Z P + 1, computed in f64,
+    exactly 0 at the sinc's zeros and past Z P, T[0] = 1; D[i] = f32(T[i + 1] - T[i])."""
+    global _PITCH_TABLE
+    if _PITCH_TABLE is None:
+        n = PITCH_Z * PITCH_P
+        i = np.arange(1, n)
+        r = i / float(PITCH_P * PITCH_Z)
+        kais = _bessel_i0(PITCH_BETA * np.sqrt(1.0 - r * r)) / float(_bessel_i0(np.float64(PITCH_BETA)))
+        sinc = np.array([math.sin(math.pi * (k / PITCH_P)) / (math.pi * (k / PITCH_P)) for k in range(1, n)])
+        t = np.zeros(n + 2, np.float32)
+        t[0] = 1.0
+        t[1:n] = (sinc * kais).astype(np.float32)
+        t[PITCH_P:n:PITCH_P] = 0.0
+        d = (t[1:].astype(np.float64) - t[:-1].astype(np.float64)).astype(np.float32)
+        _PITCH_TABLE = (t, d)
+    return _PITCH_TABLE
+
+
+def _pitch_outputs(buf: np.ndarray, base: int, n: int, m0: int, m1: int, step: int) -> np.ndarray:
+    """Outputs m0 <= m < m1 of the signal whose sample j is buf[j - base] for base <= j < n (0 outside
+    [0, n)): per output one ascending f64 chain over j = i0 - H .. i0 + H."""
+    t, d = pitch_table()
+    cq, h_side, zp = pitch_cq(step), pitch_support(step), PITCH_Z * PITCH_P
+    m = np.arange(m0, m1, dtype=np.int64)
+    pos = m * int(step)
+    i0 = pos >> 20
+    acc = np.zeros(m.size, np.float64)
+    for k in range(-h_side, h_side + 1):
+        j = i0 + k
+        q = (np.abs(pos - (j << 20)) * cq) >> 20
+        qp = q * PITCH_P
+        ti = qp >> 20
+        live = ti < zp
+        tc = np.minimum(ti, zp - 1)
+        fr = (qp & (PITCH_ONE - 1)).astype(np.float64) / float(PITCH_ONE)
+        h = (t[tc].astype(np.float64) + d[tc].astype(np.float64) * fr).astype(np.float32)
+        h[~live] = 0.0
+        inside = (j >= 0) & (j >= base) & (j < n)
+        u = np.where(inside, buf[np.clip(j - base, 0, max(buf.size - 1, 0))], np.float32(0.0)) if buf.size else \
+            np.zeros(m.size, np.float32)
+        acc += u.astype(np.float64) * h.astype(np.float64)
+    return (acc * (cq / float(PITCH_ONE))).astype(np.float32)
+
+
+def pitch_resample(x: np.ndarray, step: int, chunks=None):
+    """The fractional resampler of the pitch stage: x (f32) read at step / 2^20 input samples per
+    output sample, pitch_len(len(x), step) outputs. Every product is exact in f64 and every sum runs in
+    the stated order, so the GPU stage agrees bit for bit. chunks: the sizes in which the input
+    arrives (they sum to len(x); the last one is the row's last frame): run as the stream does,
+    keeping only the last 2 H + 2 inputs between chunks, and return the list of output chunks."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    step = int(step)
+    if not PITCH_ONE // 2 <= step <= PITCH_ONE * 2:
+        raise ValueError(f"step must be in [2^19, 2^21], got {step}")
+    if chunks is None:
+        return _pitch_outputs(x, 0, x.size, 0, pitch_len(x.size, step), step)
+    sizes = [int(c) for c in chunks]
+    if sum(sizes) != x.size or any(c < 0 for c in sizes):
+        raise ValueError("chunks must be non-negative and sum to len(x)")
+    keep = 2 * pitch_support(step) + 2
+    hist, n, e, out = np.zeros(0, np.float32), 0, 0, []
+    for f, c in enumerate(sizes):
+        buf = np.concatenate([hist, x[n:n + c]])
+        base, n = n - hist.size, n + c
+        e1 = pitch_len(n, step) if f == len(sizes) - 1 else pitch_emitted(n, step)
+        out.append(_pitch_outputs(buf, base, n, e, e1, step))
+        e, hist = e1, buf[-keep:]
+    return out

@@ -9,8 +9,8 @@ import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SlotOpts, SlotOpts2, check, fptr, lib, u8ptr)
-from .audio import speed_permille
+                   SlotOpts, SlotOpts2, SlotOpts3, check, fptr, lib, u8ptr)
+from .audio import pitch_cents, speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
 WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW, "flac": WIRE_FLAC}
@@ -49,6 +49,10 @@ class GenerationParams:
     # speech speed of the row's wire bytes (tempo-enabled engines), 0.5 .. 2.0; None or 1.0: unchanged.
     # A speed with no wire format implies 24000 / 16-bit. The f32 PCM of fetch() never depends on it.
     speed: float | None = None
+    # pitch shift of the row's wire bytes in semitones (pitch-enabled engines), -12 .. 12; None or 0:
+    # unchanged. A resampling shift (formants move too) at the duration `speed` asks for (DESIGN.md
+    # section 23). A pitch with no wire format implies 24000 / 16-bit; fetch()'s f32 PCM never depends on it.
+    pitch: float | None = None
     # latent prefix and codec continuity (ptts_slot_opts.prefix_latents / .keep_codec; DESIGN.md
     # section 20): the row starts as if it had been teacher-forced through these [n, 32] FlowLM
     # latents (values fetch() returned), and with keep_codec on the codec state its slot ended on.
@@ -73,6 +77,11 @@ class GenerationParams:
         out of range is passed on as it is (rounded to permille): the admission refuses it."""
         sp = 0 if self.speed is None else round(float(self.speed) * 1000)
         return (*self.wire(), 0 if sp == 1000 else sp)
+
+    def cents(self) -> int:
+        """pitch_cents of ptts_slot_opts: round(100 * semitones), passed on as it is (the admission
+        refuses a value out of range); 0: none."""
+        return 0 if self.pitch is None else round(100.0 * float(self.pitch))
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
@@ -140,7 +149,7 @@ class Engine:
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
                  back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
-                 tempo: bool = False, flac: bool = False):
+                 tempo: bool = False, flac: bool = False, pitch: bool = False):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -160,6 +169,8 @@ class Engine:
         get their wire bytes, converted on the GPU (fetch_wire).
         tempo=True (ptts_tempo_enable; needs wire): rows admitted with GenerationParams.speed have
         their wire bytes time-scaled on the GPU.
+        pitch=True (ptts_pitch_enable; needs tempo): rows admitted with GenerationParams.pitch have
+        their wire bytes shifted in pitch on the GPU.
         flac=True (ptts_flac_enable; needs wire): rows admitted with encoding "flac" get FLAC frames
         of their 16-bit chunks, encoded on the GPU."""
         if back_mfma is None:
@@ -197,6 +208,13 @@ class Engine:
         if tempo:
             try:
                 check(lib().ptts_tempo_enable(self.handle, 1))
+            except Exception:
+                self.close()
+                raise
+        self.pitch_enabled = bool(pitch)
+        if pitch:
+            try:
+                check(lib().ptts_pitch_enable(self.handle, 1))
             except Exception:
                 self.close()
                 raise
@@ -423,7 +441,7 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
-        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec:
+        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec or params.cents():
             return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
@@ -442,6 +460,14 @@ class Engine:
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
         pre = [p.prefix() for p in params_list]  # (kept alive until the call returns)
+        if any(p.cents() for p in params_list):  # a pitch: the 48-byte struct
+            opts = (SlotOpts3 * n)(*[SlotOpts3(C.sizeof(SlotOpts3), int(lsd[i]), *p.opts(),
+                                               pre[i].ctypes.data if pre[i] is not None else None,
+                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents())
+                                     for i, p in enumerate(params_list)])
+            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
+            return
         if any(a is not None for a in pre) or any(p.keep_codec for p in params_list):
             opts = (SlotOpts2 * n)(*[SlotOpts2(C.sizeof(SlotOpts2), int(lsd[i]), *p.opts(),
                                                pre[i].ctypes.data if pre[i] is not None else None,
@@ -538,7 +564,7 @@ class Engine:
         return out[:n].tobytes()
 
     def flac_encode(self, samples_i16: np.ndarray, sample_rate: int = 24000, first_sample: int = 0) -> bytes:
-        """The FLAC stage's chunk encoder on up to 11,058 arbitrary 16-bit samples (ptts_flac_encode):
+        """The FLAC stage's chunk encoder on up to 11,221 arbitrary 16-bit samples (ptts_flac_encode):
         the frames audio.flac_frames restates on the host, byte for byte."""
         x = np.ascontiguousarray(np.asarray(samples_i16, np.int16).reshape(-1))
         out = np.zeros(max(int(lib().ptts_flac_bound(x.size)), 1), np.uint8)
@@ -562,6 +588,21 @@ class Engine:
         n = int(lib().ptts_tempo_len(x.size, sp))
         y = np.zeros(max(n, 1), np.float32)
         check(lib().ptts_tempo(self.handle, fptr(x), x.size, sp, fptr(y)))
+        return y[:n]
+
+    @staticmethod
+    def pitch_len(n: int, step: int) -> int:
+        """Samples of n inputs read at step / 2^20 inputs per output (ptts_pitch_len; host only)."""
+        return int(lib().ptts_pitch_len(int(n), int(step)))
+
+    def pitch_resample(self, x: np.ndarray, step: int) -> np.ndarray:
+        """Whole-signal f32 read at step / 2^20 (Q20, 2^19 .. 2^21) inputs per output on the GPU
+        (ptts_pitch_resample): the tap loop of the streaming pitch stage (audio.pitch_resample is its
+        host restatement)."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        n = self.pitch_len(x.size, step)
+        y = np.zeros(max(n, 1), np.float32)
+        check(lib().ptts_pitch_resample(self.handle, fptr(x), x.size, int(step), fptr(y)))
         return y[:n]
 
     def fetch_ready(self, calls_back: int = 0) -> bool:

@@ -68,6 +68,20 @@ on a server without the stage (`--no-tempo`, `--no-wire`), gets 400.
     curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
          -d '{"input": "Hello there.", "voice": "alba", "speed": 1.25}' -o fast.wav
 
+Per-request pitch (`--pitch`, on with `--tempo`): the three audio routes also take `pitch`, in
+semitones within [-12, 12]. The row's PCM is time-scaled by the WSOLA stage to 2^(pitch / 12) times
+the duration its `speed` asks for and then read that many times faster by a streaming windowed-sinc
+resampler on the GPU, so the pitch moves and the duration stays what `speed`
+says. It is a resampling shift, the "deeper / brighter voice" control: formants move with the
+fundamental. Every later stage (rate, encoding, FLAC) runs on the result unchanged. Unset or 0
+changes nothing; a long-form request's every text segment carries the pitch and pauses keep their
+duration. A value outside the range, a combination with `speed` for which speed / 2^(pitch / 12)
+leaves [0.5, 2.0], or a pitch on a server without the stage (`--no-pitch`, `--no-tempo`, `--no-wire`),
+gets 400.
+
+    curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
+         -d '{"input": "Hello there.", "voice": "alba", "pitch": -3}' -o deeper.wav
+
 Long-form requests (`long_form` in the three audio routes' bodies; `--long-form` sets the default,
 off): the text is cut as the reference's routes cut it (generate_stream_long, handlers.rs:165,260:
 pause markers and natural pauses become silence, each piece is cut into sentence chunks of at most
@@ -111,7 +125,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, flac_stream_header, pcm_i16_le_bytes, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
+from .audio import (ENCODINGS, flac_stream_header, pcm_i16_le_bytes, pitch_cents, pitch_plan, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
 from .engine import GenerationParams, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
@@ -328,6 +342,7 @@ class Request(_Consumer):
     # converted (Engine.fetch_wire), not float32 frames; None: today's float32 frames
     wire: tuple[int, str] | None = None
     speed: int = 0         # permille of a request with a speed (its wire bytes are time-scaled); 0: none
+    pitch: int = 0         # cents of a request with a pitch (its wire bytes are shifted); 0: none
     sched: object = None   # the scheduler that holds the request (cancel())
     group: object = None   # the RequestGroup this request is a text segment of
     ended: bool = False    # the end marker was put
@@ -342,7 +357,8 @@ class Request(_Consumer):
     def __post_init__(self):
         rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
         self.speed = self.params.opts()[2] if hasattr(self.params, "opts") else 0
-        if rate or enc or self.speed:  # a speed alone: 24000 / pcm_s16le
+        self.pitch = self.params.cents() if hasattr(self.params, "cents") else 0
+        if rate or enc or self.speed or self.pitch:  # a speed or a pitch alone: 24000 / pcm_s16le
             self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
 
     def put(self, item):
@@ -700,9 +716,9 @@ class BatchScheduler:
             if fmt is not None:
                 # a resampled row's first chunk is shorter than its preview's frame (the filter's
                 # delay): it waits for its regular first chunk; a 24 kHz row's preview is encoded here
-                # a speed row's first chunk is not its first frame either
+                # a speed or pitch row's first chunk is not its first frame either
                 # a FLAC row's frames are written by the engine alone
-                if fmt[0] != SAMPLE_RATE or req.speed or fmt[1] == "flac":
+                if fmt[0] != SAMPLE_RATE or req.speed or req.pitch or fmt[1] == "flac":
                     continue
                 pcm = wire_bytes(pcm, fmt[1])
             req.preview = 1
@@ -1051,6 +1067,7 @@ class TTSService:
         self.wire = bool(getattr(eng, "wire", False))  # the engines convert to wire formats (--wire)
         self.tempo = self.wire and bool(getattr(eng, "tempo_enabled", False))  # and time-scale (--tempo)
         self.flac = self.wire and bool(getattr(eng, "flac_enabled", False))  # and encode FLAC (--flac)
+        self.pitch = self.tempo and bool(getattr(eng, "pitch_enabled", False))  # and shift the pitch (--pitch)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -1072,12 +1089,14 @@ class TTSService:
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None, sample_rate: int | None = None,
                 encoding: str | None = None, long_form: bool | None = None, speed: float | None = None,
-                continuity: bool | None = None) -> Request:
+                continuity: bool | None = None, pitch: float | None = None) -> Request:
         """continuity (None: the server's default, --continuity): the long-form
         cut, with the sentence chunks of a text piece generated one after another on one slot, each
         teacher-forced through the one before it and decoded on from its codec state, so prosody
         and the codec run across the joins. token_ids are never split, so they cannot ask for it.
         speed: 0.5 .. 2.0, the row's wire bytes time-scaled on the GPU (None or 1.0: unchanged).
+        pitch: -12 .. 12 semitones, the row's wire bytes shifted in pitch on the GPU at the duration
+        `speed` asks for (None or 0: unchanged).
         long_form (None: the server's default, --long-form): the text is split as the reference's
         routes split it (generate_stream_long: pause markers and natural pauses become silence,
         each text piece is cut into sentence chunks of at most 50 tokens) and the chunks run as
@@ -1108,6 +1127,13 @@ class TTSService:
         elif not self.tempo:
             raise ValueError("this server runs without the tempo stage (--no-tempo or --no-wire): speed is not "
                              "available")
+        if pitch_cents(pitch) == 0:  # (ValueError outside [-12, 12]); 0: the request without it
+            pitch = None
+        else:
+            if not self.pitch:
+                raise ValueError("this server runs without the pitch stage (--no-pitch, --no-tempo or --no-wire): "
+                                 "pitch is not available")
+            pitch_plan(pitch_cents(pitch), speed_permille(speed))  # (ValueError: with this speed, outside WSOLA's range)
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
@@ -1145,25 +1171,25 @@ class TTSService:
             target = clip if clip is not None else self.voices[name]
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
-                                                            lsd_steps, sample_rate, encoding, speed))
+                                                            lsd_steps, sample_rate, encoding, speed, pitch))
                         if sg[0] == "text" else sg for sg in segments]
                 wire = None  # (pauses: silence of their stated duration, whatever the speed)
-                if sample_rate is not None or encoding is not None or speed is not None:
+                if sample_rate is not None or encoding is not None or speed is not None or pitch is not None:
                     wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
                 if chain:
                     return self.scheduler.submit_group(segs, target, wire, continuity=True)
                 return self.scheduler.submit_group(segs, target, wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       sample_rate, encoding, speed)
+                                       sample_rate, encoding, speed, pitch)
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       sample_rate=None, encoding=None, speed=None) -> Request:
+                       sample_rate=None, encoding=None, speed=None, pitch=None) -> Request:
         p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding,
-                                speed)
+                                speed, pitch)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
-                       encoding=None, speed=None) -> GenerationParams:
+                       encoding=None, speed=None, pitch=None) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -1175,6 +1201,8 @@ class TTSService:
             p.sample_rate, p.encoding = sample_rate, encoding
         if speed is not None:
             p.speed = float(speed)
+        if pitch is not None:
+            p.pitch = float(pitch)
         return p
 
     # -- per-request and run-time voices
@@ -1265,6 +1293,9 @@ class GenerateRequest(BaseModel):
     encoding: str | None = None
     # speech speed, 0.5 .. 2.0 (time-scaled on the GPU, pitch kept); unset or 1.0: unchanged
     speed: float | None = None
+    # pitch shift in semitones, -12 .. 12 (resampled on the GPU at the duration `speed` asks for; formants
+    # move with the fundamental); unset or 0: unchanged
+    pitch: float | None = None
     # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
     long_form: bool | None = None
     # the long-form cut with each sentence chunk continuing the one before it (None: --continuity)
@@ -1283,6 +1314,7 @@ class OpenAIRequest(BaseModel):
     sample_rate: int | None = None
     encoding: str | None = None
     speed: float | None = None  # 0.5 .. 2.0, as in the API this route imitates (0.25 .. 4.0 there)
+    pitch: float | None = None  # -12 .. 12 semitones (no counterpart in that API)
     long_form: bool | None = None
     continuity: bool | None = None
 
@@ -1363,7 +1395,7 @@ def flac_file(r) -> bytes:
     """A FLAC request's whole output as a file: the header with the true sample count (one item per
     frame of the row, whatever its size), then the chunks untouched."""
     chunks = list(r.stream())
-    total = wire_samples(len(chunks) * FRAME, r.wire[0], getattr(r, "speed", 0))
+    total = wire_samples(len(chunks) * FRAME, r.wire[0], getattr(r, "speed", 0), getattr(r, "pitch", 0))
     return flac_stream_header(r.wire[0], total) + b"".join(chunks)
 
 
@@ -1462,7 +1494,7 @@ def create_app(service: TTSService):
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
-                   encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity)
+                   encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity, pitch=req.pitch)
         if r.wire is not None and r.wire[1] == "flac":
             return Response(flac_file(r), media_type="audio/flac", headers=hdr)
         if r.wire is not None:
@@ -1619,7 +1651,8 @@ def _worker_engine(args, Engine):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     kw = dict(max_slots=args.slots, max_ctx=args.max_ctx, weights_path=args.weights, pipeline=True,
               back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
-              wire=args.wire, tempo=args.wire and args.tempo, flac=args.wire and args.flac)
+              wire=args.wire, tempo=args.wire and args.tempo, flac=args.wire and args.flac,
+              pitch=args.wire and args.tempo and args.pitch)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1690,6 +1723,9 @@ def main(argv=None):
     ap.add_argument("--tempo", action=argparse.BooleanOptionalAction, default=True,
                     help="per-request speech speed (requests' speed) time-scaled on the GPU; needs --wire (off "
                          "with --no-wire); --no-tempo: the wire-enabled engine as before, such requests get 400")
+    ap.add_argument("--pitch", action=argparse.BooleanOptionalAction, default=True,
+                    help="per-request pitch (requests' pitch, semitones) shifted on the GPU; needs --tempo (off with "
+                         "--no-tempo or --no-wire); --no-pitch: the tempo-enabled engine as before, such requests get 400")
     ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
                     help="default of requests that do not say `long_form`: split the text into pause and sentence "
                          "segments (the reference's generate_stream_long) and run them on parallel rows")

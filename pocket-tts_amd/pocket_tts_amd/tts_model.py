@@ -29,7 +29,8 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE, WIRE_FLAC
-from .audio import flac_stream_header, read_wav, read_wav_from_bytes, speed_permille, wire_bytes, wire_samples
+from .audio import (flac_stream_header, pitch_cents, read_wav, read_wav_from_bytes, speed_permille, wire_bytes,
+                    wire_samples)
 from .engine import Engine, GenerationParams, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
@@ -87,7 +88,8 @@ class TTSModel:
                          device: int = 0, max_ctx: int = 1024, tokenizer=None,
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
-                         back_frames: int = 1, tempo: bool = False, flac: bool = False) -> "TTSModel":
+                         back_frames: int = 1, tempo: bool = False, flac: bool = False,
+                         pitch: bool = False) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
@@ -95,7 +97,8 @@ class TTSModel:
         weights_path: local safetensors with the TTSModel state-dict names (synthetic weights
         from `seed` when None); tokenizer_path: tokenizer.model (SentencePiece) or tokenizer.json.
         wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=); tempo (with wire):
-        its tempo stage too, for generate(.., speed=); flac (with wire): its FLAC stage, for
+        its tempo stage too, for generate(.., speed=); pitch (with tempo): its pitch stage, for
+        generate(.., pitch=); flac (with wire): its FLAC stage, for
         generate(.., encoding="flac")."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
@@ -104,7 +107,7 @@ class TTSModel:
         eng = Engine(device=device, max_slots=int(max_slots), max_ctx=max_ctx, pipeline=pipeline,
                      back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
-                     wire=wire, tempo=tempo, flac=flac)
+                     wire=wire, tempo=tempo, flac=flac, pitch=pitch)
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -196,10 +199,11 @@ class TTSModel:
 
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
                  sample_rate: int | None = None, encoding=None, speed: float | None = None,
-                 previous: Continuation | None = None, latents: list | None = None) -> Iterator[np.ndarray]:
+                 previous: Continuation | None = None, latents: list | None = None,
+                 pitch: float | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
-        (sample_rate / encoding; a wire-enabled engine) or a speed (a tempo-enabled one; 24 kHz
-        16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
+        (sample_rate / encoding; a wire-enabled engine), a speed (a tempo-enabled one) or a pitch (a
+        pitch-enabled one; 24 kHz 16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
         GPU (Engine.fetch_wire), instead of f32 frames.
         previous: the segment continues that one (section 20): admitted behind its ids and, as a
         teacher-forced prefix, its latents, on the codec state it left (only the new frames are
@@ -208,12 +212,12 @@ class TTSModel:
         self._check_lsd()
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
-        params.sample_rate, params.encoding, params.speed = sample_rate, encoding, speed
+        params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
         if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
                                      + max_frames <= self.engine.max_ctx):
             ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
             params.prefix_latents, params.keep_codec = np.asarray(previous.latents, np.float32), True
-        wire = params.opts() != (0, 0, 0)
+        wire = params.opts() != (0, 0, 0) or params.cents() != 0
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
@@ -233,7 +237,7 @@ class TTSModel:
 
     def generate_stream(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                         words: int | None = None, sample_rate: int | None = None, encoding=None,
-                        speed: float | None = None) -> Iterator[np.ndarray]:
+                        speed: float | None = None, pitch: float | None = None) -> Iterator[np.ndarray]:
         """tts_model.rs:894-913. Text: one segment per sentence chunk; max_gen_len and the EOS tail
         from each chunk (:968-969). Token ids (an extension for callers with their own tokenizer):
         one segment; ids carry no word count, so the caller passes `words` (the reference's rules
@@ -245,11 +249,16 @@ class TTSModel:
         speed (0.5 .. 2.0; a tempo-enabled engine): the segments' audio is time-scaled on the GPU
         ahead of that conversion, pitch kept; the items are wire bytes then
         too, 24 kHz 16-bit unless a format is given. None or 1.0 changes nothing.
+        pitch (-12 .. 12 semitones; a pitch-enabled engine): the segments' audio is shifted in pitch
+        on the GPU at the duration `speed` asks for, a resampling shift that moves the formants too
+        (DESIGN.md section 23); wire bytes as for speed. None or 0 changes nothing.
         encoding "flac" (a FLAC-enabled engine): the items are the FLAC frames of each chunk (DESIGN.md
         section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0, so
         the text must be one segment: ValueError where it splits into several."""
         if speed_permille(speed) == 0:
             speed = None
+        if pitch_cents(pitch) == 0:
+            pitch = None
         if encoding in ("flac", WIRE_FLAC) and isinstance(text_or_ids, str) and \
                 len(self.split_into_best_sentences(text_or_ids)) > 1:
             raise ValueError("flac: the text splits into several segments, each a stream of its own (section 21, Limits)")
@@ -259,28 +268,30 @@ class TTSModel:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
             yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding,
-                                     speed)
+                                     speed, pitch=pitch)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed)
+                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed, pitch=pitch)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
-                 speed: float | None = None):
+                 speed: float | None = None, pitch: float | None = None):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
-        speed, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
+        speed / pitch, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
         the stream header with the true sample count and then the frames."""
-        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed))
+        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed,
+                                           pitch))
         if not frames:
             raise RuntimeError("No audio generated")
         if encoding in ("flac", WIRE_FLAC):
             rate = int(sample_rate or SAMPLE_RATE)
-            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, speed_permille(speed))) + b"".join(frames)
-        if sample_rate is not None or encoding is not None or speed_permille(speed):
+            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, speed_permille(speed),
+                                                        pitch_cents(pitch))) + b"".join(frames)
+        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch):
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
 
@@ -344,7 +355,7 @@ class TTSModel:
     # ---- the same segments on parallel rows
     def generate_stream_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
                                  sample_rate: int | None = None, encoding=None,
-                                 speed: float | None = None) -> Iterator:
+                                 speed: float | None = None, pitch: float | None = None) -> Iterator:
         """The items of generate_stream (pauses=False) or generate_stream_long (pauses=True), in text
         order, with the text segments generated as rows of one batch: up to `rows` (default: the
         engine's max_slots) are admitted at once (Engine.open_many: one shared text prefill, the
@@ -355,7 +366,7 @@ class TTSModel:
         segment, in text order) and the field values read when this call starts.
         sample_rate / encoding: wire bytes as generate_stream yields them, and each pause as the
         encoded silence of silence_samples(ms, sample_rate) samples. speed: every text segment's row
-        carries it (generate_stream); pauses keep their stated duration. Closing the generator early
+        carries it (generate_stream), and the pitch likewise; pauses keep their stated duration. Closing the generator early
         cancels the rows it still holds (Engine.cancel_slots)."""
         self._check_lsd()
         if encoding in ("flac", WIRE_FLAC):
@@ -363,7 +374,8 @@ class TTSModel:
         tok = self._tok()
         eng = self.engine
         speed = speed if speed_permille(speed) else None
-        wire = sample_rate is not None or encoding is not None or speed is not None
+        pitch = pitch if pitch_cents(pitch) else None
+        wire = sample_rate is not None or encoding is not None or speed is not None or pitch is not None
         n_rows = max(1, min(int(rows or eng.max_slots), eng.max_slots))
         items = []  # per segment: ("pause", item) | ["text", ids, params, frames, done]
         for kind, val in long_form_segments(text, self.count_tokens, pauses):
@@ -371,7 +383,7 @@ class TTSModel:
                 ids, mgl, fae = segment_request(val, tok)
                 params = self._params(mgl, fae)
                 params.lsd_steps = int(self.lsd_decode_steps)
-                params.sample_rate, params.encoding, params.speed = sample_rate, encoding, speed
+                params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
                 items.append(["text", np.asarray(ids, np.int32), params, [], False])
             elif wire:
                 n = silence_samples(val, int(sample_rate or SAMPLE_RATE))
@@ -431,14 +443,16 @@ class TTSModel:
                 eng.cancel_slots(sorted(active))
 
     def generate_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
-                          sample_rate: int | None = None, encoding=None, speed: float | None = None):
+                          sample_rate: int | None = None, encoding=None, speed: float | None = None,
+                          pitch: float | None = None):
         """generate (pauses=False) or generate_with_pauses (pauses=True) with the text's segments on
         parallel rows: the concatenation of generate_stream_parallel's items. The name is the
         reference's own: its generate_parallel (tts_model.rs:705-854) is commented out there, "for
         future exploration with GPU acceleration"."""
-        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding, speed))
+        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding, speed,
+                                                    pitch))
         if not chunks:
             raise RuntimeError("No audio generated")
-        if sample_rate is not None or encoding is not None or speed_permille(speed):
+        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch):
             return b"".join(chunks)
         return np.concatenate(chunks, axis=2)[0]
