@@ -333,6 +333,9 @@ typedef struct ptts_slot_opts {
   int n_prefix;
   int keep_codec;
   int pitch_cents; /* pitch shift, -1200 .. 1200 cents (ptts_pitch_enable); 0: none. Size 40 -> 48 */
+  int reserved;    /* offset 44: what was the 48-byte struct's tail padding; ignored */
+  int gain_cdb;    /* volume in hundredths of a dB, -2400 .. 2400 (ptts_level_enable); 0: none. Size 48 -> 56 */
+  int limit;       /* 1: the row runs through the peak limiter even at gain 0; 0: only with a gain */
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
@@ -390,6 +393,32 @@ int ptts_pitch_plan(int cents, int speed_permille, int* wsola_permille, uint32_t
 long ptts_pitch_len(long n, uint32_t step_q20);
 int ptts_pitch_table(float* t, float* d, int n);
 int ptts_pitch_resample(ptts_engine* e, const float* x, int n, uint32_t step_q20, float* y);
+/* Volume and peak limiting (no reference counterpart). A row admitted with ptts_slot_opts.gain_cdb
+ * != 0 or .limit == 1 is in the level stage: between the pitch stage and the
+ * wire stage its samples x (f32 at 24 kHz, after speed and pitch) become u = v x with v =
+ * (float)pow(10, gain_cdb / 2000), and a look-ahead peak limiter of 126 samples (5.25 ms) keeps the
+ * result inside the engine's ceiling C = (float)pow(10, ceiling_cdb / 2000): r[n] = |u[n]| > C ? C /
+ * |u[n]| : 1, m[i] = min(r[i .. i + 126]), g[n] = (float)(sum_{k = 0..126} (64 - |k - 63|) m[n - k] /
+ * 4096) summed in f64, y[n] = clamp(g[n] u[n], -C, C). Where no |u| within 126 samples exceeds C the
+ * output is v x exactly. The output has the input's length; a streaming row emits 126 samples late and
+ * catches up in its last frame, and its chunks concatenate to the whole-signal rule (ptts_level) over
+ * the stage's input, bit for bit. Only the wire bytes change. A gain or limit with no wire format
+ * implies 24000 / PTTS_WIRE_S16. A gain outside [-2400, 2400], a limit outside {0, 1}, or either asked
+ * of an engine without ptts_level_enable, is PTTS_ERR_INVALID and admits nothing. A caller with a
+ * struct shorter than 56 bytes gets neither.
+ * ptts_level_enable: valid on a wire-enabled idle engine before its first step (PTTS_ERR_INVALID
+ * otherwise, or for ceiling_cdb outside [-4000, 0]); independent of the tempo and pitch stages; on =
+ * 0, or never called: the passes, graphs and copies the engine has without it. On a level-enabled
+ * engine a last chunk holds up to 252 more samples at 48 kHz (4,112 for a plain row, 11,448 behind
+ * the pitch stage), every row's chunk slot is PTTS_WIRE_CHUNK_MAX_LEVEL bytes and ptts_fetch_wire
+ * requires row_stride >= that. */
+#define PTTS_WIRE_CHUNK_MAX_LEVEL 23552
+int ptts_level_enable(ptts_engine* e, int on, int ceiling_cdb);
+/* The level seam alone. ptts_level_plan (host only): the two f32 factors of (gain_cdb, ceiling_cdb),
+ * PTTS_ERR_INVALID outside the ranges; either pointer may be NULL. ptts_level: the whole-signal rule
+ * on the GPU (the window function of the streaming stage), n >= 1; y receives n samples. */
+int ptts_level_plan(int gain_cdb, int ceiling_cdb, float* gain, float* ceiling);
+int ptts_level(ptts_engine* e, const float* x, int n, int gain_cdb, int ceiling_cdb, float* y);
 /* FLAC (no reference counterpart; RFC 9639, restated in DESIGN.md section 21). A row admitted with
  * wire_encoding = PTTS_WIRE_FLAC gets, per frame, the FLAC frames of the 16-bit samples its
  * PTTS_WIRE_S16 chunk at the same rate (and speed) would hold: mono, 16 bit, blocks of at most 4,608
@@ -410,7 +439,7 @@ int ptts_pitch_resample(ptts_engine* e, const float* x, int n, uint32_t step_q20
 #define PTTS_WIRE_FLAC 4
 int ptts_flac_enable(ptts_engine* e, int on);
 /* The FLAC seam alone: the bound above (0 for n < 1; host only), and the stage's chunk encoder on
- * n <= 11,221 arbitrary 16-bit samples at sample_rate (one of the wire rates), the first of which
+ * n <= 11,477 arbitrary 16-bit samples at sample_rate (one of the wire rates), the first of which
  * has index first_sample (0 <= first_sample, first_sample + n <= 2^36) in its stream; out holds
  * ptts_flac_bound(n) bytes, *n_bytes receives the frames' byte total. */
 long ptts_flac_bound(long n);

@@ -314,7 +314,7 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     const size_t size = opts[0].size ? opts[0].size : offsetof(ptts_slot_opts, pitch_cents);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n);
+    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n), gain(n), limit(n);
     std::vector<const float*> pre(n);
     for (int i = 0; i < n; ++i) {
       ptts_slot_opts o{};
@@ -328,9 +328,11 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
       npre[i] = o.n_prefix;
       keep[i] = o.keep_codec;
       pitch[i] = o.pitch_cents;
+      gain[i] = o.gain_cdb;  // (o.reserved, the four bytes behind pitch_cents, is ignored)
+      limit[i] = o.limit;
     }
     eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data(),
-                      pre.data(), npre.data(), keep.data(), pitch.data());
+                      pre.data(), npre.data(), keep.data(), pitch.data(), gain.data(), limit.data());
   });
 }
 
@@ -385,6 +387,22 @@ int ptts_pitch_table(float* t, float* d, int n) {
 
 int ptts_pitch_resample(ptts_engine* e, const float* x, int n, uint32_t step_q20, float* y) {
   return guard([&] { eng(e).pitch_host(x, n, step_q20, y); });
+}
+
+int ptts_level_enable(ptts_engine* e, int on, int ceiling_cdb) {
+  return guard([&] { eng(e).level_enable(on != 0, ceiling_cdb); });
+}
+
+int ptts_level_plan(int gain_cdb, int ceiling_cdb, float* gain, float* ceiling) {
+  float v = 0.f, c = 0.f;
+  if (!ptts::level_plan(gain_cdb, ceiling_cdb, &v, &c)) return PTTS_ERR_INVALID;
+  if (gain) *gain = v;
+  if (ceiling) *ceiling = c;
+  return PTTS_OK;
+}
+
+int ptts_level(ptts_engine* e, const float* x, int n, int gain_cdb, int ceiling_cdb, float* y) {
+  return guard([&] { eng(e).level_host(x, n, gain_cdb, ceiling_cdb, y); });
 }
 
 int ptts_flac_enable(ptts_engine* e, int on) { return guard([&] { eng(e).flac_enable(on != 0); }); }

@@ -1686,6 +1686,33 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       ops.push_back({"pitch", [pa](hipStream_t s) { pitch_stage(pa, s); }, 0.0,
                      (double)B * nfr * 4.0 * (TEMPO_OUT_MAX + PITCH_OUT_MAX)});
     }
+    if (level_) {  // then the level rows' chunks, from whatever the wire stage would read (section 24)
+      LevelArgs la{};
+      la.B = B;
+      la.nfr = nfr;
+      la.pcm_frames = pcm_frames;
+      la.out_frames = nfr_;
+      la.pcm = pcm_out;
+      for (int f = 0; f < NFR_MAX; ++f) la.flags[f] = fl[f];
+      la.gain = level_gain_;
+      la.ceiling = level_ceiling_;
+      if (tempo_) {
+        la.tempo_sp = tempo_sp_;
+        la.tin = tempo_out_;
+        la.tcnt = tempo_cnt_;
+      }
+      if (pitch_) {
+        la.pitch_step = pitch_step_;
+        la.pin = pitch_out_;
+        la.pcnt = pitch_cnt_;
+      }
+      la.state = level_state_;
+      la.hist = level_hist_;
+      la.out = level_out_;
+      la.counts = level_cnt_;
+      ops.push_back({"level", [la](hipStream_t s) { level_stage(la, s); }, 0.0,
+                     (double)B * nfr * 4.0 * (PITCH_OUT_MAX + LEVEL_OUT_MAX)});
+    }
     WireArgs w{};
     w.B = B;
     w.nfr = nfr;
@@ -1710,6 +1737,11 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       w.pitch_step = pitch_step_;
       w.pin = pitch_out_;
       w.pcnt = pitch_cnt_;
+    }
+    if (level_) {
+      w.level_gain = level_gain_;
+      w.lin = level_out_;
+      w.lcnt = level_cnt_;
     }
     if (flac_) w.first = flac_first_;
     ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
@@ -3066,7 +3098,7 @@ int Engine::lsd_run_for(int B) const {
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                         const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
                         const int* wire_enc, const int* speed, const float* const* prefix, const int* n_prefix,
-                        const int* keep_codec, const int* pitch) {
+                        const int* keep_codec, const int* pitch, const int* gain_cdb, const int* limit) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
@@ -3074,6 +3106,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
   std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
   std::vector<unsigned> wpt(n, 0u);  // the rows' pitch steps (Q20; 0: none)
+  std::vector<unsigned> wlv(n, 0u);  // the rows' gains (f32 bits; 0: not in the level stage)
   std::vector<int> npre(n, 0);  // the rows' latent prefixes (frames) and RESET_* bits (section 20)
   std::vector<int> ropt(n, 0);
   bool any_prefix = false, any_opt = false;
@@ -3095,7 +3128,16 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
                    "pitch_cents with this speed leaves the time-scaling range (speed / 2^(cents / 1200) in [0.5, 2.0])");
       wsp[i] = sp_w == 1000 ? 0 : sp_w;
     }
-    if (wr || we || wsp[i] || wpt[i]) {  // a speed or a pitch with no format: 24000 / 16 bit
+    const int gdb = gain_cdb ? gain_cdb[i] : 0, lim = limit ? limit[i] : 0;
+    PTTS_REQUIRE(gdb >= -LEVEL_GAIN_CDB_MAX && gdb <= LEVEL_GAIN_CDB_MAX, "gain_cdb must be in [-2400, 2400]");
+    PTTS_REQUIRE(lim == 0 || lim == 1, "limit must be 0 or 1");
+    if (gdb != 0 || lim == 1) {  // the row is in the level stage (section 24)
+      PTTS_REQUIRE(level_, "a gain or limit needs a level-enabled engine (ptts_level_enable before the first step)");
+      float v = 1.f;
+      level_plan(gdb, 0, &v, nullptr);
+      memcpy(&wlv[i], &v, sizeof v);
+    }
+    if (wr || we || wsp[i] || wpt[i] || wlv[i]) {  // a speed, a pitch or a gain with no format: 24000 / 16 bit
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
@@ -3289,6 +3331,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     memcpy(h_pitch_, wpt.data(), sizeof(unsigned) * n);
     PTTS_HIP(hipMemcpyAsync(admit_pitch_, h_pitch_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
   }
+  if (level_) {
+    memcpy(h_level_, wlv.data(), sizeof(unsigned) * n);
+    PTTS_HIP(hipMemcpyAsync(admit_level_, h_level_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
+  }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
   std::vector<int> fp(n);
@@ -3363,6 +3409,11 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       r.pitch_step = pitch_step_;
       r.pitch_state = pitch_state_;
     }
+    if (level_) {
+      r.level_src = admit_level_;
+      r.level_gain = level_gain_;
+      r.level_state = level_state_;
+    }
     if (any_opt) {
       r.opt_src = admit_opt_;
       r.lat_src = admit_lat_;
@@ -3424,8 +3475,9 @@ void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_st
   PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
   PTTS_REQUIRE(n_bytes != nullptr, "null argument");
   PTTS_REQUIRE(!out || row_stride >= (size_t)wire_chunk_max(),
-               tempo_ ? "row_stride must be >= PTTS_WIRE_CHUNK_MAX_TEMPO on a tempo-enabled engine"
-                      : "row_stride must be >= PTTS_WIRE_CHUNK_MAX");
+               level_   ? "row_stride must be >= PTTS_WIRE_CHUNK_MAX_LEVEL on a level-enabled engine"
+               : tempo_ ? "row_stride must be >= PTTS_WIRE_CHUNK_MAX_TEMPO on a tempo-enabled engine"
+                        : "row_stride must be >= PTTS_WIRE_CHUNK_MAX");
   // the same frame, rows and event as fetch() of that call; no bookkeeping of its own
   const int q = calls_back ? prev_hb_ : out_hb_;
   const int rows = calls_back ? prev_rows_ : out_rows_;
@@ -3508,6 +3560,7 @@ void Engine::tempo_enable(bool on) {
   }
   if (on != tempo_) {  // the chunk slots change size: new pass blocks (the old ones stay until destruction)
     tempo_ = on;
+    PTTS_REQUIRE(!level_ || level_min_chunk() >= 16, "level: a non-last chunk below 16 samples (DESIGN.md section 24)");
     const size_t bytes = wire_block_bytes(max_slots_);
     for (int p = 0; p < WIRE_BLOCKS; ++p) {
       wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
@@ -3582,6 +3635,7 @@ void Engine::pitch_enable(bool on) {
     PTTS_HIP(hipMemcpy(pitch_tab_, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
   }
   pitch_ = on;
+  PTTS_REQUIRE(!level_ || level_min_chunk() >= 16, "level: a non-last chunk below 16 samples (DESIGN.md section 24)");
 }
 
 void Engine::pitch_host(const float* x, int n, unsigned step, float* y) {
@@ -3611,6 +3665,103 @@ void Engine::pitch_host(const float* x, int n, unsigned step, float* y) {
   (void)hipFree(dx), (void)hipFree(dt), (void)hipFree(dy);
 }
 
+// ------------------------------------------------------------------ level stage
+// The smallest first chunk of a level row at the wire rate, over every valid (speed, pitch, rate) of
+// this engine's stages (section 24): the stage delays the row by L samples, so a first chunk is L
+// samples shorter than its input's and every later non-last chunk is as long as its input's.
+long Engine::level_min_chunk() const {
+  long least = 1L << 40;
+  auto through = [&](long seen) {  // the first chunk of `seen` inputs of the level stage, at each wire rate
+    const long lv = std::max(seen - LEVEL_L, 0L);
+    for (int r = 0; r < WIRE_RATES; ++r) {
+      const ResamplePlan rp = resample_plan(PTTS_SAMPLE_RATE, WIRE_RATE_HZ[r]);
+      least = std::min(least, rp.identity() || lv == 0 ? lv : (lv * rp.up - 1 - rp.half) / rp.down + 1);
+    }
+  };
+  auto tempo_first = [](int sp_w) {  // hops run in the first frame: every k with floor(k Hs sp / 1000) + R <= FRAME
+    long k = 0;
+    while ((k * TEMPO_HS * sp_w) / 1000 + TEMPO_R <= FRAME) ++k;
+    return k * TEMPO_HS;
+  };
+  through(FRAME);
+  if (tempo_)
+    for (int sp = TEMPO_SP_MIN; sp <= TEMPO_SP_MAX; ++sp) through(tempo_first(sp));
+  if (pitch_)
+    for (int cents = -PITCH_CENTS_MAX; cents <= PITCH_CENTS_MAX; ++cents) {
+      int lo = TEMPO_SP_MIN, hi = TEMPO_SP_MAX, sp_w = 0;
+      unsigned step = 0;
+      while (lo <= TEMPO_SP_MAX && !pitch_plan(cents, lo, &sp_w, &step)) ++lo;
+      while (hi >= lo && !pitch_plan(cents, hi, &sp_w, &step)) --hi;
+      for (int sp : {lo, hi}) {  // sp_w grows with the speed and the first tempo chunk shrinks with sp_w
+        if (!pitch_plan(cents, sp, &sp_w, &step)) continue;
+        const long t1 = sp_w == 1000 ? FRAME : tempo_first(sp_w), H = pitch_support(step);
+        through(t1 > H ? (((t1 - H) << 20) + step - 1) / step : 0);
+      }
+    }
+  return least;
+}
+
+void Engine::level_enable(bool on, int ceiling_cdb) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the level stage is chosen on an idle engine before its first step");
+  PTTS_REQUIRE(!on || wire_, "the level stage needs a wire-enabled engine (ptts_wire_enable first)");
+  float ceiling = 1.f;
+  PTTS_REQUIRE(!on || level_plan(0, ceiling_cdb, nullptr, &ceiling), "ceiling_cdb must be in [-4000, 0]");
+  // section 24: the largest chunk (a last frame: the largest input chunk and the L flushed outputs)
+  // fits LEVEL_OUT_MAX, the chunk slot through the 48 kHz resampler (2 n + 20 outputs at most, as in
+  // section 19) and the FLAC stage's chunk; a FLAC chunk is at most three frames; a non-last chunk
+  // is a legal FLAC block (16 samples at least) at every rate
+  const long in_max = std::max<long>(FRAME, std::max(TEMPO_OUT_MAX, PITCH_OUT_MAX)), out_max = in_max + LEVEL_L;
+  const long wire_max = 2 * out_max + 21;
+  PTTS_REQUIRE(in_max <= LEVEL_IN_MAX && out_max <= LEVEL_OUT_MAX && wire_max <= FLAC_CHUNK_SAMPLES &&
+                   wire_max * 2 <= WIRE_CHUNK_MAX_LEVEL && flac_bound(wire_max) <= WIRE_CHUNK_MAX_LEVEL &&
+                   wire_max <= 3L * FLAC_BLOCK && LEVEL_HIST + LEVEL_IN_MAX + LEVEL_L <= LEVEL_WINDOW,
+               "level constants violate the chunk bounds of DESIGN.md section 24");
+  PTTS_REQUIRE(!on || level_min_chunk() >= 16, "level: a non-last chunk below 16 samples (DESIGN.md section 24)");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !level_gain_) {
+    const size_t B = max_slots_;
+    level_gain_ = (unsigned*)dalloc(B);
+    level_state_ = (int*)dalloc(B * LEVEL_STATE);
+    level_hist_ = dalloc(B * LEVEL_HIST);
+    level_out_ = dalloc(B * nfr_ * LEVEL_OUT_MAX);
+    level_cnt_ = (int*)dalloc(B * nfr_);
+    admit_level_ = (unsigned*)dalloc(B);
+    h_level_ = (unsigned*)halloc(sizeof(unsigned) * B);
+  }
+  if (on) level_ceiling_ = ceiling;
+  if (on != level_) {  // the chunk slots change size: new pass blocks (the old ones stay until destruction)
+    level_ = on;
+    const size_t bytes = wire_block_bytes(max_slots_);
+    for (int p = 0; p < WIRE_BLOCKS; ++p) {
+      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
+      h_wireb_[p] = (unsigned char*)halloc(bytes);
+      memset(h_wireb_[p], 0, wire_head_bytes());
+    }
+  }
+}
+
+void Engine::level_host(const float* x, int n, int gain_cdb, int ceiling_cdb, float* y) {
+  PTTS_REQUIRE(x && y && n >= 1, "empty input");
+  float v = 1.f, c = 1.f;
+  PTTS_REQUIRE(level_plan(gain_cdb, ceiling_cdb, &v, &c), "gain_cdb must be in [-2400, 2400], ceiling_cdb in [-4000, 0]");
+  sync();
+  void *dx = nullptr, *dy = nullptr;
+  try {
+    PTTS_HIP(hipMalloc(&dx, sizeof(float) * n));
+    PTTS_HIP(hipMalloc(&dy, sizeof(float) * n));
+    PTTS_HIP(hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    ptts::level((const float*)dx, n, v, c, (float*)dy, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(y, dy, sizeof(float) * n, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(dy);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(dy);
+}
+
 // ------------------------------------------------------------------ FLAC stage
 void Engine::flac_enable(bool on) {
   PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the FLAC stage is chosen on an idle engine before its first step");
@@ -3624,7 +3775,7 @@ long Engine::flac_bound(long n) { return n < 1 ? 0 : ptts::flac_bound(n); }
 
 void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes) {
   PTTS_REQUIRE(x && out && n_bytes, "null argument");
-  PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11221]");
+  PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11477]");
   const int ri = wire_rate_index(rate);
   PTTS_REQUIRE(ri >= 0, "sample_rate must be one of 8000, 16000, 24000, 44100, 48000");
   PTTS_REQUIRE(first >= 0 && first + n <= (1LL << 36), "first_sample outside the 36-bit sample number");

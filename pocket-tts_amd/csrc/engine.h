@@ -88,7 +88,8 @@ class Engine {
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
                   const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
                   const int* wire_enc = nullptr, const int* speed = nullptr, const float* const* prefix = nullptr,
-                  const int* n_prefix = nullptr, const int* keep_codec = nullptr, const int* pitch = nullptr);
+                  const int* n_prefix = nullptr, const int* keep_codec = nullptr, const int* pitch = nullptr,
+                  const int* gain_cdb = nullptr, const int* limit = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -137,7 +138,7 @@ class Engine {
   // time-scaled (kernels.h tempo_stage) ahead of the wire stage; chunks grow to wire_chunk_max()
   void tempo_enable(bool on);
   bool tempo() const { return tempo_; }
-  int wire_chunk_max() const { return tempo_ ? WIRE_CHUNK_MAX_TEMPO : WIRE_CHUNK_MAX; }
+  int wire_chunk_max() const { return level_ ? WIRE_CHUNK_MAX_LEVEL : tempo_ ? WIRE_CHUNK_MAX_TEMPO : WIRE_CHUNK_MAX; }
   // the seam alone: whole-signal f32 at 24 kHz -> tempo_len(n, sp) samples
   void tempo_host(const float* pcm, int n, int sp, float* out);
   // Pitch stage (ptts_pitch_enable): rows admitted with pitch_cents have their
@@ -147,6 +148,15 @@ class Engine {
   bool pitch() const { return pitch_; }
   // the seam alone: whole-signal f32 -> pitch_len(n, step) samples
   void pitch_host(const float* x, int n, unsigned step, float* y);
+  // Level stage (ptts_level_enable): rows admitted with a gain or `limit` have
+  // their (time-scaled, pitch-shifted) PCM scaled and peak-limited to the engine's ceiling (kernels.h
+  // level_stage) ahead of the wire stage; needs the wire stage only; chunk slots grow to
+  // WIRE_CHUNK_MAX_LEVEL
+  void level_enable(bool on, int ceiling_cdb);
+  bool level() const { return level_; }
+  long level_min_chunk() const;  // the smallest non-last chunk of a level row over the engine's stages (samples)
+  // the seam alone: whole-signal f32 -> n samples
+  void level_host(const float* x, int n, int gain_cdb, int ceiling_cdb, float* y);
   // FLAC stage (ptts_flac_enable): rows admitted with PTTS_WIRE_FLAC have their
   // 16-bit chunks encoded as FLAC frames (kernels.h flac_stage) behind the wire stage
   void flac_enable(bool on);
@@ -498,6 +508,16 @@ class Engine {
   int* pitch_cnt_ = nullptr;        // [max_slots][nfr]
   unsigned* admit_pitch_ = nullptr; // staged steps of an admission (device), h_pitch_ (pinned)
   unsigned* h_pitch_ = nullptr;
+  // ---- level stage (level_enable): per-row gain and state, back-owned like the tempo state
+  bool level_ = false;
+  float level_ceiling_ = 1.f;       // the engine's ceiling (level_plan)
+  unsigned* level_gain_ = nullptr;  // [max_slots] f32 bits of the row's gain (0: not in the stage)
+  int* level_state_ = nullptr;      // [max_slots][LEVEL_STATE]
+  float* level_hist_ = nullptr;     // [max_slots][LEVEL_HIST]
+  float* level_out_ = nullptr;      // [max_slots][nfr][LEVEL_OUT_MAX]: one pass's chunks (k_level -> k_wire)
+  int* level_cnt_ = nullptr;        // [max_slots][nfr]
+  unsigned* admit_level_ = nullptr; // staged gains of an admission (device), h_level_ (pinned)
+  unsigned* h_level_ = nullptr;
   // ---- FLAC stage (flac_enable)
   bool flac_ = false;
   int* flac_first_ = nullptr;    // [max_slots][nfr] a FLAC chunk's first sample index (k_wire -> k_flac)

@@ -652,6 +652,10 @@ struct ResetArgs {
   const unsigned* pitch_src = nullptr;
   unsigned* pitch_step = nullptr;
   int* pitch_state = nullptr;  // [max_slots][PITCH_STATE]
+  // level stage (null without it): the row's gain bits from the staged array, no input yet
+  const unsigned* level_src = nullptr;
+  unsigned* level_gain = nullptr;
+  int* level_state = nullptr;  // [max_slots][LEVEL_STATE]
   // per-row RESET_* bits and staged backbone inputs [n][32] (null: no row of the admission has any)
   const int* opt_src = nullptr;
   const float* lat_src = nullptr;
@@ -783,7 +787,7 @@ struct WireArgs {
   WirePlan plan[WIRE_RATES];
   unsigned char* out;       // [B][out_frames][WIRE_CHUNK_MAX]
   int* counts;              // [B][out_frames] bytes of each chunk (0: no wire format or no frame)
-  int chunk;                // bytes per (row, frame) slot of `out`: WIRE_CHUNK_MAX, or _TEMPO
+  int chunk;                // bytes per (row, frame) slot of `out`: WIRE_CHUNK_MAX, _TEMPO or _LEVEL
   const int* tempo_sp = nullptr;  // [B] (null: no tempo stage)
   const float* tin = nullptr;
   const int* tcnt = nullptr;
@@ -793,6 +797,11 @@ struct WireArgs {
   const unsigned* pitch_step = nullptr;  // [B]
   const float* pin = nullptr;
   const int* pcnt = nullptr;
+  // level stage (null without it): a row whose level_gain is not 0 reads its level chunk instead,
+  // `lin` [B][out_frames][LEVEL_OUT_MAX] and its sample counts `lcnt`
+  const unsigned* level_gain = nullptr;  // [B]
+  const float* lin = nullptr;
+  const int* lcnt = nullptr;
 };
 void wire_stage(const WireArgs& a, hipStream_t s);
 // n samples already at the wire rate -> n (G.711) or 2 n (16-bit) bytes; `out` holds the byte count
@@ -887,6 +896,56 @@ void pitch_stage(const PitchArgs& a, hipStream_t s);
 // whole signal: x [n] -> y [pitch_len(n, step)], the tap loop of the stage
 void pitch_resample(const float* x, int n, unsigned step, const float* tab, float* y, hipStream_t s);
 
+// Level stage: a per-row gain and a look-ahead peak limiter between the pitch
+// stage and the wire stage. With v the row's gain and C the engine's ceiling (f32, from level_plan):
+// u[n] = v x[n]; r[n] = |u[n]| > C ? C / |u[n]| : 1 (1 outside the signal); m[i] = min(r[i .. i + L]);
+// g[n] = (float)(sum_k w[k] m[n - k] / 4096), w[k] = 64 - |k - 63| for k = 0 .. L, summed in f64 in
+// ascending k; y[n] = clamp(g[n] u[n], -C, C). Streaming: after N inputs a row has emitted the
+// outputs below N - L, the frame flagged `last` emits the rest up to N, so a row's chunks
+// concatenate to the whole-signal rule (level()) bit for bit. Per-row state: the gain's f32 bits
+// (0: the row is not in the stage), the inputs received, the last LEVEL_HIST values of u.
+constexpr int LEVEL_L = 126;                 // look-ahead in samples (5.25 ms); the taps are L + 1
+constexpr int LEVEL_HIST = 2 * LEVEL_L;      // 252: the first pending output N - L reads r from N - 2 L on
+constexpr int LEVEL_GAIN_CDB_MAX = 2400, LEVEL_CEIL_CDB_MIN = -4000;  // hundredths of a dB
+// a frame's input is a PCM frame, a tempo chunk or a pitch chunk; its last frame emits L more
+constexpr int LEVEL_IN_MAX = PITCH_OUT_MAX;
+constexpr int LEVEL_OUT_MAX = LEVEL_IN_MAX + LEVEL_L + 2;  // 5728
+constexpr int LEVEL_WINDOW = LEVEL_HIST + LEVEL_IN_MAX + LEVEL_L;  // 5978: history | input | L samples past it
+constexpr int LEVEL_STATE = 1;  // ints per row: inputs received
+// bytes per (row, frame) slot on a level-enabled engine: 2 LEVEL_OUT_MAX + 21 samples at 48 kHz, 16
+// bit (a plain last frame: 2 (1920 + L) + 20 = 4,112 samples, above WIRE_CHUNK_MAX already)
+constexpr int WIRE_CHUNK_MAX_LEVEL = 23552;
+static_assert(LEVEL_IN_MAX >= TEMPO_OUT_MAX && LEVEL_IN_MAX >= 1920 && LEVEL_IN_MAX % 4 == 0 && LEVEL_OUT_MAX % 4 == 0 &&
+                  LEVEL_HIST % 4 == 0 && LEVEL_OUT_MAX >= LEVEL_IN_MAX + LEVEL_L,
+              "a level chunk holds the largest input chunk and the look-ahead");
+static_assert((2L * LEVEL_OUT_MAX + 21) * 2 <= WIRE_CHUNK_MAX_LEVEL && WIRE_CHUNK_MAX_LEVEL % 8 == 0 &&
+                  WIRE_CHUNK_MAX_LEVEL >= WIRE_CHUNK_MAX_TEMPO,
+              "a level chunk at 48 kHz, 16 bit, fits the level-enabled chunk slot");
+// host only: the f32 gain and ceiling of (gain_cdb, ceiling_cdb), (float)pow(10, cdb / 2000); false: out of range
+bool level_plan(int gain_cdb, int ceiling_cdb, float* gain, float* ceiling);
+struct LevelArgs {
+  int B, nfr, pcm_frames, out_frames;      // as WireArgs
+  const float* pcm;
+  const FrameFlags* flags[NFR_MAX];
+  const unsigned* gain;                    // [B] f32 bits of the row's gain (0: the row is not in the stage)
+  float ceiling;
+  // the row's input is its pitch chunk (pin, pcnt) if pitch_step is not 0, else its tempo chunk (tin,
+  // tcnt) if tempo_sp is not 0, else the PCM frame (null: the engine has no such stage)
+  const int* tempo_sp = nullptr;
+  const float* tin = nullptr;
+  const int* tcnt = nullptr;
+  const unsigned* pitch_step = nullptr;
+  const float* pin = nullptr;
+  const int* pcnt = nullptr;
+  int* state;                              // [B][LEVEL_STATE]
+  float* hist;                             // [B][LEVEL_HIST]
+  float* out;                              // [B][out_frames][LEVEL_OUT_MAX]
+  int* counts;                             // [B][out_frames] samples of each chunk
+};
+void level_stage(const LevelArgs& a, hipStream_t s);
+// whole signal: x [n] -> y [n], the window function of the stage
+void level(const float* x, long n, float gain, float ceiling, float* y, hipStream_t s);
+
 // FLAC stage: behind the wire stage, the 16-bit chunk of every WIRE_FLAC row
 // becomes ceil(n / FLAC_BLOCK) FLAC frames (mono, 16 bit, fixed predictors of order 0..4, partitioned
 // Rice codes, the exhaustive choice rule of section 21), written back to back over the chunk slot,
@@ -894,16 +953,19 @@ void pitch_resample(const float* x, int n, unsigned step, const float* tab, floa
 // whole chunk in LDS before its first store, so encoding in place is safe. Integer arithmetic only.
 constexpr int FLAC_BLOCK = 4608;                 // the subset limit at <= 48 kHz
 constexpr int FLAC_FRAME_OVERHEAD = 17;          // 14 header, 1 subframe header, 2 CRC-16
-// the slot bound above; the longest chunk is 11,058 of a tempo row, 11,196 of a pitch row (section 23)
-constexpr int FLAC_CHUNK_SAMPLES = 2 * PITCH_OUT_MAX + 21;
+// the slot bound above; the longest chunk is 11,058 of a tempo row, 11,196 of a pitch row (section 23),
+// 11,448 of a level row behind the pitch stage (section 24)
+constexpr int FLAC_CHUNK_SAMPLES = 2 * LEVEL_OUT_MAX + 21;
 constexpr int flac_rate_code(int ri) { return ri == 0 ? 4 : ri == 1 ? 5 : ri == 2 ? 7 : ri == 3 ? 9 : 10; }  // by WIRE_RATE_HZ
 constexpr long flac_bound(long n) {              // bytes of the frames of an n-sample chunk, at most
   return 2 * n + FLAC_FRAME_OVERHEAD * ((n + FLAC_BLOCK - 1) / FLAC_BLOCK);
 }
 static_assert(flac_bound(3860) <= WIRE_CHUNK_MAX, "a FLAC chunk fits the chunk slot");
-static_assert(flac_bound(FLAC_CHUNK_SAMPLES) <= WIRE_CHUNK_MAX_TEMPO && FLAC_CHUNK_SAMPLES <= 3 * FLAC_BLOCK &&
-                  2 * FLAC_CHUNK_SAMPLES <= WIRE_CHUNK_MAX_TEMPO,
+static_assert(flac_bound(2 * PITCH_OUT_MAX + 21) <= WIRE_CHUNK_MAX_TEMPO && FLAC_CHUNK_SAMPLES <= 3 * FLAC_BLOCK &&
+                  2 * (2 * PITCH_OUT_MAX + 21) <= WIRE_CHUNK_MAX_TEMPO,
               "a FLAC chunk of a tempo row is at most three frames and fits the chunk slot");
+static_assert(flac_bound(FLAC_CHUNK_SAMPLES) <= WIRE_CHUNK_MAX_LEVEL && 2 * FLAC_CHUNK_SAMPLES <= WIRE_CHUNK_MAX_LEVEL,
+              "a FLAC chunk of a level row is at most three frames and fits the chunk slot");
 static_assert(TEMPO_HS * WIRE_RATE_HZ[0] / 24000 >= 16, "the shortest non-last chunk (one tempo hop at 8 kHz) is a legal block");
 struct FlacArgs {
   int B, out_frames;

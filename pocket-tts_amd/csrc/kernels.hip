@@ -3322,6 +3322,10 @@ __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
       a.pitch_step[slot] = a.pitch_src[i];
       for (int q = 0; q < PITCH_STATE; ++q) a.pitch_state[slot * PITCH_STATE + q] = 0;
     }
+    if (a.level_gain) {
+      a.level_gain[slot] = a.level_src[i];
+      for (int q = 0; q < LEVEL_STATE; ++q) a.level_state[slot * LEVEL_STATE + q] = 0;
+    }
   }
 }
 
@@ -3904,6 +3908,7 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
     for (int i = t; i < p.L; i += WIRE_THREADS) s_taps[i] = a.taps[p.tap_off + i];
   const int sp = a.tempo_sp ? a.tempo_sp[b] : 0;  // uniform: the row's input is its tempo chunk
   const unsigned pt = a.pitch_step ? a.pitch_step[b] : 0u;  // uniform: or its pitch chunk (behind the tempo stage)
+  const unsigned lv = a.level_gain ? a.level_gain[b] : 0u;  // uniform: or its level chunk (behind both)
   const long cap = a.chunk / (enc == WIRE_S16 ? 2 : 1);  // samples a chunk slot holds
   long n = a.frames[b];  // input samples of the row received so far
   if (t < WIRE_TAIL) s_x[t] = n > 0 ? a.tail[(long)b * WIRE_TAIL + t] : 0.f;
@@ -3915,10 +3920,12 @@ __global__ __launch_bounds__(WIRE_THREADS) void k_wire(WireArgs a) {
       continue;
     }
     any = true;
-    const float* in = pt   ? a.pin + ((long)b * a.out_frames + f) * PITCH_OUT_MAX
+    const float* in = lv   ? a.lin + ((long)b * a.out_frames + f) * LEVEL_OUT_MAX
+                      : pt ? a.pin + ((long)b * a.out_frames + f) * PITCH_OUT_MAX
                       : sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
                            : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
-    const int n_in = pt   ? min(max(a.pcnt[(long)b * a.out_frames + f], 0), PITCH_OUT_MAX)
+    const int n_in = lv   ? min(max(a.lcnt[(long)b * a.out_frames + f], 0), LEVEL_OUT_MAX)
+                     : pt ? min(max(a.pcnt[(long)b * a.out_frames + f], 0), PITCH_OUT_MAX)
                      : sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX)
                           : 1920;
     unsigned char* dst = a.out + ((long)b * a.out_frames + f) * a.chunk;
@@ -3984,7 +3991,8 @@ void wire_stage(const WireArgs& a, hipStream_t s) {
   if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
     throw std::runtime_error("wire_stage: bad pass shape");
   if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || (a.tempo_sp && (!a.tin || !a.tcnt || a.chunk < WIRE_CHUNK_MAX_TEMPO)) ||
-      (a.pitch_step && (!a.tempo_sp || !a.pin || !a.pcnt)))
+      (a.pitch_step && (!a.tempo_sp || !a.pin || !a.pcnt)) ||
+      (a.level_gain && (!a.lin || !a.lcnt || a.chunk < WIRE_CHUNK_MAX_LEVEL)))
     throw std::runtime_error("wire_stage: bad chunk slot");
   for (int r = 0; r < WIRE_RATES; ++r)
     if (a.plan[r].L > WIRE_TAPS_MAX || a.plan[r].L < 1 || 2 * a.plan[r].half > WIRE_TAIL * a.plan[r].up)
@@ -4295,7 +4303,7 @@ __global__ __launch_bounds__(FLAC_THREADS) void k_flac(FlacArgs a) {
 void flac_stage(const FlacArgs& a, hipStream_t s) {
   if (a.B < 1 || a.out_frames < 1 || a.out_frames > NFR_MAX || !a.fmt || !a.first || !a.out || !a.counts)
     throw std::runtime_error("flac_stage: bad pass shape");
-  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || a.chunk > WIRE_CHUNK_MAX_TEMPO)
+  if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || a.chunk > WIRE_CHUNK_MAX_LEVEL)
     throw std::runtime_error("flac_stage: bad chunk slot");
   hipLaunchKernelGGL(k_flac, dim3(a.B, a.out_frames), dim3(FLAC_THREADS), 0, s, a);
 }
@@ -4706,6 +4714,159 @@ void pitch_resample(const float* x, int n, unsigned step, const float* tab, floa
   if (L < 1) return;
   hipLaunchKernelGGL(k_pitch_whole, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, x, (long)n, step,
                      reinterpret_cast<const float2*>(tab), L, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Level stage (see kernels.h; the rule is DESIGN.md section 24). One window function serves the
+// streaming stage and the whole-signal seam, so they are equal by construction. The window holds u
+// of W consecutive samples (0 outside the signal, where the rule says r = 1, which is what u = 0
+// gives); outputs q0 <= q < q0 + count of it replace u[q] by y in place. It needs q0 >= LEVEL_L and
+// q0 + count + LEVEL_L <= W: output q reads r[q - L .. q + L].
+//   r: one lane per sample. m: the minimum over 127 by doubling in place (windows of 2, 4, .. 64,
+// then two windows of 64 that overlap by one), each step read into registers, barrier, written.
+//   g: 127 f64 multiply-adds per output in ascending k; every product (24 bits times an integer of
+// at most 64) is exact, so contraction changes no bit.
+constexpr int LEVEL_THREADS = 1024;
+constexpr int LEVEL_PER_LANE = (LEVEL_WINDOW + LEVEL_THREADS - 1) / LEVEL_THREADS;  // 6
+__device__ __forceinline__ void level_window(float* s_u, float* s_r, int W, int q0, int count, float C, int t) {
+  for (int p = t; p < W; p += LEVEL_THREADS) {
+    const float a = fabsf(s_u[p]);
+    s_r[p] = a > C ? __fdiv_rn(C, a) : 1.0f;
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int step = 0; step < 7; ++step) {  // uniform
+    const int sh = step < 6 ? 1 << step : 63;
+    float v[LEVEL_PER_LANE];
+#pragma unroll
+    for (int i = 0; i < LEVEL_PER_LANE; ++i) {
+      const int p = t + i * LEVEL_THREADS;
+      v[i] = p < W ? fminf(s_r[p], p + sh < W ? s_r[p + sh] : 1.0f) : 1.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < LEVEL_PER_LANE; ++i) {
+      const int p = t + i * LEVEL_THREADS;
+      if (p < W) s_r[p] = v[i];
+    }
+    __syncthreads();
+  }
+  // s_r[p] = min(r[p .. p + L]) (r = 1 past the window)
+  for (int i = t; i < count; i += LEVEL_THREADS) {
+    const int q = q0 + i;
+    double acc = 0.0;
+#pragma unroll 9
+    for (int k = 0; k <= LEVEL_L; ++k) acc += (double)(64 - abs(k - 63)) * (double)s_r[q - k];
+    const float g = (float)(acc * (1.0 / 4096.0));
+    const float y = g * s_u[q];
+    s_u[q] = fminf(fmaxf(y, -C), C);
+  }
+  __syncthreads();
+}
+
+// One workgroup per row walks the pass's frames in order, so the row's history is read and written
+// by this workgroup alone. LDS: u of the last LEVEL_HIST samples | the frame's input | L zeros, and
+// r / m of the same window. A frame that is not the last emits the outputs below N - L.
+__global__ __launch_bounds__(LEVEL_THREADS) void k_level(LevelArgs a) {
+  __shared__ __attribute__((aligned(16))) float s_u[LEVEL_WINDOW + 2];
+  __shared__ __attribute__((aligned(16))) float s_r[LEVEL_WINDOW + 2];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const unsigned gb = a.gain[b];
+  int* cnt = a.counts + (long)b * a.out_frames;
+  if (gb == 0u) {  // uniform: a row that is not in the stage
+    if (t < a.out_frames) cnt[t] = 0;
+    return;
+  }
+  const float v = __uint_as_float(gb), C = a.ceiling;
+  const int sp = a.tempo_sp ? a.tempo_sp[b] : 0;                // uniform: the row's input, as k_wire chooses it
+  const unsigned pt = a.pitch_step ? a.pitch_step[b] : 0u;
+  long n = a.state[(long)b * LEVEL_STATE];  // inputs received
+  if (t < LEVEL_HIST) s_u[t] = n > 0 ? a.hist[(long)b * LEVEL_HIST + t] : 0.f;
+  bool any = false;
+  for (int f = 0; f < a.out_frames; ++f) {
+    const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
+    if (!fl.valid) {  // uniform
+      if (t == 0) cnt[f] = 0;
+      continue;
+    }
+    any = true;
+    const float* in = pt   ? a.pin + ((long)b * a.out_frames + f) * PITCH_OUT_MAX
+                      : sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
+                           : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
+    const int n_in = pt   ? min(max(a.pcnt[(long)b * a.out_frames + f], 0), PITCH_OUT_MAX)
+                     : sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX)
+                          : 1920;
+    __syncthreads();  // the history is in place
+    for (int i = t; 4 * i < n_in; i += LEVEL_THREADS) {  // u = v x (the slots are padded to four)
+      const float4 x4 = reinterpret_cast<const float4*>(in)[i];
+      reinterpret_cast<float4*>(s_u + LEVEL_HIST)[i] = make_float4(v * x4.x, v * x4.y, v * x4.z, v * x4.w);
+    }
+    __syncthreads();  // (a count that is no multiple of four: the zeros below overwrite the excess)
+    if (t < LEVEL_L + 2) s_u[LEVEL_HIST + n_in + t] = 0.f;
+    __syncthreads();
+    const float hv = t < LEVEL_HIST ? s_u[n_in + t] : 0.f;  // the last LEVEL_HIST values of history | input
+    const long N1 = n + n_in;
+    const long e0 = max(n - LEVEL_L, 0L), e1 = fl.last ? N1 : max(N1 - LEVEL_L, 0L);
+    const int count = (int)min(max(e1 - e0, 0L), (long)LEVEL_OUT_MAX);  // (never more: n_in + L)
+    const int q0 = (int)(e0 - (n - LEVEL_HIST));  // L, or 2 L - n while the row has fewer than L inputs
+    level_window(s_u, s_r, LEVEL_HIST + n_in + LEVEL_L, q0, count, C, t);
+    float* out = a.out + ((long)b * a.out_frames + f) * LEVEL_OUT_MAX;
+    for (int i = t; 4 * i < count; i += LEVEL_THREADS) {  // zeros pad the last group (inside the slot)
+      float y[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[j] = 4 * i + j < count ? s_u[q0 + 4 * i + j] : 0.f;
+      reinterpret_cast<float4*>(out)[i] = make_float4(y[0], y[1], y[2], y[3]);
+    }
+    if (t == 0) cnt[f] = count;
+    __syncthreads();  // every lane has read the window
+    if (t < LEVEL_HIST) s_u[t] = hv;
+    n = N1;
+  }
+  if (!any) return;  // uniform
+  if (t < LEVEL_HIST) a.hist[(long)b * LEVEL_HIST + t] = s_u[t];  // each lane wrote its own entry
+  if (t == 0) a.state[(long)b * LEVEL_STATE] = (int)n;
+}
+
+void level_stage(const LevelArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
+    throw std::runtime_error("level_stage: bad pass shape");
+  if (!a.pcm || !a.gain || !a.state || !a.hist || !a.out || !a.counts || (a.tempo_sp && (!a.tin || !a.tcnt)) ||
+      (a.pitch_step && (!a.pin || !a.pcnt)) || !(a.ceiling > 0.f && a.ceiling <= 1.f))
+    throw std::runtime_error("level_stage: bad argument");
+  hipLaunchKernelGGL(k_level, dim3(a.B), dim3(LEVEL_THREADS), 0, s, a);
+}
+
+// the seam: a workgroup per LEVEL_TILE outputs, its window the 2 L samples before and L after them
+constexpr int LEVEL_TILE = LEVEL_WINDOW - LEVEL_HIST - LEVEL_L;
+__global__ __launch_bounds__(LEVEL_THREADS) void k_level_whole(const float* __restrict__ x, long n, float v, float C,
+                                                               float* __restrict__ y) {
+  __shared__ __attribute__((aligned(16))) float s_u[LEVEL_WINDOW + 2];
+  __shared__ __attribute__((aligned(16))) float s_r[LEVEL_WINDOW + 2];
+  const int t = threadIdx.x;
+  const long n0 = (long)blockIdx.x * LEVEL_TILE;
+  const int count = (int)min((long)LEVEL_TILE, n - n0);
+  const int W = LEVEL_HIST + count + LEVEL_L;
+  for (int p = t; p < W; p += LEVEL_THREADS) {
+    const long j = n0 - LEVEL_HIST + p;
+    s_u[p] = j >= 0 && j < n ? v * x[j] : 0.f;
+  }
+  __syncthreads();
+  level_window(s_u, s_r, W, LEVEL_HIST, count, C, t);
+  for (int i = t; i < count; i += LEVEL_THREADS) y[n0 + i] = s_u[LEVEL_HIST + i];
+}
+
+bool level_plan(int gain_cdb, int ceiling_cdb, float* gain, float* ceiling) {
+  if (gain_cdb < -LEVEL_GAIN_CDB_MAX || gain_cdb > LEVEL_GAIN_CDB_MAX || ceiling_cdb < LEVEL_CEIL_CDB_MIN || ceiling_cdb > 0)
+    return false;
+  if (gain) *gain = (float)std::pow(10.0, (double)gain_cdb / 2000.0);
+  if (ceiling) *ceiling = (float)std::pow(10.0, (double)ceiling_cdb / 2000.0);
+  return true;
+}
+
+void level(const float* x, long n, float gain, float ceiling, float* y, hipStream_t s) {
+  if (n < 1 || !(gain > 0.f) || !(ceiling > 0.f && ceiling <= 1.f)) throw std::runtime_error("level: bad arguments");
+  hipLaunchKernelGGL(k_level_whole, dim3((unsigned)((n + LEVEL_TILE - 1) / LEVEL_TILE)), dim3(LEVEL_THREADS), 0, s, x, n,
+                     gain, ceiling, y);
 }
 
 // whole-signal encode of n samples (already at the wire rate), four per lane

@@ -23,6 +23,7 @@ SAMPLES_F32, SAMPLES_S16 = 0, 1  # sample_format of ptts_voice_job_start (PTTS_S
 WIRE_NONE, WIRE_S16, WIRE_ULAW, WIRE_ALAW, WIRE_FLAC = 0, 1, 2, 3, 4  # PTTS_WIRE_*
 WIRE_CHUNK_MAX = 8192  # PTTS_WIRE_CHUNK_MAX
 WIRE_CHUNK_MAX_TEMPO = 22528  # PTTS_WIRE_CHUNK_MAX_TEMPO
+WIRE_CHUNK_MAX_LEVEL = 23552  # PTTS_WIRE_CHUNK_MAX_LEVEL
 WIRE_RATES = (8000, 16000, 24000, 44100, 48000)
 ABI_VERSION = 6  # PTTS_ABI_VERSION of include/pocket_tts.h that the structs below mirror
 
@@ -88,6 +89,16 @@ class SlotOpts3(C.Structure):
     ]
 
 
+class SlotOpts4(C.Structure):
+    """ptts_slot_opts with gain_cdb and limit (56 bytes): the struct of a row in the level stage. The
+    four bytes at offset 44 are the explicit pad `reserved`."""
+    _fields_ = SlotOpts3._fields_ + [
+        ("reserved", C.c_int),
+        ("gain_cdb", C.c_int),
+        ("limit", C.c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol include/pocket_tts.h (the boundary) and
 # include/pocket_tts_probe.h (measurement / test hooks) declare
 SIGNATURES = [
@@ -150,6 +161,9 @@ SIGNATURES = [
     ("ptts_pitch_len", C.c_long, [C.c_long, C.c_uint32]),
     ("ptts_pitch_table", C.c_int, [F32P, F32P, C.c_int]),
     ("ptts_pitch_resample", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_uint32, F32P]),
+    ("ptts_level_enable", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("ptts_level_plan", C.c_int, [C.c_int, C.c_int, F32P, F32P]),
+    ("ptts_level", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, F32P]),
     ("ptts_flac_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_flac_bound", C.c_long, [C.c_long]),
     ("ptts_flac_encode", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,

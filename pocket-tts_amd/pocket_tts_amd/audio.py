@@ -583,3 +583,97 @@ def pitch_resample(x: np.ndarray, step: int, chunks=None):
         out.append(_pitch_outputs(buf, base, n, e, e1, step))
         e, hist = e1, buf[-keep:]
     return out
+
+
+# ---- level: the host restatement of DESIGN.md section 24 (the GPU level stage's rule)
+LEVEL_L = 126  # samples of look-ahead (5.25 ms at 24 kHz)
+LEVEL_GAIN_DB_MAX = 24.0
+LEVEL_TAPS = (64 - np.abs(np.arange(LEVEL_L + 1) - 63)).astype(np.float64)  # a triangle: two 64-boxes convolved; sum 4096
+
+
+def level_cdb(db, lo: float = -LEVEL_GAIN_DB_MAX, hi: float = LEVEL_GAIN_DB_MAX, name: str = "volume_db") -> int:
+    """A level in dB as the integer hundredths of a dB the engine takes; 0 for None. ValueError
+    outside [lo, hi]."""
+    if db is None:
+        return 0
+    f = float(db)
+    c = round(100.0 * f) if math.isfinite(f) else None
+    if c is None or not round(100 * lo) <= c <= round(100 * hi):
+        raise ValueError(f"{name} must be in [{lo:g}, {hi:g}] dB, got {db!r}")
+    return c
+
+
+def level_plan(gain_cdb: int, ceiling_cdb: int = -100) -> tuple[np.float32, np.float32]:
+    """(v, C): the f32 gain and ceiling of (gain_cdb, ceiling_cdb), (float)pow(10, cdb / 2000), from the
+    library's ptts_level_plan (the single source of the two floats). ValueError outside [-2400, 2400]
+    and [-4000, 0]."""
+    import ctypes as C
+
+    from ._lib import lib
+    v, c = C.c_float(0), C.c_float(0)
+    if lib().ptts_level_plan(int(gain_cdb), int(ceiling_cdb), C.byref(v), C.byref(c)) != 0:
+        raise ValueError(f"gain of {gain_cdb} cdB with a ceiling of {ceiling_cdb} cdB is outside the valid range "
+                         "(gain in [-2400, 2400], ceiling in [-4000, 0])")
+    return np.float32(v.value), np.float32(c.value)
+
+
+def level_emitted(n: int) -> int:
+    """Outputs a stream has emitted after n inputs (not its last frame): max(n - L, 0)."""
+    return max(int(n) - LEVEL_L, 0)
+
+
+def level_chunk_samples(seen_before: int, seen_after: int, last: bool) -> int:
+    """Samples the level stage emits in the frame that takes a row from seen_before to seen_after
+    inputs. The last frame emits the rest up to seen_after."""
+    return (int(seen_after) if last else level_emitted(seen_after)) - level_emitted(seen_before)
+
+
+def _level_outputs(u: np.ndarray, base: int, n0: int, n1: int, c: np.float32):
+    """Outputs n0 <= n < n1 of the signal whose u[j] is u[j - base] for base <= j < base + len(u) and
+    whose r is 1 everywhere else: (y, g, r) of those outputs."""
+    L = LEVEL_L
+    lo, hi = n0 - 2 * L, n1 + L  # r over [lo, hi), m over [lo, n1), g over [n0, n1)
+    r = np.ones(hi - lo, np.float32)
+    j0, j1 = max(lo, base), min(hi, base + u.size)
+    if j1 > j0:
+        a = np.abs(u[j0 - base:j1 - base])
+        over = a > c
+        r[j0 - lo:j1 - lo] = np.where(over, c / np.where(over, a, np.float32(1.0)), np.float32(1.0))
+    m = np.lib.stride_tricks.sliding_window_view(r, L + 1).min(axis=1)  # m[i - lo], lo <= i < n1
+    acc = np.zeros(n1 - n0, np.float64)
+    for k in range(L + 1):  # ascending k, as the kernel sums
+        acc += LEVEL_TAPS[k] * m[n0 - k - lo:n1 - k - lo].astype(np.float64)
+    g = (acc / 4096.0).astype(np.float32)
+    un = np.zeros(n1 - n0, np.float32)
+    a0, a1 = max(n0, base), min(n1, base + u.size)
+    if a1 > a0:
+        un[a0 - n0:a1 - n0] = u[a0 - base:a1 - base]
+    y = np.minimum(np.maximum(g * un, -c), c)
+    return y, g, r[2 * L:2 * L + (n1 - n0)]
+
+
+def level_limit(x: np.ndarray, gain_cdb: int, ceiling_cdb: int = -100, chunks=None, detail: bool = False):
+    """The level stage's rule over a whole signal x (f32 at 24 kHz): u = v x, r = |u| > C ? C / |u| : 1
+    (1 outside the signal), m[i] = min(r[i .. i + L]), g[n] = f32(sum_k w[k] m[n - k] / 4096) in f64 in
+    ascending k, y = clamp(g u, -C, C); len(x) outputs. detail: (y, u, r, g) instead of y. Every product
+    of the sum is exact and the sum runs in the stated order, so the GPU stage agrees bit for bit.
+    chunks: the sizes in which the input arrives (they sum to len(x); the last one is the row's last
+    frame): run as the stream does, keeping only the last 2 L values of u between chunks, and return
+    the list of output chunks."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    v, c = level_plan(gain_cdb, ceiling_cdb)
+    if chunks is None:
+        u = v * x
+        y, g, r = _level_outputs(u, 0, 0, x.size, c)
+        return (y, u, r, g) if detail else y
+    sizes = [int(s) for s in chunks]
+    if sum(sizes) != x.size or any(s < 0 for s in sizes):
+        raise ValueError("chunks must be non-negative and sum to len(x)")
+    hist, n, out = np.zeros(0, np.float32), 0, []
+    for f, s in enumerate(sizes):
+        buf = np.concatenate([hist, v * x[n:n + s]])
+        base, e0, n = n - hist.size, level_emitted(n), n + s
+        e1 = n if f == len(sizes) - 1 else level_emitted(n)
+        out.append(_level_outputs(buf, base, e0, e1, c)[0])
+        hist = buf[-2 * LEVEL_L:] if buf.size else buf
+    return out

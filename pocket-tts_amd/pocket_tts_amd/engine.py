@@ -8,9 +8,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
-                   WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SlotOpts, SlotOpts2, SlotOpts3, check, fptr, lib, u8ptr)
-from .audio import pitch_cents, speed_permille
+                   WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_LEVEL, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
+                   SlotOpts, SlotOpts2, SlotOpts3, SlotOpts4, check, fptr, lib, u8ptr)
+from .audio import level_cdb, pitch_cents, speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
 WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW, "flac": WIRE_FLAC}
@@ -53,6 +53,12 @@ class GenerationParams:
     # unchanged. A resampling shift (formants move too) at the duration `speed` asks for (DESIGN.md
     # section 23). A pitch with no wire format implies 24000 / 16-bit; fetch()'s f32 PCM never depends on it.
     pitch: float | None = None
+    # volume of the row's wire bytes in dB (level-enabled engines), -24 .. 24, and `limit`: run the
+    # row through the look-ahead peak limiter (the engine's ceiling) even with no gain. A row with a
+    # gain always runs through it. None / 0 and False: unchanged. Either with
+    # no wire format implies 24000 / 16-bit; fetch()'s f32 PCM never depends on them.
+    volume_db: float | None = None
+    limit: bool = False
     # latent prefix and codec continuity (ptts_slot_opts.prefix_latents / .keep_codec; DESIGN.md
     # section 20): the row starts as if it had been teacher-forced through these [n, 32] FlowLM
     # latents (values fetch() returned), and with keep_codec on the codec state its slot ended on.
@@ -82,6 +88,11 @@ class GenerationParams:
         """pitch_cents of ptts_slot_opts: round(100 * semitones), passed on as it is (the admission
         refuses a value out of range); 0: none."""
         return 0 if self.pitch is None else round(100.0 * float(self.pitch))
+
+    def level(self) -> tuple[int, int]:
+        """(gain_cdb, limit) of ptts_slot_opts: round(100 * dB), passed on as it is (the admission
+        refuses a value out of range), and 0 / 1; (0, 0): the row is not in the level stage."""
+        return (0 if self.volume_db is None else round(100.0 * float(self.volume_db)), int(self.limit or 0))
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
@@ -149,7 +160,8 @@ class Engine:
                  defer_weights: bool = False, pipeline: bool = False, weight_quant: int = 0, fp8_gemm: bool = False,
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
                  back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
-                 tempo: bool = False, flac: bool = False, pitch: bool = False):
+                 tempo: bool = False, flac: bool = False, pitch: bool = False, level: bool = False,
+                 level_ceiling_db: float = -1.0):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -171,6 +183,9 @@ class Engine:
         their wire bytes time-scaled on the GPU.
         pitch=True (ptts_pitch_enable; needs tempo): rows admitted with GenerationParams.pitch have
         their wire bytes shifted in pitch on the GPU.
+        level=True (ptts_level_enable; needs wire): rows admitted with GenerationParams.volume_db or
+        .limit have their wire bytes scaled and peak-limited to level_ceiling_db (dBFS, -40 .. 0) on
+        the GPU.
         flac=True (ptts_flac_enable; needs wire): rows admitted with encoding "flac" get FLAC frames
         of their 16-bit chunks, encoded on the GPU."""
         if back_mfma is None:
@@ -225,7 +240,16 @@ class Engine:
             except Exception:
                 self.close()
                 raise
-        self.wire_chunk_max = WIRE_CHUNK_MAX_TEMPO if tempo else WIRE_CHUNK_MAX
+        self.level_enabled = bool(level)
+        self.level_ceiling_cdb = 0
+        if level:
+            try:
+                self.level_ceiling_cdb = level_cdb(level_ceiling_db, -40.0, 0.0, "level_ceiling_db")
+                check(lib().ptts_level_enable(self.handle, 1, self.level_ceiling_cdb))
+            except Exception:
+                self.close()
+                raise
+        self.wire_chunk_max = WIRE_CHUNK_MAX_LEVEL if level else WIRE_CHUNK_MAX_TEMPO if tempo else WIRE_CHUNK_MAX
         self._wire_buf = self._wire_n = None
 
     def test_gemm(self, layout: int, x: np.ndarray, w: np.ndarray, splits: int = 1, tail_slices: int = 0) -> np.ndarray:
@@ -441,7 +465,8 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
-        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec or params.cents():
+        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec or params.cents() \
+                or params.level() != (0, 0):
             return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
@@ -460,6 +485,15 @@ class Engine:
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
         pre = [p.prefix() for p in params_list]  # (kept alive until the call returns)
+        if any(p.level() != (0, 0) for p in params_list):  # a gain or limit: the 56-byte struct
+            opts = (SlotOpts4 * n)(*[SlotOpts4(C.sizeof(SlotOpts4), int(lsd[i]), *p.opts(),
+                                               pre[i].ctypes.data if pre[i] is not None else None,
+                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents(),
+                                               0, *p.level())
+                                     for i, p in enumerate(params_list)])
+            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
+            return
         if any(p.cents() for p in params_list):  # a pitch: the 48-byte struct
             opts = (SlotOpts3 * n)(*[SlotOpts3(C.sizeof(SlotOpts3), int(lsd[i]), *p.opts(),
                                                pre[i].ctypes.data if pre[i] is not None else None,
@@ -604,6 +638,19 @@ class Engine:
         y = np.zeros(max(n, 1), np.float32)
         check(lib().ptts_pitch_resample(self.handle, fptr(x), x.size, int(step), fptr(y)))
         return y[:n]
+
+    def level(self, x: np.ndarray, gain_db: float, ceiling_db: float | None = None) -> np.ndarray:
+        """Whole-signal f32 scaled by gain_db and peak-limited to ceiling_db (None: the engine's
+        level_ceiling_db, -1.0 where the stage is off) on the GPU (ptts_level): the window function of
+        the streaming level stage (audio.level_limit is its host restatement)."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        if ceiling_db is None:
+            ceil_cdb = self.level_ceiling_cdb if self.level_enabled else -100
+        else:
+            ceil_cdb = level_cdb(ceiling_db, -40.0, 0.0, "ceiling_db")
+        y = np.zeros(max(x.size, 1), np.float32)
+        check(lib().ptts_level(self.handle, fptr(x), x.size, level_cdb(gain_db), ceil_cdb, fptr(y)))
+        return y[:x.size]
 
     def fetch_ready(self, calls_back: int = 0) -> bool:
         """fetch(calls_back=...) would not block (ptts_fetch_ready)."""

@@ -82,6 +82,20 @@ gets 400.
     curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
          -d '{"input": "Hello there.", "voice": "alba", "pitch": -3}' -o deeper.wav
 
+Per-request volume (`--volume`, on with `--wire`): the three audio routes also take `volume_db`, a
+gain in dB within [-24, 24] (rounded to hundredths), and `limit`, a bool. A row with a gain, or with
+`limit` true, runs through the level stage on the GPU behind speed and pitch:
+the gain, then a look-ahead peak limiter (5.25 ms) that keeps every sample inside the server's
+ceiling (`--limiter-ceiling-db`, -1 dBFS by default), so a positive gain never hard-clips and G.711
+and FLAC streams come out at the asked level. Where no peak within 5.25 ms exceeds the ceiling the
+samples are the scaled input exactly. Rate, encoding and FLAC run on the result unchanged. Unset, or
+0 with `limit` unset, changes nothing; a long-form request's every text segment carries the fields
+and pauses stay host-made silence. A value outside the range, or either field on a server without
+the stage (`--no-volume`, `--no-wire`), gets 400.
+
+    curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
+         -d '{"input": "Hello there.", "voice": "alba", "volume_db": 6, "response_format": "ulaw"}' -o loud.ulaw
+
 Long-form requests (`long_form` in the three audio routes' bodies; `--long-form` sets the default,
 off): the text is cut as the reference's routes cut it (generate_stream_long, handlers.rs:165,260:
 pause markers and natural pauses become silence, each piece is cut into sentence chunks of at most
@@ -125,7 +139,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, flac_stream_header, pcm_i16_le_bytes, pitch_cents, pitch_plan, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
+from .audio import (ENCODINGS, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, pitch_cents, pitch_plan, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
 from .engine import GenerationParams, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
@@ -343,6 +357,7 @@ class Request(_Consumer):
     wire: tuple[int, str] | None = None
     speed: int = 0         # permille of a request with a speed (its wire bytes are time-scaled); 0: none
     pitch: int = 0         # cents of a request with a pitch (its wire bytes are shifted); 0: none
+    level: tuple = (0, 0)  # (gain in hundredths of a dB, limit) of a request in the level stage; (0, 0): none
     sched: object = None   # the scheduler that holds the request (cancel())
     group: object = None   # the RequestGroup this request is a text segment of
     ended: bool = False    # the end marker was put
@@ -358,7 +373,8 @@ class Request(_Consumer):
         rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
         self.speed = self.params.opts()[2] if hasattr(self.params, "opts") else 0
         self.pitch = self.params.cents() if hasattr(self.params, "cents") else 0
-        if rate or enc or self.speed or self.pitch:  # a speed or a pitch alone: 24000 / pcm_s16le
+        self.level = tuple(self.params.level()) if hasattr(self.params, "level") else (0, 0)
+        if rate or enc or self.speed or self.pitch or self.level != (0, 0):  # a speed, pitch or gain alone: 24000 / pcm_s16le
             self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
 
     def put(self, item):
@@ -718,7 +734,8 @@ class BatchScheduler:
                 # delay): it waits for its regular first chunk; a 24 kHz row's preview is encoded here
                 # a speed or pitch row's first chunk is not its first frame either
                 # a FLAC row's frames are written by the engine alone
-                if fmt[0] != SAMPLE_RATE or req.speed or req.pitch or fmt[1] == "flac":
+                # a level row's first chunk trails its first frame by the look-ahead
+                if fmt[0] != SAMPLE_RATE or req.speed or req.pitch or fmt[1] == "flac" or req.level != (0, 0):
                     continue
                 pcm = wire_bytes(pcm, fmt[1])
             req.preview = 1
@@ -1068,6 +1085,7 @@ class TTSService:
         self.tempo = self.wire and bool(getattr(eng, "tempo_enabled", False))  # and time-scale (--tempo)
         self.flac = self.wire and bool(getattr(eng, "flac_enabled", False))  # and encode FLAC (--flac)
         self.pitch = self.tempo and bool(getattr(eng, "pitch_enabled", False))  # and shift the pitch (--pitch)
+        self.level = self.wire and bool(getattr(eng, "level_enabled", False))  # and set the level (--volume)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -1089,8 +1107,12 @@ class TTSService:
                 noise_clamp: float | None = None, lsd_steps: int | None = None, words: int | None = None,
                 max_frames: int | None = None, sample_rate: int | None = None,
                 encoding: str | None = None, long_form: bool | None = None, speed: float | None = None,
-                continuity: bool | None = None, pitch: float | None = None) -> Request:
-        """continuity (None: the server's default, --continuity): the long-form
+                continuity: bool | None = None, pitch: float | None = None, volume_db: float | None = None,
+                limit: bool | None = None) -> Request:
+        """volume_db: -24 .. 24 dB (rounded to hundredths), limit: run the row through the peak limiter
+        even without a gain; the row's wire bytes are scaled and limited to the server's ceiling on the
+        GPU (None / 0 and None / False: unchanged).
+        continuity (None: the server's default, --continuity): the long-form
         cut, with the sentence chunks of a text piece generated one after another on one slot, each
         teacher-forced through the one before it and decoded on from its codec state, so prosody
         and the codec run across the joins. token_ids are never split, so they cannot ask for it.
@@ -1134,6 +1156,15 @@ class TTSService:
                 raise ValueError("this server runs without the pitch stage (--no-pitch, --no-tempo or --no-wire): "
                                  "pitch is not available")
             pitch_plan(pitch_cents(pitch), speed_permille(speed))  # (ValueError: with this speed, outside WSOLA's range)
+        if limit is not None and not isinstance(limit, (bool, np.bool_)):
+            raise ValueError(f"limit must be a bool, got {limit!r}")
+        if level_cdb(volume_db) == 0 and not limit:  # (ValueError outside [-24, 24]); the request without them
+            volume_db, limit = None, None
+        else:
+            if not self.level:
+                raise ValueError("this server runs without the level stage (--no-volume or --no-wire): volume_db / "
+                                 "limit are not available")
+            volume_db, limit = level_cdb(volume_db) / 100.0, bool(limit)
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
@@ -1171,25 +1202,27 @@ class TTSService:
             target = clip if clip is not None else self.voices[name]
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
-                                                            lsd_steps, sample_rate, encoding, speed, pitch))
+                                                            lsd_steps, sample_rate, encoding, speed, pitch,
+                                                            volume_db, limit))
                         if sg[0] == "text" else sg for sg in segments]
                 wire = None  # (pauses: silence of their stated duration, whatever the speed)
-                if sample_rate is not None or encoding is not None or speed is not None or pitch is not None:
+                if sample_rate is not None or encoding is not None or speed is not None or pitch is not None \
+                        or volume_db is not None:
                     wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
                 if chain:
                     return self.scheduler.submit_group(segs, target, wire, continuity=True)
                 return self.scheduler.submit_group(segs, target, wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       sample_rate, encoding, speed, pitch)
+                                       sample_rate, encoding, speed, pitch, volume_db, limit)
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       sample_rate=None, encoding=None, speed=None, pitch=None) -> Request:
+                       sample_rate=None, encoding=None, speed=None, pitch=None, volume_db=None, limit=None) -> Request:
         p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding,
-                                speed, pitch)
+                                speed, pitch, volume_db, limit)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
-                       encoding=None, speed=None, pitch=None) -> GenerationParams:
+                       encoding=None, speed=None, pitch=None, volume_db=None, limit=None) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -1203,6 +1236,8 @@ class TTSService:
             p.speed = float(speed)
         if pitch is not None:
             p.pitch = float(pitch)
+        if volume_db is not None:  # (set together: a request in the level stage)
+            p.volume_db, p.limit = float(volume_db), bool(limit)
         return p
 
     # -- per-request and run-time voices
@@ -1296,6 +1331,10 @@ class GenerateRequest(BaseModel):
     # pitch shift in semitones, -12 .. 12 (resampled on the GPU at the duration `speed` asks for; formants
     # move with the fundamental); unset or 0: unchanged
     pitch: float | None = None
+    # volume in dB, -24 .. 24, and `limit`: the look-ahead peak limiter even with no gain (both on the GPU,
+    # behind speed and pitch); unset, or 0 with limit unset: unchanged
+    volume_db: float | None = None
+    limit: bool | None = None
     # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
     long_form: bool | None = None
     # the long-form cut with each sentence chunk continuing the one before it (None: --continuity)
@@ -1315,6 +1354,8 @@ class OpenAIRequest(BaseModel):
     encoding: str | None = None
     speed: float | None = None  # 0.5 .. 2.0, as in the API this route imitates (0.25 .. 4.0 there)
     pitch: float | None = None  # -12 .. 12 semitones (no counterpart in that API)
+    volume_db: float | None = None  # -24 .. 24 dB (no counterpart in that API)
+    limit: bool | None = None
     long_form: bool | None = None
     continuity: bool | None = None
 
@@ -1494,7 +1535,8 @@ def create_app(service: TTSService):
         elif fmt == "pcm" and enc not in (None, "pcm_s16le"):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
-                   encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity, pitch=req.pitch)
+                   encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity, pitch=req.pitch,
+                   volume_db=req.volume_db, limit=req.limit)
         if r.wire is not None and r.wire[1] == "flac":
             return Response(flac_file(r), media_type="audio/flac", headers=hdr)
         if r.wire is not None:
@@ -1521,13 +1563,23 @@ class StandInEngine:
     """--stand-in-engine only (CPU; launcher and routing self-test of the multi-process server): the
     engine surface the scheduler drives, computing nothing. Row frames of utterance u (its first
     token id) at step k hold stand_in_sample(u, k), delivered one call late as by a pipelined
-    engine; step_s paces each step (sleep) like a GPU step."""
+    engine; step_s paces each step (sleep) like a GPU step. level=True (with wire=True): the wire
+    surface at 24 kHz and the level stage, by the host rule audio.level_limit over the row's frames;
+    every admitted row's GenerationParams are kept in `params_log`."""
 
-    def __init__(self, max_slots=32, max_ctx=1024, step_s=0.0, **_):
+    def __init__(self, max_slots=32, max_ctx=1024, step_s=0.0, wire=False, level=False, level_ceiling_db=-1.0, **_):
         self.max_slots, self.max_ctx, self.pipeline = max_slots, max_ctx, True
         self.step_s = step_s
         self.rows, self.pending = {}, None
         self.admit_log = []  # every admitted row: (slot, ids, prefix latents or None, keep_codec)
+        self.params_log = []  # and its GenerationParams
+        self.level_enabled = bool(wire and level)
+        self.level_ceiling_cdb = level_cdb(level_ceiling_db, -40.0, 0.0, "level_ceiling_db") if self.level_enabled else 0
+        if self.level_enabled:  # (without it the stand-in has no wire surface, as before)
+            self.wire = True
+        # slot -> [encoding name, (gain_cdb, limit), frames so far, utterance, max_frames, level chunks] of a wire row
+        self.fmt = {}
+        self.wire_pending = self.wire_out = self.wire_prev = None
 
     @staticmethod
     def weight_blob_bytes():
@@ -1571,19 +1623,38 @@ class StandInEngine:
 
     def open_many(self, slots, voices, ids_list, params_list):
         """Records every admitted row in `admit_log`; the latents of admission a's frame k hold a * 1000 + k."""
+        for p in params_list:  # nothing is admitted if one row is refused
+            lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
+            rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
+            if lv != (0, 0) and not self.level_enabled:
+                raise RuntimeError("a gain or limit needs a level-enabled engine")
+            if (rate or enc or lv != (0, 0)) and not (self.level_enabled and rate in (0, SAMPLE_RATE) and enc in (0, 1, 2, 3)):
+                raise RuntimeError("the stand-in engine converts to 24 kHz pcm_s16le / ulaw / alaw only, with level=True")
         for s, ids, p in zip(slots, ids_list, params_list):
             pre = getattr(p, "prefix_latents", None)
+            self.params_log.append(p)
+            self.fmt.pop(s, None)
+            lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
+            rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
+            if rate or enc or lv != (0, 0):
+                self.fmt[s] = [ENCODINGS[(enc or 1) - 1], lv, 0, int(ids[0]) if len(ids) else 0, p.max_frames, None]
             self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames, len(self.admit_log)]
             self.admit_log.append((int(s), [int(i) for i in ids], None if pre is None else np.array(pre, np.float32),
                                   bool(getattr(p, "keep_codec", False))))
             if self.pending is not None and s < self.pending[1].size:  # drop the slot's undrained frame
                 self.pending[1][s] = False
+                if self.wire_pending is not None and s < len(self.wire_pending):
+                    self.wire_pending[s] = b""
 
     def cancel_slots(self, slots):
         """Engine.cancel_slots: the rows stop and no frame of theirs is reported any more."""
         self.cancelled = getattr(self, "cancelled", []) + [sorted(int(s) for s in slots)]
         for s in slots:
             self.rows.pop(s, None)
+            self.fmt.pop(s, None)
+            for held in (self.wire_pending, self.wire_out, self.wire_prev):
+                if held is not None and s < len(held):
+                    held[s] = b""
             for held in (self.pending, getattr(self, "out", None), getattr(self, "prev_out", None)):
                 if held is not None and s < held[1].size:
                     held[1][s] = False
@@ -1593,15 +1664,22 @@ class StandInEngine:
             time.sleep(self.step_s)
         pcm, valid, last = np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool)
         lat = np.zeros((n, LDIM), np.float32)
+        wire = [b""] * n
         for s, st in list(self.rows.items()):
             if s < n:
                 pcm[s], valid[s] = stand_in_sample(st[0], st[1]), True
+                if s in self.fmt:
+                    wire[s] = self._wire_chunk(self.fmt[s])
                 lat[s] = st[3] * 1000 + st[1]
                 st[1] += 1
                 last[s] = st[1] == st[2]
                 if last[s]:
                     del self.rows[s]
         prev, self.pending = self.pending, (pcm, valid, last, lat)
+        wprev, self.wire_pending = self.wire_pending, wire
+        self.wire_prev, self.wire_out = self.wire_out, [b""] * n
+        if wprev is not None:
+            self.wire_out[:min(n, len(wprev))] = wprev[:min(n, len(wprev))]
         self.prev_out = getattr(self, "out", None)
         self.out = (np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool),
                     np.zeros((n, LDIM), np.float32))
@@ -1618,6 +1696,22 @@ class StandInEngine:
 
         out = self.out if calls_back == 0 else self.prev_out
         return SimpleNamespace(pcm=out[0], valid=out[1], last=out[2], latents=out[3])
+
+    def _wire_chunk(self, f) -> bytes:
+        """The next wire chunk of a wire row: its frame's bytes, or for a level row the frame's chunk
+        of the streaming host rule over the row's whole signal (computed once)."""
+        enc, lv, k, u, total, chunks = f
+        f[2] = k + 1
+        if lv == (0, 0):
+            return wire_bytes(np.full(FRAME, stand_in_sample(u, k), np.float32), enc)
+        if chunks is None:
+            x = np.concatenate([np.full(FRAME, stand_in_sample(u, j), np.float32) for j in range(total)])
+            chunks = f[5] = level_limit(x, lv[0], self.level_ceiling_cdb, chunks=[FRAME] * total)
+        return wire_bytes(chunks[k], enc)
+
+    def fetch_wire(self, n, calls_back=0):
+        out = self.wire_out if calls_back == 0 else self.wire_prev
+        return [out[b] if out is not None and b < len(out) else b"" for b in range(n)]
 
     def close(self):
         pass
@@ -1653,6 +1747,9 @@ def _worker_engine(args, Engine):
               back_frames=args.back_frames, lsd_decode_steps=args.lsd_steps, max_lsd_steps=args.max_lsd_steps,
               wire=args.wire, tempo=args.wire and args.tempo, flac=args.wire and args.flac,
               pitch=args.wire and args.tempo and args.pitch)
+    # (an engine without the stage is created exactly as before; the launcher's stand-in has no wire surface)
+    if args.wire and args.volume and Engine is not StandInEngine:
+        kw.update(level=True, level_ceiling_db=args.limiter_ceiling_db)
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1726,6 +1823,12 @@ def main(argv=None):
     ap.add_argument("--pitch", action=argparse.BooleanOptionalAction, default=True,
                     help="per-request pitch (requests' pitch, semitones) shifted on the GPU; needs --tempo (off with "
                          "--no-tempo or --no-wire); --no-pitch: the tempo-enabled engine as before, such requests get 400")
+    ap.add_argument("--volume", action=argparse.BooleanOptionalAction, default=True,
+                    help="per-request volume (requests' volume_db and limit): gain and a look-ahead peak limiter on the "
+                         "GPU; needs --wire (off with --no-wire); --no-volume: the engine as before, such requests get 400")
+    ap.add_argument("--limiter-ceiling-db", type=float, default=-1.0,
+                    help="the level stage's ceiling in dBFS, -40 .. 0: no sample of a row with volume_db or limit "
+                         "leaves it")
     ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
                     help="default of requests that do not say `long_form`: split the text into pause and sentence "
                          "segments (the reference's generate_stream_long) and run them on parallel rows")

@@ -29,7 +29,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE, WIRE_FLAC
-from .audio import (flac_stream_header, pitch_cents, read_wav, read_wav_from_bytes, speed_permille, wire_bytes,
+from .audio import (flac_stream_header, level_cdb, pitch_cents, read_wav, read_wav_from_bytes, speed_permille, wire_bytes,
                     wire_samples)
 from .engine import Engine, GenerationParams, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
@@ -89,7 +89,7 @@ class TTSModel:
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
                          back_frames: int = 1, tempo: bool = False, flac: bool = False,
-                         pitch: bool = False) -> "TTSModel":
+                         pitch: bool = False, level: bool = False, level_ceiling_db: float = -1.0) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
@@ -99,7 +99,8 @@ class TTSModel:
         wire: a wire-enabled engine, for generate(.., sample_rate=, encoding=); tempo (with wire):
         its tempo stage too, for generate(.., speed=); pitch (with tempo): its pitch stage, for
         generate(.., pitch=); flac (with wire): its FLAC stage, for
-        generate(.., encoding="flac")."""
+        generate(.., encoding="flac"); level (with wire): its level stage at level_ceiling_db, for
+        generate(.., volume_db=, limit=)."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
@@ -107,7 +108,8 @@ class TTSModel:
         eng = Engine(device=device, max_slots=int(max_slots), max_ctx=max_ctx, pipeline=pipeline,
                      back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
-                     wire=wire, tempo=tempo, flac=flac, pitch=pitch)
+                     wire=wire, tempo=tempo, flac=flac, pitch=pitch,
+                     **(dict(level=True, level_ceiling_db=level_ceiling_db) if level else {}))
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -200,7 +202,8 @@ class TTSModel:
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
                  sample_rate: int | None = None, encoding=None, speed: float | None = None,
                  previous: Continuation | None = None, latents: list | None = None,
-                 pitch: float | None = None) -> Iterator[np.ndarray]:
+                 pitch: float | None = None, volume_db: float | None = None,
+                 limit: bool = False) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
         (sample_rate / encoding; a wire-enabled engine), a speed (a tempo-enabled one) or a pitch (a
         pitch-enabled one; 24 kHz 16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
@@ -213,11 +216,12 @@ class TTSModel:
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
         params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
+        params.volume_db, params.limit = volume_db, bool(limit)
         if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
                                      + max_frames <= self.engine.max_ctx):
             ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
             params.prefix_latents, params.keep_codec = np.asarray(previous.latents, np.float32), True
-        wire = params.opts() != (0, 0, 0) or params.cents() != 0
+        wire = params.opts() != (0, 0, 0) or params.cents() != 0 or params.level() != (0, 0)
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
@@ -237,7 +241,8 @@ class TTSModel:
 
     def generate_stream(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                         words: int | None = None, sample_rate: int | None = None, encoding=None,
-                        speed: float | None = None, pitch: float | None = None) -> Iterator[np.ndarray]:
+                        speed: float | None = None, pitch: float | None = None, volume_db: float | None = None,
+                        limit: bool = False) -> Iterator[np.ndarray]:
         """tts_model.rs:894-913. Text: one segment per sentence chunk; max_gen_len and the EOS tail
         from each chunk (:968-969). Token ids (an extension for callers with their own tokenizer):
         one segment; ids carry no word count, so the caller passes `words` (the reference's rules
@@ -252,6 +257,9 @@ class TTSModel:
         pitch (-12 .. 12 semitones; a pitch-enabled engine): the segments' audio is shifted in pitch
         on the GPU at the duration `speed` asks for, a resampling shift that moves the formants too
         (DESIGN.md section 23); wire bytes as for speed. None or 0 changes nothing.
+        volume_db (-24 .. 24 dB) and limit (a level-enabled engine): the segments' audio is scaled and
+        run through the look-ahead peak limiter on the GPU, behind speed and pitch (DESIGN.md section
+        24); wire bytes as for speed. None / 0 with limit False changes nothing.
         encoding "flac" (a FLAC-enabled engine): the items are the FLAC frames of each chunk (DESIGN.md
         section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0, so
         the text must be one segment: ValueError where it splits into several."""
@@ -259,6 +267,8 @@ class TTSModel:
             speed = None
         if pitch_cents(pitch) == 0:
             pitch = None
+        if level_cdb(volume_db) == 0:
+            volume_db = 0.0 if limit else None
         if encoding in ("flac", WIRE_FLAC) and isinstance(text_or_ids, str) and \
                 len(self.split_into_best_sentences(text_or_ids)) > 1:
             raise ValueError("flac: the text splits into several segments, each a stream of its own (section 21, Limits)")
@@ -268,30 +278,33 @@ class TTSModel:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
             yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding,
-                                     speed, pitch=pitch)
+                                     speed, pitch=pitch, volume_db=volume_db, limit=limit)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed, pitch=pitch)
+                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed, pitch=pitch,
+                                     volume_db=volume_db, limit=limit)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
-                 speed: float | None = None, pitch: float | None = None):
+                 speed: float | None = None, pitch: float | None = None, volume_db: float | None = None,
+                 limit: bool = False):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
-        speed / pitch, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
+        speed / pitch / volume_db / limit, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
         the stream header with the true sample count and then the frames."""
         frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed,
-                                           pitch))
+                                           pitch, volume_db, limit))
         if not frames:
             raise RuntimeError("No audio generated")
         if encoding in ("flac", WIRE_FLAC):
             rate = int(sample_rate or SAMPLE_RATE)
             return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, speed_permille(speed),
                                                         pitch_cents(pitch))) + b"".join(frames)
-        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch):
+        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch) \
+                or level_cdb(volume_db) or limit:
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
 
