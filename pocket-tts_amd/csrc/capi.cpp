@@ -6,6 +6,7 @@
 #include "engine.h"
 #include "pocket_tts.h"
 #include "pocket_tts_probe.h"
+#include "test_hooks.h"
 
 struct ptts_engine {
   ptts::Engine* impl = nullptr;
@@ -223,6 +224,15 @@ int ptts_test_attention(ptts_engine* e, int kind, int m, int nh, int cap, int wi
   return guard([&] {
     eng(e).test_attention(kind, m, nh, cap, window, n_slots, splits, qkv, kv, pre, pre_len, slot0, rps, p0, pos, tab,
                           ptab, mpad, q, o);
+  });
+}
+
+int ptts_test_row_reduce(ptts_engine* e, int m, int n, int splits, int act, int ln, float eps, int front,
+                         const float* p, const float* bias, const float* gate, const float* r, const float* ln_w,
+                         const float* ln_b, const float* mscale, const float* mshift, float* y, float* h,
+                         float* hfrag) {
+  return guard([&] {
+    eng(e).test_row_reduce(m, n, splits, act, ln, eps, front, p, bias, gate, r, ln_w, ln_b, mscale, mshift, y, h, hfrag);
   });
 }
 

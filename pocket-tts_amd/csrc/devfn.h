@@ -91,6 +91,14 @@ __device__ __forceinline__ float4 f4mul(float4 a, float4 b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
 
+// 16-B load through a global-address-space pointer: for an address the compiler cannot trace to a
+// kernel argument (a select against a stand-in, a pointer read from memory), which would
+// otherwise be a flat load (counted on both wait counters, so an LDS wait stalls on it too)
+__device__ __forceinline__ float4 ldg4(const float* p) {
+  const floatx4 v = *(const __attribute__((address_space(1))) floatx4*)p;
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
 __device__ __forceinline__ void row_slot_pos(const RowMap& mp, int row, int& slot, int& pos) {
   if (mp.tab) {
     const int v = mp.tab[row];

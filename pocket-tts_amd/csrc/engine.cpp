@@ -2375,6 +2375,73 @@ void Engine::test_attention(int kind, int M, int nh, int cap, int window, int n_
   release();
 }
 
+// Row-reduce test hook: the product launcher row_reduce (k_row_reduce, or k_row_reduce4 for a
+// 512-wide row outside the front part) on host operands; absent operands are null. The tests
+// compare with the fp64 formula on shapes and operand sets the model never runs.
+void Engine::test_row_reduce(int M, int N, int S, int act, int ln, float eps, int front, const float* P,
+                             const float* bias, const float* gate, const float* R, const float* ln_w,
+                             const float* ln_b, const float* mscale, const float* mshift, float* Y, float* H,
+                             float* Hfrag) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(P && Y && M >= 1 && M <= 4096 && N >= 4 && N <= 8192 && N % 4 == 0 && S >= 1 && S <= 16,
+               "test_row_reduce: bad shape");
+  PTTS_REQUIRE(act == ACT_NONE || act == ACT_GELU, "test_row_reduce: act is none or GELU");
+  PTTS_REQUIRE(!ln || (N <= 1024 && H), "test_row_reduce: LayerNorm rows are at most 1024 wide");
+  PTTS_REQUIRE((ln_w == nullptr) == (ln_b == nullptr) && (mscale == nullptr) == (mshift == nullptr),
+               "test_row_reduce: ln_w with ln_b, mscale with mshift");
+  PTTS_REQUIRE(ln || (!ln_w && !mshift && !Hfrag), "test_row_reduce: affine, modulate and hfrag need ln");
+  PTTS_REQUIRE(!Hfrag || (N == FK_K && M <= 32), "test_row_reduce: hfrag needs n == 1024 and m <= 32");
+  sync();
+  std::vector<void*> allocs;
+  auto release = [&]() {
+    for (void* p : allocs) (void)hipFree(p);
+  };
+  try {
+    auto dalloc = [&](size_t floats) {
+      void* p = nullptr;
+      PTTS_HIP(hipMalloc(&p, sizeof(float) * std::max<size_t>(floats, 4)));
+      allocs.push_back(p);
+      return (float*)p;
+    };
+    auto up = [&](const float* src, size_t floats) -> float* {
+      if (!src) return nullptr;
+      float* p = dalloc(floats);
+      PTTS_HIP(hipMemcpyAsync(p, src, sizeof(float) * floats, hipMemcpyHostToDevice, stream_));
+      return p;
+    };
+    const size_t mn = (size_t)M * N;
+    RowReduceArgs a{};
+    a.P = up(P, (size_t)S * mn);
+    a.S = S, a.M = M, a.N = N;
+    a.bias = up(bias, N);
+    a.act = act;
+    a.gate = up(gate, mn), a.ldg = N;
+    a.R = up(R, mn), a.ldr = N;
+    a.Y = dalloc(mn), a.ldy = N;
+    a.ln = ln ? 1 : 0;
+    a.ln_w = up(ln_w, N), a.ln_b = up(ln_b, N);
+    a.eps = eps;
+    a.mscale = up(mscale, mn), a.mshift = up(mshift, mn), a.ldm = N;
+    a.front = front ? 1 : 0;
+    if (ln) a.Hout = dalloc(mn), a.ldh = N;
+    if (Hfrag) {
+      a.Hfrag = dalloc(FK_A_FLOATS);
+      PTTS_HIP(hipMemsetAsync(a.Hfrag, 0, sizeof(float) * FK_A_FLOATS, stream_));
+    }
+    row_reduce(a, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(Y, a.Y, sizeof(float) * mn, hipMemcpyDeviceToHost, stream_));
+    if (ln) PTTS_HIP(hipMemcpyAsync(H, a.Hout, sizeof(float) * mn, hipMemcpyDeviceToHost, stream_));
+    if (Hfrag) PTTS_HIP(hipMemcpyAsync(Hfrag, a.Hfrag, sizeof(float) * FK_A_FLOATS, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
+}
+
 double Engine::time_op(int B, const std::string& name, int reps) {
   xh_dirty_ = true;  // replays write fbm_.x / fbm_.h
   PTTS_REQUIRE(ready_, "engine weights not finalized");

@@ -172,6 +172,10 @@ class Engine {
   void test_attention(int kind, int M, int nh, int cap, int window, int n_slots, int S, const float* qkv, float* kvh,
                       const float* pre, const int* pre_len, int slot0, int rps, int p0, const int* pos, const int* tab,
                       const int* ptab, int mpad, float* Qh, float* Oh);
+  // Row-reduce test hook (ptts_test_row_reduce): the product launcher on host operands
+  void test_row_reduce(int M, int N, int S, int act, int ln, float eps, int front, const float* P, const float* bias,
+                       const float* gate, const float* R, const float* ln_w, const float* ln_b, const float* mscale,
+                       const float* mshift, float* Y, float* H, float* Hfrag);
   void overlap_probe(int B, int reps, double* us);
   std::vector<std::string> plan_names(int B);
   int int8_matrices() const { return (int)q8map_.size(); }

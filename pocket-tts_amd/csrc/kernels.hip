@@ -2559,12 +2559,19 @@ __global__ __launch_bounds__(64 * A16_WAVES) void k_attn16(const float* __restri
 // 4i + l/16 - exactly the key whose V dims it holds from V load i, so P.V needs no broadcast.
 // The rows (l/16) are combined once per wave at the end. Each wave issues its first block's
 // loads before the QKV/RoPE phase: the cached keys do not depend on this step's token.
-template <int NW, int KQ, bool NT = false>
+// Load order: after the kernel arguments, one scalar level (the row's position, its prefix length
+// and prefix pointer, read unconditionally from stand-in addresses where a table is absent) and
+// one vector level (the wave's first key block, the QKV slabs and the RoPE row, all requested
+// before the first wait); the only further levels are the next key blocks. SMAX: the slab count
+// the fixed-trip slab loop is unrolled to (S <= SMAX).
+template <int NW, int KQ, bool NT = false, int SMAX = 16, bool PRE = true>
 __global__ __launch_bounds__(64 * NW) void k_attn_decode_qkv(const float* __restrict__ P, int S, int M, int nh, RowMap mp,
                                                          KvStore kv, const float* __restrict__ rope,
                                                          float* __restrict__ O) {
   front_prio();
   constexpr int BLK = 4 * KQ * NW;  // keys per round: NW waves x KQ loads of 4 keys
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(1))) f4v* gf4p;  // global address space: no flat loads
   __shared__ float s_m[NW], s_l[NW];
   __shared__ __attribute__((aligned(16))) float s_o[NW][64];
   __shared__ __attribute__((aligned(16))) float s_qkv[3][64];
@@ -2572,62 +2579,113 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode_qkv(const float* __rest
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c4 = (lane & 15) * 4;  // key row within a load, first of my 4 dims
   const int row = blockIdx.x, head = blockIdx.y;
-  int slot, qp;
-  row_slot_pos(mp, row, slot, qp);
+  // every kernel argument in scalar registers here: one argument load level (left alone, the
+  // compiler reads the segment piecemeal, a few fields behind each branch)
+  asm volatile("" ::"s"(P), "s"(S), "s"(M), "s"(nh), "s"(mp.slot0), "s"(mp.rps), "s"(mp.p0), "s"(mp.pos_arr),
+               "s"(mp.tab), "s"(kv.base), "s"(kv.slot_stride), "s"(kv.cap), "s"(kv.pre), "s"(kv.pre_len),
+               "s"(kv.layer), "s"(rope), "s"(O));
+  // PRE: the launch has prefix tables (kv.pre != nullptr, the launcher's choice of instance)
+  int slot, qp, F = 0;
+  const float* pre = nullptr;
+  if (mp.tab) {  // table form (not a step launch of the engine): the slot itself is a table entry
+    row_slot_pos(mp, row, slot, qp);
+    if (PRE && slot >= 0) {
+      F = kv.pre_len[slot];
+      pre = kv.pre[slot];
+    }
+  } else {  // uniform form: the table entries in one scalar level
+    const int sr = __builtin_amdgcn_readfirstlane(row / mp.rps);
+    slot = mp.slot0 + sr;
+    // read through the constant address space: scalar loads (nothing in this launch writes the
+    // tables; behind the argument pin the compiler would no longer prove that and go through
+    // the vector memory path, a wait per entry)
+    typedef const __attribute__((address_space(4))) int* cip;
+    typedef const float* cfp;
+    const int* none = reinterpret_cast<const int*>(P);  // stand-in where the table is absent
+    const int pa = *(cip)(mp.pos_arr ? mp.pos_arr + slot : none);
+    if (PRE) {
+      F = *(cip)(kv.pre_len + slot);
+      pre = *(const __attribute__((address_space(4))) cfp*)(kv.pre + slot);
+    }
+    qp = (mp.pos_arr ? pa : mp.p0) + (row - sr * mp.rps);
+  }
+  F = max(F, 0);
   // a finished row is still stepped (its frame is discarded): once it has filled the cache
   // (qp == cap) its key/value must not be appended, or position cap would spill into the next
   // head's (or, for the slot's last head, the next slot's) position 0
   const bool append = qp < kv.cap;
   qp = min(qp, kv.cap - 1);
   const int d = nh * 64, ld = 3 * d;
-  const KvHead kh = kv_head(kv, slot, nh, head);
-  float* kbase = kh.kb;
-  float* vbase = kh.vb;
+  float* kbase = kv.base + (long)slot * kv.slot_stride + (long)head * kv.cap * 64;
+  float* vbase = kv.base + (long)slot * kv.slot_stride + (long)(nh + head) * kv.cap * 64;
+  // positions < F live in the voice's rows (KvStore::pre); addresses as integers, so that the
+  // per-element choice between the two bases stays one global load
+  const uintptr_t kb_a = reinterpret_cast<uintptr_t>(kbase), vb_a = reinterpret_cast<uintptr_t>(vbase);
+  const uintptr_t pk_a =
+      F > 0 ? reinterpret_cast<uintptr_t>(pre + ((long)kv.layer * 2 * nh + head) * F * 64) : kb_a;
+  const uintptr_t pv_a = F > 0 ? pk_a + (uintptr_t)((long)nh * F * 64) * sizeof(float) : vb_a;
   const int last = qp - 1;
   float4 k[KQ], v[KQ];
-  auto load_block = [&](int base) {
-    if (front_skip() & 4) {
-#pragma unroll
-      for (int i = 0; i < KQ; ++i) k[i] = v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      return;
-    }
-    if (base < kh.F) {  // (part of) the block in the shared voice prefix: cached loads, since
-                        // every row of the voice reads these lines (wave-uniform branch)
-#pragma unroll
-      for (int i = 0; i < KQ; ++i) {
-        const int j = min(base + 4 * i + g, last);
-        const long off = (long)j * 64 + c4;
-        k[i] = *reinterpret_cast<const float4*>((j < kh.F ? kh.pk : kbase) + off);
-        v[i] = *reinterpret_cast<const float4*>((j < kh.F ? kh.pv : vbase) + off);
-      }
-      return;
-    }
+  // (Part of) a block in the shared voice prefix: cached loads, since every row of the voice reads
+  // these lines. The row's own blocks are read once per step: non-temporal. max(.., 0): a wave
+  // without keys yet (qp <= base) still requests position 0 of its rows and drops the values (no
+  // branch around the first block's loads).
+  auto load_cached = [&](int base) {
 #pragma unroll
     for (int i = 0; i < KQ; ++i) {
-      const long off = (long)min(base + 4 * i + g, last) * 64 + c4;
-      if (NT) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v kk = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(kbase + off));
-        const f4v vv = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(vbase + off));
-        k[i] = make_float4(kk.x, kk.y, kk.z, kk.w);
-        v[i] = make_float4(vv.x, vv.y, vv.z, vv.w);
-      } else {
-        k[i] = *reinterpret_cast<const float4*>(kbase + off);
-        v[i] = *reinterpret_cast<const float4*>(vbase + off);
-      }
+      const int j = max(min(base + 4 * i + g, last), 0);
+      const uintptr_t off = (uintptr_t)((long)j * 64 + c4) * sizeof(float);
+      const f4v kk = *(gf4p)((j < F ? pk_a : kb_a) + off), vv = *(gf4p)((j < F ? pv_a : vb_a) + off);
+      k[i] = make_float4(kk.x, kk.y, kk.z, kk.w);
+      v[i] = make_float4(vv.x, vv.y, vv.z, vv.w);
     }
   };
+  auto load_own = [&](int base) {
+#pragma unroll
+    for (int i = 0; i < KQ; ++i) {
+      const uintptr_t off = (uintptr_t)((long)max(min(base + 4 * i + g, last), 0) * 64 + c4) * sizeof(float);
+      const f4v kk = __builtin_nontemporal_load((gf4p)(kb_a + off));
+      const f4v vv = __builtin_nontemporal_load((gf4p)(vb_a + off));
+      k[i] = make_float4(kk.x, kk.y, kk.z, kk.w);
+      v[i] = make_float4(vv.x, vv.y, vv.z, vv.w);
+    }
+  };
+  auto load_none = [&]() {  // probe builds: front_skip bit 2
+#pragma unroll
+    for (int i = 0; i < KQ; ++i) k[i] = v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  // The first block's policy is the launch's, not the block's: a branch between two sets of loads
+  // into the same registers makes the compiler wait for the one before issuing the other (the
+  // never-taken edge between the arms). With prefix tables (PRE) the first blocks lie in the
+  // prefix for all but short prefixes: cached; without them they are the row's own: non-temporal.
   int base = 4 * KQ * wave;
-  if (base < qp) load_block(base);
-  if (tid < 192) {  // q | k | v column of this head, summed over the slabs in z order
-    const int part = tid >> 6;
-    const float* pr = P + (long)row * ld + part * d + head * 64 + lane;
-    s_qkv[part][lane] = slab_sum(pr, (long)M * ld, S);
-  }
+  if (front_skip() & 4) load_none();
+  else if (PRE || !NT) load_cached(base);
+  else load_own(base);
+  auto load_block = [&](int base) {  // later blocks: the policy per block (wave-uniform branch)
+    if (front_skip() & 4) load_none();
+    else if (!NT || base < F) load_cached(base);
+    else load_own(base);
+  };
+  // q | k | v column of this head (waves 0-2; wave 3 requests v's again and drops it): the slabs,
+  // clamped to the last one, and this position's RoPE pair (table of rope_table()), all in the
+  // level of the key block
+  const int part = min(tid >> 6, 2);
+  const float* pr = P + (long)row * ld + part * d + head * 64 + lane;
+  const long zs = (long)M * ld;
+  float pz[SMAX];
+#pragma unroll
+  for (int z = 0; z < SMAX; ++z) pz[z] = pr[(long)max(min(z, S - 1), 0) * zs];
+  const float2 cssn = *reinterpret_cast<const float2*>(rope + (long)qp * 64 + 2 * (tid & 31));
+  __builtin_amdgcn_sched_barrier(0);
+  float qs = 0.f;  // summed over the slabs in z order (by every wave: a branch around the adds
+                   // would take the loads with it, behind the barrier above)
+#pragma unroll
+  for (int z = 0; z < SMAX; ++z) qs = z < S ? qs + pz[z] : qs;
+  if (tid < 192) s_qkv[part][lane] = qs;
   __syncthreads();
   if (tid < 64) {  // rotate the (2i, 2i+1) pairs of q (tid < 32) and k (tid >= 32)
     const int i = tid & 31, part = tid >> 5;
-    const float2 cssn = *reinterpret_cast<const float2*>(rope + (long)qp * 64 + 2 * i);  // table of rope_table()
     const float cs = cssn.x, sn = cssn.y;
     const float x0 = s_qkv[part][2 * i], x1 = s_qkv[part][2 * i + 1];
     // Spelled as the fused form k_qkv_rope compiles to (one product rounded, the other fused), so
@@ -2715,12 +2773,23 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode_qkv(const float* __rest
 
 void attention_step_qkv(const float* P, int S, int M, int nh, RowMap map, KvStore kv, const float* rope, float* O,
                         hipStream_t s) {
-  // 4 waves x 32 keys (128 keys per round, 133 VGPRs): in the pipelined step the front part's
-  // attention shares each CU with a back-part workgroup, and this register budget keeps two of
-  // its workgroups resident beside it. Steady step 0.690 -> 0.673 ms against 4 x 64 keys
+  // 4 waves x 32 keys (128 keys per round; 116 VGPRs with prefix tables, 102 without, from the
+  // code object's .vgpr_count; 158 before the load order of DESIGN section 25): in the pipelined
+  // step the front part's attention shares each CU with a back-part workgroup, and this register
+  // budget keeps two of its workgroups resident beside it. Steady step 0.690 -> 0.673 ms against 4 x 64 keys
   // (238 VGPRs, faster alone); 8 x 32, 4 x 48, 4 x 16, 2 x 64, 8 x 48 measured in between
   // (tools/sweep_env.sh). KV blocks are read once per step: non-temporal loads (-1.1 % step).
-  hipLaunchKernelGGL((k_attn_decode_qkv<4, 8, true>), dim3(M, nh), dim3(256), 0, s, P, S, M, nh, map, kv, rope, O);
+  if (S < 0 || S > 16) throw std::runtime_error("attention_step_qkv: 0 to 16 slabs");
+  // instances: the slab loop's trip count (the step's QKV GEMM writes 8 slabs) x prefix tables
+  const dim3 grid(M, nh), block(256);
+  if (S <= 8 && kv.pre)
+    hipLaunchKernelGGL((k_attn_decode_qkv<4, 8, true, 8, true>), grid, block, 0, s, P, S, M, nh, map, kv, rope, O);
+  else if (S <= 8)
+    hipLaunchKernelGGL((k_attn_decode_qkv<4, 8, true, 8, false>), grid, block, 0, s, P, S, M, nh, map, kv, rope, O);
+  else if (kv.pre)
+    hipLaunchKernelGGL((k_attn_decode_qkv<4, 8, true, 16, true>), grid, block, 0, s, P, S, M, nh, map, kv, rope, O);
+  else
+    hipLaunchKernelGGL((k_attn_decode_qkv<4, 8, true, 16, false>), grid, block, 0, s, P, S, M, nh, map, kv, rope, O);
 }
 
 __global__ __launch_bounds__(256) void k_rope_table(float* tab, int npos) {
@@ -3203,14 +3272,29 @@ __global__ __launch_bounds__(256) void k_commit(CommitArgs a) {
 // transformer.rs:66-90 norm1 of layer 0. The weight arrives transposed, Wt [32][1024], so the 64
 // lanes of a wave read one contiguous 1-KB run of Wt[k] per load. lat: the row's 32 inputs.
 // input_linear4 is the projection alone (the prefill's latent-prefix rows, k_prefill_input).
-__device__ __forceinline__ float4 input_linear4(const float* lat, const float* __restrict__ Wt) {
+// The operands that depend on nothing computed: this thread's 32 Wt quads and its LayerNorm
+// affine quads, requested at kernel entry (input_ln_request) so that they travel with the
+// caller's state loads instead of behind its barriers. A kernel without the projection (Wt ==
+// nullptr) reads the stand-in address `alt` (>= 16 B, 16-B aligned) and drops the values.
+struct InputLnOps {
+  float4 wv[32], w4, b4;
+};
+__device__ __forceinline__ void input_linear_request(const float* __restrict__ Wt, const float* alt, float4 (&wv)[32]) {
   const int n = 4 * threadIdx.x;  // N = 1024
+#pragma unroll
+  for (int k = 0; k < 32; ++k) wv[k] = ldg4(Wt ? Wt + (long)k * 1024 + n : alt);
+}
+__device__ __forceinline__ void input_ln_request(const float* __restrict__ Wt, const float* __restrict__ lnw,
+                                                 const float* __restrict__ lnb, const float* alt, InputLnOps& o) {
+  const int n = 4 * threadIdx.x;
+  input_linear_request(Wt, alt, o.wv);
+  o.w4 = ldg4(Wt ? lnw + n : alt);
+  o.b4 = ldg4(Wt ? lnb + n : alt);
+}
+__device__ __forceinline__ float4 input_linear4(const float* lat, const float4 (&wv)[32]) {
   float4 lv[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) lv[j] = *reinterpret_cast<const float4*>(lat + 4 * j);
-  float4 wv[32];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) wv[k] = *reinterpret_cast<const float4*>(Wt + (long)k * 1024 + n);
   float acc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -3226,16 +3310,15 @@ __device__ __forceinline__ float4 input_linear4(const float* lat, const float* _
   return make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-__device__ __forceinline__ void input_ln_row(const float* lat, const float* __restrict__ Wt,
-                                             const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                             float* __restrict__ xr, float* __restrict__ hr, float* sh) {
+__device__ __forceinline__ void input_ln_row(const float* lat, const InputLnOps& ops, float* __restrict__ xr,
+                                             float* __restrict__ hr, float* sh) {
   const int n = 4 * threadIdx.x;  // N = 1024
-  const float4 v = input_linear4(lat, Wt);
+  const float4 v = input_linear4(lat, ops.wv);
   *reinterpret_cast<float4*>(xr + n) = v;
   const float mean = block_sum((v.x + v.y) + (v.z + v.w), sh) / 1024.f;
   const float4 d = make_float4(v.x - mean, v.y - mean, v.z - mean, v.w - mean);
   const float den = sqrtf(block_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w), sh) / 1024.f + 1e-5f);
-  const float4 w4 = *reinterpret_cast<const float4*>(lnw + n), b4 = *reinterpret_cast<const float4*>(lnb + n);
+  const float4 w4 = ops.w4, b4 = ops.b4;
   *reinterpret_cast<float4*>(hr + n) =
       make_float4(d.x / den * w4.x + b4.x, d.y / den * w4.y + b4.y, d.z / den * w4.z + b4.z, d.w / den * w4.w + b4.w);
 }
@@ -3252,6 +3335,12 @@ __global__ __launch_bounds__(256) void k_front_commit(FrontCommitArgs a) {
   const float e = a.eos[b];                       // loaded with `active`: one round trip
   const float cv = t < 32 ? a.cur[b * 32 + t] : 0.f;
   const float li = t < 32 ? a.lat_in[b * 32 + t] : 0.f;
+  // the next step's projection weights and LN affine with the state loads: the same round trip
+  // (they depend on nothing computed here; stand-in: cur's allocation, aligned down to 16 B)
+  InputLnOps ops;
+  input_ln_request(a.Wt, a.lnw, a.lnb, reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(a.cur) & ~(uintptr_t)15),
+                   ops);
+  __builtin_amdgcn_sched_barrier(0);
   __syncthreads();  // every lane has read `active` before lane 0 updates the state
   if (t == 0) {
     FrameFlags f{0, 0};
@@ -3279,7 +3368,7 @@ __global__ __launch_bounds__(256) void k_front_commit(FrontCommitArgs a) {
   }
   if (!a.Wt) return;  // uniform
   __syncthreads();
-  input_ln_row(s_lat, a.Wt, a.lnw, a.lnb, a.x + (long)b * 1024, a.h + (long)b * 1024, sh);
+  input_ln_row(s_lat, ops, a.x + (long)b * 1024, a.h + (long)b * 1024, sh);
 }
 
 void front_commit(const FrontCommitArgs& a, hipStream_t s) {
@@ -3433,7 +3522,9 @@ __global__ __launch_bounds__(256) void k_prefill_input(const int* __restrict__ s
   if (threadIdx.x < 32)
     s_lat[threadIdx.x] = v == PREFILL_SRC_BOS ? bos[threadIdx.x] : lat[(long)(PREFILL_SRC_LAT0 - v) * 32 + threadIdx.x];
   __syncthreads();
-  *dst = input_linear4(s_lat, Wt);
+  float4 wv[32];
+  input_linear_request(Wt, Wt, wv);
+  *dst = input_linear4(s_lat, wv);
 }
 void prefill_input(const int* src, int n, const float* table, const float* lat, const float* bos, const float* Wt,
                    int dim, float* out, hipStream_t s) {
@@ -5302,7 +5393,10 @@ __global__ __launch_bounds__(256) void k_input_ln(const float* __restrict__ lat,
   front_prio();
   __shared__ float sh[4];
   const int m = blockIdx.x;
-  input_ln_row(lat + (long)m * 32, Wt, lnw, lnb, x + (long)m * 1024, h + (long)m * 1024, sh);
+  InputLnOps ops;
+  input_ln_request(Wt, lnw, lnb, Wt, ops);
+  __builtin_amdgcn_sched_barrier(0);  // all 34 in flight before the first product
+  input_ln_row(lat + (long)m * 32, ops, x + (long)m * 1024, h + (long)m * 1024, sh);
 }
 
 void input_ln(const float* lat, const float* Wt, const float* lnw, const float* lnb, float* x, float* h, int M,

@@ -310,6 +310,37 @@ class Engine:
                                         mpad, fptr(q), fptr(o)))
         return o, kv_out, q
 
+    def test_row_reduce(self, p: np.ndarray, *, bias=None, gate=None, r=None, act: int = 0, ln: bool = False,
+                        eps: float = 1e-5, ln_w=None, ln_b=None, mscale=None, mshift=None, hfrag: bool = False,
+                        front: bool = False):
+        """Row-reduce test hook (ptts_test_row_reduce): the product launcher on p [S][m][n] with the
+        optional operands bias [n], gate / r [m][n], LayerNorm (ln_w, ln_b [n]) and modulate (mscale,
+        mshift [m][n]); act 0 none, 1 GELU. Returns (y, h, hfrag): h None without ln, hfrag (the
+        [32][1024] A-fragment copy of h) None unless asked for."""
+        p = np.ascontiguousarray(p, np.float32)
+        s, m, n = p.shape
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            if a.shape != shape:
+                raise ValueError(f"test_row_reduce: expected shape {shape}, got {a.shape}")
+            return a
+
+        bias, ln_w, ln_b = arr(bias, (n,)), arr(ln_w, (n,)), arr(ln_b, (n,))
+        gate, r, mscale, mshift = (arr(a, (m, n)) for a in (gate, r, mscale, mshift))
+        y = np.empty((m, n), np.float32)
+        h = np.empty((m, n), np.float32) if ln else None
+        hf = np.empty(32 * 1024, np.float32) if hfrag else None
+        # declared in csrc/test_hooks.h, not in the headers whose symbols _lib.SIGNATURES mirrors: bound here
+        fn = lib().ptts_test_row_reduce
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_int] + [F32P] * 11
+        check(fn(self.handle, m, n, s, act, int(ln), eps, int(front), fptr(p), fptr(bias), fptr(gate), fptr(r),
+                 fptr(ln_w), fptr(ln_b), fptr(mscale), fptr(mshift), fptr(y), fptr(h), fptr(hf)))
+        return y, h, hf
+
     def lsd_steps(self) -> tuple[int, int]:
         """(cap, last_run): the cap on the per-utterance Euler step counts, and the steps the most
         recent step call ran: the largest count among its rows still open (ptts_lsd_steps)."""
