@@ -336,6 +336,8 @@ typedef struct ptts_slot_opts {
   int reserved;    /* offset 44: what was the 48-byte struct's tail padding; ignored */
   int gain_cdb;    /* volume in hundredths of a dB, -2400 .. 2400 (ptts_level_enable); 0: none. Size 48 -> 56 */
   int limit;       /* 1: the row runs through the peak limiter even at gain 0; 0: only with a gain */
+  int align;       /* 1: the row is in the align stage (ptts_align_enable); 0: not. Size 56 -> 64 */
+  int reserved2;   /* ignored */
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
@@ -502,6 +504,26 @@ int ptts_fetch_prev(ptts_engine* e, int calls_back, int n_rows, float* pcm, uint
  * tempo-enabled engine); n_bytes[b] = 0 for a row with no
  * wire format or no frame. out may be NULL (sizes only). Wire-enabled engines only. */
 int ptts_fetch_wire(ptts_engine* e, int calls_back, int n_rows, uint8_t* out, size_t row_stride, int* n_bytes);
+/* Word alignment (no reference counterpart). On an align-enabled engine a row
+ * admitted with ptts_slot_opts.align = 1 and S = n_ids <= PTTS_ALIGN_TOKENS tokens gets, with every
+ * frame, the attention its FlowLM query of that step paid to its S text tokens in layer `layer`:
+ * per head h of head_mask (bit h = head h of 16), the softmax over the text keys alone (KV
+ * positions F .. F+S-1, F the voice rows) of q_h . k_j / 8, averaged over the selected heads. The
+ * S values are >= 0 and sum to 1. One more launch in the FlowLM step computes them; every other
+ * output of the engine is bit for bit what it is without the stage. The host rule that turns the
+ * frames' rows into word times is pocket_tts_amd/align.py.
+ * ptts_align_enable: valid on an idle engine before its first step, as ptts_wire_enable
+ * (PTTS_ERR_INVALID later); a layer outside 0..5 or a mask without a bit among the 16 heads is
+ * PTTS_ERR_INVALID. on = 0, or never called: the graphs and copies the engine has without it.
+ * align = 1 on an engine without the stage, or with n_ids > PTTS_ALIGN_TOKENS, is PTTS_ERR_INVALID
+ * and admits nothing.
+ * ptts_fetch_align: the companion of ptts_fetch / ptts_fetch_prev like ptts_fetch_wire (the same
+ * call's frame, the same event): row b's n_tokens[b] floats at out + b * row_stride (row_stride >=
+ * PTTS_ALIGN_TOKENS, in floats); n_tokens[b] = 0 for a row with no valid frame or not in the
+ * stage. The count is the one the device wrote beside the row. out may be NULL (counts only). */
+#define PTTS_ALIGN_TOKENS 128
+int ptts_align_enable(ptts_engine* e, int on, int layer, unsigned head_mask);
+int ptts_fetch_align(ptts_engine* e, int calls_back, int n_rows, float* out, size_t row_stride, int* n_tokens);
 /* *ready = 1 if ptts_fetch_prev(e, calls_back, ..) would return without waiting (the call's frame
  * is complete), else 0; never blocks. A driver that also serves previews polls this and
  * ptts_preview_fetch instead of blocking in the fetch. */

@@ -227,6 +227,12 @@ int ptts_test_attention(ptts_engine* e, int kind, int m, int nh, int cap, int wi
   });
 }
 
+int ptts_test_align(ptts_engine* e, int m, int nh, int cap, int splits, const float* qkv, const float* kv,
+                    const float* pre, const int* pre_len, const int* pos, const int* tab, unsigned head_mask,
+                    float* out) {
+  return guard([&] { eng(e).test_align(m, nh, cap, splits, qkv, kv, pre, pre_len, pos, tab, head_mask, out); });
+}
+
 int ptts_test_row_reduce(ptts_engine* e, int m, int n, int splits, int act, int ln, float eps, int front,
                          const float* p, const float* bias, const float* gate, const float* r, const float* ln_w,
                          const float* ln_b, const float* mscale, const float* mshift, float* y, float* h,
@@ -324,7 +330,7 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     const size_t size = opts[0].size ? opts[0].size : offsetof(ptts_slot_opts, pitch_cents);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n), gain(n), limit(n);
+    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n), gain(n), limit(n), align(n);
     std::vector<const float*> pre(n);
     for (int i = 0; i < n; ++i) {
       ptts_slot_opts o{};
@@ -340,9 +346,10 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
       pitch[i] = o.pitch_cents;
       gain[i] = o.gain_cdb;  // (o.reserved, the four bytes behind pitch_cents, is ignored)
       limit[i] = o.limit;
+      align[i] = o.align;  // (o.reserved2 is ignored)
     }
     eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data(),
-                      pre.data(), npre.data(), keep.data(), pitch.data(), gain.data(), limit.data());
+                      pre.data(), npre.data(), keep.data(), pitch.data(), gain.data(), limit.data(), align.data());
   });
 }
 
@@ -350,6 +357,14 @@ int ptts_wire_enable(ptts_engine* e, int on) { return guard([&] { eng(e).wire_en
 
 int ptts_fetch_wire(ptts_engine* e, int calls_back, int n_rows, uint8_t* out, size_t row_stride, int* n_bytes) {
   return guard([&] { eng(e).fetch_wire(calls_back, n_rows, out, row_stride, n_bytes); });
+}
+
+int ptts_align_enable(ptts_engine* e, int on, int layer, unsigned head_mask) {
+  return guard([&] { eng(e).align_enable(on != 0, layer, head_mask); });
+}
+
+int ptts_fetch_align(ptts_engine* e, int calls_back, int n_rows, float* out, size_t row_stride, int* n_tokens) {
+  return guard([&] { eng(e).fetch_align(calls_back, n_rows, out, row_stride, n_tokens); });
 }
 
 long ptts_wire_len(long n_samples, int sample_rate, int encoding) {

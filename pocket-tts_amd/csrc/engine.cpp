@@ -905,7 +905,7 @@ void Engine::conv_op(std::vector<Op>& ops, const std::string& name, const float*
 // FlowLM transformer layers over M rows of the workspace fb (fb.x holds the residual stream, fb.h =
 // norm1_0(fb.x)). StreamingTransformerLayer::forward (transformer.rs:66-90).
 void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
-                         const FlowBufs& fb) {
+                         const FlowBufs& fb, float* align_out) {
   // (the step's fused launches hand over through hfrag_ / ffn_hand_, of which there is one set)
   PTTS_REQUIRE(!step || &fb == &fbm_, "step passes run on the engine's own buffers");
   for (int l = 0; l < NL; ++l) {
@@ -929,6 +929,32 @@ void Engine::flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, boo
       ops.push_back({p + ".attention", [=](hipStream_t s) { attention_step_qkv(P, S, M, NH, map, kv, rope, O, s); },
                      (double)M * 4096.0 * L,
                      8192.0 * kvu + (double)M * (4.0 * (S * 3.0 * D + 2.0 * D + D) + 64.0 * 4 * 2)});
+      if (align_out && l == align_layer_) {
+        // the text-attention rows of this layer (section 26), while the query's slabs are still in
+        // fb.partial (out_gemm overwrites them) and this position's keys in the store. Stream order:
+        // not a parallel branch. Cost for rows of n text tokens over h selected heads: the keys
+        // (256 B each), the q slabs and the RoPE row in, ALIGN_ROW words out; a 64-term dot per key
+        // and ~8 flops per softmax element. Stated for the rows in the stage at the time of the call
+        // (none: the launch writes one count per row).
+        AlignArgs a{};
+        a.P = P;
+        a.S = S;
+        a.M = M;
+        a.nh = NH;
+        a.pos = map.pos_arr;
+        a.kv = kv;
+        a.rope = rope;
+        a.tab = align_tab_;
+        a.head_mask = align_mask_;
+        a.out = align_out;
+        double rows = 0, keys = 0;
+        for (int b = 0; b < M; ++b)
+          if (slot_align_[b]) rows += 1, keys += slot_align_[b];
+        const double h = __builtin_popcount(align_mask_);
+        ops.push_back({p + ".align", [=](hipStream_t s) { align_step(a, s); }, h * keys * (128.0 + 8.0),
+                       h * (256.0 * keys + rows * 4.0 * (S * 64.0 + 64.0)) + rows * 4.0 * ALIGN_ROW +
+                           (M - rows) * 4.0 + M * 12.0});
+      }
     } else {
       {
         const float* P = fb.partial;
@@ -1077,7 +1103,7 @@ void Engine::build_front(std::vector<Op>& ops, int B, int hb, int lsd_run) {
   // projection + norm1 of layer 0 (fbm_.x, fbm_.h) were computed by the previous step's front_commit,
   // or by refresh_xh() after anything else wrote them or lat_in_.
   const FlowBufs& fb = fbm_;
-  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow", fb);
+  flow_layers(ops, B, RowMap{0, 1, 0, fpos_}, true, true, "flow", fb, align_ ? align_block(hb) : nullptr);
   // ---- flow head (mlp.rs:215-383): cond_embed | out_eos, EOS bookkeeping, noise, adaLN
   // modulations of all lsd steps: one launch (head_prelude) ahead of the chain, or four
   if (use_head_prelude(B)) {
@@ -1832,6 +1858,14 @@ void Engine::copy_out(int B, int hb, hipStream_t s) {
     PTTS_HIP(hipMemcpyAsync(h_wireb_[p], wireb_[p], any ? wire_block_bytes(B) : wire_head_bytes(),
                             hipMemcpyDeviceToHost, s));
   }
+  if (align_) {  // the alignment blocks of the pass's buffers, when a row of their front parts was in the stage
+    bool any = false;
+    for (int f = 0; f < nfr_; ++f) any = any || align_any_[hb + f];
+    if (any) {
+      const size_t off = (size_t)hb * max_slots_ * ALIGN_ROW, n = (size_t)nfr_ * max_slots_ * ALIGN_ROW;
+      PTTS_HIP(hipMemcpyAsync(h_alignb_ + off, alignb_ + off, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    }
+  }
 }
 
 hipGraphExec_t Engine::part_graph(int part, int B, int hb, int qp, int nfr, int lsd_run) {
@@ -1955,6 +1989,10 @@ void Engine::call_async(int B, bool run_front) {
   // its Euler step count: the largest count among the call's rows that are still open
   const int lsd_run = B > 0 ? lsd_run_for(B) : 0;
   if (B > 0) lsd_last_run_ = lsd_run;
+  if (align_) {  // the table as this front part will read it (admissions and cancels are stream-ordered)
+    align_any_[hb] = false;
+    for (int b = 0; b < B; ++b) align_any_[hb] = align_any_[hb] || slot_align_[b] > 0;
+  }
   hipGraphExec_t front = B > 0 ? part_graph(0, B, hb, 0, 0, lsd_run) : nullptr;
   auto run_front_part = [&]() {
     if (pv_read_pending_[hb]) {  // a preview still gathers from this hand-off buffer
@@ -2098,7 +2136,16 @@ void Engine::fetch(int B, float* pcm, uint8_t* valid, uint8_t* last, float* eos,
     // after that frame's call (a driver that admits the next utterance before fetching the last
     // frame of the previous one, as bench.py does): then the frame is the previous utterance's and
     // the new one's back passes are still to come
-    if (ok && hf[b].last && fk >= admit_call_[b]) drained_[b] = codec_ok_[b] = 1;  // (lsd_run_for: the row counts no more)
+    if (ok && hf[b].last && fk >= admit_call_[b]) {
+      drained_[b] = codec_ok_[b] = 1;  // (lsd_run_for: the row counts no more)
+      // a finished row is still stepped below a higher active slot: out of the align stage, so that
+      // k_align stops reading its keys (front-stream order, like the cancel; its delivered frames'
+      // rows are in host memory already, and align_any_ of the buffers in flight is set)
+      if (align_ && slot_align_[b]) {
+        PTTS_HIP(hipMemsetAsync(align_tab_ + b, 0, sizeof(AlignEntry), stream_));
+        slot_align_[b] = 0;
+      }
+    }
     if (valid) valid[b] = ok;
     if (last) last[b] = ok && hf[b].last;
     if (pcm) {
@@ -3165,10 +3212,17 @@ int Engine::lsd_run_for(int B) const {
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                         const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
                         const int* wire_enc, const int* speed, const float* const* prefix, const int* n_prefix,
-                        const int* keep_codec, const int* pitch, const int* gain_cdb, const int* limit) {
+                        const int* keep_codec, const int* pitch, const int* gain_cdb, const int* limit,
+                        const int* align) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
+  for (int i = 0; align && i < n; ++i) {  // section 26: nothing is admitted when a row's align is refused
+    PTTS_REQUIRE(align[i] == 0 || align[i] == 1, "align must be 0 or 1");
+    if (!align[i]) continue;
+    PTTS_REQUIRE(align_, "align needs an align-enabled engine (ptts_align_enable before the first step)");
+    PTTS_REQUIRE(n_ids[i] <= ALIGN_TOKENS, "align: more than PTTS_ALIGN_TOKENS token ids");
+  }
   std::vector<char> seen(max_slots_, 0);
   std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
   std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
@@ -3451,6 +3505,20 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   PTTS_HIP(hipMemcpyAsync(admit_slots_, h_slots_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_st_, h_st_, sizeof(SlotState) * n, hipMemcpyHostToDevice, stream_));
   PTTS_HIP(hipMemcpyAsync(admit_fpos_, h_fp_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  if (align_) {
+    // the rows' {first text position, tokens}: front-owned like fpos_, written on the front stream
+    // behind the front parts already issued and ahead of the row's first; from the admission's
+    // pinned staging (free again: ev_admit_ above). Only entries that change are written, so an
+    // engine whose rows never ask for alignment enqueues nothing here.
+    for (int i = 0; i < n; ++i) {
+      const int na = align && align[i] ? n_ids[i] : 0;
+      if (!na && !slot_align_[slots[i]]) continue;
+      h_align_src_[i] = AlignEntry{voices[i]->F, na};
+      PTTS_HIP(hipMemcpyAsync(align_tab_ + slots[i], h_align_src_ + i, sizeof(AlignEntry), hipMemcpyHostToDevice,
+                              stream_));
+      slot_align_[slots[i]] = na;
+    }
+  }
   if (any_opt) {  // the rows' first backbone input (the prefix's last latent) and RESET_* bits
     memcpy(h_aopt_, ropt.data(), sizeof(int) * n);
     for (int i = 0; i < n; ++i)
@@ -3596,6 +3664,131 @@ void Engine::wire_encode_host(const float* pcm, int n, int rate, int enc, unsign
     throw;
   }
   (void)hipFree(dx), (void)hipFree(dh), (void)hipFree(dy), (void)hipFree(dw);
+}
+
+// ------------------------------------------------------------------ align stage
+void Engine::align_enable(bool on, int layer, unsigned head_mask) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the align stage is chosen on an idle engine before its first step");
+  if (on) {
+    PTTS_REQUIRE(layer >= 0 && layer < NL, "align: layer must be in [0, 5]");
+    PTTS_REQUIRE((head_mask & ((1u << NH) - 1u)) != 0, "align: head_mask selects none of the 16 heads");
+  }
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !align_tab_) {
+    static_assert(sizeof(AlignEntry) == 2 * sizeof(float) && ALIGN_TOKENS == PTTS_ALIGN_TOKENS, "align layout");
+    const size_t B = max_slots_, words = (size_t)NHB * B * ALIGN_ROW;
+    align_tab_ = (AlignEntry*)dalloc(2 * B);
+    h_align_src_ = (AlignEntry*)halloc(sizeof(AlignEntry) * B);
+    slot_align_.assign(B, 0);
+    alignb_ = dalloc(words);
+    h_alignb_ = (float*)halloc(sizeof(float) * words);
+    memset(h_alignb_, 0, sizeof(float) * words);
+  }
+  align_ = on;
+  if (on) {
+    align_layer_ = layer;
+    align_mask_ = head_mask & ((1u << NH) - 1u);
+  }
+}
+
+void Engine::fetch_align(int calls_back, int B, float* out, size_t row_stride, int* n_tokens) {
+  PTTS_REQUIRE(align_, "fetch_align: the engine has no align stage (ptts_align_enable)");
+  PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
+  PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
+  PTTS_REQUIRE(n_tokens != nullptr, "null argument");
+  PTTS_REQUIRE(!out || row_stride >= (size_t)ALIGN_TOKENS, "row_stride must be >= PTTS_ALIGN_TOKENS");
+  // the same frame, rows and event as fetch() of that call; no bookkeeping of its own
+  const int q = calls_back ? prev_hb_ : out_hb_;
+  const int rows = calls_back ? prev_rows_ : out_rows_;
+  const long long fk = calls_back ? prev_k_ : out_k_;
+  if (pipeline_) PTTS_HIP(hipEventSynchronize(ev_back_[q - q % nfr_]));
+  else sync();
+  const int n = fk >= 0 && align_any_[q] ? std::min(B, rows) : 0;  // (no copy for a buffer without a row in the stage)
+  const FrameFlags* hf = (const FrameFlags*)(h_meta_[q] + (size_t)max_slots_ * LDIM);
+  const float* blk = h_alignb_ + (size_t)q * max_slots_ * ALIGN_ROW;
+  for (int b = 0; b < B; ++b) {
+    const float* r = blk + (size_t)b * ALIGN_ROW;
+    int c = 0;
+    if (b < n && hf[b].valid && (cancel_wins_.empty() || !frame_cancelled(b, fk))) memcpy(&c, r, sizeof c);
+    if (c < 0 || c > ALIGN_TOKENS) throw Error(PTTS_ERR_STATE, "fetch_align: corrupt token count");
+    if (c && out) memcpy(out + b * row_stride, r + 1, sizeof(float) * c);
+    n_tokens[b] = c;
+  }
+}
+
+// Align test hook: the product launcher align_step on host operands, modelled on test_attention's
+// step form (one row per slot: row r is slot r). qkv: dense rows [M][3 nh 64] (S == 0) or S slabs;
+// kvh [M][2][nh][cap][64]; pre / pre_len: optional shared prefixes, handed to the launcher as the
+// engine hands them (the kernel must not read them); pos [M]; tab [M][2] = {t0, n}; out
+// [M][ALIGN_ROW] in and out (a row not in the stage keeps its floats).
+void Engine::test_align(int M, int nh, int cap, int S, const float* qkv, const float* kvh, const float* pre,
+                        const int* pre_len, const int* pos, const int* tab, unsigned head_mask, float* out) {
+  PTTS_REQUIRE(ready_, "engine weights not finalized");
+  PTTS_REQUIRE(qkv && kvh && pos && tab && out && (!pre || pre_len), "test_align: bad arguments");
+  PTTS_REQUIRE(M >= 1 && M <= 64 && nh >= 1 && nh <= 16 && cap >= 1 && cap <= 65536 && S >= 0 && S <= 16,
+               "test_align: bad shape");
+  PTTS_REQUIRE((head_mask & ((1u << nh) - 1u)) != 0, "test_align: head_mask selects no head");
+  for (int r = 0; r < M; ++r) {
+    PTTS_REQUIRE(pos[r] >= 0 && pos[r] <= cap, "test_align: step position past the cache");
+    const int t0 = tab[2 * r], n = tab[2 * r + 1];
+    PTTS_REQUIRE(n >= 0 && n <= ALIGN_TOKENS && t0 >= 0 && t0 + n <= cap, "test_align: text keys outside the store");
+  }
+  size_t pre_floats = 0;
+  std::vector<size_t> pre_off(M, 0);
+  if (pre)
+    for (int sl = 0; sl < M; ++sl) {
+      PTTS_REQUIRE(pre_len[sl] >= 0 && pre_len[sl] <= cap, "test_align: bad prefix length");
+      pre_off[sl] = pre_floats;
+      pre_floats += (size_t)2 * nh * pre_len[sl] * 64;
+    }
+  sync();
+  const int d = nh * 64, Sk = std::max(S, 1);
+  std::vector<void*> allocs;
+  auto release = [&]() {
+    for (void* p : allocs) (void)hipFree(p);
+  };
+  try {
+    auto dal = [&](size_t bytes) {
+      void* p = nullptr;
+      PTTS_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+      allocs.push_back(p);
+      return p;
+    };
+    auto up = [&](const void* src, size_t bytes) {
+      void* p = dal(bytes);
+      PTTS_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, stream_));
+      return p;
+    };
+    AlignArgs a{};
+    a.P = (const float*)up(qkv, sizeof(float) * Sk * M * 3 * d);
+    a.S = Sk;
+    a.M = M;
+    a.nh = nh;
+    a.pos = (const int*)up(pos, sizeof(int) * M);
+    a.kv = KvStore{(float*)up(kvh, sizeof(float) * M * 2 * nh * cap * 64), (long)2 * nh * cap * 64, cap};
+    std::vector<const float*> prep(M, nullptr);
+    if (pre) {
+      const float* dpre = (const float*)up(pre, sizeof(float) * pre_floats);
+      for (int sl = 0; sl < M; ++sl) prep[sl] = dpre + pre_off[sl];
+      a.kv.pre = (const float* const*)up(prep.data(), sizeof(float*) * M);
+      a.kv.pre_len = (const int*)up(pre_len, sizeof(int) * M);
+    }
+    float* drope = (float*)dal(sizeof(float) * cap * 64);
+    rope_table(drope, cap, stream_);
+    a.rope = drope;
+    a.tab = (const AlignEntry*)up(tab, sizeof(AlignEntry) * M);
+    a.head_mask = head_mask;
+    a.out = (float*)up(out, sizeof(float) * M * ALIGN_ROW);
+    align_step(a, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(out, a.out, sizeof(float) * M * ALIGN_ROW, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    release();
+    throw;
+  }
+  release();
 }
 
 // ------------------------------------------------------------------ tempo stage
@@ -3983,6 +4176,10 @@ void Engine::slot_close(int slot) {
   PTTS_HIP(hipMemcpyAsync(st_ + slot, h_st_, sizeof s, hipMemcpyHostToDevice, stream_));
   for (int q = 0; q < NHB; ++q)  // drop a pending frame of the slot
     PTTS_HIP(hipMemsetAsync(flags_[q] + slot, 0, sizeof(FrameFlags), stream_));
+  if (align_ && slot_align_[slot]) {
+    PTTS_HIP(hipMemsetAsync(align_tab_ + slot, 0, sizeof(AlignEntry), stream_));
+    slot_align_[slot] = 0;
+  }
   if (share_voice_ && slot_voice_[slot]) {  // the closed row (still stepped, discarded) reads its own rows
     h_vpre_[slot] = nullptr;
     h_vlen_[slot] = 0;
@@ -4019,6 +4216,10 @@ void Engine::slots_cancel(int n, const int* slots) {
     const int slot = slots[i];
     if (drained_[slot] || cancelled_[slot]) continue;  // idle, finished or never admitted: nothing to stop
     PTTS_HIP(hipMemcpyAsync(st_ + slot, h_idle_, sizeof(SlotState), hipMemcpyHostToDevice, stream_));
+    if (align_ && slot_align_[slot]) {  // out of the align stage, in the same stream order (no staging)
+      PTTS_HIP(hipMemsetAsync(align_tab_ + slot, 0, sizeof(AlignEntry), stream_));
+      slot_align_[slot] = 0;
+    }
     // admitted inside a multi-frame pass and not started yet: it never starts
     act_slots_.erase(std::remove(act_slots_.begin(), act_slots_.end(), slot), act_slots_.end());
     cancelled_[slot] = 1;

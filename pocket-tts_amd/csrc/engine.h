@@ -89,7 +89,7 @@ class Engine {
                   const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
                   const int* wire_enc = nullptr, const int* speed = nullptr, const float* const* prefix = nullptr,
                   const int* n_prefix = nullptr, const int* keep_codec = nullptr, const int* pitch = nullptr,
-                  const int* gain_cdb = nullptr, const int* limit = nullptr);
+                  const int* gain_cdb = nullptr, const int* limit = nullptr, const int* align = nullptr);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);
@@ -165,6 +165,18 @@ class Engine {
   // the seam alone: the stage's chunk encoder on n 16-bit samples at `rate`
   void flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes);
 
+  // Align stage (ptts_align_enable / ptts_fetch_align): with it on, the front
+  // part has one more launch behind layer `layer`'s step attention, which writes the text-attention
+  // row (mean over the heads of head_mask) of every row admitted with align = 1 into the frame's
+  // hand-off buffer; the rows travel with the frame. Valid before the engine's first call only.
+  void align_enable(bool on, int layer, unsigned head_mask);
+  bool align() const { return align_; }
+  // the alignment rows of the frame fetch(.., calls_back) returns: n_tokens[b] floats at out + b * row_stride
+  void fetch_align(int calls_back, int B, float* out, size_t row_stride, int* n_tokens);
+  // the seam alone: align_step on host operands (ptts_test_align)
+  void test_align(int M, int nh, int cap, int S, const float* qkv, const float* kvh, const float* pre,
+                  const int* pre_len, const int* pos, const int* tab, unsigned head_mask, float* out);
+
   double time_op(int B, const std::string& name, int reps);
   // GEMM-core test hook (ptts_test_gemm): Y = X W^T on tile `layout` (host buffers)
   void test_gemm(int layout, int M, int N, int K, int splits, int tail_S, const float* X, const float* Wt, float* Y);
@@ -238,8 +250,9 @@ class Engine {
   void wait_unless_done(hipStream_t s, hipEvent_t e);
   void copy_out(int B, int hb, hipStream_t s);
   void push_rr(std::vector<Op>& ops, const std::string& name, const RowReduceArgs& r);
+  // align_out: the step's alignment rows (build_front of an align-enabled engine), or nullptr
   void flow_layers(std::vector<Op>& ops, int M, RowMap map, bool step, bool out_norm, const std::string& tag,
-                   const FlowBufs& fb);
+                   const FlowBufs& fb, float* align_out = nullptr);
   void linear_split(std::vector<Op>& ops, const std::string& name, const float* X, long ldx, int M, const float* Wt,
                     int N, int K, int* S_out, const FlowBufs& fb);
   void conv_op(std::vector<Op>& ops, const std::string& name, const float* X, int B, int T_in, int cin, const float* H,
@@ -533,6 +546,20 @@ class Engine {
   size_t wire_head_bytes() const { return ((size_t)max_slots_ * nfr_ * sizeof(int) + 127) / 128 * 128; }
   size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * wire_chunk_max(); }
   static int wire_rate_index(int rate);
+
+  // ---- align stage (align_enable): front-owned, one FlowLM layer
+  bool align_ = false;
+  int align_layer_ = 0;
+  unsigned align_mask_ = 0;
+  AlignEntry* align_tab_ = nullptr;    // [max_slots] {first text position, tokens} (n == 0: not in the stage)
+  AlignEntry* h_align_src_ = nullptr;  // pinned staging of one admission's entries
+  std::vector<int> slot_align_;        // host mirror of the entries' n
+  float* alignb_ = nullptr;            // [NHB][max_slots][ALIGN_ROW]: hand-off buffer q's rows
+  float* h_alignb_ = nullptr;          // pinned copy
+  // per hand-off buffer: a row of the front part that filled it was in the stage (copy_out copies
+  // the buffer's block, fetch_align reads it)
+  bool align_any_[NHB] = {};
+  float* align_block(int hb) const { return alignb_ + (size_t)hb * max_slots_ * ALIGN_ROW; }
 
   // ---- voice cloning: everything a clone writes but the voice itself lives in a VoiceWs, so a
   // clone shares only read-only weights and tables with the step pipeline

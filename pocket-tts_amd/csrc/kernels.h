@@ -413,6 +413,31 @@ void attention_step_qkv(const float* P, int S, int M, int nh, RowMap map, KvStor
 // f_i = exp(-ln(1e4) * 2i / 64), i < 32, pos < npos - the values the step kernels would compute.
 void rope_table(float* tab, int npos, hipStream_t s);
 
+// Word alignment: one layer's text-attention row per step row, from the
+// operands the step attention of that layer has just read. Row r is slot r at position pos[r]. A
+// slot with tab[r] = {t0, n}, n >= 1, gets, per head of head_mask, the softmax over j < n of
+// (q_h . K_h[t0 + j]) / 8 with q_h the slab sum of its q column rotated at min(pos, cap - 1) (the
+// attention kernel's q, bit for bit) and K_h the slot's own store (never KvStore::pre: text keys
+// lie at positions >= F), and the mean of those rows over the selected heads. out row r: the int
+// count n, then ALIGN_TOKENS floats (a[0..n), zeros behind). n == 0 (or an entry that does not fit
+// the store): count 0, the floats are left alone.
+constexpr int ALIGN_TOKENS = 128;
+constexpr int ALIGN_ROW = 1 + ALIGN_TOKENS;  // 4-byte words per row of the alignment block
+struct AlignEntry {
+  int t0, n;
+};
+struct AlignArgs {
+  const float* P;  // [S][M][3 nh 64] QKV slabs (S == 1: dense rows)
+  int S, M, nh;
+  const int* pos;  // [M] the rows' positions
+  KvStore kv;      // the layer's store (pre / pre_len unused)
+  const float* rope;
+  const AlignEntry* tab;  // [M]
+  unsigned head_mask;
+  float* out;  // [M][ALIGN_ROW]
+};
+void align_step(const AlignArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // Per-slot generation bookkeeping (device resident so the step can be replayed as a graph).
 // The step is split into a FRONT part (FlowLM + flow head: produces this step's latent and

@@ -2806,6 +2806,109 @@ void rope_table(float* tab, int npos, hipStream_t s) {
   hipLaunchKernelGGL(k_rope_table, dim3((unsigned)((npos * 32L + 255) / 256)), dim3(256), 0, s, tab, npos);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Word alignment: the step query's softmax over the row's text keys, for
+// one layer, as a launch of its own behind that layer's step attention. One 256-thread workgroup
+// per row; the selected heads are dealt to the 4 waves in rounds (the i-th selected head goes to
+// wave i % 4 in round i / 4). A wave forms q_h as k_attn_decode_qkv does (slab sum in z order from
+// 0, the fmaf RoPE form), reads its head's n keys with the same 1-KB wave loads (load i: lane l
+// holds dims 4 (l % 16) .. of key 4 i + l / 16), and leaves the head's softmax row in LDS; the
+// heads are then averaged in ascending head order. All loads are ordinary cached loads: the text
+// keys are read again by this launch at every step of the utterance (and the slabs and the RoPE
+// row were read by the attention launch right before), so the lines are wanted in L2.
+// Every address is formed from clamped indices: an entry that does not fit the store counts 0.
+// ---------------------------------------------------------------------------------------------
+template <int SMAX>
+__global__ __launch_bounds__(256) void k_align(AlignArgs a) {
+  front_prio();
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(1))) f4v* gf4p;
+  __shared__ float s_sc[4][ALIGN_TOKENS];
+  __shared__ float s_p[16][ALIGN_TOKENS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, c4 = (lane & 15) * 4;
+  const int row = blockIdx.x;
+  const AlignEntry en = a.tab[row];
+  const int cap = a.kv.cap, n = en.n, t0 = en.t0;
+  float* orow = a.out + (long)row * ALIGN_ROW;
+  if (n <= 0 || n > ALIGN_TOKENS || t0 < 0 || t0 > cap - n) {  // not in the stage (uniform)
+    if (tid == 0) *reinterpret_cast<int*>(orow) = 0;
+    return;
+  }
+  const unsigned mask = a.head_mask & (a.nh >= 32 ? ~0u : (1u << a.nh) - 1u);
+  const int nsel = __popc(mask);
+  const int qp = min(max(a.pos[row], 0), cap - 1);
+  const int d = a.nh * 64, ld = 3 * d;
+  const long zs = (long)a.M * ld;
+  const float2 cssn = *reinterpret_cast<const float2*>(a.rope + (long)qp * 64 + 2 * (lane >> 1));
+  for (int r0 = 0; r0 < nsel; r0 += 4) {
+    const int idx = r0 + wave;  // this wave's head: the idx-th set bit of the mask
+    int head = -1;
+    {
+      unsigned m = mask;
+      for (int i = 0; i < idx && m; ++i) m &= m - 1;
+      if (idx < nsel) head = __builtin_ctz(m);
+    }
+    if (head >= 0) {  // wave-uniform
+      const float* pr = a.P + (long)row * ld + head * 64 + lane;
+      float pz[SMAX];
+#pragma unroll
+      for (int z = 0; z < SMAX; ++z) pz[z] = pr[(long)max(min(z, a.S - 1), 0) * zs];
+      float qs = 0.f;
+#pragma unroll
+      for (int z = 0; z < SMAX; ++z) qs = z < a.S ? qs + pz[z] : qs;
+      // RoPE of the pair (2i, 2i+1), one dim per lane: y0 = fma(x0, c, -(x1 s)), y1 = fma(x1, c, x0 s)
+      const float xo = __shfl_xor(qs, 1, 64);
+      const float t = __fmul_rn(xo, cssn.y);
+      const float qr = __fmaf_rn(qs, cssn.x, (lane & 1) ? t : -t);
+      const float4 q = make_float4(__shfl(qr, c4, 64), __shfl(qr, c4 + 1, 64), __shfl(qr, c4 + 2, 64),
+                                   __shfl(qr, c4 + 3, 64));
+      const uintptr_t kb = reinterpret_cast<uintptr_t>(a.kv.base + (long)row * a.kv.slot_stride +
+                                                       (long)head * cap * 64 + (long)t0 * 64);
+      for (int base = 0; base < n; base += 32) {
+        f4v k[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int j = min(base + 4 * i + g, n - 1);
+          k[i] = *(gf4p)(kb + (uintptr_t)((long)j * 64 + c4) * sizeof(float));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float part = q.x * k[i].x + q.y * k[i].y + q.z * k[i].z + q.w * k[i].w;
+          const float sc = row16_sum(part) * 0.125f;
+          if ((lane & 15) == 0) s_sc[wave][base + 4 * i + g] = sc;  // base + 4 i + g < ALIGN_TOKENS
+        }
+      }
+    }
+    __syncthreads();
+    if (head >= 0) {
+      const float v0 = lane < n ? s_sc[wave][lane] : -INFINITY;
+      const float v1 = lane + 64 < n ? s_sc[wave][lane + 64] : -INFINITY;
+      const float mx = wave_max(fmaxf(v0, v1));  // n >= 1: finite
+      const float e0 = lane < n ? expf(v0 - mx) : 0.f, e1 = lane + 64 < n ? expf(v1 - mx) : 0.f;
+      const float sum = wave_sum(e0 + e1);
+      s_p[head][lane] = e0 / sum;
+      s_p[head][lane + 64] = e1 / sum;
+    }
+    __syncthreads();
+  }
+  if (tid < ALIGN_TOKENS) {
+    float acc = 0.f;
+    for (unsigned m = mask; m; m &= m - 1) acc += s_p[__builtin_ctz(m)][tid];  // ascending head order
+    orow[1 + tid] = tid < n ? acc / (float)nsel : 0.f;
+  }
+  if (tid == 0) *reinterpret_cast<int*>(orow) = n;
+}
+
+void align_step(const AlignArgs& a, hipStream_t s) {
+  if (a.S < 1 || a.S > 16) throw std::runtime_error("align_step: 1 to 16 slabs");
+  if (a.M < 1 || a.nh < 1 || a.nh > 16 || !(a.head_mask & ((1u << a.nh) - 1u)))
+    throw std::runtime_error("align_step: no row, or no head of the mask among the layer's");
+  if (a.S <= 8) hipLaunchKernelGGL(k_align<8>, dim3(a.M), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_align<16>, dim3(a.M), dim3(256), 0, s, a);
+}
+
 void attention16_qkv(const float* qkv, int M, int nh, RowMap map, KvStore kv, int window, float* O, hipStream_t s) {
   if (map.tab != nullptr || map.rps != 16) throw std::runtime_error("attention16_qkv: needs 16 rows per slot");
   if ((kv.cap & (kv.cap - 1)) != 0 || kv.cap < window + 16)

@@ -1,7 +1,7 @@
 /* test_hooks.h - C-ABI test hooks of libpocket_tts_hip.so that live beside the library's sources,
  * not under include/: include/pocket_tts_probe.h holds a fixed list of hooks (tests/test_boundary.py
  * compares the header and the Python binding's signature table with it), so a hook added for one
- * kernel's test is declared here and bound by its caller (pocket_tts_amd.Engine.test_row_reduce).
+ * kernel's test is declared here and bound by its caller (pocket_tts_amd.Engine.test_row_reduce, .test_align).
  * Same conventions as pocket_tts.h (status codes, the thread-local last-error message).
  */
 #ifndef POCKET_TTS_TEST_HOOKS_H
@@ -26,6 +26,21 @@ int ptts_test_row_reduce(ptts_engine* e, int m, int n, int splits, int act, int 
                          const float* p, const float* bias, const float* gate, const float* r, const float* ln_w,
                          const float* ln_b, const float* mscale, const float* mshift, float* y, float* h,
                          float* hfrag);
+
+
+/* Test hook of the align stage (no reference counterpart): the product launcher (k_align) on host
+ * operands, in ptts_test_attention's PTTS_ATTN_FLOW_STEP form (pocket_tts_probe.h): row r is slot r.
+ *   qkv  [m][3 nh 64] dense rows (splits == 0) or [splits][m][3 nh 64] partial slabs;
+ *   kv   [m][2][nh][cap][64], read only;
+ *   pre  optional shared prefixes as in ptts_test_attention (handed to the launcher as the engine
+ *        hands them; the text keys are never read from them);
+ *   pos  [m] the rows' positions (<= cap; the query rotates at min(pos, cap - 1));
+ *   tab  [m][2] = {t0, n}: the first text position and the token count (n == 0: not in the stage);
+ *   out  [m][1 + PTTS_ALIGN_TOKENS] 4-byte words, in and out: the int count, then the row (zeros
+ *        behind n); a row with n == 0 gets count 0 and keeps its floats. */
+int ptts_test_align(ptts_engine* e, int m, int nh, int cap, int splits, const float* qkv, const float* kv,
+                    const float* pre, const int* pre_len, const int* pos, const int* tab, unsigned head_mask,
+                    float* out);
 
 #ifdef __cplusplus
 }

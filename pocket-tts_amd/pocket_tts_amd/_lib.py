@@ -25,6 +25,7 @@ WIRE_CHUNK_MAX = 8192  # PTTS_WIRE_CHUNK_MAX
 WIRE_CHUNK_MAX_TEMPO = 22528  # PTTS_WIRE_CHUNK_MAX_TEMPO
 WIRE_CHUNK_MAX_LEVEL = 23552  # PTTS_WIRE_CHUNK_MAX_LEVEL
 WIRE_RATES = (8000, 16000, 24000, 44100, 48000)
+ALIGN_TOKENS = 128  # PTTS_ALIGN_TOKENS
 ABI_VERSION = 6  # PTTS_ABI_VERSION of include/pocket_tts.h that the structs below mirror
 
 F32P = C.POINTER(C.c_float)
@@ -99,6 +100,14 @@ class SlotOpts4(C.Structure):
     ]
 
 
+class SlotOpts5(C.Structure):
+    """ptts_slot_opts with align (64 bytes): the struct of a row in the align stage."""
+    _fields_ = SlotOpts4._fields_ + [
+        ("align", C.c_int),
+        ("reserved2", C.c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol include/pocket_tts.h (the boundary) and
 # include/pocket_tts_probe.h (measurement / test hooks) declare
 SIGNATURES = [
@@ -151,6 +160,8 @@ SIGNATURES = [
                                        C.POINTER(GenParams), C.c_void_p]),
     ("ptts_wire_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_fetch_wire", C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_size_t, C.POINTER(C.c_int)]),
+    ("ptts_align_enable", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint]),
+    ("ptts_fetch_align", C.c_int, [C.c_void_p, C.c_int, C.c_int, F32P, C.c_size_t, C.POINTER(C.c_int)]),
     ("ptts_wire_len", C.c_long, [C.c_long, C.c_int, C.c_int]),
     ("ptts_wire_encode", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, U8P]),
     ("ptts_tempo_enable", C.c_int, [C.c_void_p, C.c_int]),

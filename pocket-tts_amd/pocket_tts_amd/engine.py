@@ -9,7 +9,7 @@ import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_LEVEL, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SlotOpts, SlotOpts2, SlotOpts3, SlotOpts4, check, fptr, lib, u8ptr)
+                   SlotOpts, SlotOpts2, SlotOpts3, SlotOpts4, SlotOpts5, ALIGN_TOKENS, check, fptr, lib, u8ptr)
 from .audio import level_cdb, pitch_cents, speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
@@ -64,6 +64,10 @@ class GenerationParams:
     # latents (values fetch() returned), and with keep_codec on the codec state its slot ended on.
     prefix_latents: np.ndarray | None = None
     keep_codec: bool = False
+    # word alignment (align-enabled engines): every frame of the row also
+    # carries the attention its FlowLM step paid to the row's text tokens (Engine.fetch_align). At
+    # most ALIGN_TOKENS token ids. No other output of the row depends on it.
+    align: bool = False
 
     def prefix(self) -> np.ndarray | None:
         """The prefix as a contiguous [n, 32] float32 array; None: no prefix."""
@@ -161,7 +165,8 @@ class Engine:
                  cfg_yaml: str | None = None, back_frames: int = 1, back_bf16: bool = False,
                  back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
                  tempo: bool = False, flac: bool = False, pitch: bool = False, level: bool = False,
-                 level_ceiling_db: float = -1.0):
+                 level_ceiling_db: float = -1.0, align: bool = False, align_layer: int = 0,
+                 align_heads: int = 0xFFFF):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -187,7 +192,10 @@ class Engine:
         .limit have their wire bytes scaled and peak-limited to level_ceiling_db (dBFS, -40 .. 0) on
         the GPU.
         flac=True (ptts_flac_enable; needs wire): rows admitted with encoding "flac" get FLAC frames
-        of their 16-bit chunks, encoded on the GPU."""
+        of their 16-bit chunks, encoded on the GPU.
+        align=True (ptts_align_enable): rows admitted with GenerationParams.align get, with every
+        frame, their step's text-attention row of FlowLM layer align_layer (0 .. 5), averaged over
+        the heads of the bit mask align_heads (fetch_align)."""
         if back_mfma is None:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
@@ -249,6 +257,15 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        self.align_enabled = bool(align)
+        self.align_layer, self.align_heads = int(align_layer), int(align_heads)
+        if align:
+            try:
+                check(lib().ptts_align_enable(self.handle, 1, self.align_layer, self.align_heads & 0xFFFFFFFF))
+            except Exception:
+                self.close()
+                raise
+        self._align_buf = self._align_n = None
         self.wire_chunk_max = WIRE_CHUNK_MAX_LEVEL if level else WIRE_CHUNK_MAX_TEMPO if tempo else WIRE_CHUNK_MAX
         self._wire_buf = self._wire_n = None
 
@@ -309,6 +326,36 @@ class Engine:
                                         fptr(pre_cat), iptr(pre_len), slot0, rps, p0, iptr(pos), iptr(tab), iptr(ptab),
                                         mpad, fptr(q), fptr(o)))
         return o, kv_out, q
+
+    def test_align(self, qkv: np.ndarray, kv: np.ndarray, pos, tab, head_mask: int, out: np.ndarray, pre=None):
+        """Align test hook (ptts_test_align): the product launcher on host operands, row r = slot r.
+        qkv [m][3 nh 64] dense rows or [S][m][3 nh 64] slabs; kv [m][2][nh][cap][64]; pos [m]; tab
+        [m][2] = {t0, n}; out [m][1 + ALIGN_TOKENS] float32 words going in (sentinels). Returns
+        (counts [m] int32, rows [m][ALIGN_TOKENS] float32) as the call left them."""
+        qkv = np.ascontiguousarray(qkv, np.float32)
+        kv = np.ascontiguousarray(kv, np.float32)
+        m, two, nh, cap, hd = kv.shape
+        splits = qkv.shape[0] if qkv.ndim == 3 else 0
+        if two != 2 or hd != 64 or qkv.shape[-1] != 3 * nh * 64 or qkv.shape[-2] != m:
+            raise ValueError("test_align: qkv / kv shapes disagree")
+        pos = np.ascontiguousarray(pos, np.int32).reshape(m)
+        tab = np.ascontiguousarray(tab, np.int32).reshape(m, 2)
+        o = np.array(out, np.float32, order="C").reshape(m, 1 + ALIGN_TOKENS)
+        pre_cat = pre_len = None
+        if pre is not None:
+            parts = [np.zeros((2, nh, 0, 64), np.float32) if p is None else np.ascontiguousarray(p, np.float32)
+                     for p in pre]
+            pre_len = np.array([p.shape[2] for p in parts], np.int32)
+            pre_cat = np.concatenate([p.ravel() for p in parts] + [np.zeros(4, np.float32)])
+        i32 = C.POINTER(C.c_int32)
+        # declared in csrc/test_hooks.h, not in the headers whose symbols _lib.SIGNATURES mirrors: bound here
+        fn = lib().ptts_test_align
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 4 + [F32P] * 3 + [i32] * 3 + [C.c_uint, F32P]
+        check(fn(self.handle, m, nh, cap, splits, fptr(qkv), fptr(kv), fptr(pre_cat),
+                                    None if pre_len is None else pre_len.ctypes.data_as(i32), pos.ctypes.data_as(i32),
+                                    tab.ctypes.data_as(i32), int(head_mask) & 0xFFFFFFFF, fptr(o)))
+        return o[:, 0].copy().view(np.int32), o[:, 1:].copy()
 
     def test_row_reduce(self, p: np.ndarray, *, bias=None, gate=None, r=None, act: int = 0, ln: bool = False,
                         eps: float = 1e-5, ln_w=None, ln_b=None, mscale=None, mshift=None, hfrag: bool = False,
@@ -497,7 +544,7 @@ class Engine:
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
         if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec or params.cents() \
-                or params.level() != (0, 0):
+                or params.level() != (0, 0) or params.align:
             return self.open_many([slot], [voice], [ids], [params])
         a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
         cp = params.to_c()
@@ -516,6 +563,15 @@ class Engine:
         lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
         i32 = C.POINTER(C.c_int32)
         pre = [p.prefix() for p in params_list]  # (kept alive until the call returns)
+        if any(p.align for p in params_list):  # a row in the align stage: the 64-byte struct
+            opts = (SlotOpts5 * n)(*[SlotOpts5(C.sizeof(SlotOpts5), int(lsd[i]), *p.opts(),
+                                               pre[i].ctypes.data if pre[i] is not None else None,
+                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents(),
+                                               0, *p.level(), int(bool(p.align)), 0)
+                                     for i, p in enumerate(params_list)])
+            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
+            return
         if any(p.level() != (0, 0) for p in params_list):  # a gain or limit: the 56-byte struct
             opts = (SlotOpts4 * n)(*[SlotOpts4(C.sizeof(SlotOpts4), int(lsd[i]), *p.opts(),
                                                pre[i].ctypes.data if pre[i] is not None else None,
@@ -617,6 +673,17 @@ class Engine:
         check(lib().ptts_fetch_wire(self.handle, calls_back, n_rows, u8ptr(self._wire_buf), self.wire_chunk_max,
                                     self._wire_n.ctypes.data_as(C.POINTER(C.c_int))))
         return [self._wire_buf[b, : self._wire_n[b]].tobytes() for b in range(n_rows)]
+
+    def fetch_align(self, n_rows: int, calls_back: int = 0) -> list[np.ndarray]:
+        """The alignment rows of the frame fetch(n_rows, calls_back) returns (ptts_fetch_align): one
+        float32 array per row over the row's tokens, empty for a row with no valid frame or not in
+        the align stage."""
+        if self._align_buf is None:
+            self._align_buf = np.zeros((self.max_slots, ALIGN_TOKENS), np.float32)
+            self._align_n = np.zeros(self.max_slots, np.int32)
+        check(lib().ptts_fetch_align(self.handle, calls_back, n_rows, fptr(self._align_buf), ALIGN_TOKENS,
+                                     self._align_n.ctypes.data_as(C.POINTER(C.c_int))))
+        return [self._align_buf[b, : self._align_n[b]].copy() for b in range(n_rows)]
 
     def encode_wire(self, pcm: np.ndarray, sample_rate: int = 24000, encoding="pcm_s16le") -> bytes:
         """Whole-signal f32 PCM at 24 kHz -> wire bytes on the GPU (ptts_wire_encode): the resampler

@@ -34,6 +34,16 @@ HTTP (`create_app`, FastAPI; routes of pocket-tts-cli/src/server/routes.rs:20-30
 Wire formats follow crates/pocket-tts/src/audio.rs:110-185 (clamp to [-1, 1], x 32767,
 truncate to i16; 16-bit mono RIFF/WAVE).
 
+Word timestamps (`--align`, off by default, with `--align-layer` and `--align-heads`; DESIGN.md
+section 26): /generate and /v1/audio/speech take `timestamps: true` and then answer
+`application/json`: {"audio": base64 of the bytes the route would have sent, "content_type",
+"sample_rate", "words": [{"word", "start", "end"}]} (seconds of that audio; the rule is align.py).
+The rows deliver one text-attention row per frame from the engine's align stage; a long-form
+request's segments are offset by the samples delivered before them, pauses included. 400 for
+`timestamps` on /stream, with `continuity` (under `--continuity`: send `continuity: false`), with
+`token_ids`, with FLAC, for a row of more than 128 tokens (checked here, so that the engine never
+refuses a batched admission over it), or without `--align`.
+
 Per-request output format (`--wire`, the default; no reference counterpart: the reference emits
 24 kHz only): /generate, /stream and /v1/audio/speech also take `sample_rate` (8000, 16000, 24000,
 44100, 48000) and `encoding` (`pcm_s16le`, `ulaw`, `alaw`); one of them alone defaults the other
@@ -138,7 +148,7 @@ from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
-from ._lib import FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
+from ._lib import ALIGN_TOKENS, FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
 from .audio import (ENCODINGS, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, pitch_cents, pitch_plan, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
 from .engine import GenerationParams, Voice
@@ -283,6 +293,13 @@ class _Call:
         self.done.set()
 
 
+def item_samples(item, wire) -> int:
+    """Samples of one delivered item: wire bytes of the format `wire` (rate, encoding), or f32 frames."""
+    if isinstance(item, (bytes, bytearray)):
+        return len(item) // (1 if wire is not None and wire[1] in ("ulaw", "alaw") else 2)
+    return int(np.size(item))
+
+
 class _Consumer:
     """The consumer side of a Request or a RequestGroup: items from `out` until the end marker."""
 
@@ -368,8 +385,14 @@ class Request(_Consumer):
     lat: list | None = None
     pred: object = None
     own: np.ndarray | None = None
+    # timestamps: the alignment row of every frame of a row in the align stage
+    # (None: not in it), and the samples handed over so far at the rate they are delivered at
+    align_rows: list | None = None
+    units: int = 0
 
     def __post_init__(self):
+        if getattr(self.params, "align", False):
+            self.align_rows = []
         rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
         self.speed = self.params.opts()[2] if hasattr(self.params, "opts") else 0
         self.pitch = self.params.cents() if hasattr(self.params, "cents") else 0
@@ -381,6 +404,8 @@ class Request(_Consumer):
         """Driver side: hand over a frame (np.ndarray), the end marker (None) or an error."""
         if item is None:
             self.ended = True
+        elif not isinstance(item, BaseException):
+            self.units += item_samples(item, self.wire)
         g = self.group
         if g is not None:  # a segment of a long-form request: its group puts the items in text order
             g.deliver(self, item)
@@ -745,7 +770,7 @@ class BatchScheduler:
             req.times["first"] = time.time()
             req.put(pcm)
 
-    def _deliver(self, res, rows, wire=None, fstep: int = 0) -> list[int]:
+    def _deliver(self, res, rows, wire=None, fstep: int = 0, align=None) -> list[int]:
         """wire: the call's Engine.fetch_wire chunks (a call with wire rows): those rows get their
         bytes untouched; numpy is called for rows without a format only (by their consumers).
         fstep: the step that computed the call's frame."""
@@ -758,6 +783,8 @@ class BatchScheduler:
                     self.stale.discard(slot)
                 if req.lat is not None:  # a continuity segment: what its successor is forced through
                     req.lat.append(np.array(res.latents[slot], np.float32))
+                if req.align_rows is not None:  # (frame 0's row comes with the regular frame, preview or not)
+                    req.align_rows.append(np.array(align[slot], np.float32))
                 if req.preview == 1:  # frame 0, already delivered from the preview
                     req.preview = 2
                 else:
@@ -849,9 +876,12 @@ class BatchScheduler:
                     wire = None
                     if any(r.wire is not None for r in self.active.values()):
                         wire = self.engine.fetch_wire(issued[0], calls_back=cb)
+                    arows = None
+                    if any(r.align_rows is not None for r in self.active.values()):
+                        arows = self.engine.fetch_align(issued[0], calls_back=cb)
                     self._deliver_previews()  # those that completed while fetch() waited: ahead of it
                     fstep = self.steps - len(issued) - self.lag
-                    done = self._deliver(res, issued.popleft(), wire, fstep)
+                    done = self._deliver(res, issued.popleft(), wire, fstep, arows)
                     if done:
                         with self.cv:
                             for slot in done:
@@ -1086,6 +1116,7 @@ class TTSService:
         self.flac = self.wire and bool(getattr(eng, "flac_enabled", False))  # and encode FLAC (--flac)
         self.pitch = self.tempo and bool(getattr(eng, "pitch_enabled", False))  # and shift the pitch (--pitch)
         self.level = self.wire and bool(getattr(eng, "level_enabled", False))  # and set the level (--volume)
+        self.align = bool(getattr(eng, "align_enabled", False))  # and deliver alignment rows (--align)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -1108,8 +1139,11 @@ class TTSService:
                 max_frames: int | None = None, sample_rate: int | None = None,
                 encoding: str | None = None, long_form: bool | None = None, speed: float | None = None,
                 continuity: bool | None = None, pitch: float | None = None, volume_db: float | None = None,
-                limit: bool | None = None) -> Request:
-        """volume_db: -24 .. 24 dB (rounded to hundredths), limit: run the row through the peak limiter
+                limit: bool | None = None, timestamps: bool | None = None) -> Request:
+        """timestamps: the rows also deliver their alignment rows (DESIGN.md section 26), for words();
+        a text request on a server with the align stage (--align), not with continuity (that row's
+        text also holds the previous chunk's ids) and not with token_ids (they carry no words).
+        volume_db: -24 .. 24 dB (rounded to hundredths), limit: run the row through the peak limiter
         even without a gain; the row's wire bytes are scaled and limited to the server's ceiling on the
         GPU (None / 0 and None / False: unchanged).
         continuity (None: the server's default, --continuity): the long-form
@@ -1129,6 +1163,20 @@ class TTSService:
         if continuity and token_ids is not None:
             raise ValueError("continuity needs `text`: token_ids are never split")
         chain = token_ids is None and (self.continuity if continuity is None else bool(continuity))
+        if timestamps:
+            if not self.align:
+                raise ValueError("this server runs without the align stage (--align): timestamps are not available")
+            if token_ids is not None:
+                raise ValueError("timestamps need `text`: token_ids carry no words")
+            if chain:
+                raise ValueError("timestamps with continuity are not available: a continuing row's text also holds "
+                                 "the previous chunk's ids"
+                                 + (" (this server's default is --continuity: send `continuity: false`)"
+                                    if continuity is None else ""))
+            if encoding == "flac":
+                raise ValueError("timestamps with flac are not available")
+            if not hasattr(self.tokenizer, "pieces"):
+                raise ValueError("timestamps need a tokenizer that names its pieces")
         if sample_rate is not None or encoding is not None:
             if sample_rate is not None and sample_rate not in WIRE_RATES:
                 raise ValueError(f"sample_rate must be one of {list(WIRE_RATES)}")
@@ -1192,6 +1240,13 @@ class TTSService:
                 mgl, fae = max_frames or max_gen_len(prepared), estimate_frames_after_eos(text)
         else:
             raise ValueError("text or token_ids required")
+        if timestamps:  # refused here, not by the engine: its refusal fails a whole batched admission
+            longest = max((sg[1].size for sg in segments if sg[0] == "text"), default=0) if segments is not None \
+                else ids.size
+            if longest > ALIGN_TOKENS:
+                raise ValueError(f"timestamps: a row of {longest} tokens exceeds the align stage's {ALIGN_TOKENS}"
+                                 + ("" if segments is not None else " (send `long_form: true`: every sentence chunk "
+                                                                    "is a row of at most 50 tokens)"))
         name = voice or self.default_voice
         # not a registered name: base64 audio (decoded outside the lock), or refused
         clip = None if name in self.voices else self.voice_clip(name)
@@ -1203,7 +1258,7 @@ class TTSService:
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
                                                             lsd_steps, sample_rate, encoding, speed, pitch,
-                                                            volume_db, limit))
+                                                            volume_db, limit, bool(timestamps)))
                         if sg[0] == "text" else sg for sg in segments]
                 wire = None  # (pauses: silence of their stated duration, whatever the speed)
                 if sample_rate is not None or encoding is not None or speed is not None or pitch is not None \
@@ -1213,16 +1268,41 @@ class TTSService:
                     return self.scheduler.submit_group(segs, target, wire, continuity=True)
                 return self.scheduler.submit_group(segs, target, wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       sample_rate, encoding, speed, pitch, volume_db, limit)
+                                       sample_rate, encoding, speed, pitch, volume_db, limit, bool(timestamps))
+
+    def words(self, r) -> list[dict]:
+        """[{"word", "start", "end"}] of a finished timestamps request (its audio consumed), in seconds
+        of the audio delivered: align.timestamps per text segment, each offset by the samples handed
+        over before it (a long-form request's pauses included)."""
+        from . import align as _align
+
+        rate = r.wire[0] if r.wire else SAMPLE_RATE
+        out, at = [], 0
+        for it in (r.items if isinstance(r, RequestGroup) else [r]):
+            if not isinstance(it, Request):
+                at += item_samples(it, r.wire)
+                continue
+            p, n = it.params, len(it.align_rows or [])
+            A = np.zeros((n, it.ids.size), np.float64)
+            for t, row in enumerate(it.align_rows or []):
+                A[t, :min(row.size, it.ids.size)] = row[:it.ids.size]
+            eos = max(n - p.frames_after_eos, 0) if n < p.max_frames else None
+            for w in _align.timestamps(self.tokenizer, it.ids, A, p.speed or 1.0, eos, it.units / rate):
+                out.append({"word": w["word"], "start": round(w["start"] + at / rate, 6),
+                            "end": round(w["end"] + at / rate, 6)})
+            at += it.units
+        return out
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       sample_rate=None, encoding=None, speed=None, pitch=None, volume_db=None, limit=None) -> Request:
+                       sample_rate=None, encoding=None, speed=None, pitch=None, volume_db=None, limit=None,
+                       align=False) -> Request:
         p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding,
-                                speed, pitch, volume_db, limit)
+                                speed, pitch, volume_db, limit, align)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
-                       encoding=None, speed=None, pitch=None, volume_db=None, limit=None) -> GenerationParams:
+                       encoding=None, speed=None, pitch=None, volume_db=None, limit=None,
+                       align=False) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -1238,6 +1318,8 @@ class TTSService:
             p.pitch = float(pitch)
         if volume_db is not None:  # (set together: a request in the level stage)
             p.volume_db, p.limit = float(volume_db), bool(limit)
+        if align:
+            p.align = True
         return p
 
     # -- per-request and run-time voices
@@ -1339,6 +1421,8 @@ class GenerateRequest(BaseModel):
     long_form: bool | None = None
     # the long-form cut with each sentence chunk continuing the one before it (None: --continuity)
     continuity: bool | None = None
+    # word timestamps (a server with --align; not on /stream): the answer is JSON, the audio in base64
+    timestamps: bool | None = None
 
 
 class OpenAIRequest(BaseModel):
@@ -1358,6 +1442,7 @@ class OpenAIRequest(BaseModel):
     limit: bool | None = None
     long_form: bool | None = None
     continuity: bool | None = None
+    timestamps: bool | None = None  # as in GenerateRequest
 
 
 # /stream: at most one chunk per stream per 20 ms after the first (32 streams x 50 wakes/s keep the
@@ -1452,6 +1537,12 @@ def create_app(service: TTSService):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e)) from e
 
+    def timed(r, data: bytes, media: str):
+        """The answer of a timestamps request: what the route would have sent, in base64, and the words."""
+        return JSONResponse({"audio": base64.b64encode(data).decode(), "content_type": media,
+                             "sample_rate": r.wire[0] if r.wire else SAMPLE_RATE, "words": service.words(r)},
+                            headers=hdr)
+
     worker = getattr(service, "worker", None) or {"rank": 0, "world": 1, "pid": os.getpid()}
     hdr = {"X-PTTS-Rank": str(worker["rank"])}
     board: LoadBoard | None = getattr(service, "board", None)
@@ -1498,9 +1589,10 @@ def create_app(service: TTSService):
         r = submit(**req.model_dump())
         if r.wire is not None and r.wire[1] == "flac":
             return Response(flac_file(r), media_type="audio/flac", headers=hdr)
-        if r.wire is not None:
-            return Response(wav_bytes(r.wire_audio(), *r.wire), media_type="audio/wav", headers=hdr)
-        return Response(wav_bytes(r.audio()), media_type="audio/wav", headers=hdr)
+        data = wav_bytes(r.wire_audio(), *r.wire) if r.wire is not None else wav_bytes(r.audio())
+        if req.timestamps:
+            return timed(r, data, "audio/wav")
+        return Response(data, media_type="audio/wav", headers=hdr)
 
     @app.post("/stream")
     async def stream(req: GenerateRequest, request: StarletteRequest):
@@ -1508,6 +1600,8 @@ def create_app(service: TTSService):
         redirect = overflow(request)
         if redirect is not None:
             return redirect
+        if req.timestamps:
+            raise HTTPException(status_code=400, detail="timestamps are not available on /stream: ask /generate")
         r = submit(**req.model_dump())
         r.times["route"] = t_route
         if r.wire is not None and r.wire[1] == "flac":
@@ -1536,19 +1630,21 @@ def create_app(service: TTSService):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
                    encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity, pitch=req.pitch,
-                   volume_db=req.volume_db, limit=req.limit)
+                   volume_db=req.volume_db, limit=req.limit, timestamps=req.timestamps)
         if r.wire is not None and r.wire[1] == "flac":
             return Response(flac_file(r), media_type="audio/flac", headers=hdr)
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
-                return Response(wav_bytes(data, *r.wire), media_type="audio/wav", headers=hdr)
-            media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1], "audio/pcm")
-            return Response(data, media_type=media, headers=hdr)
-        audio = r.audio()
-        if fmt == "pcm":
-            return Response(pcm_i16_le_bytes(audio), media_type="audio/pcm", headers=hdr)
-        return Response(wav_bytes(audio), media_type="audio/wav", headers=hdr)
+                data, media = wav_bytes(data, *r.wire), "audio/wav"
+            else:
+                media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1], "audio/pcm")
+        else:
+            audio = r.audio()
+            data, media = (pcm_i16_le_bytes(audio), "audio/pcm") if fmt == "pcm" else (wav_bytes(audio), "audio/wav")
+        if req.timestamps:
+            return timed(r, data, media)
+        return Response(data, media_type=media, headers=hdr)
 
     return app
 
@@ -1559,6 +1655,15 @@ def stand_in_sample(u: int, k: int) -> float:
     return ((u % 128) * 256 + k % 256 + 0.5) / 32767.0
 
 
+def stand_in_align_row(k: int, frames: int, n: int) -> np.ndarray:
+    """The stand-in engine's alignment row of frame k of a row of `frames` frames over n tokens: a
+    band, 0.9 on token min(n - 1, k * n // frames) and 0.1 spread over all n."""
+    a = np.full(n, 0.1 / max(n, 1), np.float32)
+    if n:
+        a[min(n - 1, k * n // max(frames, 1))] += np.float32(0.9)
+    return a
+
+
 class StandInEngine:
     """--stand-in-engine only (CPU; launcher and routing self-test of the multi-process server): the
     engine surface the scheduler drives, computing nothing. Row frames of utterance u (its first
@@ -1567,8 +1672,14 @@ class StandInEngine:
     surface at 24 kHz and the level stage, by the host rule audio.level_limit over the row's frames;
     every admitted row's GenerationParams are kept in `params_log`."""
 
-    def __init__(self, max_slots=32, max_ctx=1024, step_s=0.0, wire=False, level=False, level_ceiling_db=-1.0, **_):
+    def __init__(self, max_slots=32, max_ctx=1024, step_s=0.0, wire=False, level=False, level_ceiling_db=-1.0,
+                 align=False, **_):
         self.max_slots, self.max_ctx, self.pipeline = max_slots, max_ctx, True
+        # align=True: rows admitted with GenerationParams.align deliver a planted alignment row per
+        # frame (stand_in_align_row) through fetch_align, one call late like the frames
+        self.align_enabled = bool(align)
+        self.arow = {}  # slot -> tokens of a row in the align stage
+        self.align_pending = self.align_out = self.align_prev = None
         self.step_s = step_s
         self.rows, self.pending = {}, None
         self.admit_log = []  # every admitted row: (slot, ids, prefix latents or None, keep_codec)
@@ -1623,17 +1734,25 @@ class StandInEngine:
 
     def open_many(self, slots, voices, ids_list, params_list):
         """Records every admitted row in `admit_log`; the latents of admission a's frame k hold a * 1000 + k."""
+        for ids, p in zip(ids_list, params_list):  # as the engine: more than PTTS_ALIGN_TOKENS ids with align
+            if getattr(p, "align", False) and len(ids) > ALIGN_TOKENS:
+                raise RuntimeError("align: more than PTTS_ALIGN_TOKENS token ids")
         for p in params_list:  # nothing is admitted if one row is refused
             lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
             rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
             if lv != (0, 0) and not self.level_enabled:
                 raise RuntimeError("a gain or limit needs a level-enabled engine")
+            if getattr(p, "align", False) and not self.align_enabled:
+                raise RuntimeError("align needs an align-enabled engine")
             if (rate or enc or lv != (0, 0)) and not (self.level_enabled and rate in (0, SAMPLE_RATE) and enc in (0, 1, 2, 3)):
                 raise RuntimeError("the stand-in engine converts to 24 kHz pcm_s16le / ulaw / alaw only, with level=True")
         for s, ids, p in zip(slots, ids_list, params_list):
             pre = getattr(p, "prefix_latents", None)
             self.params_log.append(p)
             self.fmt.pop(s, None)
+            self.arow.pop(s, None)
+            if getattr(p, "align", False):
+                self.arow[s] = len(ids)
             lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
             rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
             if rate or enc or lv != (0, 0):
@@ -1652,6 +1771,10 @@ class StandInEngine:
         for s in slots:
             self.rows.pop(s, None)
             self.fmt.pop(s, None)
+            self.arow.pop(s, None)
+            for held in (self.align_pending, self.align_out, self.align_prev):
+                if held is not None and s < len(held):
+                    held[s] = np.zeros(0, np.float32)
             for held in (self.wire_pending, self.wire_out, self.wire_prev):
                 if held is not None and s < len(held):
                     held[s] = b""
@@ -1665,9 +1788,12 @@ class StandInEngine:
         pcm, valid, last = np.zeros((n, FRAME), np.float32), np.zeros(n, bool), np.zeros(n, bool)
         lat = np.zeros((n, LDIM), np.float32)
         wire = [b""] * n
+        arows = [np.zeros(0, np.float32)] * n
         for s, st in list(self.rows.items()):
             if s < n:
                 pcm[s], valid[s] = stand_in_sample(st[0], st[1]), True
+                if s in self.arow:
+                    arows[s] = stand_in_align_row(st[1], st[2], self.arow[s])
                 if s in self.fmt:
                     wire[s] = self._wire_chunk(self.fmt[s])
                 lat[s] = st[3] * 1000 + st[1]
@@ -1676,6 +1802,10 @@ class StandInEngine:
                 if last[s]:
                     del self.rows[s]
         prev, self.pending = self.pending, (pcm, valid, last, lat)
+        aprev, self.align_pending = self.align_pending, arows
+        self.align_prev, self.align_out = self.align_out, [np.zeros(0, np.float32)] * n
+        if aprev is not None:
+            self.align_out[:min(n, len(aprev))] = aprev[:min(n, len(aprev))]
         wprev, self.wire_pending = self.wire_pending, wire
         self.wire_prev, self.wire_out = self.wire_out, [b""] * n
         if wprev is not None:
@@ -1708,6 +1838,10 @@ class StandInEngine:
             x = np.concatenate([np.full(FRAME, stand_in_sample(u, j), np.float32) for j in range(total)])
             chunks = f[5] = level_limit(x, lv[0], self.level_ceiling_cdb, chunks=[FRAME] * total)
         return wire_bytes(chunks[k], enc)
+
+    def fetch_align(self, n, calls_back=0):
+        out = self.align_out if calls_back == 0 else self.align_prev
+        return [out[b] if out is not None and b < len(out) else np.zeros(0, np.float32) for b in range(n)]
 
     def fetch_wire(self, n, calls_back=0):
         out = self.wire_out if calls_back == 0 else self.wire_prev
@@ -1750,6 +1884,8 @@ def _worker_engine(args, Engine):
     # (an engine without the stage is created exactly as before; the launcher's stand-in has no wire surface)
     if args.wire and args.volume and Engine is not StandInEngine:
         kw.update(level=True, level_ceiling_db=args.limiter_ceiling_db)
+    if args.align:  # off by default: the engine is created exactly as before
+        kw.update(align=True, align_layer=args.align_layer, align_heads=int(str(args.align_heads), 0))
     if Engine is StandInEngine:
         kw["step_s"] = args.stand_in_step_ms / 1000.0
     if "WORLD_SIZE" not in os.environ:  # a plain single-GPU server
@@ -1829,6 +1965,13 @@ def main(argv=None):
     ap.add_argument("--limiter-ceiling-db", type=float, default=-1.0,
                     help="the level stage's ceiling in dBFS, -40 .. 0: no sample of a row with volume_db or limit "
                          "leaves it")
+    ap.add_argument("--align", action=argparse.BooleanOptionalAction, default=False,
+                    help="word timestamps (requests' `timestamps` on /generate and /v1/audio/speech): one more launch in "
+                         "the FlowLM step delivers a text-attention row per frame; off by default (which layer and "
+                         "heads align is a property of the checkpoint: tools/align_heads.py)")
+    ap.add_argument("--align-layer", type=int, default=0, help="the FlowLM layer (0 .. 5) the align stage reads")
+    ap.add_argument("--align-heads", default="0xFFFF",
+                    help="bit mask of the heads (bit h = head h of 16) the align stage averages")
     ap.add_argument("--long-form", action=argparse.BooleanOptionalAction, default=False,
                     help="default of requests that do not say `long_form`: split the text into pause and sentence "
                          "segments (the reference's generate_stream_long) and run them on parallel rows")

@@ -323,6 +323,14 @@ class Tokenizer:
         """text.rs:305-313."""
         return len(self.encode(text))
 
+    def pieces(self, ids) -> list[str]:
+        """The vocabulary piece of every id of an encoding (a word's first piece begins with the
+        metaspace U+2581; byte-fallback pieces read "<0xNN>"); an added token reads as its content,
+        an id outside the vocabulary as ""."""
+        added = {i: t for t, i in self.added.items()}
+        n = len(self.model.vocab)
+        return [added[i] if i in added else self.model.vocab[i][0] if 0 <= i < n else "" for i in map(int, ids)]
+
     @property
     def vocab_size(self) -> int:
         return len(self.model.vocab)

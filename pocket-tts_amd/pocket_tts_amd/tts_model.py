@@ -17,6 +17,9 @@ Reference surface kept:
     `estimate_generation_steps` (:1187-1190);
   * `generate_parallel` / `generate_stream_parallel` (:705-854, commented out in the reference):
     the same segments as rows of one batch, on an engine loaded with `max_slots` > 1.
+Not in the reference: `generate(.., timestamps=True)` and `generate_parallel(.., timestamps=True)`
+return `(audio, words)`, the words with their start and end in seconds of that audio (align.py;
+DESIGN.md section 26), on a model loaded with `align=True`.
 Text goes through the text front end (text.py: tokenizer, prompt preparation); token-id input
 is accepted too (one segment, no splitting).
 """
@@ -31,6 +34,7 @@ import numpy as np
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE, WIRE_FLAC
 from .audio import (flac_stream_header, level_cdb, pitch_cents, read_wav, read_wav_from_bytes, speed_permille, wire_bytes,
                     wire_samples)
+from . import align as _align
 from .engine import Engine, GenerationParams, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
@@ -89,7 +93,8 @@ class TTSModel:
                          weight_quant: int = QUANT_NONE, max_lsd_decode_steps: int | None = None,
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
                          back_frames: int = 1, tempo: bool = False, flac: bool = False,
-                         pitch: bool = False, level: bool = False, level_ceiling_db: float = -1.0) -> "TTSModel":
+                         pitch: bool = False, level: bool = False, level_ceiling_db: float = -1.0,
+                         align: bool = False, align_layer: int = 0, align_heads: int = 0xFFFF) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
@@ -100,7 +105,8 @@ class TTSModel:
         its tempo stage too, for generate(.., speed=); pitch (with tempo): its pitch stage, for
         generate(.., pitch=); flac (with wire): its FLAC stage, for
         generate(.., encoding="flac"); level (with wire): its level stage at level_ceiling_db, for
-        generate(.., volume_db=, limit=)."""
+        generate(.., volume_db=, limit=). align: its align stage on FlowLM layer align_layer over the
+        heads of the mask align_heads, for generate(.., timestamps=True)."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
@@ -109,7 +115,8 @@ class TTSModel:
                      back_frames=back_frames, lsd_decode_steps=lsd_decode_steps, seed=seed,
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
                      wire=wire, tempo=tempo, flac=flac, pitch=pitch,
-                     **(dict(level=True, level_ceiling_db=level_ceiling_db) if level else {}))
+                     **(dict(level=True, level_ceiling_db=level_ceiling_db) if level else {}),
+                     **(dict(align=True, align_layer=align_layer, align_heads=align_heads) if align else {}))
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -203,7 +210,7 @@ class TTSModel:
                  sample_rate: int | None = None, encoding=None, speed: float | None = None,
                  previous: Continuation | None = None, latents: list | None = None,
                  pitch: float | None = None, volume_db: float | None = None,
-                 limit: bool = False) -> Iterator[np.ndarray]:
+                 limit: bool = False, align: list | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
         (sample_rate / encoding; a wire-enabled engine), a speed (a tempo-enabled one) or a pitch (a
         pitch-enabled one; 24 kHz 16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
@@ -211,12 +218,14 @@ class TTSModel:
         previous: the segment continues that one (section 20): admitted behind its ids and, as a
         teacher-forced prefix, its latents, on the codec state it left (only the new frames are
         yielded); where that exceeds the engine's max_ctx, as a plain segment. latents: a list that
-        receives the latent of every frame yielded."""
+        receives the latent of every frame yielded. align: a list that receives the alignment row of
+        every frame yielded (an align-enabled engine; the row is admitted with align)."""
         self._check_lsd()
         params = self._params(max_frames, frames_after_eos)
         params.lsd_steps = int(self.lsd_decode_steps)
         params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
         params.volume_db, params.limit = volume_db, bool(limit)
+        params.align = align is not None
         if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
                                      + max_frames <= self.engine.max_ctx):
             ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
@@ -235,6 +244,8 @@ class TTSModel:
             lead = 0
             if latents is not None:
                 latents.append(np.array(r.latents[0], np.float32))
+            if align is not None:
+                align.append(self.engine.fetch_align(1)[0])
             yield self.engine.fetch_wire(1)[0] if wire else r.pcm[0].reshape(1, 1, FRAME).copy()
             if r.last[0]:
                 return
@@ -291,10 +302,16 @@ class TTSModel:
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
                  speed: float | None = None, pitch: float | None = None, volume_db: float | None = None,
-                 limit: bool = False):
+                 limit: bool = False, timestamps: bool = False):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
         speed / pitch / volume_db / limit, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
-        the stream header with the true sample count and then the frames."""
+        the stream header with the true sample count and then the frames.
+        timestamps=True (text input, a model loaded with align=True and a tokenizer that names its
+        pieces): returns (audio, words), words = [{"word", "start", "end"}] in seconds of that audio
+        (align.py: each sentence chunk's words offset by the audio delivered before it)."""
+        if timestamps:
+            return self._generate_timed(text_or_ids, voice_state, max_frames, sample_rate, encoding, speed, pitch,
+                                        volume_db, limit)
         frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed,
                                            pitch, volume_db, limit))
         if not frames:
@@ -307,6 +324,55 @@ class TTSModel:
                 or level_cdb(volume_db) or limit:
             return b"".join(frames)
         return np.concatenate(frames, axis=2)[0]
+
+    def _units(self, chunk, sample_rate, encoding) -> int:
+        """Samples of one delivered item at the rate it is delivered at (f32 frames: 24 kHz)."""
+        if not isinstance(chunk, (bytes, bytearray)):
+            return int(np.asarray(chunk).shape[-1])
+        return len(chunk) // (1 if encoding in ("ulaw", "alaw", 2, 3) else 2)
+
+    def _words_of(self, ids, rows, n_frames, max_frames, fae, speed, seconds) -> list[dict]:
+        """The words of one segment over its own audio of `seconds`: the EOS frame is the frame the
+        tail of frames_after_eos frames began at, where the row ended before max_frames."""
+        tok = self._tok()
+        if not hasattr(tok, "pieces"):
+            raise ValueError("timestamps need a tokenizer that names its pieces (text.Tokenizer)")
+        A = np.zeros((n_frames, len(ids)), np.float64)
+        for t, r in enumerate(rows[:n_frames]):
+            A[t, :len(r)] = r[:len(ids)]
+        eos = max(n_frames - fae, 0) if n_frames < max_frames else None
+        return _align.timestamps(tok, ids, A, speed or 1.0, eos, seconds)
+
+    def _generate_timed(self, text, voice_state, max_frames, sample_rate, encoding, speed, pitch, volume_db, limit):
+        if not isinstance(text, str):
+            raise ValueError("timestamps: token ids carry no words, pass text")
+        if not self.engine.align_enabled:
+            raise ValueError("timestamps need a model loaded with align=True")
+        if encoding in ("flac", WIRE_FLAC):
+            raise ValueError("timestamps: not with flac (ask for pcm_s16le and encode the result)")
+        speed = speed if speed_permille(speed) else None
+        pitch = pitch if pitch_cents(pitch) else None
+        if level_cdb(volume_db) == 0:
+            volume_db = 0.0 if limit else None
+        wire = sample_rate is not None or encoding is not None or speed is not None or pitch is not None \
+            or volume_db is not None
+        rate = int(sample_rate or SAMPLE_RATE) if wire else SAMPLE_RATE
+        tok = self._tok()
+        out, words, at = [], [], 0.0
+        for chunk in self.split_into_best_sentences(text):
+            prepared = prepare_text_prompt(chunk)
+            ids = np.asarray(tok(prepared), np.int32)
+            mf, fae, rows = max_frames or max_gen_len(prepared), estimate_frames_after_eos(chunk), []
+            frames = list(self._segment(ids, voice_state, mf, fae, sample_rate, encoding, speed, pitch=pitch,
+                                        volume_db=volume_db, limit=limit, align=rows))
+            seconds = sum(self._units(f, rate, encoding) for f in frames) / rate
+            for w in self._words_of(ids, rows, len(frames), mf, fae, speed, seconds):
+                words.append({"word": w["word"], "start": round(w["start"] + at, 6), "end": round(w["end"] + at, 6)})
+            at += seconds
+            out += frames
+        if not out:
+            raise RuntimeError("No audio generated")
+        return (b"".join(out) if wire else np.concatenate(out, axis=2)[0]), words
 
     def generate_stream_long(self, text: str, voice_state: Voice, continuity: bool = False) -> Iterator[np.ndarray]:
         """tts_model.rs:1074-1131: text segments between pause markers, silence for each pause.
@@ -368,7 +434,8 @@ class TTSModel:
     # ---- the same segments on parallel rows
     def generate_stream_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
                                  sample_rate: int | None = None, encoding=None,
-                                 speed: float | None = None, pitch: float | None = None) -> Iterator:
+                                 speed: float | None = None, pitch: float | None = None,
+                                 timed: list | None = None) -> Iterator:
         """The items of generate_stream (pauses=False) or generate_stream_long (pauses=True), in text
         order, with the text segments generated as rows of one batch: up to `rows` (default: the
         engine's max_slots) are admitted at once (Engine.open_many: one shared text prefill, the
@@ -380,7 +447,11 @@ class TTSModel:
         sample_rate / encoding: wire bytes as generate_stream yields them, and each pause as the
         encoded silence of silence_samples(ms, sample_rate) samples. speed: every text segment's row
         carries it (generate_stream), and the pitch likewise; pauses keep their stated duration. Closing the generator early
-        cancels the rows it still holds (Engine.cancel_slots)."""
+        cancels the rows it still holds (Engine.cancel_slots).
+        timed: a list that receives one record per item, in text order (generate_parallel's
+        timestamps): ("pause", samples) or ("text", ids, params, frames_after_eos, meta), meta the
+        segment's alignment rows, frame count and delivered samples, complete once it is delivered;
+        the text rows are then admitted with align."""
         self._check_lsd()
         if encoding in ("flac", WIRE_FLAC):
             raise ValueError("flac: parallel rows are separate streams, each numbered from 0 (section 21, Limits)")
@@ -397,12 +468,20 @@ class TTSModel:
                 params = self._params(mgl, fae)
                 params.lsd_steps = int(self.lsd_decode_steps)
                 params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
-                items.append(["text", np.asarray(ids, np.int32), params, [], False])
+                params.align = timed is not None
+                meta = {"rows": [], "frames": 0, "units": 0, "encoding": encoding}
+                items.append(["text", np.asarray(ids, np.int32), params, [], False, meta if timed is not None else None])
+                if timed is not None:
+                    timed.append(("text", items[-1][1], params, fae, meta))
             elif wire:
                 n = silence_samples(val, int(sample_rate or SAMPLE_RATE))
                 items.append(("pause", wire_bytes(np.zeros(n, np.float32), encoding or "pcm_s16le")))
+                if timed is not None:
+                    timed.append(("pause", n))
             else:
                 items.append(("pause", np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)))
+                if timed is not None:
+                    timed.append(("pause", silence_samples(val, self.sample_rate)))
         return self._run_parallel(items, voice_state, n_rows, wire)
 
     def _run_parallel(self, items, voice_state: Voice, n_rows: int, wire: bool) -> Iterator:
@@ -437,6 +516,7 @@ class TTSModel:
                 B = max(active) + 1
                 r = eng.step(B)
                 chunks = eng.fetch_wire(B) if wire else None
+                arows = eng.fetch_align(B) if any(it[5] is not None for it in active.values()) else None
                 for s in sorted(active):
                     it = active[s]
                     if not r.valid[s]:
@@ -448,6 +528,10 @@ class TTSModel:
                         continue
                     lead[s] = 0
                     it[3].append(chunks[s] if wire else r.pcm[s].reshape(1, 1, FRAME).copy())
+                    if it[5] is not None:
+                        it[5]["rows"].append(arows[s])
+                        it[5]["frames"] += 1
+                        it[5]["units"] += self._units(it[3][-1], 0, it[5]["encoding"])
                     if r.last[s]:
                         it[4] = True
                         del active[s]
@@ -457,15 +541,36 @@ class TTSModel:
 
     def generate_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
                           sample_rate: int | None = None, encoding=None, speed: float | None = None,
-                          pitch: float | None = None):
+                          pitch: float | None = None, timestamps: bool = False):
         """generate (pauses=False) or generate_with_pauses (pauses=True) with the text's segments on
         parallel rows: the concatenation of generate_stream_parallel's items. The name is the
         reference's own: its generate_parallel (tts_model.rs:705-854) is commented out there, "for
-        future exploration with GPU acceleration"."""
+        future exploration with GPU acceleration".
+        timestamps=True (a model loaded with align=True): returns (audio, words); each segment's words
+        are offset by the samples delivered before it, pauses included."""
+        if timestamps and not self.engine.align_enabled:
+            raise ValueError("timestamps need a model loaded with align=True")
+        timed = [] if timestamps else None
         chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding, speed,
-                                                    pitch))
+                                                    pitch, timed=timed))
         if not chunks:
             raise RuntimeError("No audio generated")
+        if timestamps:
+            wire = sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch)
+            rate = int(sample_rate or SAMPLE_RATE) if wire else SAMPLE_RATE
+            words, at = [], 0
+            for rec in timed:
+                if rec[0] == "pause":
+                    at += rec[1]
+                    continue
+                _, ids, params, fae, meta = rec
+                for w in self._words_of(ids, meta["rows"], meta["frames"], params.max_frames, fae,
+                                        speed if speed_permille(speed) else None, meta["units"] / rate):
+                    words.append({"word": w["word"], "start": round(w["start"] + at / rate, 6),
+                                  "end": round(w["end"] + at / rate, 6)})
+                at += meta["units"]
+            audio = b"".join(chunks) if wire else np.concatenate(chunks, axis=2)[0]
+            return audio, words
         if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch):
             return b"".join(chunks)
         return np.concatenate(chunks, axis=2)[0]
