@@ -316,7 +316,11 @@ int ptts_slot_open_ex(ptts_engine* e, int slot, const ptts_voice* v, const int32
 
 int ptts_slots_open_ex(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps) {
-  return guard([&] { eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd_steps); });
+  return guard([&] {
+    std::vector<ptts_slot_opts> o(lsd_steps && n > 0 ? n : 0);  // (a bad n: the engine refuses it)
+    for (size_t i = 0; i < o.size(); ++i) o[i].lsd_steps = lsd_steps[i];
+    eng(e).slots_open(n, slots, voices, ids, n_ids, params, o.empty() ? nullptr : o.data());
+  });
 }
 
 int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
@@ -330,26 +334,13 @@ int ptts_slots_open_opts(ptts_engine* e, int n, const int* slots, const ptts_voi
     const size_t size = opts[0].size ? opts[0].size : offsetof(ptts_slot_opts, pitch_cents);
     if (size < offsetof(ptts_slot_opts, lsd_steps) + sizeof(int) || size % alignof(ptts_slot_opts))
       throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size: not a ptts_slot_opts of any version");
-    std::vector<int> lsd(n), rate(n), enc(n), speed(n), npre(n), keep(n), pitch(n), gain(n), limit(n), align(n);
-    std::vector<const float*> pre(n);
+    std::vector<ptts_slot_opts> own(n);  // this library's struct, zero-filled (reserved, reserved2 are ignored)
     for (int i = 0; i < n; ++i) {
-      ptts_slot_opts o{};
-      std::memcpy(&o, (const char*)opts + (size_t)i * size, std::min(size, sizeof o));
-      if (o.size != opts[0].size) throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size differs between entries");
-      lsd[i] = o.lsd_steps;
-      rate[i] = o.wire_rate;
-      enc[i] = o.wire_encoding;
-      speed[i] = o.speed_permille;
-      pre[i] = o.prefix_latents;
-      npre[i] = o.n_prefix;
-      keep[i] = o.keep_codec;
-      pitch[i] = o.pitch_cents;
-      gain[i] = o.gain_cdb;  // (o.reserved, the four bytes behind pitch_cents, is ignored)
-      limit[i] = o.limit;
-      align[i] = o.align;  // (o.reserved2 is ignored)
+      std::memcpy(&own[i], (const char*)opts + (size_t)i * size, std::min(size, sizeof own[i]));
+      if (own[i].size != opts[0].size)
+        throw ptts::Error(PTTS_ERR_INVALID, "ptts_slot_opts.size differs between entries");
     }
-    eng(e).slots_open(n, slots, voices, ids, n_ids, params, lsd.data(), rate.data(), enc.data(), speed.data(),
-                      pre.data(), npre.data(), keep.data(), pitch.data(), gain.data(), limit.data(), align.data());
+    eng(e).slots_open(n, slots, voices, ids, n_ids, params, own.data());
   });
 }
 

@@ -3190,7 +3190,9 @@ ptts_voice* Engine::voice_job_audio(const void* samples, int n_in, int fmt, int 
 
 void Engine::slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
                        int lsd_steps) {
-  slots_open(1, &slot, &v, ids, &n, &p, &lsd_steps);
+  ptts_slot_opts o{};
+  o.lsd_steps = lsd_steps;
+  slots_open(1, &slot, &v, ids, &n, &p, &o);
 }
 
 // Euler steps of a front part over rows [0, B): the largest per-row count among the rows the
@@ -3210,92 +3212,100 @@ int Engine::lsd_run_for(int B) const {
 // per slot, padded to 16-row groups (the 16-query attention tiles), and mapped to (slot, position)
 // through a row table.
 void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids,
-                        const int* n_ids, const ptts_gen_params* params, const int* lsd_steps, const int* wire_rate,
-                        const int* wire_enc, const int* speed, const float* const* prefix, const int* n_prefix,
-                        const int* keep_codec, const int* pitch, const int* gain_cdb, const int* limit,
-                        const int* align) {
+                        const int* n_ids, const ptts_gen_params* params, const ptts_slot_opts* opts) {
   PTTS_REQUIRE(ready_, "engine weights not finalized");
   PTTS_REQUIRE(n >= 1 && n <= max_slots_, "number of admissions out of range");
   PTTS_REQUIRE(slots && voices && n_ids && params, "null argument");
-  for (int i = 0; align && i < n; ++i) {  // section 26: nothing is admitted when a row's align is refused
-    PTTS_REQUIRE(align[i] == 0 || align[i] == 1, "align must be 0 or 1");
-    if (!align[i]) continue;
-    PTTS_REQUIRE(align_, "align needs an align-enabled engine (ptts_align_enable before the first step)");
-    PTTS_REQUIRE(n_ids[i] <= ALIGN_TOKENS, "align: more than PTTS_ALIGN_TOKENS token ids");
-  }
-  std::vector<char> seen(max_slots_, 0);
-  std::vector<int> wfmt(n, 0);  // the rows' wire formats (encoding | rate index << 8; 0: none)
-  std::vector<int> wsp(n, 0);   // the rows' speeds (permille; 0: none)
-  std::vector<unsigned> wpt(n, 0u);  // the rows' pitch steps (Q20; 0: none)
-  std::vector<unsigned> wlv(n, 0u);  // the rows' gains (f32 bits; 0: not in the level stage)
-  std::vector<int> npre(n, 0);  // the rows' latent prefixes (frames) and RESET_* bits (section 20)
-  std::vector<int> ropt(n, 0);
-  bool any_prefix = false, any_opt = false;
-  long total_ids = 0;
-  for (int i = 0; i < n; ++i) {
-    const int wr = wire_rate ? wire_rate[i] : 0, we = wire_enc ? wire_enc[i] : 0;
-    const int sp = speed ? speed[i] : 0;
+  // What a row's options come to: checked, and in the units the tables and the reset kernel take
+  struct Row {
+    int lsd = 0;                    // Euler steps
+    int wfmt = 0;                   // wire format (encoding | rate index << 8; 0: none)
+    int speed = 0;                  // WSOLA speed (permille; 0: none)
+    unsigned pitch = 0;             // pitch step (Q20; 0: none)
+    unsigned gain = 0;              // gain (f32 bits; 0: not in the level stage)
+    const float* prefix = nullptr;  // latent prefix and its frames (section 20)
+    int npre = 0;
+    int reset = 0;                  // RESET_* bits
+    int align = 0;                  // text tokens in the align stage (0: the row is not in it)
+  };
+  const auto plan = [&](const ptts_slot_opts& o, const ptts_voice* v, int nid, const ptts_gen_params& p) {
+    Row r;
+    PTTS_REQUIRE(o.align == 0 || o.align == 1, "align must be 0 or 1");
+    if (o.align) {  // section 26
+      PTTS_REQUIRE(align_, "align needs an align-enabled engine (ptts_align_enable before the first step)");
+      PTTS_REQUIRE(nid <= ALIGN_TOKENS, "align: more than PTTS_ALIGN_TOKENS token ids");
+    }
+    const int sp = o.speed_permille;
     if (sp != 0 && sp != 1000) {  // 1000: no tempo stage for the row, like no speed at all
       PTTS_REQUIRE(sp >= TEMPO_SP_MIN && sp <= TEMPO_SP_MAX, "speed_permille must be 0 or in [500, 2000]");
       PTTS_REQUIRE(tempo_, "a speed needs a tempo-enabled engine (ptts_tempo_enable before the first step)");
-      wsp[i] = sp;
+      r.speed = sp;
     }
-    const int cents = pitch ? pitch[i] : 0;
+    const int cents = o.pitch_cents;
     if (cents != 0) {  // the WSOLA stage runs at sp_w, the resampler at step (section 23)
       PTTS_REQUIRE(cents >= -PITCH_CENTS_MAX && cents <= PITCH_CENTS_MAX, "pitch_cents must be in [-1200, 1200]");
       PTTS_REQUIRE(pitch_, "a pitch needs a pitch-enabled engine (ptts_pitch_enable before the first step)");
       int sp_w = 0;
-      PTTS_REQUIRE(pitch_plan(cents, sp, &sp_w, &wpt[i]),
+      PTTS_REQUIRE(pitch_plan(cents, sp, &sp_w, &r.pitch),
                    "pitch_cents with this speed leaves the time-scaling range (speed / 2^(cents / 1200) in [0.5, 2.0])");
-      wsp[i] = sp_w == 1000 ? 0 : sp_w;
+      r.speed = sp_w == 1000 ? 0 : sp_w;
     }
-    const int gdb = gain_cdb ? gain_cdb[i] : 0, lim = limit ? limit[i] : 0;
+    const int gdb = o.gain_cdb, lim = o.limit;
     PTTS_REQUIRE(gdb >= -LEVEL_GAIN_CDB_MAX && gdb <= LEVEL_GAIN_CDB_MAX, "gain_cdb must be in [-2400, 2400]");
     PTTS_REQUIRE(lim == 0 || lim == 1, "limit must be 0 or 1");
     if (gdb != 0 || lim == 1) {  // the row is in the level stage (section 24)
       PTTS_REQUIRE(level_, "a gain or limit needs a level-enabled engine (ptts_level_enable before the first step)");
-      float v = 1.f;
-      level_plan(gdb, 0, &v, nullptr);
-      memcpy(&wlv[i], &v, sizeof v);
+      float g = 1.f;
+      level_plan(gdb, 0, &g, nullptr);
+      memcpy(&r.gain, &g, sizeof g);
     }
-    if (wr || we || wsp[i] || wpt[i] || wlv[i]) {  // a speed, a pitch or a gain with no format: 24000 / 16 bit
+    const int wr = o.wire_rate, we = o.wire_encoding;
+    if (wr || we || r.speed || r.pitch || r.gain) {  // a speed, a pitch or a gain with no format: 24000 / 16 bit
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
       PTTS_REQUIRE(we != WIRE_FLAC || flac_, "PTTS_WIRE_FLAC needs a FLAC-enabled engine (ptts_flac_enable before the first step)");
       PTTS_REQUIRE(we >= 0 && we <= WIRE_FLAC, "wire_encoding must be 0 (s16) or PTTS_WIRE_S16 / _ULAW / _ALAW / _FLAC");
-      wfmt[i] = (we ? we : WIRE_S16) | ri << 8;
+      r.wfmt = (we ? we : WIRE_S16) | ri << 8;
     }
+    PTTS_REQUIRE(v != nullptr && v->owner == this, "voice belongs to another engine");
+    PTTS_REQUIRE(nid >= 0 && (nid == 0 || ids != nullptr), "bad token ids");
+    PTTS_REQUIRE(p.max_frames >= 1, "max_frames must be >= 1");
+    // 0: the engine's default (its cap)
+    PTTS_REQUIRE(o.lsd_steps == 0 || (o.lsd_steps >= 1 && o.lsd_steps <= lsd_),
+                 "lsd_steps must be 0 (the default) or in [1, " + std::to_string(lsd_) + "] (the engine's lsd_decode_steps)");
+    PTTS_REQUIRE(p.frames_after_eos >= 0, "frames_after_eos must be >= 0");
+    PTTS_REQUIRE(o.n_prefix >= 0, "n_prefix must be >= 0");
+    PTTS_REQUIRE(o.n_prefix == 0 || o.prefix_latents, "n_prefix > 0 with no prefix_latents");
+    PTTS_REQUIRE(o.keep_codec == 0 || o.keep_codec == 1, "keep_codec must be 0 or 1");
+    PTTS_REQUIRE((long)v->F + nid + o.n_prefix + p.max_frames <= max_ctx_,
+                 o.n_prefix ? "voice + text + prefix + max_frames exceeds max_ctx" : "voice + text + max_frames exceeds max_ctx");
+    r.lsd = o.lsd_steps ? o.lsd_steps : lsd_;
+    r.prefix = o.prefix_latents;
+    r.npre = o.n_prefix;
+    r.reset = (o.keep_codec ? RESET_KEEP_CODEC : 0) | (o.n_prefix ? RESET_LAT_SRC : 0);
+    r.align = o.align ? nid : 0;
+    return r;
+  };
+  std::vector<char> seen(max_slots_, 0);
+  std::vector<Row> row(n);
+  bool any_prefix = false, any_opt = false;
+  long total_ids = 0;
+  for (int i = 0; i < n; ++i) {  // nothing is admitted when one row is refused
     const int slot = slots[i];
     PTTS_REQUIRE(slot >= 0 && slot < max_slots_, "slot out of range");
     PTTS_REQUIRE(!seen[slot], "slot admitted twice in one call");
     seen[slot] = 1;
-    const ptts_voice* v = voices[i];
-    PTTS_REQUIRE(v != nullptr && v->owner == this, "voice belongs to another engine");
-    const ptts_gen_params& p = params[i];
-    PTTS_REQUIRE(n_ids[i] >= 0 && (n_ids[i] == 0 || ids != nullptr), "bad token ids");
-    PTTS_REQUIRE(p.max_frames >= 1, "max_frames must be >= 1");
-    // 0: the engine's default (its cap)
-    PTTS_REQUIRE(!lsd_steps || lsd_steps[i] == 0 || (lsd_steps[i] >= 1 && lsd_steps[i] <= lsd_),
-                 "lsd_steps must be 0 (the default) or in [1, " + std::to_string(lsd_) + "] (the engine's lsd_decode_steps)");
-    PTTS_REQUIRE(p.frames_after_eos >= 0, "frames_after_eos must be >= 0");
-    npre[i] = n_prefix ? n_prefix[i] : 0;
-    const int keep = keep_codec ? keep_codec[i] : 0;
-    PTTS_REQUIRE(npre[i] >= 0, "n_prefix must be >= 0");
-    PTTS_REQUIRE(npre[i] == 0 || (prefix && prefix[i]), "n_prefix > 0 with no prefix_latents");
-    PTTS_REQUIRE(keep == 0 || keep == 1, "keep_codec must be 0 or 1");
-    PTTS_REQUIRE((long)v->F + n_ids[i] + npre[i] + p.max_frames <= max_ctx_,
-                 npre[i] ? "voice + text + prefix + max_frames exceeds max_ctx" : "voice + text + max_frames exceeds max_ctx");
-    ropt[i] = (keep ? RESET_KEEP_CODEC : 0) | (npre[i] ? RESET_LAT_SRC : 0);
-    any_prefix = any_prefix || npre[i] > 0;
-    any_opt = any_opt || ropt[i] != 0;
+    row[i] = plan(opts ? opts[i] : ptts_slot_opts{}, voices[i], n_ids[i], params[i]);
+    any_prefix = any_prefix || row[i].npre > 0;
+    any_opt = any_opt || row[i].reset != 0;
     for (int j = 0; j < n_ids[i]; ++j)
       PTTS_REQUIRE(ids[total_ids + j] >= 0 && ids[total_ids + j] < VOCAB, "token id out of range");
     total_ids += n_ids[i];
   }
   // keep_codec: the slot's codec state must be that of a whole utterance, with nothing in flight
   for (int i = 0; i < n; ++i)
-    if ((ropt[i] & RESET_KEEP_CODEC) && !(drained_[slots[i]] && codec_ok_[slots[i]]))
+    if ((row[i].reset & RESET_KEEP_CODEC) && !(drained_[slots[i]] && codec_ok_[slots[i]]))
       throw Error(PTTS_ERR_STATE, "keep_codec: the slot's previous utterance was closed or cancelled, or its last "
                                   "frame is not fetched yet");
   // Stream-ordered admission (no drain of the pipeline: a full sync() here stalled the front part
@@ -3351,11 +3361,11 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       tab.push_back(slots[i] << 16 | (voices[i]->F + j));
       rid.push_back(ids[off + j]);
     }
-    for (int j = 0; j < npre[i]; ++j) {
+    for (int j = 0; j < row[i].npre; ++j) {
       tab.push_back(slots[i] << 16 | (voices[i]->F + n_ids[i] + j));
       rid.push_back(j == 0 ? PREFILL_SRC_BOS : PREFILL_SRC_LAT0);
       rlat.resize(tab.size(), nullptr);
-      if (j > 0) rlat.back() = prefix[i] + (size_t)(j - 1) * LDIM;
+      if (j > 0) rlat.back() = row[i].prefix + (size_t)(j - 1) * LDIM;
     }
     while (tab.size() % 16) {
       tab.push_back(-1);
@@ -3441,19 +3451,19 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     codec_ok_[slots[i]] = 0;
     cancelled_[slots[i]] = 0;
     admit_call_[slots[i]] = k_;
-    slot_lsd_[slots[i]] = lsd_steps && lsd_steps[i] ? lsd_steps[i] : lsd_;
-    if (wire_) slot_wire_[slots[i]] = wfmt[i];
+    slot_lsd_[slots[i]] = row[i].lsd;
+    if (wire_) slot_wire_[slots[i]] = row[i].wfmt;
   }
   if (tempo_) {
-    memcpy(h_tempo_, wsp.data(), sizeof(int) * n);
+    for (int i = 0; i < n; ++i) h_tempo_[i] = row[i].speed;
     PTTS_HIP(hipMemcpyAsync(admit_tempo_, h_tempo_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   }
   if (pitch_) {
-    memcpy(h_pitch_, wpt.data(), sizeof(unsigned) * n);
+    for (int i = 0; i < n; ++i) h_pitch_[i] = row[i].pitch;
     PTTS_HIP(hipMemcpyAsync(admit_pitch_, h_pitch_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
   }
   if (level_) {
-    memcpy(h_level_, wlv.data(), sizeof(unsigned) * n);
+    for (int i = 0; i < n; ++i) h_level_[i] = row[i].gain;
     PTTS_HIP(hipMemcpyAsync(admit_level_, h_level_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
   }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
@@ -3473,7 +3483,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     s.noise_clamp = p.noise_clamp;
     s.seed = p.seed;
     s.lsd = slot_lsd_[slots[i]];
-    fp[i] = voices[i]->F + n_ids[i] + npre[i];
+    fp[i] = voices[i]->F + n_ids[i] + row[i].npre;
   }
   // staged through pinned buffers so the copies are truly asynchronous: admission returns with
   // the prefill still running and the caller's first step queued right behind it (no host
@@ -3494,12 +3504,12 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
   // (a preview decodes from the fresh codec state: not the frame a keep_codec row produces)
   if (pv_max_ > 0)
     for (int i = 0; i < n; ++i)
-      if (!(ropt[i] & RESET_KEEP_CODEC)) pv_pending_.push_back({slots[i], k_ + admit_delay_});
+      if (!(row[i].reset & RESET_KEEP_CODEC)) pv_pending_.push_back({slots[i], k_ + admit_delay_});
   memcpy(h_slots_, slots, sizeof(int) * n);
   memcpy(h_st_, st.data(), sizeof(SlotState) * n);
   memcpy(h_fp_, fp.data(), sizeof(int) * n);
   if (wire_) {
-    memcpy(h_wire_, wfmt.data(), sizeof(int) * n);
+    for (int i = 0; i < n; ++i) h_wire_[i] = row[i].wfmt;
     PTTS_HIP(hipMemcpyAsync(admit_wire_, h_wire_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
   }
   PTTS_HIP(hipMemcpyAsync(admit_slots_, h_slots_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
@@ -3511,7 +3521,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     // pinned staging (free again: ev_admit_ above). Only entries that change are written, so an
     // engine whose rows never ask for alignment enqueues nothing here.
     for (int i = 0; i < n; ++i) {
-      const int na = align && align[i] ? n_ids[i] : 0;
+      const int na = row[i].align;
       if (!na && !slot_align_[slots[i]]) continue;
       h_align_src_[i] = AlignEntry{voices[i]->F, na};
       PTTS_HIP(hipMemcpyAsync(align_tab_ + slots[i], h_align_src_ + i, sizeof(AlignEntry), hipMemcpyHostToDevice,
@@ -3520,9 +3530,11 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     }
   }
   if (any_opt) {  // the rows' first backbone input (the prefix's last latent) and RESET_* bits
-    memcpy(h_aopt_, ropt.data(), sizeof(int) * n);
-    for (int i = 0; i < n; ++i)
-      if (npre[i]) memcpy(h_alat_ + (size_t)i * LDIM, prefix[i] + (size_t)(npre[i] - 1) * LDIM, sizeof(float) * LDIM);
+    for (int i = 0; i < n; ++i) {
+      h_aopt_[i] = row[i].reset;
+      if (row[i].npre)
+        memcpy(h_alat_ + (size_t)i * LDIM, row[i].prefix + (size_t)(row[i].npre - 1) * LDIM, sizeof(float) * LDIM);
+    }
     PTTS_HIP(hipMemcpyAsync(admit_opt_, h_aopt_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
     if (any_prefix)
       PTTS_HIP(hipMemcpyAsync(admit_lat_, h_alat_, sizeof(float) * n * LDIM, hipMemcpyHostToDevice, stream_));

@@ -80,16 +80,10 @@ class Engine {
   // the engine's default, the cap (cfg.lsd_decode_steps)
   void slot_open(int slot, const ptts_voice* v, const int32_t* ids, int n, const ptts_gen_params& p,
                  int lsd_steps = 0);
-  // wire_rate / wire_enc (wire-enabled engines): the row's output format, per row; 0 in both (or null
-  // arrays) = none, 0 in one = its default (24000 Hz, PTTS_WIRE_S16)
-  // prefix / n_prefix / keep_codec (null arrays: none): row i starts behind
-  // n_prefix[i] teacher-forced latents prefix[i] [n_prefix[i]][32] (host memory, read before the
-  // call returns), and with keep_codec[i] = 1 on the codec state its slot's last utterance ended on
+  // opts: one entry per row, this library's own struct whole (its fields: pocket_tts.h; `size` is
+  // not read here), or nullptr for the defaults in every row. A prefix is read before the call returns
   void slots_open(int n, const int* slots, const ptts_voice* const* voices, const int32_t* ids, const int* n_ids,
-                  const ptts_gen_params* params, const int* lsd_steps = nullptr, const int* wire_rate = nullptr,
-                  const int* wire_enc = nullptr, const int* speed = nullptr, const float* const* prefix = nullptr,
-                  const int* n_prefix = nullptr, const int* keep_codec = nullptr, const int* pitch = nullptr,
-                  const int* gain_cdb = nullptr, const int* limit = nullptr, const int* align = nullptr);
+                  const ptts_gen_params* params, const ptts_slot_opts* opts);
   int lsd_cap() const { return lsd_; }
   int lsd_last_run() const { return lsd_last_run_; }  // Euler steps of the latest front part (0: none yet)
   void slot_close(int slot);

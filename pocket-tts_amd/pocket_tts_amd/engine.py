@@ -9,8 +9,8 @@ import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_LEVEL, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SlotOpts, SlotOpts2, SlotOpts3, SlotOpts4, SlotOpts5, ALIGN_TOKENS, check, fptr, lib, u8ptr)
-from .audio import level_cdb, pitch_cents, speed_permille
+                   SAMPLE_RATE, SlotOpts5, ALIGN_TOKENS, check, fptr, lib, u8ptr)
+from .audio import ENCODINGS, level_cdb, pitch_cents, pitch_plan, speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
 WIRE_ENCODINGS = {"pcm_s16le": WIRE_S16, "ulaw": WIRE_ULAW, "alaw": WIRE_ALAW, "flac": WIRE_FLAC}
@@ -39,7 +39,7 @@ class GenerationParams:
     seed: int = 0
     # the utterance's own LSD Euler step count (TTSModel.lsd_decode_steps, the server's lsd_steps),
     # 1 .. the engine's cap; None: the engine's lsd_decode_steps. Not part of ptts_gen_params: the
-    # admission passes it beside the struct (ptts_slot_open_ex).
+    # admission passes it beside the struct (ptts_slot_opts.lsd_steps).
     lsd_steps: int | None = None
     # wire format of the row (wire-enabled engines; Engine.fetch_wire returns its bytes): sample_rate
     # one of WIRE_RATES, encoding "pcm_s16le" / "ulaw" / "alaw" / "flac" (or a PTTS_WIRE_* code). None in both:
@@ -78,30 +78,90 @@ class GenerationParams:
             raise ValueError(f"prefix_latents must be [n, {LDIM}], got {a.shape}")
         return a if a.shape[0] else None
 
+    def output(self) -> "OutputOptions":
+        """The six output fields as they stand (not normalised: Engine callers may set any value)."""
+        return OutputOptions(self.sample_rate, self.encoding, self.speed, self.pitch, self.volume_db, self.limit)
+
     def wire(self) -> tuple[int, int]:
         """(wire_rate, wire_encoding) of ptts_slot_opts; (0, 0): none."""
-        return int(self.sample_rate or 0), wire_encoding_code(self.encoding)
+        return self.output().codes()[:2]
 
     def opts(self) -> tuple[int, int, int]:
-        """(wire_rate, wire_encoding, speed_permille) of ptts_slot_opts; all 0: the defaults. A speed
-        out of range is passed on as it is (rounded to permille): the admission refuses it."""
-        sp = 0 if self.speed is None else round(float(self.speed) * 1000)
-        return (*self.wire(), 0 if sp == 1000 else sp)
+        """(wire_rate, wire_encoding, speed_permille) of ptts_slot_opts; all 0: the defaults."""
+        return self.output().codes()[:3]
 
     def cents(self) -> int:
-        """pitch_cents of ptts_slot_opts: round(100 * semitones), passed on as it is (the admission
-        refuses a value out of range); 0: none."""
-        return 0 if self.pitch is None else round(100.0 * float(self.pitch))
+        """pitch_cents of ptts_slot_opts; 0: none."""
+        return self.output().codes()[3]
 
     def level(self) -> tuple[int, int]:
-        """(gain_cdb, limit) of ptts_slot_opts: round(100 * dB), passed on as it is (the admission
-        refuses a value out of range), and 0 / 1; (0, 0): the row is not in the level stage."""
-        return (0 if self.volume_db is None else round(100.0 * float(self.volume_db)), int(self.limit or 0))
+        """(gain_cdb, limit) of ptts_slot_opts; (0, 0): the row is not in the level stage."""
+        return self.output().codes()[4:]
+
+    def slot_opts(self, default_lsd: int = 0) -> SlotOpts5:
+        """The row's ptts_slot_opts, the whole 64-byte struct (fields it does not name are 0).
+        default_lsd: lsd_steps of a row that names none (0: the engine's cap). The struct keeps the
+        prefix array it points into alive."""
+        o = SlotOpts5(size=C.sizeof(SlotOpts5), lsd_steps=int(default_lsd if self.lsd_steps is None else self.lsd_steps))
+        o.wire_rate, o.wire_encoding, o.speed_permille, o.pitch_cents, o.gain_cdb, o.limit = self.output().codes()
+        o.keep_codec, o.align = int(self.keep_codec), int(bool(self.align))
+        pre = o._prefix = self.prefix()
+        if pre is not None:
+            o.prefix_latents, o.n_prefix = pre.ctypes.data, pre.shape[0]
+        return o
 
     def to_c(self) -> GenParams:
         return GenParams(float(self.temp), float(self.eos_threshold),
                          float(self.noise_clamp) if self.noise_clamp is not None else 0.0,
                          int(self.frames_after_eos), int(self.max_frames), int(self.seed) & (2**64 - 1))
+
+
+@dataclass(frozen=True)
+class OutputOptions:
+    """What a request asks of its row's audio output, the fields of the same names of
+    GenerationParams: the one place that says what they come to. of() is the way in from a caller's
+    raw values; a value it returns holds None / False in every field that changes nothing."""
+
+    sample_rate: int | None = None
+    encoding: str | int | None = None
+    speed: float | None = None
+    pitch: float | None = None
+    volume_db: float | None = None
+    limit: bool = False
+
+    @classmethod
+    def of(cls, sample_rate=None, encoding=None, speed=None, pitch=None, volume_db=None, limit=None):
+        """Normalised: speed 1.0 is no speed, pitch 0 no pitch, volume 0 without limit no level (else
+        rounded to hundredths of a dB). ValueError for a value out of range, or a pitch that with
+        this speed leaves the time-scaling range."""
+        speed = float(speed) if speed_permille(speed) else None
+        pitch = float(pitch) if pitch_cents(pitch) else None
+        if pitch is not None:
+            pitch_plan(pitch_cents(pitch), speed_permille(speed))
+        cdb = level_cdb(volume_db)
+        volume_db = cdb / 100.0 if cdb or limit else None
+        return cls(sample_rate, encoding, speed, pitch, volume_db, bool(limit) and volume_db is not None)
+
+    def codes(self) -> tuple[int, int, int, int, int, int]:
+        """(wire_rate, wire_encoding, speed_permille, pitch_cents, gain_cdb, limit) of ptts_slot_opts,
+        0 for none. Values out of range are passed on as they are, rounded: the admission refuses them."""
+        sp = 0 if self.speed is None else round(float(self.speed) * 1000)
+        return (int(self.sample_rate or 0), wire_encoding_code(self.encoding), 0 if sp == 1000 else sp,
+                0 if self.pitch is None else round(100.0 * float(self.pitch)),
+                0 if self.volume_db is None else round(100.0 * float(self.volume_db)), int(self.limit or 0))
+
+    @property
+    def wire(self) -> tuple[int, str] | None:
+        """(rate, encoding name) of a wire row, whose items are bytes the engine converted: a row
+        with any of the options, at 24000 / pcm_s16le unless it says otherwise (the engine's rule,
+        Engine::slots_open). None: f32 frames."""
+        c = self.codes()
+        return (c[0] or SAMPLE_RATE, ENCODINGS[(c[1] or WIRE_S16) - 1]) if any(c) else None
+
+    def apply(self, p: GenerationParams) -> GenerationParams:
+        p.sample_rate, p.encoding, p.speed, p.pitch = self.sample_rate, self.encoding, self.speed, self.pitch
+        p.volume_db, p.limit = self.volume_db, self.limit
+        return p
 
 
 class Voice:
@@ -543,16 +603,10 @@ class Engine:
 
     # -- slots
     def open(self, slot: int, voice: Voice, ids, params: GenerationParams):
-        if params.opts() != (0, 0, 0) or params.prefix() is not None or params.keep_codec or params.cents() \
-                or params.level() != (0, 0) or params.align:
-            return self.open_many([slot], [voice], [ids], [params])
-        a = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
-        cp = params.to_c()
-        check(lib().ptts_slot_open_ex(self.handle, slot, voice.handle, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size,
-                                      C.byref(cp), self._row_lsd(params)))
+        self.open_many([slot], [voice], [ids], [params])
 
     def open_many(self, slots, voices, ids_list, params_list):
-        """Batched admission (ptts_slots_open_ex): row slots[i] <- (voices[i], ids_list[i], params_list[i])."""
+        """Batched admission (ptts_slots_open_opts): row slots[i] <- (voices[i], ids_list[i], params_list[i])."""
         n = len(slots)
         sl = np.ascontiguousarray(np.asarray(slots, np.int32))
         arrs = [np.asarray(x, np.int32).reshape(-1) for x in ids_list]
@@ -560,51 +614,11 @@ class Engine:
         cat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int32))
         vh = (C.c_void_p * n)(*[v.handle for v in voices])
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
-        lsd = np.ascontiguousarray(np.array([self._row_lsd(p) for p in params_list], np.int32))
+        rows = [p.slot_opts(self.lsd_decode_steps) for p in params_list]  # (they keep the prefixes alive)
+        opts = (SlotOpts5 * n)(*rows)
         i32 = C.POINTER(C.c_int32)
-        pre = [p.prefix() for p in params_list]  # (kept alive until the call returns)
-        if any(p.align for p in params_list):  # a row in the align stage: the 64-byte struct
-            opts = (SlotOpts5 * n)(*[SlotOpts5(C.sizeof(SlotOpts5), int(lsd[i]), *p.opts(),
-                                               pre[i].ctypes.data if pre[i] is not None else None,
-                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents(),
-                                               0, *p.level(), int(bool(p.align)), 0)
-                                     for i, p in enumerate(params_list)])
-            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
-            return
-        if any(p.level() != (0, 0) for p in params_list):  # a gain or limit: the 56-byte struct
-            opts = (SlotOpts4 * n)(*[SlotOpts4(C.sizeof(SlotOpts4), int(lsd[i]), *p.opts(),
-                                               pre[i].ctypes.data if pre[i] is not None else None,
-                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents(),
-                                               0, *p.level())
-                                     for i, p in enumerate(params_list)])
-            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
-            return
-        if any(p.cents() for p in params_list):  # a pitch: the 48-byte struct
-            opts = (SlotOpts3 * n)(*[SlotOpts3(C.sizeof(SlotOpts3), int(lsd[i]), *p.opts(),
-                                               pre[i].ctypes.data if pre[i] is not None else None,
-                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec), p.cents())
-                                     for i, p in enumerate(params_list)])
-            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
-            return
-        if any(a is not None for a in pre) or any(p.keep_codec for p in params_list):
-            opts = (SlotOpts2 * n)(*[SlotOpts2(C.sizeof(SlotOpts2), int(lsd[i]), *p.opts(),
-                                               pre[i].ctypes.data if pre[i] is not None else None,
-                                               0 if pre[i] is None else pre[i].shape[0], int(p.keep_codec))
-                                     for i, p in enumerate(params_list)])
-            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
-            return
-        if any(p.opts() != (0, 0, 0) for p in params_list):  # a wire format or a speed: ptts_slots_open_opts
-            opts = (SlotOpts * n)(*[SlotOpts(C.sizeof(SlotOpts), int(lsd[i]), *p.opts())
-                                    for i, p in enumerate(params_list)])
-            check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                             nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
-            return
-        check(lib().ptts_slots_open_ex(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
-                                       nid.ctypes.data_as(i32), ps, lsd.ctypes.data_as(i32)))
+        check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
+                                         nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
 
     def close_slot(self, slot: int):
         check(lib().ptts_slot_close(self.handle, slot))

@@ -149,9 +149,9 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import ALIGN_TOKENS, FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, pitch_cents, pitch_plan, speed_permille, wav_bytes,  # noqa: F401 (re-exported wire formats)
+from .audio import (ENCODINGS, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
-from .engine import GenerationParams, Voice
+from .engine import GenerationParams, OutputOptions, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
                    silence_samples)
 
@@ -293,6 +293,11 @@ class _Call:
         self.done.set()
 
 
+def row_output(params) -> OutputOptions:
+    """The output options of a row's params (a foreign params object that has none: the defaults)."""
+    return params.output() if hasattr(params, "output") else OutputOptions()
+
+
 def item_samples(item, wire) -> int:
     """Samples of one delivered item: wire bytes of the format `wire` (rate, encoding), or f32 frames."""
     if isinstance(item, (bytes, bytearray)):
@@ -393,12 +398,10 @@ class Request(_Consumer):
     def __post_init__(self):
         if getattr(self.params, "align", False):
             self.align_rows = []
-        rate, enc = self.params.wire() if hasattr(self.params, "wire") else (0, 0)
-        self.speed = self.params.opts()[2] if hasattr(self.params, "opts") else 0
-        self.pitch = self.params.cents() if hasattr(self.params, "cents") else 0
-        self.level = tuple(self.params.level()) if hasattr(self.params, "level") else (0, 0)
-        if rate or enc or self.speed or self.pitch or self.level != (0, 0):  # a speed, pitch or gain alone: 24000 / pcm_s16le
-            self.wire = (rate or SAMPLE_RATE, ENCODINGS[(enc or 1) - 1])
+        out = row_output(self.params)
+        self.wire = out.wire or self.wire
+        _, _, self.speed, self.pitch, *lv = out.codes()
+        self.level = tuple(lv)
 
     def put(self, item):
         """Driver side: hand over a frame (np.ndarray), the end marker (None) or an error."""
@@ -1192,27 +1195,19 @@ class TTSService:
             if chain or (token_ids is None and (self.long_form if long_form is None else long_form)):
                 raise ValueError("flac with long_form or continuity is not available: the segments of one response "
                                  "are separate rows, each numbering its samples from 0")
-        if speed_permille(speed) == 0:  # (ValueError outside [0.5, 2.0]); 1.0: the request without it
-            speed = None
-        elif not self.tempo:
-            raise ValueError("this server runs without the tempo stage (--no-tempo or --no-wire): speed is not "
-                             "available")
-        if pitch_cents(pitch) == 0:  # (ValueError outside [-12, 12]); 0: the request without it
-            pitch = None
-        else:
-            if not self.pitch:
-                raise ValueError("this server runs without the pitch stage (--no-pitch, --no-tempo or --no-wire): "
-                                 "pitch is not available")
-            pitch_plan(pitch_cents(pitch), speed_permille(speed))  # (ValueError: with this speed, outside WSOLA's range)
         if limit is not None and not isinstance(limit, (bool, np.bool_)):
             raise ValueError(f"limit must be a bool, got {limit!r}")
-        if level_cdb(volume_db) == 0 and not limit:  # (ValueError outside [-24, 24]); the request without them
-            volume_db, limit = None, None
-        else:
-            if not self.level:
-                raise ValueError("this server runs without the level stage (--no-volume or --no-wire): volume_db / "
-                                 "limit are not available")
-            volume_db, limit = level_cdb(volume_db) / 100.0, bool(limit)
+        # (ValueError: a value out of range); a field that changes nothing is the request without it
+        out = OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit)
+        if out.speed is not None and not self.tempo:
+            raise ValueError("this server runs without the tempo stage (--no-tempo or --no-wire): speed is not "
+                             "available")
+        if out.pitch is not None and not self.pitch:
+            raise ValueError("this server runs without the pitch stage (--no-pitch, --no-tempo or --no-wire): "
+                             "pitch is not available")
+        if out.volume_db is not None and not self.level:
+            raise ValueError("this server runs without the level stage (--no-volume or --no-wire): volume_db / "
+                             "limit are not available")
         if lsd_steps is not None and not 1 <= lsd_steps <= self.max_lsd_steps:
             raise ValueError(f"lsd_steps must be in [1, {self.max_lsd_steps}], the engine's cap (--max-lsd-steps); "
                              f"the default is {self.lsd_decode_steps}")
@@ -1257,18 +1252,14 @@ class TTSService:
             target = clip if clip is not None else self.voices[name]
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
-                                                            lsd_steps, sample_rate, encoding, speed, pitch,
-                                                            volume_db, limit, bool(timestamps)))
+                                                            lsd_steps, out, bool(timestamps)))
                         if sg[0] == "text" else sg for sg in segments]
-                wire = None  # (pauses: silence of their stated duration, whatever the speed)
-                if sample_rate is not None or encoding is not None or speed is not None or pitch is not None \
-                        or volume_db is not None:
-                    wire = (sample_rate or SAMPLE_RATE, encoding or "pcm_s16le")
+                # (pauses: silence of their stated duration in the rows' format, whatever the speed)
                 if chain:
-                    return self.scheduler.submit_group(segs, target, wire, continuity=True)
-                return self.scheduler.submit_group(segs, target, wire)
+                    return self.scheduler.submit_group(segs, target, out.wire, continuity=True)
+                return self.scheduler.submit_group(segs, target, out.wire)
             return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       sample_rate, encoding, speed, pitch, volume_db, limit, bool(timestamps))
+                                       out, bool(timestamps))
 
     def words(self, r) -> list[dict]:
         """[{"word", "start", "end"}] of a finished timestamps request (its audio consumed), in seconds
@@ -1294,14 +1285,11 @@ class TTSService:
         return out
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       sample_rate=None, encoding=None, speed=None, pitch=None, volume_db=None, limit=None,
-                       align=False) -> Request:
-        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate, encoding,
-                                speed, pitch, volume_db, limit, align)
+                       out=OutputOptions(), align=False) -> Request:
+        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, out, align)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
-    def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, sample_rate=None,
-                       encoding=None, speed=None, pitch=None, volume_db=None, limit=None,
+    def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, out=OutputOptions(),
                        align=False) -> GenerationParams:
         self._seed += 1
         seed = self._seed
@@ -1309,18 +1297,8 @@ class TTSService:
                              eos_threshold=self.eos_threshold if eos_threshold is None else eos_threshold,
                              noise_clamp=self.noise_clamp if noise_clamp is None else noise_clamp,
                              frames_after_eos=fae, max_frames=mgl, seed=seed,
-                             lsd_steps=None if lsd_steps is None else int(lsd_steps))
-        if sample_rate is not None or encoding is not None:  # a request that names neither: as before
-            p.sample_rate, p.encoding = sample_rate, encoding
-        if speed is not None:
-            p.speed = float(speed)
-        if pitch is not None:
-            p.pitch = float(pitch)
-        if volume_db is not None:  # (set together: a request in the level stage)
-            p.volume_db, p.limit = float(volume_db), bool(limit)
-        if align:
-            p.align = True
-        return p
+                             lsd_steps=None if lsd_steps is None else int(lsd_steps), align=bool(align))
+        return out.apply(p)
 
     # -- per-request and run-time voices
     def voice_clip(self, spec: str) -> VoiceClip:
@@ -1738,13 +1716,13 @@ class StandInEngine:
             if getattr(p, "align", False) and len(ids) > ALIGN_TOKENS:
                 raise RuntimeError("align: more than PTTS_ALIGN_TOKENS token ids")
         for p in params_list:  # nothing is admitted if one row is refused
-            lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
-            rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
+            out = row_output(p)
+            lv = out.codes()[4:]
             if lv != (0, 0) and not self.level_enabled:
                 raise RuntimeError("a gain or limit needs a level-enabled engine")
             if getattr(p, "align", False) and not self.align_enabled:
                 raise RuntimeError("align needs an align-enabled engine")
-            if (rate or enc or lv != (0, 0)) and not (self.level_enabled and rate in (0, SAMPLE_RATE) and enc in (0, 1, 2, 3)):
+            if out.wire and not (self.level_enabled and out.wire[0] == SAMPLE_RATE and out.wire[1] != "flac"):
                 raise RuntimeError("the stand-in engine converts to 24 kHz pcm_s16le / ulaw / alaw only, with level=True")
         for s, ids, p in zip(slots, ids_list, params_list):
             pre = getattr(p, "prefix_latents", None)
@@ -1753,10 +1731,9 @@ class StandInEngine:
             self.arow.pop(s, None)
             if getattr(p, "align", False):
                 self.arow[s] = len(ids)
-            lv = tuple(p.level()) if hasattr(p, "level") else (0, 0)
-            rate, enc = p.wire() if hasattr(p, "wire") else (0, 0)
-            if rate or enc or lv != (0, 0):
-                self.fmt[s] = [ENCODINGS[(enc or 1) - 1], lv, 0, int(ids[0]) if len(ids) else 0, p.max_frames, None]
+            out = row_output(p)
+            if out.wire:
+                self.fmt[s] = [out.wire[1], out.codes()[4:], 0, int(ids[0]) if len(ids) else 0, p.max_frames, None]
             self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames, len(self.admit_log)]
             self.admit_log.append((int(s), [int(i) for i in ids], None if pre is None else np.array(pre, np.float32),
                                   bool(getattr(p, "keep_codec", False))))

@@ -31,11 +31,10 @@ from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
-from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE, WIRE_FLAC
-from .audio import (flac_stream_header, level_cdb, pitch_cents, read_wav, read_wav_from_bytes, speed_permille, wire_bytes,
-                    wire_samples)
+from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
+from .audio import flac_stream_header, read_wav, read_wav_from_bytes, wire_bytes, wire_samples
 from . import align as _align
-from .engine import Engine, GenerationParams, Voice
+from .engine import Engine, GenerationParams, OutputOptions, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
 
@@ -207,30 +206,26 @@ class TTSModel:
                              "(max_lsd_decode_steps at load)")
 
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
-                 sample_rate: int | None = None, encoding=None, speed: float | None = None,
-                 previous: Continuation | None = None, latents: list | None = None,
-                 pitch: float | None = None, volume_db: float | None = None,
-                 limit: bool = False, align: list | None = None) -> Iterator[np.ndarray]:
-        """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. With a wire format
-        (sample_rate / encoding; a wire-enabled engine), a speed (a tempo-enabled one) or a pitch (a
-        pitch-enabled one; 24 kHz 16-bit unless a format is given) the items are the row's wire chunks, bytes converted on the
-        GPU (Engine.fetch_wire), instead of f32 frames.
+                 out: OutputOptions = OutputOptions(), previous: Continuation | None = None,
+                 latents: list | None = None, align: list | None = None) -> Iterator[np.ndarray]:
+        """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. For a wire row (out.wire:
+        a format on a wire-enabled engine, a speed on a tempo-enabled one, a pitch, a gain or limit
+        likewise) the items are the row's wire chunks, bytes converted on the GPU (Engine.fetch_wire),
+        instead of f32 frames.
         previous: the segment continues that one (section 20): admitted behind its ids and, as a
         teacher-forced prefix, its latents, on the codec state it left (only the new frames are
         yielded); where that exceeds the engine's max_ctx, as a plain segment. latents: a list that
         receives the latent of every frame yielded. align: a list that receives the alignment row of
         every frame yielded (an align-enabled engine; the row is admitted with align)."""
         self._check_lsd()
-        params = self._params(max_frames, frames_after_eos)
+        params = out.apply(self._params(max_frames, frames_after_eos))
         params.lsd_steps = int(self.lsd_decode_steps)
-        params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
-        params.volume_db, params.limit = volume_db, bool(limit)
         params.align = align is not None
         if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
                                      + max_frames <= self.engine.max_ctx):
             ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
             params.prefix_latents, params.keep_codec = np.asarray(previous.latents, np.float32), True
-        wire = params.opts() != (0, 0, 0) or params.cents() != 0 or params.level() != (0, 0)
+        wire = out.wire is not None
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
@@ -274,13 +269,11 @@ class TTSModel:
         encoding "flac" (a FLAC-enabled engine): the items are the FLAC frames of each chunk (DESIGN.md
         section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0, so
         the text must be one segment: ValueError where it splits into several."""
-        if speed_permille(speed) == 0:
-            speed = None
-        if pitch_cents(pitch) == 0:
-            pitch = None
-        if level_cdb(volume_db) == 0:
-            volume_db = 0.0 if limit else None
-        if encoding in ("flac", WIRE_FLAC) and isinstance(text_or_ids, str) and \
+        yield from self._stream(text_or_ids, voice_state, max_frames, words,
+                                OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit))
+
+    def _stream(self, text_or_ids, voice_state, max_frames, words, out: OutputOptions) -> Iterator[np.ndarray]:
+        if out.wire and out.wire[1] == "flac" and isinstance(text_or_ids, str) and \
                 len(self.split_into_best_sentences(text_or_ids)) > 1:
             raise ValueError("flac: the text splits into several segments, each a stream of its own (section 21, Limits)")
         if not isinstance(text_or_ids, str):
@@ -288,16 +281,14 @@ class TTSModel:
             if words is None and max_frames is None:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
-            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, sample_rate, encoding,
-                                     speed, pitch=pitch, volume_db=volume_db, limit=limit)
+            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, out)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), sample_rate, encoding, speed, pitch=pitch,
-                                     volume_db=volume_db, limit=limit)
+                                     estimate_frames_after_eos(chunk), out)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
@@ -309,27 +300,22 @@ class TTSModel:
         timestamps=True (text input, a model loaded with align=True and a tokenizer that names its
         pieces): returns (audio, words), words = [{"word", "start", "end"}] in seconds of that audio
         (align.py: each sentence chunk's words offset by the audio delivered before it)."""
+        out = OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit)
         if timestamps:
-            return self._generate_timed(text_or_ids, voice_state, max_frames, sample_rate, encoding, speed, pitch,
-                                        volume_db, limit)
-        frames = list(self.generate_stream(text_or_ids, voice_state, max_frames, words, sample_rate, encoding, speed,
-                                           pitch, volume_db, limit))
+            return self._generate_timed(text_or_ids, voice_state, max_frames, out)
+        frames = list(self._stream(text_or_ids, voice_state, max_frames, words, out))
         if not frames:
             raise RuntimeError("No audio generated")
-        if encoding in ("flac", WIRE_FLAC):
-            rate = int(sample_rate or SAMPLE_RATE)
-            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, speed_permille(speed),
-                                                        pitch_cents(pitch))) + b"".join(frames)
-        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch) \
-                or level_cdb(volume_db) or limit:
-            return b"".join(frames)
-        return np.concatenate(frames, axis=2)[0]
+        if out.wire and out.wire[1] == "flac":
+            rate, (sp, cents) = out.wire[0], out.codes()[2:4]
+            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, sp, cents)) + b"".join(frames)
+        return b"".join(frames) if out.wire else np.concatenate(frames, axis=2)[0]
 
-    def _units(self, chunk, sample_rate, encoding) -> int:
+    def _units(self, chunk, encoding) -> int:
         """Samples of one delivered item at the rate it is delivered at (f32 frames: 24 kHz)."""
         if not isinstance(chunk, (bytes, bytearray)):
             return int(np.asarray(chunk).shape[-1])
-        return len(chunk) // (1 if encoding in ("ulaw", "alaw", 2, 3) else 2)
+        return len(chunk) // (1 if encoding in ("ulaw", "alaw") else 2)
 
     def _words_of(self, ids, rows, n_frames, max_frames, fae, speed, seconds) -> list[dict]:
         """The words of one segment over its own audio of `seconds`: the EOS frame is the frame the
@@ -343,36 +329,29 @@ class TTSModel:
         eos = max(n_frames - fae, 0) if n_frames < max_frames else None
         return _align.timestamps(tok, ids, A, speed or 1.0, eos, seconds)
 
-    def _generate_timed(self, text, voice_state, max_frames, sample_rate, encoding, speed, pitch, volume_db, limit):
+    def _generate_timed(self, text, voice_state, max_frames, out: OutputOptions):
         if not isinstance(text, str):
             raise ValueError("timestamps: token ids carry no words, pass text")
         if not self.engine.align_enabled:
             raise ValueError("timestamps need a model loaded with align=True")
-        if encoding in ("flac", WIRE_FLAC):
+        rate, enc = out.wire or (SAMPLE_RATE, None)
+        if enc == "flac":
             raise ValueError("timestamps: not with flac (ask for pcm_s16le and encode the result)")
-        speed = speed if speed_permille(speed) else None
-        pitch = pitch if pitch_cents(pitch) else None
-        if level_cdb(volume_db) == 0:
-            volume_db = 0.0 if limit else None
-        wire = sample_rate is not None or encoding is not None or speed is not None or pitch is not None \
-            or volume_db is not None
-        rate = int(sample_rate or SAMPLE_RATE) if wire else SAMPLE_RATE
         tok = self._tok()
-        out, words, at = [], [], 0.0
+        chunks, words, at = [], [], 0.0
         for chunk in self.split_into_best_sentences(text):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             mf, fae, rows = max_frames or max_gen_len(prepared), estimate_frames_after_eos(chunk), []
-            frames = list(self._segment(ids, voice_state, mf, fae, sample_rate, encoding, speed, pitch=pitch,
-                                        volume_db=volume_db, limit=limit, align=rows))
-            seconds = sum(self._units(f, rate, encoding) for f in frames) / rate
-            for w in self._words_of(ids, rows, len(frames), mf, fae, speed, seconds):
+            frames = list(self._segment(ids, voice_state, mf, fae, out, align=rows))
+            seconds = sum(self._units(f, enc) for f in frames) / rate
+            for w in self._words_of(ids, rows, len(frames), mf, fae, out.speed, seconds):
                 words.append({"word": w["word"], "start": round(w["start"] + at, 6), "end": round(w["end"] + at, 6)})
             at += seconds
-            out += frames
-        if not out:
+            chunks += frames
+        if not chunks:
             raise RuntimeError("No audio generated")
-        return (b"".join(out) if wire else np.concatenate(out, axis=2)[0]), words
+        return (b"".join(chunks) if out.wire else np.concatenate(chunks, axis=2)[0]), words
 
     def generate_stream_long(self, text: str, voice_state: Voice, continuity: bool = False) -> Iterator[np.ndarray]:
         """tts_model.rs:1074-1131: text segments between pause markers, silence for each pause.
@@ -452,37 +431,38 @@ class TTSModel:
         timestamps): ("pause", samples) or ("text", ids, params, frames_after_eos, meta), meta the
         segment's alignment rows, frame count and delivered samples, complete once it is delivered;
         the text rows are then admitted with align."""
+        return self._stream_parallel(text, voice_state, pauses, rows, OutputOptions.of(sample_rate, encoding, speed, pitch),
+                                     timed)
+
+    def _stream_parallel(self, text, voice_state, pauses, rows, out: OutputOptions, timed) -> Iterator:
         self._check_lsd()
-        if encoding in ("flac", WIRE_FLAC):
+        wire = out.wire
+        if wire and wire[1] == "flac":
             raise ValueError("flac: parallel rows are separate streams, each numbered from 0 (section 21, Limits)")
         tok = self._tok()
         eng = self.engine
-        speed = speed if speed_permille(speed) else None
-        pitch = pitch if pitch_cents(pitch) else None
-        wire = sample_rate is not None or encoding is not None or speed is not None or pitch is not None
         n_rows = max(1, min(int(rows or eng.max_slots), eng.max_slots))
         items = []  # per segment: ("pause", item) | ["text", ids, params, frames, done]
         for kind, val in long_form_segments(text, self.count_tokens, pauses):
             if kind == "text":
                 ids, mgl, fae = segment_request(val, tok)
-                params = self._params(mgl, fae)
+                params = out.apply(self._params(mgl, fae))
                 params.lsd_steps = int(self.lsd_decode_steps)
-                params.sample_rate, params.encoding, params.speed, params.pitch = sample_rate, encoding, speed, pitch
                 params.align = timed is not None
-                meta = {"rows": [], "frames": 0, "units": 0, "encoding": encoding}
+                meta = {"rows": [], "frames": 0, "units": 0, "encoding": wire and wire[1]}
                 items.append(["text", np.asarray(ids, np.int32), params, [], False, meta if timed is not None else None])
                 if timed is not None:
                     timed.append(("text", items[-1][1], params, fae, meta))
             elif wire:
-                n = silence_samples(val, int(sample_rate or SAMPLE_RATE))
-                items.append(("pause", wire_bytes(np.zeros(n, np.float32), encoding or "pcm_s16le")))
+                n = silence_samples(val, wire[0])
+                items.append(("pause", wire_bytes(np.zeros(n, np.float32), wire[1])))
                 if timed is not None:
                     timed.append(("pause", n))
             else:
                 items.append(("pause", np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)))
                 if timed is not None:
                     timed.append(("pause", silence_samples(val, self.sample_rate)))
-        return self._run_parallel(items, voice_state, n_rows, wire)
+        return self._run_parallel(items, voice_state, n_rows, wire is not None)
 
     def _run_parallel(self, items, voice_state: Voice, n_rows: int, wire: bool) -> Iterator:
         eng = self.engine
@@ -531,7 +511,7 @@ class TTSModel:
                     if it[5] is not None:
                         it[5]["rows"].append(arows[s])
                         it[5]["frames"] += 1
-                        it[5]["units"] += self._units(it[3][-1], 0, it[5]["encoding"])
+                        it[5]["units"] += self._units(it[3][-1], it[5]["encoding"])
                     if r.last[s]:
                         it[4] = True
                         del active[s]
@@ -551,26 +531,23 @@ class TTSModel:
         if timestamps and not self.engine.align_enabled:
             raise ValueError("timestamps need a model loaded with align=True")
         timed = [] if timestamps else None
-        chunks = list(self.generate_stream_parallel(text, voice_state, pauses, rows, sample_rate, encoding, speed,
-                                                    pitch, timed=timed))
+        out = OutputOptions.of(sample_rate, encoding, speed, pitch)
+        chunks = list(self._stream_parallel(text, voice_state, pauses, rows, out, timed))
         if not chunks:
             raise RuntimeError("No audio generated")
+        audio = b"".join(chunks) if out.wire else np.concatenate(chunks, axis=2)[0]
         if timestamps:
-            wire = sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch)
-            rate = int(sample_rate or SAMPLE_RATE) if wire else SAMPLE_RATE
+            rate = out.wire[0] if out.wire else SAMPLE_RATE
             words, at = [], 0
             for rec in timed:
                 if rec[0] == "pause":
                     at += rec[1]
                     continue
                 _, ids, params, fae, meta = rec
-                for w in self._words_of(ids, meta["rows"], meta["frames"], params.max_frames, fae,
-                                        speed if speed_permille(speed) else None, meta["units"] / rate):
+                for w in self._words_of(ids, meta["rows"], meta["frames"], params.max_frames, fae, out.speed,
+                                        meta["units"] / rate):
                     words.append({"word": w["word"], "start": round(w["start"] + at / rate, 6),
                                   "end": round(w["end"] + at / rate, 6)})
                 at += meta["units"]
-            audio = b"".join(chunks) if wire else np.concatenate(chunks, axis=2)[0]
             return audio, words
-        if sample_rate is not None or encoding is not None or speed_permille(speed) or pitch_cents(pitch):
-            return b"".join(chunks)
-        return np.concatenate(chunks, axis=2)[0]
+        return audio
