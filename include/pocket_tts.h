@@ -447,6 +447,37 @@ int ptts_flac_enable(ptts_engine* e, int on);
 long ptts_flac_bound(long n);
 int ptts_flac_encode(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
                      uint8_t* out, int* n_bytes);
+/* The frame index. A chunk is at most three frames and carries no length
+ * field, so the FLAC stage writes, beside each chunk, every frame's byte length and block size.
+ * ptts_fetch_flac_index is the companion of ptts_fetch_wire (the same calls_back, rows and event, no
+ * bookkeeping of its own): index[b][i] = {byte length, block size} of frame i of row b's chunk for
+ * i < n_frames[b], zeros behind; n_frames[b] is 0 for a row that is not FLAC and for a slot with no
+ * chunk, and the lengths of a chunk's frames sum to the n_bytes[b] of ptts_fetch_wire.
+ * PTTS_ERR_INVALID on an engine without ptts_flac_enable. ptts_flac_encode_ex is ptts_flac_encode
+ * with the index of its frames (index [3][2] and n_frames: both, or both NULL). */
+int ptts_fetch_flac_index(ptts_engine* e, int calls_back, int n_rows, int* index /* [n_rows][3][2] */,
+                          int* n_frames /* [n_rows] */);
+int ptts_flac_encode_ex(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
+                        uint8_t* out, int* n_bytes, int* index, int* n_frames);
+/* Joining segments (host only: no engine, no GPU). A row numbers its frames from sample 0 of its own
+ * utterance; a response of several rows and pauses is one stream when every frame's number is moved
+ * to its place. ptts_flac_rebase writes the n_frames frames at `in` (n_bytes in all; index
+ * [n_frames][2] as above) to `out` with the coded sample number of each raised by delta >= 0, in its
+ * shortest form, and the CRC-8 and CRC-16 renewed; the body bits are untouched (moved by whole bytes
+ * where the number's width changes), so a frame grows by at most 6 bytes: out_cap >= n_bytes +
+ * 6 n_frames. `in` and `out` must not overlap. Everything is checked before the first byte is
+ * written; PTTS_ERR_INVALID (and `out` untouched) for a frame that does not start with FF F9 or is
+ * not a header of section 21.1, a CRC-8 or CRC-16 that does not verify, index lengths that do not sum
+ * to n_bytes, a block size that differs from the index, delta < 0, a number + delta + block size
+ * above 2^36, or a short out_cap.
+ * ptts_flac_silence writes n >= 0 zero samples at sample_rate (one of the wire rates) as CONSTANT
+ * frames in blocks of 4,608, the last one shorter, numbered from first_sample (first_sample + n <=
+ * 2^36): the frames of section 21's rule on zeros. out_cap >= ptts_flac_silence_bound(n) =
+ * 19 ceil(n / 4608) (0 for n < 1). */
+int ptts_flac_rebase(const uint8_t* in, int n_bytes, const int* index, int n_frames, long long delta, uint8_t* out,
+                     int out_cap, int* out_bytes);
+long ptts_flac_silence_bound(long long n);
+int ptts_flac_silence(long long n, int sample_rate, long long first_sample, uint8_t* out, long out_cap, long* out_bytes);
 
 /* *cap: cfg.lsd_decode_steps. *last_run: the Euler steps the most recent step call ran (0 before
  * the first): the largest count among that call's rows still open (admitted, not closed, last

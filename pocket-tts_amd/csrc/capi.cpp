@@ -4,6 +4,7 @@
 #include <string>
 
 #include "engine.h"
+#include "flac_join.h"
 #include "pocket_tts.h"
 #include "pocket_tts_probe.h"
 #include "test_hooks.h"
@@ -427,7 +428,37 @@ long ptts_flac_bound(long n) { return ptts::Engine::flac_bound(n); }
 
 int ptts_flac_encode(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
                      uint8_t* out, int* n_bytes) {
-  return guard([&] { eng(e).flac_encode_host(samples, n, sample_rate, first_sample, out, n_bytes); });
+  return ptts_flac_encode_ex(e, samples, n, sample_rate, first_sample, out, n_bytes, nullptr, nullptr);
+}
+
+int ptts_flac_encode_ex(ptts_engine* e, const int16_t* samples, int n, int sample_rate, long long first_sample,
+                        uint8_t* out, int* n_bytes, int* index, int* n_frames) {
+  return guard([&] { eng(e).flac_encode_host(samples, n, sample_rate, first_sample, out, n_bytes, index, n_frames); });
+}
+
+int ptts_fetch_flac_index(ptts_engine* e, int calls_back, int n_rows, int* index, int* n_frames) {
+  return guard([&] { eng(e).fetch_flac_index(calls_back, n_rows, index, n_frames); });
+}
+
+static_assert(ptts::FLAC_JOIN_BLOCK == ptts::FLAC_BLOCK && ptts::FLAC_SILENCE_FRAME == ptts::FLAC_FRAME_OVERHEAD + 2 &&
+                  ptts::flac_silence_bound(ptts::FLAC_BLOCK + 1) == 2 * (ptts::FLAC_FRAME_OVERHEAD + 2),
+              "a CONSTANT frame is the frame overhead and one 16-bit sample: the silence bound");
+
+int ptts_flac_rebase(const uint8_t* in, int n_bytes, const int* index, int n_frames, long long delta, uint8_t* out,
+                     int out_cap, int* out_bytes) {
+  return guard([&] {
+    if (const char* err = ptts::flac_rebase(in, n_bytes, index, n_frames, delta, out, out_cap, out_bytes))
+      throw ptts::Error(PTTS_ERR_INVALID, err);
+  });
+}
+
+long ptts_flac_silence_bound(long long n) { return ptts::flac_silence_bound(n); }
+
+int ptts_flac_silence(long long n, int sample_rate, long long first_sample, uint8_t* out, long out_cap, long* out_bytes) {
+  return guard([&] {
+    if (const char* err = ptts::flac_silence(n, sample_rate, first_sample, out, out_cap, out_bytes))
+      throw ptts::Error(PTTS_ERR_INVALID, err);
+  });
 }
 
 int ptts_lsd_steps(const ptts_engine* e, int* cap, int* last_run) {

@@ -1781,6 +1781,8 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       fa.out = w.out;
       fa.counts = w.counts;
       fa.chunk = w.chunk;
+      fa.nframes = w.counts + (size_t)max_slots_ * nfr_;  // the block's head: counts | frame counts | index
+      fa.index = fa.nframes + (size_t)max_slots_ * nfr_;
       Op op{"flac", [fa](hipStream_t s) { flac_stage(fa, s); }, 0.0, (double)B * nfr * 2.0 * wire_chunk_max()};
       // an isolated replay (time_op) encodes fresh 16-bit chunks: the stage overwrites its input
       op.prep = [w](hipStream_t s) { wire_stage(w, s); };
@@ -3606,14 +3608,18 @@ void Engine::wire_enable(bool on) {
     }
     wire_taps_ = dalloc(taps.size());
     PTTS_HIP(hipMemcpy(wire_taps_, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice));
-    const size_t bytes = wire_block_bytes(max_slots_);
-    for (int p = 0; p < WIRE_BLOCKS; ++p) {
-      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
-      h_wireb_[p] = (unsigned char*)halloc(bytes);
-      memset(h_wireb_[p], 0, wire_head_bytes());
-    }
+    wire_blocks_alloc();
   }
   wire_ = on;
+}
+
+void Engine::wire_blocks_alloc() {
+  const size_t bytes = wire_block_bytes(max_slots_);
+  for (int p = 0; p < WIRE_BLOCKS; ++p) {
+    wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
+    h_wireb_[p] = (unsigned char*)halloc(bytes);
+    memset(h_wireb_[p], 0, wire_head_bytes());
+  }
 }
 
 void Engine::fetch_wire(int calls_back, int B, unsigned char* out, size_t row_stride, int* n_bytes) {
@@ -3833,12 +3839,7 @@ void Engine::tempo_enable(bool on) {
   if (on != tempo_) {  // the chunk slots change size: new pass blocks (the old ones stay until destruction)
     tempo_ = on;
     PTTS_REQUIRE(!level_ || level_min_chunk() >= 16, "level: a non-last chunk below 16 samples (DESIGN.md section 24)");
-    const size_t bytes = wire_block_bytes(max_slots_);
-    for (int p = 0; p < WIRE_BLOCKS; ++p) {
-      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
-      h_wireb_[p] = (unsigned char*)halloc(bytes);
-      memset(h_wireb_[p], 0, wire_head_bytes());
-    }
+    wire_blocks_alloc();
   }
 }
 
@@ -4003,12 +4004,7 @@ void Engine::level_enable(bool on, int ceiling_cdb) {
   if (on) level_ceiling_ = ceiling;
   if (on != level_) {  // the chunk slots change size: new pass blocks (the old ones stay until destruction)
     level_ = on;
-    const size_t bytes = wire_block_bytes(max_slots_);
-    for (int p = 0; p < WIRE_BLOCKS; ++p) {
-      wireb_[p] = (unsigned char*)dalloc((bytes + 3) / 4);
-      h_wireb_[p] = (unsigned char*)halloc(bytes);
-      memset(h_wireb_[p], 0, wire_head_bytes());
-    }
+    wire_blocks_alloc();
   }
 }
 
@@ -4040,13 +4036,46 @@ void Engine::flac_enable(bool on) {
   PTTS_REQUIRE(!on || wire_, "the FLAC stage needs a wire-enabled engine (ptts_wire_enable first)");
   PTTS_HIP(hipSetDevice(dev_));
   if (on && !flac_first_) flac_first_ = (int*)dalloc((size_t)max_slots_ * nfr_);
-  flac_ = on;
+  if (on != flac_) {  // the blocks' head holds the frame index on a FLAC-enabled engine only
+    flac_ = on;
+    wire_blocks_alloc();
+  }
+}
+
+void Engine::fetch_flac_index(int calls_back, int B, int* index, int* n_frames) {
+  PTTS_REQUIRE(flac_, "fetch_flac_index: the engine has no FLAC stage (ptts_flac_enable)");
+  PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
+  PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
+  PTTS_REQUIRE(index != nullptr && n_frames != nullptr, "null argument");
+  // the same frame, rows and event as fetch_wire() of that call
+  const int q = calls_back ? prev_hb_ : out_hb_;
+  const int rows = calls_back ? prev_rows_ : out_rows_;
+  const long long fk = calls_back ? prev_k_ : out_k_;
+  if (pipeline_) PTTS_HIP(hipEventSynchronize(ev_back_[q - q % nfr_]));
+  else sync();
+  const int n = std::min(B, rows), f = q % nfr_;
+  const size_t slots = (size_t)max_slots_ * nfr_;
+  const int* cnt = (const int*)h_wireb_[nfr_ > 1 ? q / nfr_ : q];
+  memset(index, 0, sizeof(int) * 2 * FLAC_CHUNK_FRAMES * B);
+  for (int b = 0; b < B; ++b) {
+    const size_t at = (size_t)b * nfr_ + f;
+    int c = b < n && cnt[at] ? cnt[slots + at] : 0;
+    if (c && !cancel_wins_.empty() && frame_cancelled(b, fk)) c = 0;  // as fetch_wire: no byte of that utterance
+    if (c < 0 || c > FLAC_CHUNK_FRAMES) throw Error(PTTS_ERR_STATE, "fetch_flac_index: corrupt frame count");
+    long sum = 0;
+    for (int i = 0; i < 2 * c; ++i) index[b * 2 * FLAC_CHUNK_FRAMES + i] = cnt[2 * slots + at * 2 * FLAC_CHUNK_FRAMES + i];
+    for (int i = 0; i < c; ++i) sum += index[b * 2 * FLAC_CHUNK_FRAMES + 2 * i];
+    if (c && sum != cnt[at]) throw Error(PTTS_ERR_STATE, "fetch_flac_index: the frame lengths do not sum to the chunk");
+    n_frames[b] = c;
+  }
 }
 
 long Engine::flac_bound(long n) { return n < 1 ? 0 : ptts::flac_bound(n); }
 
-void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes) {
+void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes,
+                              int* index, int* n_frames) {
   PTTS_REQUIRE(x && out && n_bytes, "null argument");
+  PTTS_REQUIRE((index == nullptr) == (n_frames == nullptr), "index and n_frames: both or neither");
   PTTS_REQUIRE(n >= 1 && n <= FLAC_CHUNK_SAMPLES, "flac_encode: n must be in [1, 11477]");
   const int ri = wire_rate_index(rate);
   PTTS_REQUIRE(ri >= 0, "sample_rate must be one of 8000, 16000, 24000, 44100, 48000");
@@ -4054,25 +4083,31 @@ void Engine::flac_encode_host(const int16_t* x, int n, int rate, long long first
   const size_t cap = ((size_t)flac_bound(n) + 3) / 4 * 4;
   sync();
   void *dx = nullptr, *dy = nullptr, *dn = nullptr;
-  int got = 0;
+  int got[1 + 2 * FLAC_CHUNK_FRAMES] = {};  // the byte total, then the index
+  const int nf = (n + FLAC_BLOCK - 1) / FLAC_BLOCK;
   try {
     PTTS_HIP(hipMalloc(&dx, sizeof(int16_t) * n));
     PTTS_HIP(hipMalloc(&dy, cap));
-    PTTS_HIP(hipMalloc(&dn, sizeof(int)));
+    PTTS_HIP(hipMalloc(&dn, sizeof(got)));
     PTTS_HIP(hipMemcpyAsync(dx, x, sizeof(int16_t) * n, hipMemcpyHostToDevice, stream_));
-    ptts::flac_encode((const short*)dx, n, ri, first, (unsigned char*)dy, (int*)dn, stream_);
+    ptts::flac_encode((const short*)dx, n, ri, first, (unsigned char*)dy, (int*)dn, index ? (int*)dn + 1 : nullptr, stream_);
     PTTS_HIP(hipGetLastError());
-    PTTS_HIP(hipMemcpyAsync(&got, dn, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipMemcpyAsync(got, dn, sizeof(int) * (index ? 1 + 2 * nf : 1), hipMemcpyDeviceToHost, stream_));
     PTTS_HIP(hipStreamSynchronize(stream_));
-    if (got < 1 || (size_t)got > cap) throw Error(PTTS_ERR_STATE, "flac_encode: corrupt byte count");
-    PTTS_HIP(hipMemcpy(out, dy, (size_t)got, hipMemcpyDeviceToHost));
+    if (got[0] < 1 || (size_t)got[0] > cap) throw Error(PTTS_ERR_STATE, "flac_encode: corrupt byte count");
+    PTTS_HIP(hipMemcpy(out, dy, (size_t)got[0], hipMemcpyDeviceToHost));
   } catch (...) {
     (void)hipStreamSynchronize(stream_);
     (void)hipFree(dx), (void)hipFree(dy), (void)hipFree(dn);
     throw;
   }
   (void)hipFree(dx), (void)hipFree(dy), (void)hipFree(dn);
-  *n_bytes = got;
+  *n_bytes = got[0];
+  if (index) {
+    memset(index, 0, sizeof(int) * 2 * FLAC_CHUNK_FRAMES);
+    memcpy(index, got + 1, sizeof(int) * 2 * nf);
+    *n_frames = nf;
+  }
 }
 
 void Engine::mark_admission() {

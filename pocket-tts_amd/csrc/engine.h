@@ -156,8 +156,13 @@ class Engine {
   void flac_enable(bool on);
   bool flac() const { return flac_; }
   static long flac_bound(long n);  // bytes of an n-sample chunk's frames, at most (0: n < 1)
-  // the seam alone: the stage's chunk encoder on n 16-bit samples at `rate`
-  void flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes);
+  // the seam alone: the stage's chunk encoder on n 16-bit samples at `rate`; index [3][2] and n_frames
+  // (both or neither) receive each frame's byte length and block size, and the frame count
+  void flac_encode_host(const int16_t* x, int n, int rate, long long first, unsigned char* out, int* n_bytes,
+                        int* index, int* n_frames);
+  // the frame index of the chunks fetch_wire(calls_back, ..) returns (section 21.5): index [B][3][2]
+  // (byte length, block size; zeros behind n_frames[b]); the same event, no bookkeeping of its own
+  void fetch_flac_index(int calls_back, int B, int* index, int* n_frames);
 
   // Align stage (ptts_align_enable / ptts_fetch_align): with it on, the front
   // part has one more launch behind layer `layer`'s step attention, which writes the text-attention
@@ -532,12 +537,16 @@ class Engine {
   // ---- FLAC stage (flac_enable)
   bool flac_ = false;
   int* flac_first_ = nullptr;    // [max_slots][nfr] a FLAC chunk's first sample index (k_wire -> k_flac)
-  // per pass (index: hand-off buffer / frames per pass): counts [max_slots][nfr] | chunks
+  // per pass (index: hand-off buffer / frames per pass): counts [max_slots][nfr] | on a FLAC-enabled
+  // engine the chunks' frame counts [max_slots][nfr] and frame index [max_slots][nfr][3][2] | chunks
   // [max_slots][nfr][WIRE_CHUNK_MAX], and its pinned host copy
   static constexpr int WIRE_BLOCKS = 3;
   unsigned char* wireb_[WIRE_BLOCKS] = {};
   unsigned char* h_wireb_[WIRE_BLOCKS] = {};
-  size_t wire_head_bytes() const { return ((size_t)max_slots_ * nfr_ * sizeof(int) + 127) / 128 * 128; }
+  size_t wire_head_bytes() const {
+    return ((size_t)max_slots_ * nfr_ * sizeof(int) * (flac_ ? 2 + 2 * FLAC_CHUNK_FRAMES : 1) + 127) / 128 * 128;
+  }
+  void wire_blocks_alloc();  // new pass blocks of the current head and chunk sizes (the old ones stay until destruction)
   size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * wire_chunk_max(); }
   static int wire_rate_index(int rate);
 

@@ -978,6 +978,7 @@ void level(const float* x, long n, float gain, float ceiling, float* y, hipStrea
 // whole chunk in LDS before its first store, so encoding in place is safe. Integer arithmetic only.
 constexpr int FLAC_BLOCK = 4608;                 // the subset limit at <= 48 kHz
 constexpr int FLAC_FRAME_OVERHEAD = 17;          // 14 header, 1 subframe header, 2 CRC-16
+constexpr int FLAC_CHUNK_FRAMES = 3;             // frames of a chunk, at most
 // the slot bound above; the longest chunk is 11,058 of a tempo row, 11,196 of a pitch row (section 23),
 // 11,448 of a level row behind the pitch stage (section 24)
 constexpr int FLAC_CHUNK_SAMPLES = 2 * LEVEL_OUT_MAX + 21;
@@ -986,7 +987,7 @@ constexpr long flac_bound(long n) {              // bytes of the frames of an n-
   return 2 * n + FLAC_FRAME_OVERHEAD * ((n + FLAC_BLOCK - 1) / FLAC_BLOCK);
 }
 static_assert(flac_bound(3860) <= WIRE_CHUNK_MAX, "a FLAC chunk fits the chunk slot");
-static_assert(flac_bound(2 * PITCH_OUT_MAX + 21) <= WIRE_CHUNK_MAX_TEMPO && FLAC_CHUNK_SAMPLES <= 3 * FLAC_BLOCK &&
+static_assert(flac_bound(2 * PITCH_OUT_MAX + 21) <= WIRE_CHUNK_MAX_TEMPO && FLAC_CHUNK_SAMPLES <= FLAC_CHUNK_FRAMES * FLAC_BLOCK &&
                   2 * (2 * PITCH_OUT_MAX + 21) <= WIRE_CHUNK_MAX_TEMPO,
               "a FLAC chunk of a tempo row is at most three frames and fits the chunk slot");
 static_assert(flac_bound(FLAC_CHUNK_SAMPLES) <= WIRE_CHUNK_MAX_LEVEL && 2 * FLAC_CHUNK_SAMPLES <= WIRE_CHUNK_MAX_LEVEL,
@@ -999,12 +1000,17 @@ struct FlacArgs {
   unsigned char* out;       // the wire stage's chunk slots, encoded in place
   int* counts;              // [B][out_frames] in: bytes of the s16 chunk; out: bytes of its frames
   int chunk;
+  // the frame index beside the chunk (section 21.5): each frame's byte length and block size, and the
+  // chunk's frame count (0: the row is not FLAC, or the slot holds no chunk)
+  int* index;               // [B][out_frames][FLAC_CHUNK_FRAMES][2]
+  int* nframes;             // [B][out_frames]
 };
 void flac_stage(const FlacArgs& a, hipStream_t s);
 // the stage's chunk encoder on n <= FLAC_CHUNK_SAMPLES samples (device pointers): frames into `out`
-// (flac_bound(n) bytes rounded up to a multiple of 4), their byte total into *n_bytes
+// (flac_bound(n) bytes rounded up to a multiple of 4), their byte total into *n_bytes, and (index
+// not null) each frame's byte length and block size into index [ceil(n / FLAC_BLOCK)][2]
 void flac_encode(const short* x, int n, int rate_index, long long first_sample, unsigned char* out, int* n_bytes,
-                 hipStream_t s);
+                 int* index, hipStream_t s);
 
 // dst [nch][rows][cols]: row r of chunk c = src[c * chunk_stride .. + cols) (each encoder chunk's
 // first row replicated: the history of the chunked ConvDownsample1d), one launch over all chunks

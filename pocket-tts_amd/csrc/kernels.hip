@@ -4260,7 +4260,9 @@ __device__ __forceinline__ int flac_number_bytes(long long v) {
 
 // The chunk s_x [n_total] (LDS) -> its frames at dst (dwords; may be the chunk's own global slot,
 // which is not read here); returns their byte total. Called by every lane of a FLAC_THREADS workgroup.
-__device__ int flac_chunk(const short* s_x, int n_total, int rc, long long first, unsigned* dst) {
+// index (global, may be null): frame i's byte length and block size go to index[2 i], index[2 i + 1]
+// for the ceil(n_total / FLAC_BLOCK) <= FLAC_CHUNK_FRAMES frames, from where the frame is stored.
+__device__ int flac_chunk(const short* s_x, int n_total, int rc, long long first, unsigned* dst, int* index) {
   __shared__ unsigned long long s_sum[FLAC_SUMS];  // [order][finest partition][k], then prefix sums over partitions
   __shared__ unsigned s_pcost[FLAC_ORDERS][128];   // [order][(1 << p) - 1 + partition]: best cost, saturated
   __shared__ unsigned char s_pk[FLAC_ORDERS][128]; // and its parameter
@@ -4472,6 +4474,10 @@ __device__ int flac_chunk(const short* s_x, int n_total, int rc, long long first
     carry = tb & 3 ? s_bits[nfull] : 0u;
     wbase += nfull;
     total_bytes += tb - boff;
+    if (index && t == 0) {
+      index[2 * (off / FLAC_BLOCK)] = tb - boff;
+      index[2 * (off / FLAC_BLOCK) + 1] = n;
+    }
     boff = tb & 3;
   }
   if (boff && t == 0) dst[wbase] = __builtin_bswap32(carry);  // zeros pad the last dword (inside the slot)
@@ -4482,20 +4488,23 @@ __global__ __launch_bounds__(FLAC_THREADS) void k_flac(FlacArgs a) {
   __shared__ __attribute__((aligned(16))) short s_x[(FLAC_CHUNK_SAMPLES + 7) / 8 * 8];
   const int b = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
   const int fmt = a.fmt[b], ri = fmt >> 8;
-  if ((fmt & 0xFF) != WIRE_FLAC || ri < 0 || ri >= WIRE_RATES) return;  // uniform
   const long idx = (long)b * a.out_frames + f;
   // k_wire's 16-bit chunk (never more than the frames of which fit the slot: the chunk sizes of kernels.h)
-  const int n = min(min(a.counts[idx] / 2, (a.chunk - 3 * FLAC_FRAME_OVERHEAD) / 2), FLAC_CHUNK_SAMPLES);
+  int n = 0;
+  if ((fmt & 0xFF) == WIRE_FLAC && ri >= 0 && ri < WIRE_RATES)  // uniform
+    n = min(min(a.counts[idx] / 2, (a.chunk - FLAC_CHUNK_FRAMES * FLAC_FRAME_OVERHEAD) / 2), FLAC_CHUNK_SAMPLES);
+  if (t == 0) a.nframes[idx] = n > 0 ? (n + FLAC_BLOCK - 1) / FLAC_BLOCK : 0;  // no FLAC row, or no chunk: 0
   if (n <= 0) return;
   unsigned* slot = reinterpret_cast<unsigned*>(a.out + idx * a.chunk);
   for (int i = t; i < (n + 1) / 2; i += FLAC_THREADS) reinterpret_cast<unsigned*>(s_x)[i] = slot[i];
   __syncthreads();
-  const int bytes = flac_chunk(s_x, n, flac_rate_code(ri), a.first[idx], slot);
+  const int bytes = flac_chunk(s_x, n, flac_rate_code(ri), a.first[idx], slot, a.index + idx * (2 * FLAC_CHUNK_FRAMES));
   if (t == 0) a.counts[idx] = bytes;
 }
 
 void flac_stage(const FlacArgs& a, hipStream_t s) {
-  if (a.B < 1 || a.out_frames < 1 || a.out_frames > NFR_MAX || !a.fmt || !a.first || !a.out || !a.counts)
+  if (a.B < 1 || a.out_frames < 1 || a.out_frames > NFR_MAX || !a.fmt || !a.first || !a.out || !a.counts ||
+      !a.index || !a.nframes)
     throw std::runtime_error("flac_stage: bad pass shape");
   if (a.chunk < WIRE_CHUNK_MAX || a.chunk % 8 || a.chunk > WIRE_CHUNK_MAX_LEVEL)
     throw std::runtime_error("flac_stage: bad chunk slot");
@@ -4503,20 +4512,21 @@ void flac_stage(const FlacArgs& a, hipStream_t s) {
 }
 
 __global__ __launch_bounds__(FLAC_THREADS) void k_flac_encode(const short* __restrict__ x, int n, int rc,
-                                                              long long first, unsigned* out, int* n_bytes) {
+                                                              long long first, unsigned* out, int* n_bytes,
+                                                              int* index) {
   __shared__ __attribute__((aligned(16))) short s_x[(FLAC_CHUNK_SAMPLES + 7) / 8 * 8];
   for (int i = threadIdx.x; i < n; i += FLAC_THREADS) s_x[i] = x[i];
   __syncthreads();
-  const int bytes = flac_chunk(s_x, n, rc, first, out);
+  const int bytes = flac_chunk(s_x, n, rc, first, out, index);
   if (threadIdx.x == 0) *n_bytes = bytes;
 }
 void flac_encode(const short* x, int n, int rate_index, long long first_sample, unsigned char* out, int* n_bytes,
-                 hipStream_t s) {
+                 int* index, hipStream_t s) {
   if (n < 1 || n > FLAC_CHUNK_SAMPLES || rate_index < 0 || rate_index >= WIRE_RATES || first_sample < 0 ||
       first_sample + n > (1LL << 36))
     throw std::runtime_error("flac_encode: bad chunk");
   hipLaunchKernelGGL(k_flac_encode, dim3(1), dim3(FLAC_THREADS), 0, s, x, n, flac_rate_code(rate_index), first_sample,
-                     reinterpret_cast<unsigned*>(out), n_bytes);
+                     reinterpret_cast<unsigned*>(out), n_bytes, index);
 }
 
 // ---------------------------------------------------------------------------------------------

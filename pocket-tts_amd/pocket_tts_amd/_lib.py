@@ -179,6 +179,12 @@ SIGNATURES = [
     ("ptts_flac_bound", C.c_long, [C.c_long]),
     ("ptts_flac_encode", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,
                                    C.POINTER(C.c_int)]),
+    ("ptts_flac_encode_ex", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,
+                                      C.POINTER(C.c_int), I32P, C.POINTER(C.c_int)]),
+    ("ptts_fetch_flac_index", C.c_int, [C.c_void_p, C.c_int, C.c_int, I32P, I32P]),
+    ("ptts_flac_rebase", C.c_int, [U8P, C.c_int, I32P, C.c_int, C.c_longlong, U8P, C.c_int, C.POINTER(C.c_int)]),
+    ("ptts_flac_silence_bound", C.c_long, [C.c_longlong]),
+    ("ptts_flac_silence", C.c_int, [C.c_longlong, C.c_int, C.c_longlong, U8P, C.c_long, C.POINTER(C.c_long)]),
     ("ptts_lsd_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("ptts_probe_overlap", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     ("ptts_slot_close", C.c_int, [C.c_void_p, C.c_int]),

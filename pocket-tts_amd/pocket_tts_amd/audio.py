@@ -14,6 +14,8 @@ Mirrors crates/pocket-tts/src/audio.rs:
     that did not go through it.
   * `flac_stream_header` / `flac_frames`: the host restatement of the engine's FLAC stage
     (DESIGN.md section 21): the same blocks and the same choice rule, byte for byte.
+  * `flac_rebase` / `flac_silence` / `FlacJoiner`: several rows and pauses as one FLAC stream
+    (section 21.5), over the library's host-only ptts_flac_rebase / ptts_flac_silence.
   * `normalize_peak` (audio.rs:187-194).
 Resampling to 24 kHz is not here: it runs on the GPU inside `ptts_voice_from_audio`
 (the polyphase resampler of pocket-tts_amd/csrc/kernels.hip).
@@ -337,6 +339,79 @@ def flac_frames(samples_i16, first_sample: int, rate: int) -> bytes:
     if first_sample < 0 or first_sample + s.size > 1 << 36:
         raise ValueError("sample indices must fit 36 bits")
     return b"".join(flac_frame(s[a:a + FLAC_BLOCK], first_sample + a, rate) for a in range(0, s.size, FLAC_BLOCK))
+
+
+def flac_frames_index(samples_i16, first_sample: int, rate: int) -> tuple[bytes, list[tuple[int, int]]]:
+    """flac_frames with the chunk's frame index: (frames, [(byte length, block size) per frame]), what
+    the FLAC stage writes beside the chunk (ptts_fetch_flac_index)."""
+    s = np.asarray(samples_i16, np.int16).reshape(-1)
+    frames = [flac_frames(s[a:a + FLAC_BLOCK], first_sample + a, rate) for a in range(0, s.size, FLAC_BLOCK)]
+    return b"".join(frames), [(len(f), min(FLAC_BLOCK, s.size - a)) for f, a in zip(frames, range(0, s.size, FLAC_BLOCK))]
+
+
+def flac_rebase(chunk: bytes, index, delta: int) -> bytes:
+    """The frames of `chunk` (index: (byte length, block size) per frame) with every sample number
+    raised by delta >= 0 and both CRCs renewed, the body bits untouched (ptts_flac_rebase; host only):
+    flac_rebase(flac_frames(s, f, rate), index, d) == flac_frames(s, f + d, rate). ValueError for
+    frames that do not verify against their CRCs or the index, and for numbers past 2^36."""
+    import ctypes as C
+
+    from ._lib import I32P, U8P, lib
+    idx = np.ascontiguousarray(np.asarray(index, np.int32).reshape(-1, 2))
+    src = np.frombuffer(bytes(chunk), np.uint8)
+    out = np.zeros(max(src.size + 6 * idx.shape[0], 1), np.uint8)
+    n = C.c_int(0)
+    if lib().ptts_flac_rebase(src.ctypes.data_as(U8P), src.size, idx.ctypes.data_as(I32P), idx.shape[0], int(delta),
+                              out.ctypes.data_as(U8P), out.size, C.byref(n)) != 0:
+        raise ValueError(lib().ptts_last_error().decode(errors="replace"))
+    return out[: n.value].tobytes()
+
+
+def flac_silence(n: int, first_sample: int, rate: int) -> bytes:
+    """n zero samples as CONSTANT frames in blocks of 4,608 (ptts_flac_silence; host only): equal to
+    flac_frames(np.zeros(n, np.int16), first_sample, rate), without the search."""
+    import ctypes as C
+
+    from ._lib import U8P, lib
+    out = np.zeros(max(int(lib().ptts_flac_silence_bound(int(n))), 1), np.uint8)
+    got = C.c_long(0)
+    if lib().ptts_flac_silence(int(n), int(rate), int(first_sample), out.ctypes.data_as(U8P), out.size, C.byref(got)) != 0:
+        raise ValueError(lib().ptts_last_error().decode(errors="replace"))
+    return out[: got.value].tobytes()
+
+
+class FlacJoiner:
+    """The segments of one response as one FLAC stream: every row numbers its
+    frames from sample 0 of its own utterance, and this is the only place that knows where a segment
+    starts. chunk() and pause() return the bytes to send behind flac_stream_header(rate); a segment's
+    chunks go in order, end_segment() closes it (pause() does too). total: the samples so far."""
+
+    def __init__(self, rate: int):
+        if rate not in FLAC_RATE_CODES:
+            raise ValueError(f"sample rate must be one of {sorted(FLAC_RATE_CODES)}")
+        self.rate = int(rate)
+        self.total = 0   # samples of everything returned so far
+        self._base = 0   # where the open segment's sample 0 lies
+
+    def chunk(self, data: bytes, index) -> bytes:
+        """One chunk of the open segment with its frame index, renumbered to its place."""
+        if not data:
+            return b""
+        out = flac_rebase(data, index, self._base) if self._base else bytes(data)
+        self.total += sum(int(bs) for _, bs in index)
+        return out
+
+    def end_segment(self) -> None:
+        """The next chunk is the first of another row: it starts where this one ends."""
+        self._base = self.total
+
+    def pause(self, n_samples: int) -> bytes:
+        """n_samples of silence between two segments (closes the open one)."""
+        self.end_segment()
+        out = flac_silence(n_samples, self.total, self.rate) if n_samples > 0 else b""
+        self.total += max(int(n_samples), 0)
+        self._base = self.total
+        return out
 
 
 def normalize_peak(audio: np.ndarray) -> np.ndarray:

@@ -7,7 +7,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
+from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, I32P, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_LEVEL, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
                    SAMPLE_RATE, SlotOpts5, ALIGN_TOKENS, check, fptr, lib, u8ptr)
 from .audio import ENCODINGS, level_cdb, pitch_cents, pitch_plan, speed_permille
@@ -709,15 +709,32 @@ class Engine:
         check(lib().ptts_wire_encode(self.handle, fptr(x), x.size, int(sample_rate), enc, out.ctypes.data_as(U8P)))
         return out[:n].tobytes()
 
-    def flac_encode(self, samples_i16: np.ndarray, sample_rate: int = 24000, first_sample: int = 0) -> bytes:
-        """The FLAC stage's chunk encoder on up to 11,221 arbitrary 16-bit samples (ptts_flac_encode):
-        the frames audio.flac_frames restates on the host, byte for byte."""
+    def fetch_flac_index(self, n_rows: int, calls_back: int = 0) -> list[list[tuple[int, int]]]:
+        """The frame index of the chunks fetch_wire(n_rows, calls_back) returns (ptts_fetch_flac_index;
+        a FLAC-enabled engine): per row the (byte length, block size) of each frame of its chunk, empty
+        for a row that is not FLAC or has no chunk. What audio.flac_rebase needs to renumber them."""
+        idx = np.zeros((n_rows, 3, 2), np.int32)
+        nf = np.zeros(n_rows, np.int32)
+        check(lib().ptts_fetch_flac_index(self.handle, calls_back, n_rows, idx.ctypes.data_as(I32P), nf.ctypes.data_as(I32P)))
+        return [[(int(a), int(b)) for a, b in idx[r, : nf[r]]] for r in range(n_rows)]
+
+    def flac_encode(self, samples_i16: np.ndarray, sample_rate: int = 24000, first_sample: int = 0,
+                    index: bool = False):
+        """The FLAC stage's chunk encoder on up to 11,477 arbitrary 16-bit samples (ptts_flac_encode):
+        the frames audio.flac_frames restates on the host, byte for byte. index=True
+        (ptts_flac_encode_ex): (frames, [(byte length, block size) per frame])."""
         x = np.ascontiguousarray(np.asarray(samples_i16, np.int16).reshape(-1))
         out = np.zeros(max(int(lib().ptts_flac_bound(x.size)), 1), np.uint8)
         n = C.c_int(0)
-        check(lib().ptts_flac_encode(self.handle, x.ctypes.data_as(C.POINTER(C.c_int16)), x.size, int(sample_rate),
-                                     int(first_sample), out.ctypes.data_as(U8P), C.byref(n)))
-        return out[: n.value].tobytes()
+        if not index:
+            check(lib().ptts_flac_encode(self.handle, x.ctypes.data_as(C.POINTER(C.c_int16)), x.size, int(sample_rate),
+                                         int(first_sample), out.ctypes.data_as(U8P), C.byref(n)))
+            return out[: n.value].tobytes()
+        idx, nf = np.zeros((3, 2), np.int32), C.c_int(0)
+        check(lib().ptts_flac_encode_ex(self.handle, x.ctypes.data_as(C.POINTER(C.c_int16)), x.size, int(sample_rate),
+                                        int(first_sample), out.ctypes.data_as(U8P), C.byref(n), idx.ctypes.data_as(I32P),
+                                        C.byref(nf)))
+        return out[: n.value].tobytes(), [(int(a), int(b)) for a, b in idx[: nf.value]]
 
     @staticmethod
     def tempo_len(n: int, speed) -> int:

@@ -60,8 +60,10 @@ routes, or `response_format: "flac"` on /v1/audio/speech, answers `audio/flac`: 
 samples at its `sample_rate` (and `speed`) as lossless FLAC frames, encoded on the GPU behind the
 wire stage. /stream sends the 42-byte stream header and then the row's chunks untouched; /generate
 and /v1/audio/speech send a complete file whose header holds the sample count. A row numbers its
-samples from 0, so FLAC with `long_form` or `continuity` (several rows behind one response) gets
-400, as does FLAC on a server without the stage (`--no-flac`, `--no-wire`).
+samples from 0: with `long_form` or `continuity` (several rows behind one response) the engine's
+frame index travels with every chunk and the frames are renumbered on the host as they are handed
+over in text order, pauses being CONSTANT frames (audio.FlacJoiner), so the
+response is one stream. FLAC on a server without the stage (`--no-flac`, `--no-wire`) gets 400.
 
     curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
          -d '{"input": "Hello there.", "voice": "alba", "response_format": "flac"}' -o hello.flac
@@ -149,7 +151,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import ALIGN_TOKENS, FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, wav_bytes,  # noqa: F401 (re-exported wire formats)
+from .audio import (ENCODINGS, FlacJoiner, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
 from .engine import GenerationParams, OutputOptions, Voice
 from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
@@ -299,7 +301,10 @@ def row_output(params) -> OutputOptions:
 
 
 def item_samples(item, wire) -> int:
-    """Samples of one delivered item: wire bytes of the format `wire` (rate, encoding), or f32 frames."""
+    """Samples of one delivered item: wire bytes of the format `wire` (rate, encoding), a FLAC chunk
+    with its frame index (a segment of a FLAC group), or f32 frames."""
+    if isinstance(item, tuple):
+        return sum(int(bs) for _, bs in item[1])
     if isinstance(item, (bytes, bytearray)):
         return len(item) // (1 if wire is not None and wire[1] in ("ulaw", "alaw") else 2)
     return int(np.size(item))
@@ -429,11 +434,15 @@ class RequestGroup(_Consumer):
     other), behind the consumer surface of one Request. A segment's items are held back until every
     earlier segment and pause has been handed over; at most `rows` text segments are waiting or
     active at once, the next one joining the tail of the scheduler's queue when one finishes.
-    deliver() runs on the scheduler thread only."""
+    deliver() runs on the scheduler thread only.
+    A FLAC group (section 21.5): its segments' items are (chunk, frame index), its pauses sample
+    counts, and both pass through `joiner` as they are handed over, which numbers them as one stream;
+    joiner.total is the response's sample count once it has ended."""
 
     def __init__(self, sched, items, rows: int, wire, continuity: bool = False):
         self.sched, self.items, self.rows, self.wire = sched, items, max(1, int(rows)), wire
         self.continuity = bool(continuity)  # one segment at a time, each continuing the one before it
+        self.joiner = FlacJoiner(wire[0]) if wire is not None and wire[1] == "flac" else None
         self.out = FrameChannel()
         self.waker: Callable[[], None] | None = None
         self.times: dict = {"submit": time.time()}
@@ -469,10 +478,20 @@ class RequestGroup(_Consumer):
                 buf = self.buf[id(it)]
                 for x in buf:
                     self.frames += 1
+                    if self.joiner is not None:
+                        x = self.joiner.chunk(*x)
+                        if not x:
+                            continue
                     self._emit(x)
                 buf.clear()
                 if not it.ended:
                     return
+                if self.joiner is not None:
+                    self.joiner.end_segment()
+            elif self.joiner is not None:
+                x = self.joiner.pause(it)
+                if x:
+                    self._emit(x)
             else:
                 self._emit(it)
             self.head += 1
@@ -584,6 +603,8 @@ class BatchScheduler:
                     items[-1].lat, items[-1].own = [], items[-1].ids
                     if len(items) > 1 and isinstance(items[-2], Request):
                         items[-1].pred = items[-2]
+            elif wire is not None and wire[1] == "flac":
+                items.append(silence_samples(seg[1], wire[0]))  # encoded at its place (RequestGroup._pump)
             elif wire is not None:
                 items.append(wire_bytes(np.zeros(silence_samples(seg[1], wire[0]), np.float32), wire[1]))
             else:
@@ -773,9 +794,11 @@ class BatchScheduler:
             req.times["first"] = time.time()
             req.put(pcm)
 
-    def _deliver(self, res, rows, wire=None, fstep: int = 0, align=None) -> list[int]:
+    def _deliver(self, res, rows, wire=None, fstep: int = 0, align=None, findex=None) -> list[int]:
         """wire: the call's Engine.fetch_wire chunks (a call with wire rows): those rows get their
         bytes untouched; numpy is called for rows without a format only (by their consumers).
+        findex: the call's Engine.fetch_flac_index (a call with a FLAC segment of a group): such a
+        row's item is (chunk, index), which its group renumbers.
         fstep: the step that computed the call's frame."""
         done = []
         for slot, req in list(self.active.items()):
@@ -796,7 +819,12 @@ class BatchScheduler:
                     if req.frames == 1:
                         req.times["first"] = time.time()
                     # a view: fetch() returns fresh arrays every step
-                    req.put(res.pcm[slot] if req.wire is None else wire[slot])
+                    if req.wire is None:
+                        req.put(res.pcm[slot])
+                    elif findex is not None and req.group is not None and req.wire[1] == "flac":
+                        req.put((wire[slot], findex[slot]))
+                    else:
+                        req.put(wire[slot])
                 if res.last[slot]:
                     req.times["last"] = time.time()
                     if self.trace:
@@ -879,12 +907,15 @@ class BatchScheduler:
                     wire = None
                     if any(r.wire is not None for r in self.active.values()):
                         wire = self.engine.fetch_wire(issued[0], calls_back=cb)
+                    findex = None  # the segments of a FLAC group are renumbered: their chunks need the frame index
+                    if any(r.group is not None and r.wire is not None and r.wire[1] == "flac" for r in self.active.values()):
+                        findex = self.engine.fetch_flac_index(issued[0], calls_back=cb)
                     arows = None
                     if any(r.align_rows is not None for r in self.active.values()):
                         arows = self.engine.fetch_align(issued[0], calls_back=cb)
                     self._deliver_previews()  # those that completed while fetch() waited: ahead of it
                     fstep = self.steps - len(issued) - self.lag
-                    done = self._deliver(res, issued.popleft(), wire, fstep, arows)
+                    done = self._deliver(res, issued.popleft(), wire, fstep, arows, findex)
                     if done:
                         with self.cv:
                             for slot in done:
@@ -1117,6 +1148,7 @@ class TTSService:
         self.wire = bool(getattr(eng, "wire", False))  # the engines convert to wire formats (--wire)
         self.tempo = self.wire and bool(getattr(eng, "tempo_enabled", False))  # and time-scale (--tempo)
         self.flac = self.wire and bool(getattr(eng, "flac_enabled", False))  # and encode FLAC (--flac)
+        self.flac_join = self.flac and hasattr(eng, "fetch_flac_index")  # and say where a chunk's frames are
         self.pitch = self.tempo and bool(getattr(eng, "pitch_enabled", False))  # and shift the pitch (--pitch)
         self.level = self.wire and bool(getattr(eng, "level_enabled", False))  # and set the level (--volume)
         self.align = bool(getattr(eng, "align_enabled", False))  # and deliver alignment rows (--align)
@@ -1192,9 +1224,10 @@ class TTSService:
             if not self.flac:
                 raise ValueError("this server runs without the FLAC stage (--no-flac or --no-wire): encoding flac is "
                                  "not available")
-            if chain or (token_ids is None and (self.long_form if long_form is None else long_form)):
+            if not self.flac_join and (chain or (token_ids is None and (self.long_form if long_form is None else long_form))):
                 raise ValueError("flac with long_form or continuity is not available: the segments of one response "
-                                 "are separate rows, each numbering its samples from 0")
+                                 "are separate rows, each numbering its samples from 0, and this engine has no frame "
+                                 "index to renumber them by")
         if limit is not None and not isinstance(limit, (bool, np.bool_)):
             raise ValueError(f"limit must be a bool, got {limit!r}")
         # (ValueError: a value out of range); a field that changes nothing is the request without it
@@ -1489,7 +1522,8 @@ async def pcm_chunks(r: Request):
 
 
 async def flac_chunks(r: Request):
-    """/stream body of a FLAC request: the stream header (sample count unknown), then pcm_chunks."""
+    """/stream body of a FLAC request: the stream header (sample count unknown), then pcm_chunks (a
+    group's items are already renumbered: RequestGroup._pump)."""
     yield flac_stream_header(r.wire[0])
     async for chunk in pcm_chunks(r):
         yield chunk
@@ -1497,8 +1531,11 @@ async def flac_chunks(r: Request):
 
 def flac_file(r) -> bytes:
     """A FLAC request's whole output as a file: the header with the true sample count (one item per
-    frame of the row, whatever its size), then the chunks untouched."""
+    frame of the row, whatever its size; a group's joiner has counted), then the chunks untouched."""
     chunks = list(r.stream())
+    joiner = getattr(r, "joiner", None)
+    if joiner is not None:
+        return flac_stream_header(r.wire[0], joiner.total) + b"".join(chunks)
     total = wire_samples(len(chunks) * FRAME, r.wire[0], getattr(r, "speed", 0), getattr(r, "pitch", 0))
     return flac_stream_header(r.wire[0], total) + b"".join(chunks)
 

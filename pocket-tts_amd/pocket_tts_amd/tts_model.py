@@ -32,7 +32,7 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
-from .audio import flac_stream_header, read_wav, read_wav_from_bytes, wire_bytes, wire_samples
+from .audio import FlacJoiner, flac_stream_header, read_wav, read_wav_from_bytes, wire_bytes
 from . import align as _align
 from .engine import Engine, GenerationParams, OutputOptions, Voice
 from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
@@ -207,7 +207,8 @@ class TTSModel:
 
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
                  out: OutputOptions = OutputOptions(), previous: Continuation | None = None,
-                 latents: list | None = None, align: list | None = None) -> Iterator[np.ndarray]:
+                 latents: list | None = None, align: list | None = None,
+                 joiner: FlacJoiner | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. For a wire row (out.wire:
         a format on a wire-enabled engine, a speed on a tempo-enabled one, a pitch, a gain or limit
         likewise) the items are the row's wire chunks, bytes converted on the GPU (Engine.fetch_wire),
@@ -216,7 +217,9 @@ class TTSModel:
         teacher-forced prefix, its latents, on the codec state it left (only the new frames are
         yielded); where that exceeds the engine's max_ctx, as a plain segment. latents: a list that
         receives the latent of every frame yielded. align: a list that receives the alignment row of
-        every frame yielded (an align-enabled engine; the row is admitted with align)."""
+        every frame yielded (an align-enabled engine; the row is admitted with align). joiner (a FLAC
+        row): the chunks are renumbered to the segment's place in the joiner's stream (section 21.5),
+        and the segment is closed there when it ends."""
         self._check_lsd()
         params = out.apply(self._params(max_frames, frames_after_eos))
         params.lsd_steps = int(self.lsd_decode_steps)
@@ -229,21 +232,28 @@ class TTSModel:
         self.engine.open(0, voice_state, ids, params)
         lag, delay = self.engine.frame_lag()  # overlapped stepping: frames arrive lag (+ delay) calls late
         lead = lag + delay
-        while True:
-            r = self.engine.step(1)
-            if not r.valid[0]:
-                if lead > 0:
-                    lead -= 1
-                    continue
-                return
-            lead = 0
-            if latents is not None:
-                latents.append(np.array(r.latents[0], np.float32))
-            if align is not None:
-                align.append(self.engine.fetch_align(1)[0])
-            yield self.engine.fetch_wire(1)[0] if wire else r.pcm[0].reshape(1, 1, FRAME).copy()
-            if r.last[0]:
-                return
+        try:
+            while True:
+                r = self.engine.step(1)
+                if not r.valid[0]:
+                    if lead > 0:
+                        lead -= 1
+                        continue
+                    return
+                lead = 0
+                if latents is not None:
+                    latents.append(np.array(r.latents[0], np.float32))
+                if align is not None:
+                    align.append(self.engine.fetch_align(1)[0])
+                if joiner is not None:
+                    yield joiner.chunk(self.engine.fetch_wire(1)[0], self.engine.fetch_flac_index(1)[0])
+                else:
+                    yield self.engine.fetch_wire(1)[0] if wire else r.pcm[0].reshape(1, 1, FRAME).copy()
+                if r.last[0]:
+                    return
+        finally:
+            if joiner is not None:
+                joiner.end_segment()
 
     def generate_stream(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                         words: int | None = None, sample_rate: int | None = None, encoding=None,
@@ -267,28 +277,33 @@ class TTSModel:
         run through the look-ahead peak limiter on the GPU, behind speed and pitch (DESIGN.md section
         24); wire bytes as for speed. None / 0 with limit False changes nothing.
         encoding "flac" (a FLAC-enabled engine): the items are the FLAC frames of each chunk (DESIGN.md
-        section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0, so
-        the text must be one segment: ValueError where it splits into several."""
+        section 21), to be sent behind audio.flac_stream_header. A row numbers its samples from 0; the
+        frames of every segment after the first are renumbered on the host to follow the one before
+        (audio.FlacJoiner, section 21.5), so the items are one stream."""
         yield from self._stream(text_or_ids, voice_state, max_frames, words,
                                 OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit))
 
-    def _stream(self, text_or_ids, voice_state, max_frames, words, out: OutputOptions) -> Iterator[np.ndarray]:
-        if out.wire and out.wire[1] == "flac" and isinstance(text_or_ids, str) and \
-                len(self.split_into_best_sentences(text_or_ids)) > 1:
-            raise ValueError("flac: the text splits into several segments, each a stream of its own (section 21, Limits)")
+    @staticmethod
+    def _joiner(out: OutputOptions) -> FlacJoiner | None:
+        """The joiner of a FLAC response (None: another format)."""
+        return FlacJoiner(out.wire[0]) if out.wire and out.wire[1] == "flac" else None
+
+    def _stream(self, text_or_ids, voice_state, max_frames, words, out: OutputOptions,
+                joiner: FlacJoiner | None = None) -> Iterator[np.ndarray]:
+        joiner = joiner or self._joiner(out)
         if not isinstance(text_or_ids, str):
             ids = np.asarray(text_or_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
-            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, out)
+            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, out, joiner=joiner)
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), out)
+                                     estimate_frames_after_eos(chunk), out, joiner=joiner)
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
@@ -296,19 +311,19 @@ class TTSModel:
                  limit: bool = False, timestamps: bool = False):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
         speed / pitch / volume_db / limit, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
-        the stream header with the true sample count and then the frames.
+        the stream header with the true sample count and then the frames (of every segment, joined).
         timestamps=True (text input, a model loaded with align=True and a tokenizer that names its
         pieces): returns (audio, words), words = [{"word", "start", "end"}] in seconds of that audio
         (align.py: each sentence chunk's words offset by the audio delivered before it)."""
         out = OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit)
         if timestamps:
             return self._generate_timed(text_or_ids, voice_state, max_frames, out)
-        frames = list(self._stream(text_or_ids, voice_state, max_frames, words, out))
+        joiner = self._joiner(out)
+        frames = list(self._stream(text_or_ids, voice_state, max_frames, words, out, joiner))
         if not frames:
             raise RuntimeError("No audio generated")
-        if out.wire and out.wire[1] == "flac":
-            rate, (sp, cents) = out.wire[0], out.codes()[2:4]
-            return flac_stream_header(rate, wire_samples(len(frames) * FRAME, rate, sp, cents)) + b"".join(frames)
+        if joiner is not None:
+            return flac_stream_header(joiner.rate, joiner.total) + b"".join(frames)
         return b"".join(frames) if out.wire else np.concatenate(frames, axis=2)[0]
 
     def _units(self, chunk, encoding) -> int:
@@ -353,33 +368,47 @@ class TTSModel:
             raise RuntimeError("No audio generated")
         return (b"".join(chunks) if out.wire else np.concatenate(chunks, axis=2)[0]), words
 
-    def generate_stream_long(self, text: str, voice_state: Voice, continuity: bool = False) -> Iterator[np.ndarray]:
+    def generate_stream_long(self, text: str, voice_state: Voice, continuity: bool = False,
+                             sample_rate: int | None = None, encoding=None,
+                             joiner: FlacJoiner | None = None) -> Iterator[np.ndarray]:
         """tts_model.rs:1074-1131: text segments between pause markers, silence for each pause.
         continuity (what tts_model.py:397-400 of the reference names and leaves
         out): the sentence chunks of one text piece run one after another on one slot, chunk k+1
         admitted with ids = ids(chunk k) ++ ids(chunk k+1), every delivered latent of chunk k as a
         teacher-forced prefix and keep_codec, so neither the prosody nor the codec restarts at the
-        join; only the new frames are yielded. A pause starts a new chain."""
+        join; only the new frames are yielded. A pause starts a new chain.
+        sample_rate / encoding: wire bytes as generate_stream yields them, each pause as the encoded
+        silence of silence_samples(ms, sample_rate) samples. encoding "flac": one stream, to be sent
+        behind audio.flac_stream_header; the pauses are CONSTANT frames (section 21.5). joiner: the
+        FlacJoiner to use (generate_with_pauses reads its total)."""
+        out = OutputOptions.of(sample_rate, encoding)
+        joiner = joiner or self._joiner(out)
         for kind, val in long_text_segments(text):
             if kind != "text":
-                yield np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)
+                if joiner is not None:
+                    yield joiner.pause(silence_samples(val, joiner.rate))
+                elif out.wire:
+                    yield wire_bytes(np.zeros(silence_samples(val, out.wire[0]), np.float32), out.wire[1])
+                else:
+                    yield np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)
             elif not continuity:
-                yield from self.generate_stream(val, voice_state)
+                yield from self._stream(val, voice_state, None, None, out, joiner)
             else:
                 prev = None
                 for chunk in self.split_into_best_sentences(val):
-                    link = self._link(chunk, voice_state, prev)
+                    link = self._link(chunk, voice_state, prev, out, joiner)
                     yield from link
                     prev = link.continuation
 
-    def _link(self, chunk: str, voice_state: Voice, previous: Continuation | None):
+    def _link(self, chunk: str, voice_state: Voice, previous: Continuation | None,
+              out: OutputOptions = OutputOptions(), joiner: FlacJoiner | None = None):
         """One sentence chunk as a link of a continuity chain: an iterator over its frames whose
         `continuation` is complete once it is exhausted."""
         prepared = prepare_text_prompt(chunk)
         ids = np.asarray(self._tok()(prepared), np.int32)
         lat: list = []
-        frames = self._segment(ids, voice_state, max_gen_len(prepared), estimate_frames_after_eos(chunk),
-                               previous=previous, latents=lat)
+        frames = self._segment(ids, voice_state, max_gen_len(prepared), estimate_frames_after_eos(chunk), out,
+                               previous=previous, latents=lat, joiner=joiner)
 
         class Link:
             continuation = None
@@ -390,25 +419,35 @@ class TTSModel:
 
         return Link()
 
-    def generate_continued(self, text: str, voice_state: Voice,
-                           previous: Continuation | None = None) -> tuple[np.ndarray, Continuation]:
+    def generate_continued(self, text: str, voice_state: Voice, previous: Continuation | None = None,
+                           sample_rate: int | None = None, encoding=None,
+                           joiner: FlacJoiner | None = None) -> tuple[np.ndarray, Continuation]:
         """One link of a continuity chain (section 20): `text` as ONE segment (no sentence split),
         continuing `previous` (the Continuation an earlier call returned; None: a plain segment).
         Returns the new audio [1, N*1920] and the Continuation to hand to the next call. The chain
         lives on engine row 0: nothing else may be generated on this model between two links that
-        are to join seamlessly."""
-        link = self._link(text, voice_state, previous)
+        are to join seamlessly. sample_rate / encoding: the new audio as wire bytes. encoding "flac":
+        the link's frames alone (no stream header), numbered on from joiner.total where the caller
+        hands the same audio.FlacJoiner to every link of the chain, from 0 without one."""
+        out = OutputOptions.of(sample_rate, encoding)
+        link = self._link(text, voice_state, previous, out, joiner or self._joiner(out))
         frames = list(link)
         if not frames:
             raise RuntimeError("No audio generated")
-        return np.concatenate(frames, axis=2)[0], link.continuation
+        return (b"".join(frames) if out.wire else np.concatenate(frames, axis=2)[0]), link.continuation
 
-    def generate_with_pauses(self, text: str, voice_state: Voice, continuity: bool = False) -> np.ndarray:
-        """tts_model.rs:856-883."""
-        chunks = list(self.generate_stream_long(text, voice_state, continuity))
+    def generate_with_pauses(self, text: str, voice_state: Voice, continuity: bool = False,
+                             sample_rate: int | None = None, encoding=None):
+        """tts_model.rs:856-883. sample_rate / encoding: the wire bytes of generate_stream_long joined;
+        encoding "flac": a complete .flac file with the true sample count."""
+        out = OutputOptions.of(sample_rate, encoding)
+        joiner = self._joiner(out)
+        chunks = list(self.generate_stream_long(text, voice_state, continuity, sample_rate, encoding, joiner))
         if not chunks:
             raise RuntimeError("No audio generated")
-        return np.concatenate(chunks, axis=2)[0]
+        if joiner is not None:
+            return flac_stream_header(joiner.rate, joiner.total) + b"".join(chunks)
+        return b"".join(chunks) if out.wire else np.concatenate(chunks, axis=2)[0]
 
     # ---- the same segments on parallel rows
     def generate_stream_parallel(self, text: str, voice_state: Voice, pauses: bool = False, rows: int | None = None,
@@ -426,7 +465,9 @@ class TTSModel:
         sample_rate / encoding: wire bytes as generate_stream yields them, and each pause as the
         encoded silence of silence_samples(ms, sample_rate) samples. speed: every text segment's row
         carries it (generate_stream), and the pitch likewise; pauses keep their stated duration. Closing the generator early
-        cancels the rows it still holds (Engine.cancel_slots).
+        cancels the rows it still holds (Engine.cancel_slots). encoding "flac": the rows' chunks travel
+        with their frame index and are renumbered as they are delivered in text order, the pauses
+        are CONSTANT frames: one stream behind audio.flac_stream_header (section 21.5).
         timed: a list that receives one record per item, in text order (generate_parallel's
         timestamps): ("pause", samples) or ("text", ids, params, frames_after_eos, meta), meta the
         segment's alignment rows, frame count and delivered samples, complete once it is delivered;
@@ -434,11 +475,13 @@ class TTSModel:
         return self._stream_parallel(text, voice_state, pauses, rows, OutputOptions.of(sample_rate, encoding, speed, pitch),
                                      timed)
 
-    def _stream_parallel(self, text, voice_state, pauses, rows, out: OutputOptions, timed) -> Iterator:
+    def _stream_parallel(self, text, voice_state, pauses, rows, out: OutputOptions, timed,
+                         joiner: FlacJoiner | None = None) -> Iterator:
         self._check_lsd()
         wire = out.wire
-        if wire and wire[1] == "flac":
-            raise ValueError("flac: parallel rows are separate streams, each numbered from 0 (section 21, Limits)")
+        joiner = joiner or self._joiner(out)
+        if joiner is not None and timed is not None:
+            raise ValueError("timestamps: not with flac (ask for pcm_s16le and encode the result)")
         tok = self._tok()
         eng = self.engine
         n_rows = max(1, min(int(rows or eng.max_slots), eng.max_slots))
@@ -453,6 +496,8 @@ class TTSModel:
                 items.append(["text", np.asarray(ids, np.int32), params, [], False, meta if timed is not None else None])
                 if timed is not None:
                     timed.append(("text", items[-1][1], params, fae, meta))
+            elif joiner is not None:
+                items.append(("pause", silence_samples(val, wire[0])))  # encoded where it is delivered: at its place
             elif wire:
                 n = silence_samples(val, wire[0])
                 items.append(("pause", wire_bytes(np.zeros(n, np.float32), wire[1])))
@@ -462,9 +507,12 @@ class TTSModel:
                 items.append(("pause", np.zeros((1, 1, silence_samples(val, self.sample_rate)), np.float32)))
                 if timed is not None:
                     timed.append(("pause", silence_samples(val, self.sample_rate)))
-        return self._run_parallel(items, voice_state, n_rows, wire is not None)
+        return self._run_parallel(items, voice_state, n_rows, wire is not None, joiner)
 
-    def _run_parallel(self, items, voice_state: Voice, n_rows: int, wire: bool) -> Iterator:
+    def _run_parallel(self, items, voice_state: Voice, n_rows: int, wire: bool,
+                      joiner: FlacJoiner | None = None) -> Iterator:
+        """joiner: the rows are FLAC; a segment's items are held as (chunk, index) and pass through the
+        joiner, pauses too, as they are delivered."""
         eng = self.engine
         todo = [it for it in items if it[0] == "text"]  # not yet admitted, text order
         active: dict[int, list] = {}  # slot -> its segment
@@ -475,12 +523,14 @@ class TTSModel:
                 while head < len(items):  # deliver, strictly in text order
                     it = items[head]
                     if it[0] == "pause":
-                        yield it[1]
+                        yield joiner.pause(it[1]) if joiner is not None else it[1]
                     else:
                         while it[3]:
-                            yield it[3].pop(0)
+                            yield joiner.chunk(*it[3].pop(0)) if joiner is not None else it[3].pop(0)
                         if not it[4]:
                             break
+                        if joiner is not None:
+                            joiner.end_segment()
                     head += 1
                 if head == len(items):
                     return
@@ -496,6 +546,8 @@ class TTSModel:
                 B = max(active) + 1
                 r = eng.step(B)
                 chunks = eng.fetch_wire(B) if wire else None
+                if joiner is not None:
+                    chunks = list(zip(chunks, eng.fetch_flac_index(B)))
                 arows = eng.fetch_align(B) if any(it[5] is not None for it in active.values()) else None
                 for s in sorted(active):
                     it = active[s]
@@ -523,19 +575,25 @@ class TTSModel:
                           sample_rate: int | None = None, encoding=None, speed: float | None = None,
                           pitch: float | None = None, timestamps: bool = False):
         """generate (pauses=False) or generate_with_pauses (pauses=True) with the text's segments on
-        parallel rows: the concatenation of generate_stream_parallel's items. The name is the
+        parallel rows: the concatenation of generate_stream_parallel's items (encoding "flac": behind
+        the stream header with the true sample count, a complete file). The name is the
         reference's own: its generate_parallel (tts_model.rs:705-854) is commented out there, "for
         future exploration with GPU acceleration".
         timestamps=True (a model loaded with align=True): returns (audio, words); each segment's words
         are offset by the samples delivered before it, pauses included."""
+        out = OutputOptions.of(sample_rate, encoding, speed, pitch)
+        joiner = self._joiner(out)
+        if timestamps and joiner is not None:
+            raise ValueError("timestamps: not with flac (ask for pcm_s16le and encode the result)")
         if timestamps and not self.engine.align_enabled:
             raise ValueError("timestamps need a model loaded with align=True")
         timed = [] if timestamps else None
-        out = OutputOptions.of(sample_rate, encoding, speed, pitch)
-        chunks = list(self._stream_parallel(text, voice_state, pauses, rows, out, timed))
+        chunks = list(self._stream_parallel(text, voice_state, pauses, rows, out, timed, joiner))
         if not chunks:
             raise RuntimeError("No audio generated")
         audio = b"".join(chunks) if out.wire else np.concatenate(chunks, axis=2)[0]
+        if joiner is not None:  # a complete file (section 21.5)
+            audio = flac_stream_header(joiner.rate, joiner.total) + audio
         if timestamps:
             rate = out.wire[0] if out.wire else SAMPLE_RATE
             words, at = [], 0
