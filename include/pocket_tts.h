@@ -338,6 +338,8 @@ typedef struct ptts_slot_opts {
   int limit;       /* 1: the row runs through the peak limiter even at gain 0; 0: only with a gain */
   int align;       /* 1: the row is in the align stage (ptts_align_enable); 0: not. Size 56 -> 64 */
   int reserved2;   /* ignored */
+  int loud;        /* 1: the row is metered (ptts_loud_enable); 0: not. Size 64 -> 72 */
+  int reserved3;   /* ignored */
 } ptts_slot_opts;
 /* ptts_slots_open_ex with one opts entry per row (NULL: defaults; the four admission calls above
  * are this call with defaults). A rate or encoding outside the lists, or a format asked of an
@@ -421,6 +423,38 @@ int ptts_level_enable(ptts_engine* e, int on, int ceiling_cdb);
  * on the GPU (the window function of the streaming stage), n >= 1; y receives n samples. */
 int ptts_level_plan(int gain_cdb, int ceiling_cdb, float* gain, float* ceiling);
 int ptts_level(ptts_engine* e, const float* x, int n, int gain_cdb, int ceiling_cdb, float* y);
+/* Loudness (no reference counterpart; ITU-R BS.1770 / EBU R128, restated in DESIGN.md section 27). A
+ * row admitted with ptts_slot_opts.loud = 1 is metered: the f32 signal at 24 kHz that the wire stage
+ * reads for it (behind speed, pitch and level) runs through the K-weighting at 24 kHz in f64, and
+ * for every complete sub-block of 2,400 samples (100 ms) of the row the pass reports the energy sum
+ * of y^2, at most PTTS_LOUD_BLOCKS_MAX per frame. Samples behind the row's last complete sub-block
+ * are never measured. The energies of a row, concatenated over its frames, are the whole-signal
+ * rule (ptts_loud_blocks) over that signal, bit for bit as f64. The meter only reads: no other
+ * output depends on it. A metered row with no wire format gets 24000 / PTTS_WIRE_S16. loud outside
+ * {0, 1}, or loud = 1 on an engine without ptts_loud_enable, is PTTS_ERR_INVALID and admits nothing.
+ * A caller with a struct shorter than 72 bytes gets no meter.
+ * ptts_loud_enable: valid on a wire-enabled idle engine before its first step (PTTS_ERR_INVALID
+ * otherwise); independent of the tempo, pitch, level and FLAC stages; on = 0, or never called: the
+ * passes, graphs and copies the engine has without it.
+ * ptts_fetch_loud: the companion of ptts_fetch / ptts_fetch_prev like ptts_fetch_wire (the same
+ * call, the same event, no bookkeeping of its own): per row the sub-blocks its frame of that call
+ * completed and their energies (unused entries 0). PTTS_ERR_INVALID on an engine without the stage. */
+#define PTTS_LOUD_SUB 2400
+#define PTTS_LOUD_BLOCKS_MAX 3
+int ptts_loud_enable(ptts_engine* e, int on);
+int ptts_fetch_loud(ptts_engine* e, int calls_back, int n_rows, double* energy /* [n_rows][3] */, int* n_blocks /* [n_rows] */);
+/* The loudness seam alone. ptts_loud_coeffs (host only): c = shelf b0 b1 b2 a1 a2, high-pass b0 b1
+ * b2 a1 a2 at 24 kHz; p_q = [biquad][p, q][32], the correction tables; either pointer may be NULL.
+ * ptts_loud_len: sub-blocks of n samples, n / 2400 (0 for n < 0). ptts_loud_blocks: the whole-signal
+ * rule on the GPU (the block function of the streaming stage); energy receives ptts_loud_len(n)
+ * doubles. ptts_loud_integrated (host only): the gated loudness in LUFS of n sub-block energies (400
+ * ms blocks of four, 75 % overlap, the absolute gate at -70 and the relative gate 10 LU below the
+ * mean); *measurable = 0 and *lufs untouched with fewer than four sub-blocks or when the absolute
+ * gate keeps nothing. */
+int ptts_loud_coeffs(double* c /* [10] */, double* p_q /* [2][2][32] */);
+long ptts_loud_len(long n);
+int ptts_loud_blocks(ptts_engine* e, const float* x, int n, double* energy);
+int ptts_loud_integrated(const double* energy, int n, double* lufs, int* measurable);
 /* FLAC (no reference counterpart; RFC 9639, restated in DESIGN.md section 21). A row admitted with
  * wire_encoding = PTTS_WIRE_FLAC gets, per frame, the FLAC frames of the 16-bit samples its
  * PTTS_WIRE_S16 chunk at the same rate (and speed) would hold: mono, 16 bit, blocks of at most 4,608

@@ -422,6 +422,50 @@ int ptts_level(ptts_engine* e, const float* x, int n, int gain_cdb, int ceiling_
   return guard([&] { eng(e).level_host(x, n, gain_cdb, ceiling_cdb, y); });
 }
 
+int ptts_loud_enable(ptts_engine* e, int on) { return guard([&] { eng(e).loud_enable(on != 0); }); }
+
+int ptts_fetch_loud(ptts_engine* e, int calls_back, int n_rows, double* energy, int* n_blocks) {
+  return guard([&] { eng(e).fetch_loud(calls_back, n_rows, energy, n_blocks); });
+}
+
+int ptts_loud_coeffs(double* c, double* p_q) {
+  ptts::LoudCoef k;
+  ptts::loud_coef(&k);
+  if (c) std::memcpy(c, k.c, sizeof k.c);
+  if (p_q) std::memcpy(p_q, k.pq, sizeof k.pq);
+  return PTTS_OK;
+}
+
+long ptts_loud_len(long n) { return n < 0 ? 0 : n / ptts::LOUD_SUB; }
+
+int ptts_loud_blocks(ptts_engine* e, const float* x, int n, double* energy) {
+  return guard([&] { eng(e).loud_host(x, n, energy); });
+}
+
+// BS.1770 gating over sub-block energies: plain f64, host only
+int ptts_loud_integrated(const double* energy, int n, double* lufs, int* measurable) {
+  if (!lufs || !measurable || n < 0 || (n > 0 && !energy)) return PTTS_ERR_INVALID;
+  *measurable = 0;
+  if (n < 4) return PTTS_OK;
+  std::vector<double> B(n - 3);
+  for (int i = 0; i + 3 < n; ++i) B[i] = (energy[i] + energy[i + 1] + energy[i + 2] + energy[i + 3]) / (4.0 * ptts::LOUD_SUB);
+  const auto lk = [](double ms) { return -0.691 + 10.0 * std::log10(ms); };
+  double sum = 0.0;
+  long kept = 0;
+  for (double b : B)
+    if (b > 0.0 && lk(b) > -70.0) sum += b, ++kept;
+  if (!kept) return PTTS_OK;
+  const double gate = lk(sum / kept) - 10.0;
+  double sum2 = 0.0;
+  long kept2 = 0;
+  for (double b : B)
+    if (b > 0.0 && lk(b) > -70.0 && lk(b) > gate) sum2 += b, ++kept2;
+  if (!kept2) return PTTS_OK;
+  *lufs = lk(sum2 / kept2);
+  *measurable = 1;
+  return PTTS_OK;
+}
+
 int ptts_flac_enable(ptts_engine* e, int on) { return guard([&] { eng(e).flac_enable(on != 0); }); }
 
 long ptts_flac_bound(long n) { return ptts::Engine::flac_bound(n); }

@@ -1770,6 +1770,24 @@ void Engine::build_back(std::vector<Op>& ops, int B, const BackBufs& bb, const B
       w.lcnt = level_cnt_;
     }
     if (flac_) w.first = flac_first_;
+    if (loud_) {  // the metered rows' sub-block energies, from what the wire stage reads (section 27)
+      LoudArgs lo{};
+      lo.B = B;
+      lo.nfr = nfr;
+      lo.pcm_frames = pcm_frames;
+      lo.out_frames = nfr_;
+      lo.pcm = pcm_out;
+      for (int f = 0; f < NFR_MAX; ++f) lo.flags[f] = fl[f];
+      lo.tempo_sp = w.tempo_sp, lo.tin = w.tin, lo.tcnt = w.tcnt;
+      lo.pitch_step = w.pitch_step, lo.pin = w.pin, lo.pcnt = w.pcnt;
+      lo.level_gain = w.level_gain, lo.lin = w.lin, lo.lcnt = w.lcnt;
+      lo.state = loud_state_;
+      lo.pend = loud_pend_;
+      lo.filt = loud_filt_;
+      lo.out = (LoudRecord*)(pass.wire + wire_loud_off());
+      lo.k = loud_coef_;
+      ops.push_back({"loud", [lo](hipStream_t s) { loud_stage(lo, s); }, 0.0, (double)B * nfr * 4.0 * LOUD_IN_MAX});
+    }
     ops.push_back({"wire", [w](hipStream_t s) { wire_stage(w, s); }, 0.0,
                    (double)B * nfr * (4.0 * FRAME + wire_chunk_max())});
     if (flac_) {  // the FLAC rows' 16-bit chunks become frames, in place (section 21)
@@ -3229,6 +3247,7 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     int npre = 0;
     int reset = 0;                  // RESET_* bits
     int align = 0;                  // text tokens in the align stage (0: the row is not in it)
+    int loud = 0;                   // 1: the row is metered (section 27)
   };
   const auto plan = [&](const ptts_slot_opts& o, const ptts_voice* v, int nid, const ptts_gen_params& p) {
     Row r;
@@ -3261,8 +3280,13 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       level_plan(gdb, 0, &g, nullptr);
       memcpy(&r.gain, &g, sizeof g);
     }
+    PTTS_REQUIRE(o.loud == 0 || o.loud == 1, "loud must be 0 or 1");
+    if (o.loud) {  // section 27
+      PTTS_REQUIRE(loud_, "loud needs a loudness-enabled engine (ptts_loud_enable before the first step)");
+      r.loud = 1;
+    }
     const int wr = o.wire_rate, we = o.wire_encoding;
-    if (wr || we || r.speed || r.pitch || r.gain) {  // a speed, a pitch or a gain with no format: 24000 / 16 bit
+    if (wr || we || r.speed || r.pitch || r.gain || r.loud) {  // a speed, a pitch, a gain or a meter with no format: 24000 / 16 bit
       PTTS_REQUIRE(wire_, "a wire format needs a wire-enabled engine (ptts_wire_enable before the first step)");
       const int ri = wire_rate_index(wr ? wr : PTTS_SAMPLE_RATE);
       PTTS_REQUIRE(ri >= 0, "wire_rate must be 0 (24000) or one of 8000, 16000, 24000, 44100, 48000");
@@ -3468,6 +3492,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
     for (int i = 0; i < n; ++i) h_level_[i] = row[i].gain;
     PTTS_HIP(hipMemcpyAsync(admit_level_, h_level_, sizeof(unsigned) * n, hipMemcpyHostToDevice, stream_));
   }
+  if (loud_) {
+    for (int i = 0; i < n; ++i) h_loud_[i] = row[i].loud;
+    PTTS_HIP(hipMemcpyAsync(admit_loud_, h_loud_, sizeof(int) * n, hipMemcpyHostToDevice, stream_));
+  }
   // fresh Mimi decoder state (init_states(1, 1000) per segment, tts_model.rs:941) + slot states
   std::vector<SlotState> st(n);
   std::vector<int> fp(n);
@@ -3562,6 +3590,10 @@ void Engine::slots_open(int n, const int* slots, const ptts_voice* const* voices
       r.level_src = admit_level_;
       r.level_gain = level_gain_;
       r.level_state = level_state_;
+    }
+    if (loud_) {
+      r.loud_src = admit_loud_;
+      r.loud_state = loud_state_;
     }
     if (any_opt) {
       r.opt_src = admit_opt_;
@@ -4028,6 +4060,74 @@ void Engine::level_host(const float* x, int n, int gain_cdb, int ceiling_cdb, fl
     throw;
   }
   (void)hipFree(dx), (void)hipFree(dy);
+}
+
+// ------------------------------------------------------------------ loudness stage
+void Engine::loud_enable(bool on) {
+  PTTS_REQUIRE(k_ == 0 && graphs_.empty(), "the loudness stage is chosen on an idle engine before its first step");
+  PTTS_REQUIRE(!on || wire_, "the loudness stage needs a wire-enabled engine (ptts_wire_enable first)");
+  PTTS_HIP(hipSetDevice(dev_));
+  if (on && !loud_state_) {
+    const size_t B = max_slots_;
+    loud_coef(&loud_coef_);
+    loud_state_ = (int*)dalloc(B * LOUD_STATE);
+    loud_pend_ = dalloc(B * LOUD_SUB);
+    loud_filt_ = (double*)dalloc(B * LOUD_FILT * 2);
+    admit_loud_ = (int*)dalloc(B);
+    h_loud_ = (int*)halloc(sizeof(int) * B);
+  }
+  if (on != loud_) {  // the blocks' head holds the records on a loudness-enabled engine only
+    loud_ = on;
+    wire_blocks_alloc();
+  }
+}
+
+void Engine::fetch_loud(int calls_back, int B, double* energy, int* n_blocks) {
+  PTTS_REQUIRE(loud_, "fetch_loud: the engine has no loudness stage (ptts_loud_enable)");
+  PTTS_REQUIRE(B >= 1 && B <= max_slots_, "n_rows out of range");
+  PTTS_REQUIRE(calls_back == 0 || calls_back == 1, "calls_back must be 0 or 1");
+  PTTS_REQUIRE(energy != nullptr && n_blocks != nullptr, "null argument");
+  // the same frame, rows and event as fetch_wire() of that call
+  const int q = calls_back ? prev_hb_ : out_hb_;
+  const int rows = calls_back ? prev_rows_ : out_rows_;
+  const long long fk = calls_back ? prev_k_ : out_k_;
+  if (pipeline_) PTTS_HIP(hipEventSynchronize(ev_back_[q - q % nfr_]));
+  else sync();
+  const int n = std::min(B, rows), f = q % nfr_;
+  const unsigned char* blk = h_wireb_[nfr_ > 1 ? q / nfr_ : q];
+  const LoudRecord* rec = (const LoudRecord*)(blk + wire_loud_off());
+  for (int b = 0; b < B; ++b) {
+    const size_t at = (size_t)b * nfr_ + f;
+    int c = b < n ? rec[at].n_blocks : 0;  // (the stage writes every record of the pass's rows: 0 without a frame)
+    if (c && !cancel_wins_.empty() && frame_cancelled(b, fk)) c = 0;  // as fetch_wire: nothing of that utterance
+    if (c < 0 || c > LOUD_BLOCKS_MAX) throw Error(PTTS_ERR_STATE, "fetch_loud: corrupt block count");
+    for (int i = 0; i < LOUD_BLOCKS_MAX; ++i) energy[(size_t)b * LOUD_BLOCKS_MAX + i] = i < c ? rec[at].e[i] : 0.0;
+    n_blocks[b] = c;
+  }
+}
+
+void Engine::loud_host(const float* x, int n, double* energy) {
+  PTTS_REQUIRE(x && n >= 0 && (energy || n < LOUD_SUB), "null argument");
+  if (n < LOUD_SUB) return;
+  LoudCoef k;
+  loud_coef(&k);
+  sync();
+  void *dx = nullptr, *de = nullptr;
+  const size_t nb = (size_t)n / LOUD_SUB;
+  try {
+    PTTS_HIP(hipMalloc(&dx, sizeof(float) * n));
+    PTTS_HIP(hipMalloc(&de, sizeof(double) * nb));
+    PTTS_HIP(hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyHostToDevice, stream_));
+    ptts::loud_blocks((const float*)dx, n, k, (double*)de, stream_);
+    PTTS_HIP(hipGetLastError());
+    PTTS_HIP(hipMemcpyAsync(energy, de, sizeof(double) * nb, hipMemcpyDeviceToHost, stream_));
+    PTTS_HIP(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dx), (void)hipFree(de);
+    throw;
+  }
+  (void)hipFree(dx), (void)hipFree(de);
 }
 
 // ------------------------------------------------------------------ FLAC stage

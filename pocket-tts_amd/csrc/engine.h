@@ -151,6 +151,14 @@ class Engine {
   long level_min_chunk() const;  // the smallest non-last chunk of a level row over the engine's stages (samples)
   // the seam alone: whole-signal f32 -> n samples
   void level_host(const float* x, int n, int gain_cdb, int ceiling_cdb, float* y);
+  // Loudness stage (ptts_loud_enable): rows admitted with ptts_slot_opts.loud
+  // have the signal the wire stage reads metered (kernels.h loud_stage); needs the wire stage only.
+  // The records ride in the pass blocks' head; no chunk slot changes size
+  void loud_enable(bool on);
+  bool loud() const { return loud_; }
+  void fetch_loud(int calls_back, int B, double* energy, int* n_blocks);
+  // the seam alone: whole-signal f32 -> n / LOUD_SUB sub-block energies
+  void loud_host(const float* x, int n, double* energy);
   // FLAC stage (ptts_flac_enable): rows admitted with PTTS_WIRE_FLAC have their
   // 16-bit chunks encoded as FLAC frames (kernels.h flac_stage) behind the wire stage
   void flac_enable(bool on);
@@ -534,6 +542,14 @@ class Engine {
   int* level_cnt_ = nullptr;        // [max_slots][nfr]
   unsigned* admit_level_ = nullptr; // staged gains of an admission (device), h_level_ (pinned)
   unsigned* h_level_ = nullptr;
+  // ---- loudness stage (loud_enable): per-row state, back-owned like the level state
+  bool loud_ = false;
+  LoudCoef loud_coef_{};
+  int* loud_state_ = nullptr;     // [max_slots][LOUD_STATE]
+  float* loud_pend_ = nullptr;    // [max_slots][LOUD_SUB]
+  double* loud_filt_ = nullptr;   // [max_slots][LOUD_FILT]
+  int* admit_loud_ = nullptr;     // staged flags of an admission (device), h_loud_ (pinned)
+  int* h_loud_ = nullptr;
   // ---- FLAC stage (flac_enable)
   bool flac_ = false;
   int* flac_first_ = nullptr;    // [max_slots][nfr] a FLAC chunk's first sample index (k_wire -> k_flac)
@@ -543,8 +559,13 @@ class Engine {
   static constexpr int WIRE_BLOCKS = 3;
   unsigned char* wireb_[WIRE_BLOCKS] = {};
   unsigned char* h_wireb_[WIRE_BLOCKS] = {};
+  // the head: byte counts | (FLAC: frame counts | index) | (loudness: a LoudRecord per (row, frame))
+  size_t wire_loud_off() const {
+    return ((size_t)max_slots_ * nfr_ * sizeof(int) * (flac_ ? 2 + 2 * FLAC_CHUNK_FRAMES : 1) + 15) / 16 * 16;
+  }
   size_t wire_head_bytes() const {
-    return ((size_t)max_slots_ * nfr_ * sizeof(int) * (flac_ ? 2 + 2 * FLAC_CHUNK_FRAMES : 1) + 127) / 128 * 128;
+    const size_t ints = (size_t)max_slots_ * nfr_ * sizeof(int) * (flac_ ? 2 + 2 * FLAC_CHUNK_FRAMES : 1);
+    return ((loud_ ? wire_loud_off() + (size_t)max_slots_ * nfr_ * sizeof(LoudRecord) : ints) + 127) / 128 * 128;
   }
   void wire_blocks_alloc();  // new pass blocks of the current head and chunk sizes (the old ones stay until destruction)
   size_t wire_block_bytes(int rows) const { return wire_head_bytes() + (size_t)rows * nfr_ * wire_chunk_max(); }

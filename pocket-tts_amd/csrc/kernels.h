@@ -681,6 +681,9 @@ struct ResetArgs {
   const unsigned* level_src = nullptr;
   unsigned* level_gain = nullptr;
   int* level_state = nullptr;  // [max_slots][LEVEL_STATE]
+  // loudness stage (null without it): the row's metered flag from the staged array, no sample yet
+  const int* loud_src = nullptr;
+  int* loud_state = nullptr;   // [max_slots][LOUD_STATE]
   // per-row RESET_* bits and staged backbone inputs [n][32] (null: no row of the admission has any)
   const int* opt_src = nullptr;
   const float* lat_src = nullptr;
@@ -970,6 +973,62 @@ struct LevelArgs {
 void level_stage(const LevelArgs& a, hipStream_t s);
 // whole signal: x [n] -> y [n], the window function of the stage
 void level(const float* x, long n, float gain, float ceiling, float* y, hipStream_t s);
+
+// Loudness stage: a BS.1770 meter beside the wire stage. It reads what k_wire
+// reads for the row (PCM frame, tempo, pitch or level chunk), widens it to f64, runs the K-weighting
+// (shelf, then high-pass; two biquads at 24 kHz) and writes the energy sum of y^2 of every complete
+// sub-block of LOUD_SUB samples. Each biquad runs in segments of LOUD_G samples on the row's absolute
+// sample index: a zero-state pass per segment, a sequential chain of two values per segment, a
+// correction from the tables p and q. Every f64 operation is rounded once (no contraction) in the
+// order section 27 states, so audio.loudness_blocks agrees bit for bit. Per-row state: the metered
+// flag and the samples seen, the samples behind the last complete sub-block, six doubles (the last
+// two inputs, shelf outputs and high-pass outputs at that sub-block's end).
+constexpr int LOUD_SUB = 2400;       // samples of a sub-block (100 ms)
+constexpr int LOUD_G = 32;           // samples of a segment
+constexpr int LOUD_SEGS = LOUD_SUB / LOUD_G;  // 75
+constexpr int LOUD_BLOCKS_MAX = 3;   // sub-blocks one chunk completes at most
+constexpr int LOUD_IN_MAX = LEVEL_OUT_MAX;  // the largest chunk the wire stage reads
+constexpr int LOUD_STATE = 2;        // ints per row: metered (0 / 1), samples seen
+constexpr int LOUD_FILT = 6;         // doubles per row: x[-1], x[-2], shelf y[-1], y[-2], high-pass y[-1], y[-2]
+static_assert(LOUD_SEGS * LOUD_G == LOUD_SUB, "a sub-block is a whole number of segments");
+static_assert(LOUD_IN_MAX >= PITCH_OUT_MAX && LOUD_IN_MAX >= TEMPO_OUT_MAX && LOUD_IN_MAX >= 1920 &&
+                  (LOUD_SUB - 1 + LOUD_IN_MAX) / LOUD_SUB == LOUD_BLOCKS_MAX,
+              "a chunk completes at most three sub-blocks");
+struct LoudCoef {
+  double c[2][5];        // shelf, high-pass: b0 b1 b2 a1 a2
+  double pq[2][2][LOUD_G];  // per biquad: p, q
+};
+struct LoudRecord {      // per (row, frame), in the pass block's head
+  int n_blocks;          // 0 .. LOUD_BLOCKS_MAX
+  int pad;
+  double e[LOUD_BLOCKS_MAX];
+};
+static_assert(sizeof(LoudRecord) == 32, "a loudness record is 32 bytes");
+// host only: the coefficients of section 27 at 24 kHz and their tables
+void loud_coef(LoudCoef* k);
+struct LoudArgs {
+  int B, nfr, pcm_frames, out_frames;      // as WireArgs
+  const float* pcm;
+  const FrameFlags* flags[NFR_MAX];
+  // the row's input, chosen as k_wire chooses it (null: the engine has no such stage)
+  const int* tempo_sp = nullptr;
+  const float* tin = nullptr;
+  const int* tcnt = nullptr;
+  const unsigned* pitch_step = nullptr;
+  const float* pin = nullptr;
+  const int* pcnt = nullptr;
+  const unsigned* level_gain = nullptr;
+  const float* lin = nullptr;
+  const int* lcnt = nullptr;
+  int* state;                              // [B][LOUD_STATE]
+  float* pend;                             // [B][LOUD_SUB]
+  double* filt;                            // [B][LOUD_FILT]
+  LoudRecord* out;                         // [B][out_frames]
+  LoudCoef k;
+};
+void loud_stage(const LoudArgs& a, hipStream_t s);
+// whole signal: x [n] -> energy [n / LOUD_SUB], the block function of the stage
+void loud_blocks(const float* x, long n, const LoudCoef& k, double* energy, hipStream_t s);
 
 // FLAC stage: behind the wire stage, the 16-bit chunk of every WIRE_FLAC row
 // becomes ceil(n / FLAC_BLOCK) FLAC frames (mono, 16 bit, fixed predictors of order 0..4, partitioned

@@ -3518,6 +3518,10 @@ __global__ __launch_bounds__(256) void k_slot_reset(ResetArgs a) {
       a.level_gain[slot] = a.level_src[i];
       for (int q = 0; q < LEVEL_STATE; ++q) a.level_state[slot * LEVEL_STATE + q] = 0;
     }
+    if (a.loud_state) {
+      a.loud_state[slot * LOUD_STATE] = a.loud_src[i];
+      a.loud_state[slot * LOUD_STATE + 1] = 0;
+    }
   }
 }
 
@@ -5071,6 +5075,251 @@ void level(const float* x, long n, float gain, float ceiling, float* y, hipStrea
   if (n < 1 || !(gain > 0.f) || !(ceiling > 0.f && ceiling <= 1.f)) throw std::runtime_error("level: bad arguments");
   hipLaunchKernelGGL(k_level_whole, dim3((unsigned)((n + LEVEL_TILE - 1) / LEVEL_TILE)), dim3(LEVEL_THREADS), 0, s, x, n,
                      gain, ceiling, y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Loudness stage (see kernels.h; the rule is DESIGN.md section 27). One block function serves the
+// streaming stage and the whole-signal seam, so they are equal by construction. It takes nb <= 3
+// sub-blocks of f32 samples from LDS, starting at a sub-block boundary of the row, and the six
+// doubles of filter state at that boundary, and leaves the nb energies and the state at the end.
+//   One lane per segment (at most 225 of 256) keeps its 32 samples in registers through both
+// biquads: zero-state pass, correction, zero-state pass, correction, squares. Between them lane 0
+// walks the chain of (e1, e2) over the segments from the last two zero-state values of each; the
+// shelf's chain values are also the high-pass's x[n - 1], x[n - 2] at each segment start. The work is
+// a few thousand dependent f64 operations; nothing here is bandwidth.
+//   No operation may be contracted: the functions below state `fp contract(off)` and use plain
+// operators (the __dmul_rn family is plain operators compiled elsewhere, which would not carry it).
+constexpr int LOUD_THREADS = 256;
+constexpr int LOUD_LANES = LOUD_BLOCKS_MAX * LOUD_SEGS;  // 225
+static_assert(LOUD_LANES <= LOUD_THREADS, "a lane per segment of the largest window");
+// the window in LDS: sample i at i + i / 32, so that lanes reading a segment each hit banks of their own
+__device__ __forceinline__ int loud_at(int i) { return i + (i >> 5); }
+constexpr int LOUD_WINDOW = LOUD_SUB - 1 + LOUD_IN_MAX;            // 8127 samples
+constexpr int LOUD_WINDOW_LDS = LOUD_WINDOW + LOUD_WINDOW / 32 + 2;
+
+// z[k] = ((((b0 x[k] + b1 x[k-1]) + b2 x[k-2]) - a1 z[k-1]) - a2 z[k-2]) with z = 0 before the segment
+__device__ __forceinline__ void loud_zero_state(const double* c, double x1, double x2, double (&v)[LOUD_G]) {
+#pragma clang fp contract(off)
+  double z1 = 0.0, z2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < LOUD_G; ++k) {
+    const double x = v[k];
+    double acc = c[0] * x + c[1] * x1;
+    acc = acc + c[2] * x2;
+    acc = acc - c[3] * z1;
+    acc = acc - c[4] * z2;
+    x2 = x1, x1 = x;
+    z2 = z1, z1 = acc;
+    v[k] = acc;
+  }
+}
+// y[k] = (z[k] + p[k] e1) + q[k] e2
+__device__ __forceinline__ void loud_correct(const double* p, const double* q, double e1, double e2, double (&v)[LOUD_G]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < LOUD_G; ++k) v[k] = (v[k] + p[k] * e1) + q[k] * e2;
+}
+// lane 0: e[s + 1] = y of the last two samples of segment s, from e[s] and that segment's zero-state values
+__device__ __forceinline__ void loud_chain(const double* p, const double* q, const double* za, const double* zb,
+                                           double* e1s, double* e2s, double e1, double e2, int S) {
+#pragma clang fp contract(off)
+  const double p1 = p[LOUD_G - 1], q1 = q[LOUD_G - 1], p2 = p[LOUD_G - 2], q2 = q[LOUD_G - 2];
+  e1s[0] = e1, e2s[0] = e2;
+#pragma unroll 5
+  for (int s = 0; s < S; ++s) {
+    const double n1 = (za[s] + p1 * e1) + q1 * e2;
+    const double n2 = (zb[s] + p2 * e1) + q2 * e2;
+    e1 = n1, e2 = n2;
+    e1s[s + 1] = e1, e2s[s + 1] = e2;
+  }
+}
+
+struct LoudLds {
+  double za[LOUD_LANES], zb[LOUD_LANES];            // z[31], z[30] of each segment (one biquad at a time)
+  double e1[2][LOUD_LANES + 1], e2[2][LOUD_LANES + 1];  // per biquad: y[-1], y[-2] at each segment start, and at the end
+  double seg[LOUD_LANES];                           // sum of y^2 of each segment
+  double f[LOUD_FILT];                              // the filter state at the window's start, then at its end
+  double E[LOUD_BLOCKS_MAX];
+};
+
+// uniform: every lane of the workgroup calls it (barriers inside); 1 <= nb <= LOUD_BLOCKS_MAX
+__device__ __forceinline__ void loud_window(const float* s_x, int nb, LoudLds& L, const LoudCoef& K, int t) {
+  const int S = nb * LOUD_SEGS;
+  const bool on = t < S;
+  double v[LOUD_G];
+  double x1 = 0.0, x2 = 0.0;
+  double nx1 = 0.0, nx2 = 0.0;  // (lane S - 1: the inputs the next window starts behind)
+  if (on) {
+#pragma unroll
+    for (int k = 0; k < LOUD_G; ++k) v[k] = (double)s_x[loud_at(t * LOUD_G + k)];
+    x1 = t ? (double)s_x[loud_at(t * LOUD_G - 1)] : L.f[0];
+    x2 = t ? (double)s_x[loud_at(t * LOUD_G - 2)] : L.f[1];
+    nx1 = v[LOUD_G - 1], nx2 = v[LOUD_G - 2];
+  }
+#pragma unroll
+  for (int bq = 0; bq < 2; ++bq) {
+    if (on) {
+      loud_zero_state(K.c[bq], x1, x2, v);
+      L.za[t] = v[LOUD_G - 1], L.zb[t] = v[LOUD_G - 2];
+    }
+    __syncthreads();
+    if (t == 0) loud_chain(K.pq[bq][0], K.pq[bq][1], L.za, L.zb, L.e1[bq], L.e2[bq], L.f[2 + 2 * bq], L.f[3 + 2 * bq], S);
+    __syncthreads();
+    if (on) {
+      x1 = L.e1[bq][t], x2 = L.e2[bq][t];  // this biquad's outputs ahead of the segment: the next one's inputs
+      loud_correct(K.pq[bq][0], K.pq[bq][1], x1, x2, v);
+    }
+  }
+  if (on) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < LOUD_G; ++k) acc = acc + v[k] * v[k];
+    L.seg[t] = acc;
+  }
+  __syncthreads();
+  if (t < nb) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int s = 0; s < LOUD_SEGS; ++s) acc = acc + L.seg[t * LOUD_SEGS + s];
+    L.E[t] = acc;
+  }
+  if (t == S - 1) L.f[0] = nx1, L.f[1] = nx2;
+  if (t == 0) {
+    L.f[2] = L.e1[0][S], L.f[3] = L.e2[0][S];
+    L.f[4] = L.e1[1][S], L.f[5] = L.e2[1][S];
+  }
+  __syncthreads();
+}
+
+// One workgroup per row walks the pass's frames in order, so the row's state is read and written by
+// this workgroup alone. LDS: the samples behind the row's last complete sub-block | the frame's input.
+__global__ __launch_bounds__(LOUD_THREADS) void k_loud(LoudArgs a) {
+  __shared__ float s_x[LOUD_WINDOW_LDS];
+  __shared__ LoudLds L;
+  const int b = blockIdx.x, t = threadIdx.x;
+  LoudRecord* rec = a.out + (long)b * a.out_frames;
+  if (a.state[(long)b * LOUD_STATE] == 0) {  // uniform: a row that is not metered
+    if (t < a.out_frames) rec[t].n_blocks = 0;
+    return;
+  }
+  const int sp = a.tempo_sp ? a.tempo_sp[b] : 0;  // uniform: the row's input, as k_wire chooses it
+  const unsigned pt = a.pitch_step ? a.pitch_step[b] : 0u;
+  const unsigned lv = a.level_gain ? a.level_gain[b] : 0u;
+  long seen = a.state[(long)b * LOUD_STATE + 1];
+  int np = (int)(seen % LOUD_SUB);  // samples behind the last complete sub-block
+  for (int i = t; i < np; i += LOUD_THREADS) s_x[loud_at(i)] = a.pend[(long)b * LOUD_SUB + i];
+  if (t < LOUD_FILT) L.f[t] = seen >= LOUD_SUB ? a.filt[(long)b * LOUD_FILT + t] : 0.0;
+  bool any = false;
+  for (int f = 0; f < a.out_frames; ++f) {
+    const FrameFlags fl = f < a.nfr ? a.flags[f][b] : FrameFlags{0, 0};
+    if (!fl.valid) {  // uniform
+      if (t == 0) rec[f].n_blocks = 0;
+      continue;
+    }
+    any = true;
+    const float* in = lv   ? a.lin + ((long)b * a.out_frames + f) * LEVEL_OUT_MAX
+                      : pt ? a.pin + ((long)b * a.out_frames + f) * PITCH_OUT_MAX
+                      : sp ? a.tin + ((long)b * a.out_frames + f) * TEMPO_OUT_MAX
+                           : a.pcm + ((long)b * a.pcm_frames + f) * 1920;
+    const int n_in = lv   ? min(max(a.lcnt[(long)b * a.out_frames + f], 0), LEVEL_OUT_MAX)
+                     : pt ? min(max(a.pcnt[(long)b * a.out_frames + f], 0), PITCH_OUT_MAX)
+                     : sp ? min(max(a.tcnt[(long)b * a.out_frames + f], 0), TEMPO_OUT_MAX)
+                          : 1920;
+    for (int i = t; i < n_in; i += LOUD_THREADS) s_x[loud_at(np + i)] = in[i];
+    __syncthreads();  // the window and the state are in place
+    const int total = np + n_in, nb = total / LOUD_SUB;  // nb <= LOUD_BLOCKS_MAX: np < LOUD_SUB, n_in <= LOUD_IN_MAX
+    if (nb > 0) {  // uniform
+      loud_window(s_x, nb, L, a.k, t);
+      if (t < nb) rec[f].e[t] = L.E[t];
+      const int rem = total - nb * LOUD_SUB;
+      constexpr int PER = (LOUD_SUB + LOUD_THREADS - 1) / LOUD_THREADS;
+      float keep[PER];
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        const int i = t + j * LOUD_THREADS;
+        keep[j] = i < rem ? s_x[loud_at(nb * LOUD_SUB + i)] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        const int i = t + j * LOUD_THREADS;
+        if (i < rem) s_x[loud_at(i)] = keep[j];
+      }
+      np = rem;
+    } else {
+      np = total;
+    }
+    if (t == 0) rec[f].n_blocks = nb;
+    seen += n_in;
+  }
+  if (!any) return;  // uniform
+  __syncthreads();
+  for (int i = t; i < np; i += LOUD_THREADS) a.pend[(long)b * LOUD_SUB + i] = s_x[loud_at(i)];
+  if (t < LOUD_FILT && seen >= LOUD_SUB) a.filt[(long)b * LOUD_FILT + t] = L.f[t];
+  if (t == 0) a.state[(long)b * LOUD_STATE + 1] = (int)seen;
+}
+
+void loud_stage(const LoudArgs& a, hipStream_t s) {
+  if (a.B < 1 || a.nfr < 1 || a.nfr > a.out_frames || a.out_frames > NFR_MAX || a.pcm_frames < a.nfr)
+    throw std::runtime_error("loud_stage: bad pass shape");
+  if (!a.pcm || !a.state || !a.pend || !a.filt || !a.out || (a.tempo_sp && (!a.tin || !a.tcnt)) ||
+      (a.pitch_step && (!a.pin || !a.pcnt)) || (a.level_gain && (!a.lin || !a.lcnt)))
+    throw std::runtime_error("loud_stage: bad argument");
+  hipLaunchKernelGGL(k_loud, dim3(a.B), dim3(LOUD_THREADS), 0, s, a);
+}
+
+// the seam: one workgroup walks the signal in windows of three sub-blocks from a zero state
+__global__ __launch_bounds__(LOUD_THREADS) void k_loud_whole(const float* __restrict__ x, long n_blocks, LoudCoef k,
+                                                             double* __restrict__ energy) {
+  __shared__ float s_x[LOUD_WINDOW_LDS];
+  __shared__ LoudLds L;
+  const int t = threadIdx.x;
+  if (t < LOUD_FILT) L.f[t] = 0.0;
+  for (long w = 0; w < n_blocks; w += LOUD_BLOCKS_MAX) {
+    const int nb = (int)min((long)LOUD_BLOCKS_MAX, n_blocks - w);
+    for (int i = t; i < nb * LOUD_SUB; i += LOUD_THREADS) s_x[loud_at(i)] = x[w * LOUD_SUB + i];
+    __syncthreads();
+    loud_window(s_x, nb, L, k, t);
+    if (t < nb) energy[w + t] = L.E[t];
+  }
+}
+
+void loud_coef(LoudCoef* k) {
+#pragma clang fp contract(off)
+  const double fs = 24000.0, pi = 3.141592653589793;
+  {  // the shelf
+    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    const double K = std::tan(pi * f0 / fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+    const double a0 = 1.0 + K / Q + K * K;
+    k->c[0][0] = (Vh + Vb * K / Q + K * K) / a0;
+    k->c[0][1] = 2.0 * (K * K - Vh) / a0;
+    k->c[0][2] = (Vh - Vb * K / Q + K * K) / a0;
+    k->c[0][3] = 2.0 * (K * K - 1.0) / a0;
+    k->c[0][4] = (1.0 - K / Q + K * K) / a0;
+  }
+  {  // the high-pass
+    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+    const double K = std::tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+    k->c[1][0] = 1.0, k->c[1][1] = -2.0, k->c[1][2] = 1.0;
+    k->c[1][3] = 2.0 * (K * K - 1.0) / a0;
+    k->c[1][4] = (1.0 - K / Q + K * K) / a0;
+  }
+  for (int bq = 0; bq < 2; ++bq)
+    for (int w = 0; w < 2; ++w) {  // p from (y1, y2) = (1, 0), q from (0, 1)
+      double y1 = w == 0 ? 1.0 : 0.0, y2 = w == 0 ? 0.0 : 1.0;
+      for (int i = 0; i < LOUD_G; ++i) {
+        const double m1 = -k->c[bq][3] * y1, m2 = k->c[bq][4] * y2;
+        const double v = m1 - m2;
+        k->pq[bq][w][i] = v;
+        y2 = y1, y1 = v;
+      }
+    }
+}
+
+void loud_blocks(const float* x, long n, const LoudCoef& k, double* energy, hipStream_t s) {
+  if (n < LOUD_SUB) throw std::runtime_error("loud_blocks: no complete sub-block");
+  hipLaunchKernelGGL(k_loud_whole, dim3(1), dim3(LOUD_THREADS), 0, s, x, n / LOUD_SUB, k, energy);
 }
 
 // whole-signal encode of n samples (already at the wire rate), four per lane

@@ -108,6 +108,14 @@ class SlotOpts5(C.Structure):
     ]
 
 
+class SlotOpts6(C.Structure):
+    """ptts_slot_opts with loud (72 bytes): the struct of a metered row."""
+    _fields_ = SlotOpts5._fields_ + [
+        ("loud", C.c_int),
+        ("reserved3", C.c_int),
+    ]
+
+
 # (name, restype, argtypes) for every symbol include/pocket_tts.h (the boundary) and
 # include/pocket_tts_probe.h (measurement / test hooks) declare
 SIGNATURES = [
@@ -175,6 +183,12 @@ SIGNATURES = [
     ("ptts_level_enable", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("ptts_level_plan", C.c_int, [C.c_int, C.c_int, F32P, F32P]),
     ("ptts_level", C.c_int, [C.c_void_p, F32P, C.c_int, C.c_int, C.c_int, F32P]),
+    ("ptts_loud_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("ptts_fetch_loud", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("ptts_loud_coeffs", C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("ptts_loud_len", C.c_long, [C.c_long]),
+    ("ptts_loud_blocks", C.c_int, [C.c_void_p, F32P, C.c_int, C.POINTER(C.c_double)]),
+    ("ptts_loud_integrated", C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("ptts_flac_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("ptts_flac_bound", C.c_long, [C.c_long]),
     ("ptts_flac_encode", C.c_int, [C.c_void_p, C.POINTER(C.c_int16), C.c_int, C.c_int, C.c_longlong, U8P,

@@ -752,3 +752,162 @@ def level_limit(x: np.ndarray, gain_cdb: int, ceiling_cdb: int = -100, chunks=No
         out.append(_level_outputs(buf, base, e0, e1, c)[0])
         hist = buf[-2 * LEVEL_L:] if buf.size else buf
     return out
+
+
+# ---- loudness: the host restatement of DESIGN.md section 27 (the GPU loudness stage's rule)
+LOUD_SUB = 2400  # samples of a sub-block (100 ms at 24 kHz)
+LOUD_G = 32      # samples of a segment
+_LOUD_SHELF = (1681.974450955533, 3.999843853973347, 0.7071752369554196)  # f0, G (dB), Q
+_LOUD_HIGHPASS = (38.13547087602444, 0.5003270373238773)                  # f0, Q
+
+
+def kweight_coeffs(fs: float = 24000.0) -> np.ndarray:
+    """The K-weighting of ITU-R BS.1770 at sample rate fs: [2, 5] float64, the shelf then the
+    high-pass, each (b0, b1, b2, a1, a2). At 48000 this is the standard's table; the engine uses
+    24000 (ptts_loud_coeffs returns the same bits). Scalar libm calls only, each operation once."""
+    fs = float(fs)
+    f0, G, Q = _LOUD_SHELF
+    K = math.tan(math.pi * f0 / fs)
+    Vh = math.pow(10.0, G / 20.0)
+    Vb = math.pow(Vh, 0.4996667741545416)
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = _LOUD_HIGHPASS
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    high = [1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    return np.array([shelf, high], np.float64)
+
+
+def loudness_tables(c: np.ndarray) -> np.ndarray:
+    """[2, 2, 32]: per biquad of c the correction tables p and q of section 27, the recursion
+    v = (-a1 y1) - a2 y2 run from (y1, y2) = (1, 0) and from (0, 1)."""
+    out = np.zeros((2, 2, LOUD_G), np.float64)
+    for bq in range(2):
+        a1, a2 = float(c[bq][3]), float(c[bq][4])
+        for w, (y1, y2) in enumerate(((1.0, 0.0), (0.0, 1.0))):
+            for i in range(LOUD_G):
+                v = (-a1 * y1) - a2 * y2
+                out[bq, w, i] = v
+                y2, y1 = y1, v
+    return out
+
+
+def _loud_biquad(c, pq, x: np.ndarray, xs, ys):
+    """One biquad over x (f64, a multiple of 32 samples starting on a segment boundary) by the three
+    steps of section 27. xs = (x[-1], x[-2]), ys = (y[-1], y[-2]). Returns y."""
+    b0, b1, b2, a1, a2 = (np.float64(v) for v in c)
+    S = x.size // LOUD_G
+    ext = np.concatenate([np.array([xs[1], xs[0]], np.float64), x])
+    X = np.lib.stride_tricks.sliding_window_view(ext, LOUD_G + 2)[::LOUD_G]  # [S, 34]: x[-2], x[-1], x[0..31]
+    z = np.zeros((S, LOUD_G), np.float64)
+    z1 = np.zeros(S, np.float64)
+    z2 = np.zeros(S, np.float64)
+    for k in range(LOUD_G):  # the zero-state pass, all segments at once
+        acc = b0 * X[:, k + 2] + b1 * X[:, k + 1]
+        acc = acc + b2 * X[:, k]
+        acc = acc - a1 * z1
+        acc = acc - a2 * z2
+        z[:, k] = acc
+        z2, z1 = z1, acc
+    p, q = pq
+    p1, q1, p2, q2 = p[-1], q[-1], p[-2], q[-2]
+    e1 = np.zeros(S + 1, np.float64)
+    e2 = np.zeros(S + 1, np.float64)
+    e1[0], e2[0] = ys
+    za, zb = z[:, -1], z[:, -2]
+    a, b = np.float64(ys[0]), np.float64(ys[1])
+    for s in range(S):  # the chain: two values per segment
+        a, b = (za[s] + p1 * a) + q1 * b, (zb[s] + p2 * a) + q2 * b
+        e1[s + 1], e2[s + 1] = a, b
+    y = (z + p[None, :] * e1[:S, None]) + q[None, :] * e2[:S, None]
+    return y.reshape(-1)
+
+
+class LoudnessMeter:
+    """The streaming state of the loudness stage (section 27): feed() takes f32 samples in any chunk
+    sizes and returns the energies of the sub-blocks they complete, bit for bit what the GPU stage
+    reports for the same chunks, and what loudness_blocks gives for the whole signal."""
+
+    def __init__(self):
+        self.c = kweight_coeffs(24000.0)
+        self.pq = loudness_tables(self.c)
+        self.pend = np.zeros(0, np.float32)
+        self.seen = 0
+        self.f = [0.0] * 6  # x[-1], x[-2], shelf y[-1], y[-2], high-pass y[-1], y[-2]
+
+    def feed(self, x: np.ndarray) -> np.ndarray:
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        self.seen += x.size
+        buf = np.concatenate([self.pend, x])
+        nb = buf.size // LOUD_SUB
+        self.pend = buf[nb * LOUD_SUB:]
+        if nb == 0:
+            return np.zeros(0, np.float64)
+        w = buf[:nb * LOUD_SUB].astype(np.float64)
+        f = self.f
+        y1 = _loud_biquad(self.c[0], self.pq[0], w, (f[0], f[1]), (f[2], f[3]))
+        y2 = _loud_biquad(self.c[1], self.pq[1], y1, (f[2], f[3]), (f[4], f[5]))
+        self.f = [w[-1], w[-2], y1[-1], y1[-2], y2[-1], y2[-2]]
+        sq = (y2 * y2).reshape(nb, LOUD_SUB // LOUD_G, LOUD_G)
+        seg = np.zeros(sq.shape[:2], np.float64)
+        for k in range(LOUD_G):  # a segment's 32 terms in ascending order
+            seg = seg + sq[:, :, k]
+        e = np.zeros(nb, np.float64)
+        for s in range(seg.shape[1]):  # then the 75 segment sums in ascending order
+            e = e + seg[:, s]
+        return e
+
+
+def loudness_blocks(x: np.ndarray, chunks=None):
+    """The loudness stage's rule over a signal x (f32 at 24 kHz): the K-weighted energy sum of y^2 of
+    each complete sub-block of 2,400 samples, float64 [len(x) // 2400]; samples behind the last
+    complete sub-block are not measured. Every f64 operation is rounded once, in the order section
+    27 states, so the GPU stage agrees bit for bit. chunks: the sizes in which the input arrives
+    (they sum to len(x)): run as the stream does and return the list of per-chunk energy arrays,
+    whose concatenation is the whole-signal result."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    m = LoudnessMeter()
+    if chunks is None:
+        return m.feed(x)
+    sizes = [int(s) for s in chunks]
+    if sum(sizes) != x.size or any(s < 0 for s in sizes):
+        raise ValueError("chunks must be non-negative and sum to len(x)")
+    out, n = [], 0
+    for s in sizes:
+        out.append(m.feed(x[n:n + s]))
+        n += s
+    return out
+
+
+def loudness_integrated(energy) -> float | None:
+    """Integrated loudness in LUFS (BS.1770 / EBU R128 gating) from sub-block energies: one array
+    (one row), or a list of arrays (the rows of one response: each row's 400 ms gating blocks, four
+    sub-blocks at 75 % overlap, are pooled and gated once). None: unmeasurable (no row with four
+    sub-blocks, or the absolute gate at -70 keeps nothing)."""
+    rows = [energy] if isinstance(energy, np.ndarray) or (len(energy) and np.isscalar(energy[0])) else list(energy)
+    blocks = []
+    for e in rows:
+        e = np.asarray(e, np.float64).reshape(-1)
+        if e.size >= 4:
+            blocks.append((e[:-3] + e[1:-2] + e[2:-1] + e[3:]) / (4.0 * LOUD_SUB))
+    if not blocks:
+        return None
+    B = np.concatenate(blocks)
+    B = B[B > 0.0]
+    lk = lambda ms: -0.691 + 10.0 * np.log10(ms)  # noqa: E731
+    B = B[lk(B) > -70.0]
+    if B.size == 0:
+        return None
+    gate = lk(B.mean()) - 10.0
+    B = B[lk(B) > gate]
+    if B.size == 0:
+        return None
+    return float(lk(B.mean()))
+
+
+def loudness_gain_cdb(target_lufs: float, voice_lufs: float) -> int:
+    """The gain in hundredths of a dB that brings a voice calibrated at voice_lufs to target_lufs:
+    round(100 (target - voice)), clamped to the level stage's [-2400, 2400]."""
+    return int(max(-2400, min(2400, round(100.0 * (float(target_lufs) - float(voice_lufs))))))

@@ -9,7 +9,7 @@ import numpy as np
 
 from ._lib import (BACK_BF16, BACK_F32, BACK_F32X6, DIM, F32P, FRAME, I32P, LDIM, SAMPLES_F32, SAMPLES_S16, U8P,
                    WIRE_ALAW, WIRE_FLAC, WIRE_CHUNK_MAX, WIRE_CHUNK_MAX_LEVEL, WIRE_CHUNK_MAX_TEMPO, WIRE_NONE, WIRE_RATES, WIRE_S16, WIRE_ULAW, EngineConfig, GenParams,
-                   SAMPLE_RATE, SlotOpts5, ALIGN_TOKENS, check, fptr, lib, u8ptr)
+                   SAMPLE_RATE, SlotOpts5, SlotOpts6, ALIGN_TOKENS, check, fptr, lib, u8ptr)
 from .audio import ENCODINGS, level_cdb, pitch_cents, pitch_plan, speed_permille
 
 # wire encodings by the names the server's `encoding` field uses (PTTS_WIRE_*)
@@ -68,6 +68,11 @@ class GenerationParams:
     # carries the attention its FlowLM step paid to the row's text tokens (Engine.fetch_align). At
     # most ALIGN_TOKENS token ids. No other output of the row depends on it.
     align: bool = False
+    # loudness meter (loudness-enabled engines): every frame of the row also
+    # carries the K-weighted energies of the 100 ms sub-blocks it completed (Engine.fetch_loud),
+    # measured on the signal the wire stage reads. With no wire format it implies 24000 / 16-bit.
+    # No other output of the row depends on it.
+    loudness: bool = False
 
     def prefix(self) -> np.ndarray | None:
         """The prefix as a contiguous [n, 32] float32 array; None: no prefix."""
@@ -98,11 +103,15 @@ class GenerationParams:
         """(gain_cdb, limit) of ptts_slot_opts; (0, 0): the row is not in the level stage."""
         return self.output().codes()[4:]
 
-    def slot_opts(self, default_lsd: int = 0) -> SlotOpts5:
-        """The row's ptts_slot_opts, the whole 64-byte struct (fields it does not name are 0).
+    def slot_opts(self, default_lsd: int = 0, metered: bool | None = None) -> SlotOpts5 | SlotOpts6:
+        """The row's ptts_slot_opts, the whole 64-byte struct (fields it does not name are 0), or the
+        72-byte struct for a metered row (metered=True: that struct whatever the row asks).
         default_lsd: lsd_steps of a row that names none (0: the engine's cap). The struct keeps the
         prefix array it points into alive."""
-        o = SlotOpts5(size=C.sizeof(SlotOpts5), lsd_steps=int(default_lsd if self.lsd_steps is None else self.lsd_steps))
+        K = SlotOpts6 if (self.loudness if metered is None else metered) else SlotOpts5
+        o = K(size=C.sizeof(K), lsd_steps=int(default_lsd if self.lsd_steps is None else self.lsd_steps))
+        if K is SlotOpts6:
+            o.loud = int(bool(self.loudness))
         o.wire_rate, o.wire_encoding, o.speed_permille, o.pitch_cents, o.gain_cdb, o.limit = self.output().codes()
         o.keep_codec, o.align = int(self.keep_codec), int(bool(self.align))
         pre = o._prefix = self.prefix()
@@ -226,7 +235,7 @@ class Engine:
                  back_mfma: int | None = None, max_lsd_steps: int | None = None, wire: bool = False,
                  tempo: bool = False, flac: bool = False, pitch: bool = False, level: bool = False,
                  level_ceiling_db: float = -1.0, align: bool = False, align_layer: int = 0,
-                 align_heads: int = 0xFFFF):
+                 align_heads: int = 0xFFFF, loud: bool = False):
         """lsd_decode_steps: the Euler step count of an utterance whose GenerationParams names none.
         max_lsd_steps: the cap on the per-utterance counts (GenerationParams.lsd_steps), the engine's
         ptts_engine_config.lsd_decode_steps; None: lsd_decode_steps itself. Rows with different
@@ -255,7 +264,10 @@ class Engine:
         of their 16-bit chunks, encoded on the GPU.
         align=True (ptts_align_enable): rows admitted with GenerationParams.align get, with every
         frame, their step's text-attention row of FlowLM layer align_layer (0 .. 5), averaged over
-        the heads of the bit mask align_heads (fetch_align)."""
+        the heads of the bit mask align_heads (fetch_align).
+        loud=True (ptts_loud_enable; needs wire): rows admitted with GenerationParams.loudness get, with
+        every frame, the K-weighted energies of the 100 ms sub-blocks of their output that the frame
+        completed (fetch_loud)."""
         if back_mfma is None:
             back_mfma = BACK_BF16 if back_bf16 else BACK_F32
         elif back_bf16 and back_mfma != BACK_BF16:
@@ -326,6 +338,13 @@ class Engine:
                 self.close()
                 raise
         self._align_buf = self._align_n = None
+        self.loud_enabled = bool(loud)
+        if loud:
+            try:
+                check(lib().ptts_loud_enable(self.handle, 1))
+            except Exception:
+                self.close()
+                raise
         self.wire_chunk_max = WIRE_CHUNK_MAX_LEVEL if level else WIRE_CHUNK_MAX_TEMPO if tempo else WIRE_CHUNK_MAX
         self._wire_buf = self._wire_n = None
 
@@ -614,8 +633,9 @@ class Engine:
         cat = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0, np.int32))
         vh = (C.c_void_p * n)(*[v.handle for v in voices])
         ps = (GenParams * n)(*[p.to_c() for p in params_list])
-        rows = [p.slot_opts(self.lsd_decode_steps) for p in params_list]  # (they keep the prefixes alive)
-        opts = (SlotOpts5 * n)(*rows)
+        metered = any(getattr(p, "loudness", False) for p in params_list)  # one struct size per call: 72 bytes then
+        rows = [p.slot_opts(self.lsd_decode_steps, metered) for p in params_list]  # (they keep the prefixes alive)
+        opts = ((SlotOpts6 if metered else SlotOpts5) * n)(*rows)
         i32 = C.POINTER(C.c_int32)
         check(lib().ptts_slots_open_opts(self.handle, n, sl.ctypes.data_as(i32), vh, cat.ctypes.data_as(i32),
                                          nid.ctypes.data_as(i32), ps, C.cast(opts, C.c_void_p)))
@@ -687,6 +707,26 @@ class Engine:
         check(lib().ptts_fetch_wire(self.handle, calls_back, n_rows, u8ptr(self._wire_buf), self.wire_chunk_max,
                                     self._wire_n.ctypes.data_as(C.POINTER(C.c_int))))
         return [self._wire_buf[b, : self._wire_n[b]].tobytes() for b in range(n_rows)]
+
+    def fetch_loud(self, n_rows: int, calls_back: int = 0) -> list[np.ndarray]:
+        """The loudness records of the frame fetch(n_rows, calls_back) returns (ptts_fetch_loud): one
+        float64 array per row, the energies of the sub-blocks the row's frame completed (0 to 3),
+        empty for a row that is not metered or has no frame. A row's arrays concatenated are
+        audio.loudness_blocks of the signal its wire stage read; audio.loudness_integrated turns them
+        into LUFS."""
+        e = np.zeros((n_rows, 3), np.float64)
+        nb = np.zeros(n_rows, np.int32)
+        check(lib().ptts_fetch_loud(self.handle, calls_back, n_rows, e.ctypes.data_as(C.POINTER(C.c_double)),
+                                    nb.ctypes.data_as(C.POINTER(C.c_int))))
+        return [e[b, : nb[b]].copy() for b in range(n_rows)]
+
+    def loudness_blocks(self, x: np.ndarray) -> np.ndarray:
+        """Sub-block energies of a whole f32 signal at 24 kHz on the GPU (ptts_loud_blocks): the block
+        function of the streaming loudness stage (audio.loudness_blocks is its host restatement)."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        e = np.zeros(max(int(lib().ptts_loud_len(x.size)), 1), np.float64)
+        check(lib().ptts_loud_blocks(self.handle, fptr(x), x.size, e.ctypes.data_as(C.POINTER(C.c_double))))
+        return e[: x.size // 2400]
 
     def fetch_align(self, n_rows: int, calls_back: int = 0) -> list[np.ndarray]:
         """The alignment rows of the frame fetch(n_rows, calls_back) returns (ptts_fetch_align): one

@@ -108,6 +108,21 @@ the stage (`--no-volume`, `--no-wire`), gets 400.
     curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
          -d '{"input": "Hello there.", "voice": "alba", "volume_db": 6, "response_format": "ulaw"}' -o loud.ulaw
 
+Loudness (`--loudness`, off by default; needs `--wire`, and `--volume` for `loudness_lufs`): a
+BS.1770 meter on the GPU beside the wire stage. Every voice is calibrated once
+on a fixed sentence (CALIBRATION_TEXT, CALIBRATION_SEED, the server's default parameters, no gain) as
+an ordinary request through the scheduler: when it is registered (`--voice`, `POST /voices/NAME`), or
+on first use for a per-request clip; `GET /voices/NAME` answers `{"name", "frames",
+"loudness_lufs"}`. `loudness_lufs` on the three audio routes, a target in [-40, -5], gives the rows
+the constant gain round(100 (target - voice loudness)) / 100 dB within [-24, 24], limiter on, reported
+as `X-Gain-dB`; it excludes `volume_db`. `loudness: true` on /generate and /v1/audio/speech meters
+the response (`X-Loudness-LUFS`, `none` if unmeasurable; a `loudness_lufs` key with `timestamps`),
+pooled over a long-form request's segments; /stream answers 400 to it. A target out of range, a
+server without the stages, or a voice whose calibration is unmeasurable gets 400.
+
+    curl -s localhost:8000/v1/audio/speech -H 'content-type: application/json' \
+         -d '{"input": "Hello there.", "voice": "alba", "loudness_lufs": -16}' -o level.wav
+
 Long-form requests (`long_form` in the three audio routes' bodies; `--long-form` sets the default,
 off): the text is cut as the reference's routes cut it (generate_stream_long, handlers.rs:165,260:
 pause markers and natural pauses become silence, each piece is cut into sentence chunks of at most
@@ -151,10 +166,11 @@ from typing import Callable, Iterator, Sequence
 import numpy as np
 
 from ._lib import ALIGN_TOKENS, FRAME, LDIM, SAMPLE_RATE, WIRE_RATES
-from .audio import (ENCODINGS, FlacJoiner, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, wav_bytes,  # noqa: F401 (re-exported wire formats)
+from .audio import (LoudnessMeter, loudness_gain_cdb, loudness_integrated,  # noqa: F401
+                    ENCODINGS, FlacJoiner, flac_stream_header, level_cdb, level_limit, pcm_i16_le_bytes, wav_bytes,  # noqa: F401 (re-exported wire formats)
                     wire_bytes, wire_samples)
 from .engine import GenerationParams, OutputOptions, Voice
-from .text import (estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
+from .text import (CALIBRATION_SEED, CALIBRATION_TEXT, estimate_frames_after_eos, long_form_segments, max_gen_len, prepare_text_prompt, segment_request,
                    silence_samples)
 
 VERSION = "0.1.0"
@@ -313,6 +329,13 @@ def item_samples(item, wire) -> int:
 class _Consumer:
     """The consumer side of a Request or a RequestGroup: items from `out` until the end marker."""
 
+    def loudness(self) -> float | None:
+        """Integrated loudness in LUFS of a finished metered request (its audio consumed), the gating
+        blocks of all its rows pooled and gated once; None: unmeasurable, or not metered."""
+        rows = [it for it in getattr(self, "items", [self]) if isinstance(it, Request) and it.loud_rows is not None]
+        energy = [np.concatenate(it.loud_rows) if it.loud_rows else np.zeros(0, np.float64) for it in rows]
+        return loudness_integrated(energy) if energy else None
+
     def stream(self, timeout: float | None = None) -> Iterator[np.ndarray]:
         """Frames [1920] float32 as they are produced; raises the driver's error if any."""
         while True:
@@ -399,10 +422,16 @@ class Request(_Consumer):
     # (None: not in it), and the samples handed over so far at the rate they are delivered at
     align_rows: list | None = None
     units: int = 0
+    # loudness: the sub-block energies of every frame of a metered row (None:
+    # not metered), and the gain in dB a `loudness_lufs` request was given (None: none)
+    loud_rows: list | None = None
+    gain_db: float | None = None
 
     def __post_init__(self):
         if getattr(self.params, "align", False):
             self.align_rows = []
+        if getattr(self.params, "loudness", False):
+            self.loud_rows = []
         out = row_output(self.params)
         self.wire = out.wire or self.wire
         _, _, self.speed, self.pitch, *lv = out.codes()
@@ -794,7 +823,7 @@ class BatchScheduler:
             req.times["first"] = time.time()
             req.put(pcm)
 
-    def _deliver(self, res, rows, wire=None, fstep: int = 0, align=None, findex=None) -> list[int]:
+    def _deliver(self, res, rows, wire=None, fstep: int = 0, align=None, findex=None, loud=None) -> list[int]:
         """wire: the call's Engine.fetch_wire chunks (a call with wire rows): those rows get their
         bytes untouched; numpy is called for rows without a format only (by their consumers).
         findex: the call's Engine.fetch_flac_index (a call with a FLAC segment of a group): such a
@@ -811,6 +840,8 @@ class BatchScheduler:
                     req.lat.append(np.array(res.latents[slot], np.float32))
                 if req.align_rows is not None:  # (frame 0's row comes with the regular frame, preview or not)
                     req.align_rows.append(np.array(align[slot], np.float32))
+                if req.loud_rows is not None:  # (likewise: the meter saw the regular frame)
+                    req.loud_rows.append(np.array(loud[slot], np.float64))
                 if req.preview == 1:  # frame 0, already delivered from the preview
                     req.preview = 2
                 else:
@@ -913,9 +944,12 @@ class BatchScheduler:
                     arows = None
                     if any(r.align_rows is not None for r in self.active.values()):
                         arows = self.engine.fetch_align(issued[0], calls_back=cb)
+                    lrows = None
+                    if any(r.loud_rows is not None for r in self.active.values()):
+                        lrows = self.engine.fetch_loud(issued[0], calls_back=cb)
                     self._deliver_previews()  # those that completed while fetch() waited: ahead of it
                     fstep = self.steps - len(issued) - self.lag
-                    done = self._deliver(res, issued.popleft(), wire, fstep, arows, findex)
+                    done = self._deliver(res, issued.popleft(), wire, fstep, arows, findex, lrows)
                     if done:
                         with self.cv:
                             for slot in done:
@@ -1122,6 +1156,14 @@ def wav_wire_samples(data: bytes) -> tuple[np.ndarray, int]:
     return np.ascontiguousarray(x[0], np.float32), sr
 
 
+class _Calibration:
+    """One clip's loudness calibration: `done` is set once `value` (LUFS, or None: unmeasurable) or
+    `error` is in place."""
+
+    def __init__(self):
+        self.done, self.value, self.error = threading.Event(), None, None
+
+
 class TTSService:
     """Request-level logic shared by the HTTP routes: text -> ids, voice lookup, params."""
 
@@ -1152,6 +1194,14 @@ class TTSService:
         self.pitch = self.tempo and bool(getattr(eng, "pitch_enabled", False))  # and shift the pitch (--pitch)
         self.level = self.wire and bool(getattr(eng, "level_enabled", False))  # and set the level (--volume)
         self.align = bool(getattr(eng, "align_enabled", False))  # and deliver alignment rows (--align)
+        self.loud = self.wire and bool(getattr(eng, "loud_enabled", False))  # and meter loudness (--loudness)
+        # calibrated loudness (LUFS; None: unmeasurable) of the registered voices by name and of
+        # per-request clips by their key, the latter bounded like the clone cache
+        self.voice_lufs: dict = {}
+        self.clip_lufs: OrderedDict = OrderedDict()  # clip key -> _Calibration, under _cal_lock
+        self._cal_lock = threading.Lock()
+        sch0 = getattr(scheduler, "schedulers", [scheduler])[0]
+        self._cal_capacity = max(int(getattr(getattr(sch0, "voices", None), "capacity", 64)), 1)
         self.scheduler = scheduler
         self.voices = voices
         self.default_voice = default_voice
@@ -1163,6 +1213,63 @@ class TTSService:
         self.continuity = bool(continuity)
         self._seed = 0
         self._lock = threading.Lock()
+        if self.loud:  # the voices the server starts with (--voice)
+            for name in list(self.voices):
+                self.voice_lufs[name] = self.calibrate(self.voices[name])
+
+    def calibrate(self, target) -> float | None:
+        """The loudness of a voice (a registered voice or a clip) in LUFS: the calibration sentence at
+        the server's default parameters and a fixed seed, no gain, 24000 / pcm_s16le with the bytes
+        discarded, metered; an ordinary request through the scheduler. None: unmeasurable (also a
+        server with no tokenizer, which cannot say the sentence)."""
+        if not self.loud or self.tokenizer is None:
+            return None
+        ids, mgl, fae = segment_request(CALIBRATION_TEXT, self.tokenizer)
+        p = GenerationParams(temp=self.temp, eos_threshold=self.eos_threshold, noise_clamp=self.noise_clamp,
+                             frames_after_eos=fae, max_frames=mgl, seed=CALIBRATION_SEED, sample_rate=SAMPLE_RATE,
+                             encoding="pcm_s16le", loudness=True)
+        r = self.scheduler.submit(np.asarray(ids, np.int32), target, p)
+        r.wire_audio()
+        return r.loudness()
+
+    def clip_loudness(self, clip: VoiceClip) -> float | None:
+        """The loudness of a per-request clip, calibrated on its first use and kept by the clip's key
+        beside the clone caches: the same key, capacity and least-recently-used order (the caches
+        themselves belong to the scheduler threads, one per engine). A second request that comes
+        while the first still calibrates waits for that one run. Called from request threads."""
+        with self._cal_lock:
+            ent = self.clip_lufs.get(clip.key)
+            mine = ent is None
+            if mine:
+                ent = self.clip_lufs[clip.key] = _Calibration()
+                while len(self.clip_lufs) > self._cal_capacity:
+                    self.clip_lufs.popitem(last=False)
+            else:
+                self.clip_lufs.move_to_end(clip.key)
+        if not mine:
+            ent.done.wait()
+            if ent.error is not None:
+                raise RuntimeError("the voice's calibration failed") from ent.error
+            return ent.value
+        try:
+            ent.value = self.calibrate(clip)
+        except BaseException as e:
+            ent.error = e
+            with self._cal_lock:
+                if self.clip_lufs.get(clip.key) is ent:
+                    del self.clip_lufs[clip.key]
+            raise
+        finally:
+            ent.done.set()
+        return ent.value
+
+    def voice_info(self, name: str) -> dict:
+        """GET /voices/NAME. KeyError: no such voice."""
+        with self._lock:
+            v = self.voices[name]
+            lufs = self.voice_lufs.get(name)
+        v0 = v[0] if isinstance(v, (list, tuple)) else v
+        return {"name": name, "frames": int(getattr(v0, "n_frames", 0)), "loudness_lufs": lufs}
 
     def _count_tokens(self, text: str) -> int:
         tok = self.tokenizer
@@ -1174,8 +1281,14 @@ class TTSService:
                 max_frames: int | None = None, sample_rate: int | None = None,
                 encoding: str | None = None, long_form: bool | None = None, speed: float | None = None,
                 continuity: bool | None = None, pitch: float | None = None, volume_db: float | None = None,
-                limit: bool | None = None, timestamps: bool | None = None) -> Request:
-        """timestamps: the rows also deliver their alignment rows (DESIGN.md section 26), for words();
+                limit: bool | None = None, timestamps: bool | None = None, loudness_lufs: float | None = None,
+                loudness: bool | None = None) -> Request:
+        """loudness_lufs: a target in [-40, -5] LUFS: the rows get the constant gain target - the voice's
+        calibrated loudness (within +-24 dB) through the level stage, limiter on; the gain is the
+        returned object's gain_db. It excludes volume_db and needs --loudness and --volume.
+        loudness: the rows are metered; loudness() of the returned object, once its audio is consumed,
+        is the response's integrated loudness.
+        timestamps: the rows also deliver their alignment rows (DESIGN.md section 26), for words();
         a text request on a server with the align stage (--align), not with continuity (that row's
         text also holds the previous chunk's ids) and not with token_ids (they carry no words).
         volume_db: -24 .. 24 dB (rounded to hundredths), limit: run the row through the peak limiter
@@ -1230,6 +1343,19 @@ class TTSService:
                                  "index to renumber them by")
         if limit is not None and not isinstance(limit, (bool, np.bool_)):
             raise ValueError(f"limit must be a bool, got {limit!r}")
+        if loudness is not None and not isinstance(loudness, (bool, np.bool_)):
+            raise ValueError(f"loudness must be a bool, got {loudness!r}")
+        if loudness and not self.loud:
+            raise ValueError("this server runs without the loudness stage (--loudness): loudness is not available")
+        gain_db = None
+        if loudness_lufs is not None:  # (the gain itself: below, once everything else about the request is valid)
+            if not (math.isfinite(float(loudness_lufs)) and -40.0 <= float(loudness_lufs) <= -5.0):
+                raise ValueError(f"loudness_lufs must be in [-40, -5] LUFS, got {loudness_lufs!r}")
+            if volume_db is not None:
+                raise ValueError("loudness_lufs and volume_db exclude each other")
+            if not (self.loud and self.level):
+                raise ValueError("this server runs without the loudness stage or the level stage (--loudness, "
+                                 "--volume): loudness_lufs is not available")
         # (ValueError: a value out of range); a field that changes nothing is the request without it
         out = OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit)
         if out.speed is not None and not self.tempo:
@@ -1278,6 +1404,12 @@ class TTSService:
         name = voice or self.default_voice
         # not a registered name: base64 audio (decoded outside the lock), or refused
         clip = None if name in self.voices else self.voice_clip(name)
+        if loudness_lufs is not None:  # the last check: a per-request clip's calibration is a generation
+            cal = self.clip_loudness(clip) if clip is not None else self.voice_lufs.get(name)
+            if cal is None:
+                raise ValueError("the voice's loudness is unmeasurable: no loudness target for it")
+            gain_db = loudness_gain_cdb(float(loudness_lufs), cal) / 100.0
+            out = OutputOptions.of(sample_rate, encoding, speed, pitch, gain_db, True)
         # the name is resolved and the request queued under the lock register_voice swaps the name
         # under: a replaced voice is retired only after every request that got it is queued, and
         # the scheduler closes it only once none of them is still waiting (BatchScheduler.retire)
@@ -1285,14 +1417,19 @@ class TTSService:
             target = clip if clip is not None else self.voices[name]
             if segments is not None:  # one seed per text segment, in text order
                 segs = [("text", sg[1], self._params_locked(temperature, eos_threshold, noise_clamp, sg[3], sg[2],
-                                                            lsd_steps, out, bool(timestamps)))
+                                                            lsd_steps, out, bool(timestamps), bool(loudness)))
                         if sg[0] == "text" else sg for sg in segments]
                 # (pauses: silence of their stated duration in the rows' format, whatever the speed)
                 if chain:
-                    return self.scheduler.submit_group(segs, target, out.wire, continuity=True)
-                return self.scheduler.submit_group(segs, target, out.wire)
-            return self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                                       out, bool(timestamps))
+                    r = self.scheduler.submit_group(segs, target, out.wire, continuity=True)
+                else:
+                    r = self.scheduler.submit_group(segs, target, out.wire)
+            else:
+                r = self._submit_locked(ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
+                                        out, bool(timestamps), bool(loudness))
+        if gain_db is not None:
+            r.gain_db = gain_db
+        return r
 
     def words(self, r) -> list[dict]:
         """[{"word", "start", "end"}] of a finished timestamps request (its audio consumed), in seconds
@@ -1318,12 +1455,12 @@ class TTSService:
         return out
 
     def _submit_locked(self, ids, target, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps,
-                       out=OutputOptions(), align=False) -> Request:
-        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, out, align)
+                       out=OutputOptions(), align=False, loud=False) -> Request:
+        p = self._params_locked(temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, out, align, loud)
         return self.scheduler.submit(ids, target, p)  # MultiGpuScheduler: one voice per GPU, or the clip
 
     def _params_locked(self, temperature, eos_threshold, noise_clamp, fae, mgl, lsd_steps, out=OutputOptions(),
-                       align=False) -> GenerationParams:
+                       align=False, loud=False) -> GenerationParams:
         self._seed += 1
         seed = self._seed
         p = GenerationParams(temp=self.temp if temperature is None else temperature,
@@ -1331,6 +1468,8 @@ class TTSService:
                              noise_clamp=self.noise_clamp if noise_clamp is None else noise_clamp,
                              frames_after_eos=fae, max_frames=mgl, seed=seed,
                              lsd_steps=None if lsd_steps is None else int(lsd_steps), align=bool(align))
+        if loud:  # (set only then: a request without it submits the params of before)
+            p.loudness = True
         return out.apply(p)
 
     # -- per-request and run-time voices
@@ -1384,8 +1523,11 @@ class TTSService:
             new = self.scheduler.call(lambda: clip.start(self.scheduler.engine))
         else:
             new = [s.call(lambda s=s: clip.start(s.engine)) for s in scheds]
+        lufs = self.calibrate(new) if self.loud else None  # (before the swap: the name never lacks its value)
         with self._lock:
             old, self.voices[name] = self.voices.get(name), new
+            if self.loud:
+                self.voice_lufs[name] = lufs
         if old is not None:  # closed once no queued request holds it; rows reading it keep it alive
             if scheds is None:
                 self.scheduler.retire(old)
@@ -1428,6 +1570,10 @@ class GenerateRequest(BaseModel):
     # behind speed and pitch); unset, or 0 with limit unset: unchanged
     volume_db: float | None = None
     limit: bool | None = None
+    # loudness target in LUFS, -40 .. -5 (a constant gain from the voice's calibrated loudness, limiter on;
+    # excludes volume_db), and `loudness`: meter the response (X-Loudness-LUFS); DESIGN.md section 27
+    loudness_lufs: float | None = None
+    loudness: bool | None = None
     # split the text into segments on parallel rows, pauses as silence (None: the server's --long-form)
     long_form: bool | None = None
     # the long-form cut with each sentence chunk continuing the one before it (None: --continuity)
@@ -1451,6 +1597,10 @@ class OpenAIRequest(BaseModel):
     pitch: float | None = None  # -12 .. 12 semitones (no counterpart in that API)
     volume_db: float | None = None  # -24 .. 24 dB (no counterpart in that API)
     limit: bool | None = None
+    # loudness target in LUFS, -40 .. -5 (a constant gain from the voice's calibrated loudness, limiter on;
+    # excludes volume_db), and `loudness`: meter the response (X-Loudness-LUFS); DESIGN.md section 27
+    loudness_lufs: float | None = None
+    loudness: bool | None = None
     long_form: bool | None = None
     continuity: bool | None = None
     timestamps: bool | None = None  # as in GenerateRequest
@@ -1552,11 +1702,13 @@ def create_app(service: TTSService):
         except ValueError as e:
             raise HTTPException(status_code=400, detail=str(e)) from e
 
-    def timed(r, data: bytes, media: str):
+    def timed(r, data: bytes, media: str, metered=False):
         """The answer of a timestamps request: what the route would have sent, in base64, and the words."""
-        return JSONResponse({"audio": base64.b64encode(data).decode(), "content_type": media,
-                             "sample_rate": r.wire[0] if r.wire else SAMPLE_RATE, "words": service.words(r)},
-                            headers=hdr)
+        body = {"audio": base64.b64encode(data).decode(), "content_type": media,
+                "sample_rate": r.wire[0] if r.wire else SAMPLE_RATE, "words": service.words(r)}
+        if metered:
+            body["loudness_lufs"] = r.loudness()
+        return JSONResponse(body, headers=loud_headers(r, metered))
 
     worker = getattr(service, "worker", None) or {"rank": 0, "world": 1, "pid": os.getpid()}
     hdr = {"X-PTTS-Rank": str(worker["rank"])}
@@ -1585,6 +1737,23 @@ def create_app(service: TTSService):
     def list_voices():
         return JSONResponse({"voices": service.voice_names(), "default": service.default_voice}, headers=hdr)
 
+    @app.get("/voices/{name}")
+    def voice_info(name: str):
+        try:
+            return JSONResponse(service.voice_info(name), headers=hdr)
+        except KeyError:
+            raise HTTPException(status_code=404, detail=f"no voice {name!r}") from None
+
+    def loud_headers(r, metered) -> dict:
+        """X-Gain-dB of a loudness_lufs request; X-Loudness-LUFS of a metered one (its audio consumed)."""
+        h = dict(hdr)
+        if getattr(r, "gain_db", None) is not None:
+            h["X-Gain-dB"] = f"{r.gain_db:.2f}"
+        if metered:
+            v = r.loudness()
+            h["X-Loudness-LUFS"] = "none" if v is None else f"{v:.2f}"
+        return h
+
     @app.post("/voices/{name}")
     async def register_voice(name: str, request: StarletteRequest):
         from starlette.concurrency import run_in_threadpool
@@ -1603,11 +1772,12 @@ def create_app(service: TTSService):
             return redirect
         r = submit(**req.model_dump())
         if r.wire is not None and r.wire[1] == "flac":
-            return Response(flac_file(r), media_type="audio/flac", headers=hdr)
+            data = flac_file(r)
+            return Response(data, media_type="audio/flac", headers=loud_headers(r, req.loudness))
         data = wav_bytes(r.wire_audio(), *r.wire) if r.wire is not None else wav_bytes(r.audio())
         if req.timestamps:
-            return timed(r, data, "audio/wav")
-        return Response(data, media_type="audio/wav", headers=hdr)
+            return timed(r, data, "audio/wav", req.loudness)
+        return Response(data, media_type="audio/wav", headers=loud_headers(r, req.loudness))
 
     @app.post("/stream")
     async def stream(req: GenerateRequest, request: StarletteRequest):
@@ -1617,14 +1787,21 @@ def create_app(service: TTSService):
             return redirect
         if req.timestamps:
             raise HTTPException(status_code=400, detail="timestamps are not available on /stream: ask /generate")
-        r = submit(**req.model_dump())
+        if req.loudness:
+            raise HTTPException(status_code=400, detail="loudness is not available on /stream (a stream has no place "
+                                                        "for the value): ask /generate")
+        if req.loudness_lufs is not None:  # may calibrate an inline clip, a whole generation: not on the event loop
+            from starlette.concurrency import run_in_threadpool
+
+            r = await run_in_threadpool(lambda: submit(**req.model_dump()))
+        else:
+            r = submit(**req.model_dump())
         r.times["route"] = t_route
+        sh = {**loud_headers(r, False), "X-PTTS-Route-Time": f"{t_route:.6f}"}  # (the gain is known at admission)
         if r.wire is not None and r.wire[1] == "flac":
-            return StreamingResponse(flac_chunks(r), media_type="audio/flac",
-                                     headers={**hdr, "X-PTTS-Route-Time": f"{t_route:.6f}"})
+            return StreamingResponse(flac_chunks(r), media_type="audio/flac", headers=sh)
         media = {"ulaw": "audio/PCMU", "alaw": "audio/PCMA"}.get(r.wire[1] if r.wire else "", "audio/pcm")
-        return StreamingResponse(pcm_chunks(r), media_type=media,
-                                 headers={**hdr, "X-PTTS-Route-Time": f"{t_route:.6f}"})
+        return StreamingResponse(pcm_chunks(r), media_type=media, headers=sh)
 
     @app.post("/v1/audio/speech")
     def openai_speech(req: OpenAIRequest, request: StarletteRequest):
@@ -1645,9 +1822,11 @@ def create_app(service: TTSService):
             raise HTTPException(status_code=400, detail=f"response_format pcm contradicts encoding {enc}")
         r = submit(text=req.input, token_ids=req.token_ids, voice=req.voice, words=req.words, sample_rate=rate,
                    encoding=enc, long_form=req.long_form, speed=req.speed, continuity=req.continuity, pitch=req.pitch,
-                   volume_db=req.volume_db, limit=req.limit, timestamps=req.timestamps)
+                   volume_db=req.volume_db, limit=req.limit, timestamps=req.timestamps,
+                   loudness_lufs=req.loudness_lufs, loudness=req.loudness)
         if r.wire is not None and r.wire[1] == "flac":
-            return Response(flac_file(r), media_type="audio/flac", headers=hdr)
+            data = flac_file(r)
+            return Response(data, media_type="audio/flac", headers=loud_headers(r, req.loudness))
         if r.wire is not None:
             data = r.wire_audio()
             if fmt not in ("pcm", "ulaw", "alaw"):  # wav, and (as before) anything else
@@ -1658,8 +1837,8 @@ def create_app(service: TTSService):
             audio = r.audio()
             data, media = (pcm_i16_le_bytes(audio), "audio/pcm") if fmt == "pcm" else (wav_bytes(audio), "audio/wav")
         if req.timestamps:
-            return timed(r, data, media)
-        return Response(data, media_type=media, headers=hdr)
+            return timed(r, data, media, req.loudness)
+        return Response(data, media_type=media, headers=loud_headers(r, req.loudness))
 
     return app
 
@@ -1679,6 +1858,19 @@ def stand_in_align_row(k: int, frames: int, n: int) -> np.ndarray:
     return a
 
 
+@dataclass
+class _StandInWire:
+    """A wire row of the stand-in engine."""
+
+    enc: str                 # encoding name
+    level: tuple             # (gain_cdb, limit); (0, 0): not in the level stage
+    u: int                   # the utterance (its first token id)
+    total: int               # max_frames
+    k: int = 0               # frames so far
+    chunks: list | None = None        # a level row's chunks by the streaming host rule (computed once)
+    last: np.ndarray | None = None    # the f32 chunk the latest bytes were made of: what a metered row's meter reads
+
+
 class StandInEngine:
     """--stand-in-engine only (CPU; launcher and routing self-test of the multi-process server): the
     engine surface the scheduler drives, computing nothing. Row frames of utterance u (its first
@@ -1688,8 +1880,14 @@ class StandInEngine:
     every admitted row's GenerationParams are kept in `params_log`."""
 
     def __init__(self, max_slots=32, max_ctx=1024, step_s=0.0, wire=False, level=False, level_ceiling_db=-1.0,
-                 align=False, **_):
+                 align=False, loud=False, **_):
         self.max_slots, self.max_ctx, self.pipeline = max_slots, max_ctx, True
+        # loud=True (with wire=True): rows admitted with GenerationParams.loudness deliver, through
+        # fetch_loud, the host rule's sub-block energies (audio.LoudnessMeter) over what their wire
+        # stage reads, one call late like the frames
+        self.loud_enabled = bool(wire and loud)
+        self.meter = {}  # slot -> the row's LoudnessMeter
+        self.loud_pending = self.loud_out = self.loud_prev = None
         # align=True: rows admitted with GenerationParams.align deliver a planted alignment row per
         # frame (stand_in_align_row) through fetch_align, one call late like the frames
         self.align_enabled = bool(align)
@@ -1701,10 +1899,9 @@ class StandInEngine:
         self.params_log = []  # and its GenerationParams
         self.level_enabled = bool(wire and level)
         self.level_ceiling_cdb = level_cdb(level_ceiling_db, -40.0, 0.0, "level_ceiling_db") if self.level_enabled else 0
-        if self.level_enabled:  # (without it the stand-in has no wire surface, as before)
+        if self.level_enabled or self.loud_enabled:  # (without them the stand-in has no wire surface, as before)
             self.wire = True
-        # slot -> [encoding name, (gain_cdb, limit), frames so far, utterance, max_frames, level chunks] of a wire row
-        self.fmt = {}
+        self.fmt = {}  # slot -> _StandInWire of a wire row
         self.wire_pending = self.wire_out = self.wire_prev = None
 
     @staticmethod
@@ -1759,18 +1956,24 @@ class StandInEngine:
                 raise RuntimeError("a gain or limit needs a level-enabled engine")
             if getattr(p, "align", False) and not self.align_enabled:
                 raise RuntimeError("align needs an align-enabled engine")
-            if out.wire and not (self.level_enabled and out.wire[0] == SAMPLE_RATE and out.wire[1] != "flac"):
+            if getattr(p, "loudness", False) and not self.loud_enabled:
+                raise RuntimeError("loud needs a loudness-enabled engine")
+            if out.wire and not ((self.level_enabled or self.loud_enabled) and out.wire[0] == SAMPLE_RATE and out.wire[1] != "flac"):
                 raise RuntimeError("the stand-in engine converts to 24 kHz pcm_s16le / ulaw / alaw only, with level=True")
         for s, ids, p in zip(slots, ids_list, params_list):
             pre = getattr(p, "prefix_latents", None)
             self.params_log.append(p)
             self.fmt.pop(s, None)
             self.arow.pop(s, None)
+            self.meter.pop(s, None)
             if getattr(p, "align", False):
                 self.arow[s] = len(ids)
             out = row_output(p)
-            if out.wire:
-                self.fmt[s] = [out.wire[1], out.codes()[4:], 0, int(ids[0]) if len(ids) else 0, p.max_frames, None]
+            if getattr(p, "loudness", False):
+                self.meter[s] = LoudnessMeter()
+            if out.wire or s in self.meter:  # (a metered row with no format: 24000 / pcm_s16le, as the engine's)
+                self.fmt[s] = _StandInWire((out.wire or (SAMPLE_RATE, "pcm_s16le"))[1], out.codes()[4:],
+                                           int(ids[0]) if len(ids) else 0, p.max_frames)
             self.rows[s] = [int(ids[0]) if len(ids) else 0, 0, p.max_frames, len(self.admit_log)]
             self.admit_log.append((int(s), [int(i) for i in ids], None if pre is None else np.array(pre, np.float32),
                                   bool(getattr(p, "keep_codec", False))))
@@ -1786,6 +1989,10 @@ class StandInEngine:
             self.rows.pop(s, None)
             self.fmt.pop(s, None)
             self.arow.pop(s, None)
+            self.meter.pop(s, None)
+            for held in (self.loud_pending, self.loud_out, self.loud_prev):
+                if held is not None and s < len(held):
+                    held[s] = np.zeros(0, np.float64)
             for held in (self.align_pending, self.align_out, self.align_prev):
                 if held is not None and s < len(held):
                     held[s] = np.zeros(0, np.float32)
@@ -1803,6 +2010,7 @@ class StandInEngine:
         lat = np.zeros((n, LDIM), np.float32)
         wire = [b""] * n
         arows = [np.zeros(0, np.float32)] * n
+        lrows = [np.zeros(0, np.float64)] * n
         for s, st in list(self.rows.items()):
             if s < n:
                 pcm[s], valid[s] = stand_in_sample(st[0], st[1]), True
@@ -1810,12 +2018,18 @@ class StandInEngine:
                     arows[s] = stand_in_align_row(st[1], st[2], self.arow[s])
                 if s in self.fmt:
                     wire[s] = self._wire_chunk(self.fmt[s])
+                    if s in self.meter:  # what the wire stage read for the frame
+                        lrows[s] = self.meter[s].feed(self.fmt[s].last)
                 lat[s] = st[3] * 1000 + st[1]
                 st[1] += 1
                 last[s] = st[1] == st[2]
                 if last[s]:
                     del self.rows[s]
         prev, self.pending = self.pending, (pcm, valid, last, lat)
+        lprev, self.loud_pending = self.loud_pending, lrows
+        self.loud_prev, self.loud_out = self.loud_out, [np.zeros(0, np.float64)] * n
+        if lprev is not None:
+            self.loud_out[:min(n, len(lprev))] = lprev[:min(n, len(lprev))]
         aprev, self.align_pending = self.align_pending, arows
         self.align_prev, self.align_out = self.align_out, [np.zeros(0, np.float32)] * n
         if aprev is not None:
@@ -1844,14 +2058,21 @@ class StandInEngine:
     def _wire_chunk(self, f) -> bytes:
         """The next wire chunk of a wire row: its frame's bytes, or for a level row the frame's chunk
         of the streaming host rule over the row's whole signal (computed once)."""
-        enc, lv, k, u, total, chunks = f
-        f[2] = k + 1
-        if lv == (0, 0):
-            return wire_bytes(np.full(FRAME, stand_in_sample(u, k), np.float32), enc)
-        if chunks is None:
-            x = np.concatenate([np.full(FRAME, stand_in_sample(u, j), np.float32) for j in range(total)])
-            chunks = f[5] = level_limit(x, lv[0], self.level_ceiling_cdb, chunks=[FRAME] * total)
-        return wire_bytes(chunks[k], enc)
+        k = f.k
+        f.k = k + 1
+        if f.level == (0, 0):
+            x = np.full(FRAME, stand_in_sample(f.u, k), np.float32)
+        else:
+            if f.chunks is None:
+                x = np.concatenate([np.full(FRAME, stand_in_sample(f.u, j), np.float32) for j in range(f.total)])
+                f.chunks = level_limit(x, f.level[0], self.level_ceiling_cdb, chunks=[FRAME] * f.total)
+            x = f.chunks[k]
+        f.last = x
+        return wire_bytes(x, f.enc)
+
+    def fetch_loud(self, n, calls_back=0):
+        out = self.loud_out if calls_back == 0 else self.loud_prev
+        return [out[b] if out is not None and b < len(out) else np.zeros(0, np.float64) for b in range(n)]
 
     def fetch_align(self, n, calls_back=0):
         out = self.align_out if calls_back == 0 else self.align_prev
@@ -1898,6 +2119,8 @@ def _worker_engine(args, Engine):
     # (an engine without the stage is created exactly as before; the launcher's stand-in has no wire surface)
     if args.wire and args.volume and Engine is not StandInEngine:
         kw.update(level=True, level_ceiling_db=args.limiter_ceiling_db)
+    if args.wire and args.loudness and Engine is not StandInEngine:  # off by default
+        kw.update(loud=True)
     if args.align:  # off by default: the engine is created exactly as before
         kw.update(align=True, align_layer=args.align_layer, align_heads=int(str(args.align_heads), 0))
     if Engine is StandInEngine:
@@ -1979,6 +2202,10 @@ def main(argv=None):
     ap.add_argument("--limiter-ceiling-db", type=float, default=-1.0,
                     help="the level stage's ceiling in dBFS, -40 .. 0: no sample of a row with volume_db or limit "
                          "leaves it")
+    ap.add_argument("--loudness", action=argparse.BooleanOptionalAction, default=False,
+                    help="loudness (requests' `loudness` and `loudness_lufs`; GET /voices/NAME): a BS.1770 meter on the "
+                         "GPU, every registered voice calibrated on a fixed sentence; needs --wire, and --volume for "
+                         "`loudness_lufs`; off by default: the engine as before, such requests get 400")
     ap.add_argument("--align", action=argparse.BooleanOptionalAction, default=False,
                     help="word timestamps (requests' `timestamps` on /generate and /v1/audio/speech): one more launch in "
                          "the FlowLM step delivers a text-attention row per frame; off by default (which layer and "

@@ -461,6 +461,13 @@ def estimate_frames_after_eos(text: str) -> int:
     return 5 if len(text.split()) <= 4 else 3
 
 
+# The fixed sentence a voice's loudness is calibrated on: a voice's
+# `loudness_lufs` is the integrated loudness of this text at the default generation parameters. At
+# most 50 tokens; changing it changes every calibrated gain.
+CALIBRATION_SEED = 0x10DD  # the calibration row's seed
+CALIBRATION_TEXT = "The quick brown fox jumps over the lazy dog, and then it walks slowly back home along the river."
+
+
 def max_gen_len(prepared_text: str) -> int:
     """tts_model.rs:968: (words + 2) * 13 frames."""
     return (len(prepared_text.split()) + 2) * 13

@@ -26,16 +26,19 @@ is accepted too (one segment, no splitting).
 
 from __future__ import annotations
 
+import math
+import weakref
 from dataclasses import dataclass
 from typing import Callable, Iterator, Sequence
 
 import numpy as np
 
 from ._lib import FRAME, QUANT_ALL, QUANT_FLOW_LM, QUANT_NONE, SAMPLE_RATE
-from .audio import FlacJoiner, flac_stream_header, read_wav, read_wav_from_bytes, wire_bytes
+from .audio import (FlacJoiner, flac_stream_header, loudness_gain_cdb, loudness_integrated, read_wav,
+                    read_wav_from_bytes, wire_bytes)
 from . import align as _align
 from .engine import Engine, GenerationParams, OutputOptions, Voice
-from .text import (estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
+from .text import (CALIBRATION_SEED, CALIBRATION_TEXT, estimate_frames_after_eos, load_tokenizer, long_form_segments, long_text_segments, max_gen_len,
                    prepare_text_prompt, segment_request, silence_samples, split_into_best_sentences)
 
 DEFAULT_VARIANT = "b6369a24"
@@ -79,6 +82,8 @@ class TTSModel:
         # audio.rs:197-255; restated, parity unpinned)
         self.voice_resampler: str = "poly"
         self._seed = 0
+        # Voice -> LUFS or None (voice_loudness); weak, so a value dies with its Voice object
+        self._voice_loudness: weakref.WeakKeyDictionary = weakref.WeakKeyDictionary()
 
     @classmethod
     def load(cls, variant: str = DEFAULT_VARIANT, **kw) -> "TTSModel":
@@ -93,7 +98,8 @@ class TTSModel:
                          wire: bool = False, max_slots: int = 1, pipeline: bool = False,
                          back_frames: int = 1, tempo: bool = False, flac: bool = False,
                          pitch: bool = False, level: bool = False, level_ceiling_db: float = -1.0,
-                         align: bool = False, align_layer: int = 0, align_heads: int = 0xFFFF) -> "TTSModel":
+                         align: bool = False, align_layer: int = 0, align_heads: int = 0xFFFF,
+                         loud: bool = False) -> "TTSModel":
         """max_slots: the engine's row count (generate_parallel runs a text's segments on them; the
         other methods use row 0). pipeline / back_frames: overlapped stepping (Engine).
         max_lsd_decode_steps: the largest value the `lsd_decode_steps` field may later be set to
@@ -105,7 +111,8 @@ class TTSModel:
         generate(.., pitch=); flac (with wire): its FLAC stage, for
         generate(.., encoding="flac"); level (with wire): its level stage at level_ceiling_db, for
         generate(.., volume_db=, limit=). align: its align stage on FlowLM layer align_layer over the
-        heads of the mask align_heads, for generate(.., timestamps=True)."""
+        heads of the mask align_heads, for generate(.., timestamps=True). loud (with wire): its
+        loudness stage, for generate(.., measure_loudness=True) and, with level, loudness_lufs=."""
         if variant != DEFAULT_VARIANT:
             raise ValueError(f"unsupported variant {variant!r} (only {DEFAULT_VARIANT})")
         if tokenizer is None and tokenizer_path:
@@ -115,7 +122,8 @@ class TTSModel:
                      weights_path=weights_path, weight_quant=weight_quant, max_lsd_steps=max_lsd_decode_steps,
                      wire=wire, tempo=tempo, flac=flac, pitch=pitch,
                      **(dict(level=True, level_ceiling_db=level_ceiling_db) if level else {}),
-                     **(dict(align=True, align_layer=align_layer, align_heads=align_heads) if align else {}))
+                     **(dict(align=True, align_layer=align_layer, align_heads=align_heads) if align else {}),
+                     **(dict(loud=True) if loud else {}))
         return cls(eng, temp, lsd_decode_steps, eos_threshold, noise_clamp, tokenizer)
 
     # ---- quantized loading (tts_model.rs:108-181, feature "quantized"). The reference's version
@@ -194,10 +202,13 @@ class TTSModel:
         return max_gen_len(prepare_text_prompt(text))
 
     # ---- generation
-    def _params(self, max_frames: int, frames_after_eos: int) -> GenerationParams:
-        self._seed += 1
+    def _params(self, max_frames: int, frames_after_eos: int, seed: int | None = None) -> GenerationParams:
+        """seed: the row's own seed (the calibration row); None: the next of the model's counter."""
+        if seed is None:
+            self._seed += 1
+            seed = self._seed
         return GenerationParams(temp=self.temp, eos_threshold=self.eos_threshold, noise_clamp=self.noise_clamp,
-                                frames_after_eos=frames_after_eos, max_frames=max_frames, seed=self._seed)
+                                frames_after_eos=frames_after_eos, max_frames=max_frames, seed=seed)
 
     def _check_lsd(self):
         cap = self.engine.max_lsd_steps
@@ -208,7 +219,8 @@ class TTSModel:
     def _segment(self, ids: np.ndarray, voice_state: Voice, max_frames: int, frames_after_eos: int,
                  out: OutputOptions = OutputOptions(), previous: Continuation | None = None,
                  latents: list | None = None, align: list | None = None,
-                 joiner: FlacJoiner | None = None) -> Iterator[np.ndarray]:
+                 joiner: FlacJoiner | None = None, loud: list | None = None,
+                 seed: int | None = None) -> Iterator[np.ndarray]:
         """generate_stream_segment (tts_model.rs:935-1071) on engine row 0. For a wire row (out.wire:
         a format on a wire-enabled engine, a speed on a tempo-enabled one, a pitch, a gain or limit
         likewise) the items are the row's wire chunks, bytes converted on the GPU (Engine.fetch_wire),
@@ -219,11 +231,14 @@ class TTSModel:
         receives the latent of every frame yielded. align: a list that receives the alignment row of
         every frame yielded (an align-enabled engine; the row is admitted with align). joiner (a FLAC
         row): the chunks are renumbered to the segment's place in the joiner's stream (section 21.5),
-        and the segment is closed there when it ends."""
+        and the segment is closed there when it ends. loud: a list that receives the sub-block
+        energies of every frame yielded (a loudness-enabled engine; the row is admitted metered).
+        seed: the row's seed in place of the model's counter, which then stays as it is."""
         self._check_lsd()
-        params = out.apply(self._params(max_frames, frames_after_eos))
+        params = out.apply(self._params(max_frames, frames_after_eos, seed))
         params.lsd_steps = int(self.lsd_decode_steps)
         params.align = align is not None
+        params.loudness = loud is not None
         if previous is not None and (voice_state.n_frames + previous.ids.size + ids.size + len(previous.latents)
                                      + max_frames <= self.engine.max_ctx):
             ids = np.concatenate([np.asarray(previous.ids, np.int32), ids])
@@ -245,6 +260,8 @@ class TTSModel:
                     latents.append(np.array(r.latents[0], np.float32))
                 if align is not None:
                     align.append(self.engine.fetch_align(1)[0])
+                if loud is not None:
+                    loud.append(self.engine.fetch_loud(1)[0])
                 if joiner is not None:
                     yield joiner.chunk(self.engine.fetch_wire(1)[0], self.engine.fetch_flac_index(1)[0])
                 else:
@@ -289,42 +306,91 @@ class TTSModel:
         return FlacJoiner(out.wire[0]) if out.wire and out.wire[1] == "flac" else None
 
     def _stream(self, text_or_ids, voice_state, max_frames, words, out: OutputOptions,
-                joiner: FlacJoiner | None = None) -> Iterator[np.ndarray]:
+                joiner: FlacJoiner | None = None, loud: list | None = None) -> Iterator[np.ndarray]:
+        """loud: a list that receives, per segment (a row of its own), the list of its frames' energies."""
         joiner = joiner or self._joiner(out)
+
+        def row():
+            if loud is None:
+                return None
+            loud.append([])
+            return loud[-1]
+
         if not isinstance(text_or_ids, str):
             ids = np.asarray(text_or_ids, np.int32).reshape(-1)
             if words is None and max_frames is None:
                 raise ValueError("token ids carry no word count: pass words= or max_frames=")
             fae = 3 if words is None else (5 if words <= 4 else 3)
-            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, out, joiner=joiner)
+            yield from self._segment(ids, voice_state, max_frames or (words + 2) * 13, fae, out, joiner=joiner,
+                                     loud=row())
             return
         tok = self._tok()
         for chunk in self.split_into_best_sentences(text_or_ids):
             prepared = prepare_text_prompt(chunk)
             ids = np.asarray(tok(prepared), np.int32)
             yield from self._segment(ids, voice_state, max_frames or max_gen_len(prepared),
-                                     estimate_frames_after_eos(chunk), out, joiner=joiner)
+                                     estimate_frames_after_eos(chunk), out, joiner=joiner, loud=row())
 
     def generate(self, text_or_ids, voice_state: Voice, max_frames: int | None = None,
                  words: int | None = None, sample_rate: int | None = None, encoding=None,
                  speed: float | None = None, pitch: float | None = None, volume_db: float | None = None,
-                 limit: bool = False, timestamps: bool = False):
+                 limit: bool = False, timestamps: bool = False, measure_loudness: bool = False,
+                 loudness_lufs: float | None = None):
         """tts_model.rs:687-703: all frames concatenated, [1, N*1920]; with sample_rate / encoding /
         speed / pitch / volume_db / limit, the wire bytes of generate_stream concatenated. encoding "flac": a complete .flac file,
         the stream header with the true sample count and then the frames (of every segment, joined).
         timestamps=True (text input, a model loaded with align=True and a tokenizer that names its
         pieces): returns (audio, words), words = [{"word", "start", "end"}] in seconds of that audio
-        (align.py: each sentence chunk's words offset by the audio delivered before it)."""
+        (align.py: each sentence chunk's words offset by the audio delivered before it).
+        measure_loudness=True (a loudness-enabled engine): returns (audio, lufs),
+        the integrated loudness of what the wire stage read (the 24 kHz signal behind speed, pitch
+        and level), gated once over all segments; None where it is unmeasurable.
+        loudness_lufs (-40 .. -5; a level- and loudness-enabled engine): the audio gets the constant
+        gain target - voice_loudness(voice_state), within +-24 dB, through the level stage (so it is
+        wire bytes); it excludes volume_db. ValueError for a voice whose calibration is unmeasurable."""
+        if loudness_lufs is not None:
+            if volume_db is not None:
+                raise ValueError("loudness_lufs and volume_db exclude each other")
+            t = float(loudness_lufs)
+            if not (math.isfinite(t) and -40.0 <= t <= -5.0):
+                raise ValueError(f"loudness_lufs must be in [-40, -5], got {loudness_lufs!r}")
+            cal = self.voice_loudness(voice_state)
+            if cal is None:
+                raise ValueError("the voice's loudness is unmeasurable: no loudness target for it")
+            volume_db, limit = loudness_gain_cdb(t, cal) / 100.0, True
         out = OutputOptions.of(sample_rate, encoding, speed, pitch, volume_db, limit)
         if timestamps:
+            if measure_loudness:
+                raise ValueError("measure_loudness with timestamps is not available here")
             return self._generate_timed(text_or_ids, voice_state, max_frames, out)
         joiner = self._joiner(out)
-        frames = list(self._stream(text_or_ids, voice_state, max_frames, words, out, joiner))
+        loud = [] if measure_loudness else None
+        frames = list(self._stream(text_or_ids, voice_state, max_frames, words, out, joiner, loud))
         if not frames:
             raise RuntimeError("No audio generated")
         if joiner is not None:
-            return flac_stream_header(joiner.rate, joiner.total) + b"".join(frames)
-        return b"".join(frames) if out.wire else np.concatenate(frames, axis=2)[0]
+            audio = flac_stream_header(joiner.rate, joiner.total) + b"".join(frames)
+        else:
+            audio = b"".join(frames) if out.wire else np.concatenate(frames, axis=2)[0]
+        if not measure_loudness:
+            return audio
+        rows = [np.concatenate(r) if r else np.zeros(0, np.float64) for r in loud]
+        return audio, loudness_integrated(rows)
+
+    def voice_loudness(self, voice_state: Voice) -> float | None:
+        """The voice's integrated loudness in LUFS, measured on the GPU: the calibration the server
+        runs. One row says text.CALIBRATION_TEXT at the model's parameters with
+        the seed text.CALIBRATION_SEED, no gain, metered. The model's seed counter is not touched, so
+        the value does not depend on what was generated before and later calls get the seeds they
+        would have got without it. None: unmeasurable. Kept with the Voice object."""
+        if voice_state not in self._voice_loudness:
+            ids, mgl, fae = segment_request(CALIBRATION_TEXT, self._tok())
+            loud: list = []
+            for _ in self._segment(np.asarray(ids, np.int32), voice_state, mgl, fae, loud=loud, seed=CALIBRATION_SEED):
+                pass
+            energy = np.concatenate(loud) if loud else np.zeros(0, np.float64)
+            self._voice_loudness[voice_state] = loudness_integrated(energy)
+        return self._voice_loudness[voice_state]
 
     def _units(self, chunk, encoding) -> int:
         """Samples of one delivered item at the rate it is delivered at (f32 frames: 24 kHz)."""
